@@ -1,6 +1,8 @@
 """bench.py -- clips/sec of the DSTformer hot path (fwd + bwd + AdamW) on N MI355X of one node.
 
-    python bench.py                               # N=1, defaults finish in a couple of minutes
+    python bench.py                               # N=1: the headline figure alone, in seconds
+    python bench.py --full                        # ... and every side measurement below (a couple of minutes)
+    python bench.py --dump-outputs DIR            # ... and what the last timed step computed, as DIR/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -9,9 +11,11 @@ forward + backward of the full MotionBERT backbone (configs/pretrain/MB_pretrain
 configs/pose3d/MB_train_h36m.yaml: dim_feat 512, depth 5, 8 heads, mlp_ratio 2, T=243, J=17) at
 64 clips per GPU (MB_pretrain.yaml:10), a pose loss, and the AdamW update -- nothing is skipped
 inside the timed region.  One process per GPU; gradients are all-reduced over RCCL (weak scaling:
-the per-GPU batch is fixed).  Rank 0 prints ONE JSON line.
+the per-GPU batch is fixed).  Rank 0 prints ONE JSON line.  The inputs and the initial weights are
+seeded: with the same arguments every run computes on the same data.
 
-Extra objects on the line:
+Extra objects on the line, measured only with --full (null without it):
+  multi_gpu     N > 1: ranks seen, bytes per bucket, exposed all-reduce time, the same step without the exchange
   roofline      dominant kernel (the bf16 MFMA GEMM gemm_nt): algorithmic FLOPs per launch /
                 average launch duration measured here with HIP events on the launch stream during one
                 extra, untimed, instrumented step; peak = 2.5 PFLOP/s dense bf16 (MI355X_MICROARCH.md)
@@ -20,6 +24,7 @@ Extra objects on the line:
   forward_only  BASELINE config 1 (eval, no_grad) on the same batch
   gate_1e-3_modes  the same train step in the precisions that meet the north-star 1e-3 gate (bf16x3 split-operand, fp32)
   block_b256    the north-star target configuration: one Block at B=256 (forward / forward+backward, % of MFMA peak)
+  config3_b32, full_model_b256, lite_b64, config4_pretrain, config5_action   the other BASELINE configurations and sizes
 `python bench.py --gpus N` without a launcher spawns its own N ranks; `--block` prints only the Block benchmark.
 """
 from __future__ import annotations
@@ -360,7 +365,7 @@ def make_pretrain(net, model, opt, B, J, rank, dev):
     def macro():
         step(x30, x30, has_3d=False, has_gt=True)
         step(x81, x81, has_3d=False, has_gt=False)
-        return step(x243, gt243, has_3d=True, has_gt=True)
+        return dict(losses=step(x243, gt243, has_3d=True, has_gt=True))
     frames = B * (30 + 81 + 243)
     flops = 3.0 * B * (model_flops_fwd(FULL, 30) + model_flops_fwd(FULL, 81) + model_flops_fwd(FULL, 243))
     return macro, frames, flops
@@ -379,7 +384,7 @@ def make_action(model, N, J, rank, dev, distributed):
     x = x.reshape(N, 2, 243, J, 3)
     labels = torch.randint(0, 60, (N,), generator=torch.Generator().manual_seed(600 + rank)).to(dev)
     flops = 3.0 * 2 * N * model_flops_fwd(FULL, 243) + 3.0 * 2 * N * (J * FULL['dim_rep'] * 2048 + 2048 * 60)
-    return (lambda: step(x, labels)), step, flops
+    return (lambda: dict(zip(('loss', 'scores'), step(x, labels)))), step, flops
 
 
 def time_steps(fn, steps, warmup):
@@ -391,6 +396,32 @@ def time_steps(fn, steps, warmup):
         fn()
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / steps
+
+
+DUMP_MAX_ELEMENTS = 1 << 21     # per array (8 MiB of float32): a larger array is dumped as a fixed, seeded sample of its elements
+
+
+def dump_outputs(out_dir, outputs, model):
+    """`--dump-outputs`: what the last timed step handed its caller -- `outputs` (name -> tensor, the step's return value) and
+    the model it left behind: every parameter after the optimizer update and every gradient of that step, flattened in
+    named_parameters() order -- as out_dir/<name>.npy in float32.  Arrays above DUMP_MAX_ELEMENTS keep a sample whose positions
+    depend only on the array's length, so two builds of the project can be compared output for output."""
+    import numpy as np
+    named = list(model.named_parameters())
+    arrays = dict(outputs)
+    arrays['params'] = torch.cat([p.detach().reshape(-1) for _, p in named])
+    arrays['grads'] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for _, p in named])
+    os.makedirs(out_dir, exist_ok=True)
+    written = []
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMENTS:
+            idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMENTS,), generator=torch.Generator().manual_seed(t.numel())).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+            name += '_sample'
+        np.save(os.path.join(out_dir, name + '.npy'), t.float().cpu().numpy())
+        written.append(name + '.npy')
+    log(f'outputs of the last timed step -> {out_dir}: {", ".join(written)}')
 
 
 def spawn_ranks(args):
@@ -424,14 +455,19 @@ def main():
     ap.add_argument('--batch', type=int, default=64, help='clips per GPU')
     ap.add_argument('--frames', type=int, default=243)
     ap.add_argument('--precision', default='bf16', choices=['bf16', 'fp32', 'bf16x3'])
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip the forward-only / Block B=256 / fp32-class side measurements')
+    ap.add_argument('--full', action='store_true', help='after the headline, every side measurement of the line: per-kernel roofline, '
+                    'multi-GPU diagnostics, CPU baseline, other precisions, sizes and BASELINE configs (off: the headline alone)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the forward-only / Block B=256 / fp32-class side measurements')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed to DIR/<name>.npy (float32)')
     ap.add_argument('--block', action='store_true', help='only the north-star Block benchmark (B=256), printed as its own JSON line')
     ap.add_argument('--workload', default='pose', choices=['pose', 'pretrain', 'action'],
                     help="pose: BASELINE configs 2-3 (3D pose train step, the headline); pretrain: config 4 (masked / noisy 2D input, 2D + 3D "
                          "batches of T = 30 / 81 / 243 alternating in lock-step across ranks); action: config 5 (ActionNet finetune, two LR groups)")
     ap.add_argument('--backend', default='nccl', help="torch.distributed backend for N>1 ('nccl' = RCCL; 'gloo' only for wiring tests)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         spawn_ranks(args)            # does not return
@@ -488,10 +524,11 @@ def main():
 
     def pose_step(n=net):
         opt.zero_grad(set_to_none=True)
-        total, losses = fused_pose_loss(n(x), gt, LAMBDA_SCALE, LAMBDA_VELOCITY)
+        pred = n(x)
+        total, losses = fused_pose_loss(pred, gt, LAMBDA_SCALE, LAMBDA_VELOCITY)
         total.backward()
         opt.step()
-        return losses
+        return dict(pred=pred.detach(), losses=losses)
     if args.workload == 'pose':
         step = pose_step
 
@@ -506,12 +543,12 @@ def main():
         if i == 0:
             torch.cuda.synchronize()
             log(f'first step done, HBM in use {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB')
-    if world > 1 and hasattr(net, 'diagnostics'):
+    if args.full and world > 1 and hasattr(net, 'diagnostics'):
         net.diagnostics = {}
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        outputs = step()
     sync()
     dt = time.perf_counter() - t0
     if dist is not None:
@@ -521,12 +558,15 @@ def main():
     ms = dt / args.steps * 1e3
     clips = wl_units * world * args.steps / dt
     log(f'timed region: {ms:.2f} ms/step, {clips:.1f} clips/s')
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs, model)
+    del outputs
 
     # ---- N > 1: make the run self-diagnosing -- how many ranks really took part, what the gradient exchange
     # moved and how much of it was NOT hidden under backward, and the same step WITHOUT the exchange on this very GPU in this very
     # process (the N = 1 leg the scaling efficiency is quoted against; weak scaling: the per-GPU work is the same)
     multi = None
-    if world > 1:
+    if args.full and world > 1:
         ones = torch.ones(1, device=dev)
         dist.all_reduce(ones)
         diag = getattr(net, 'diagnostics', None) or {}
@@ -560,7 +600,7 @@ def main():
 
     # ---- BASELINE config 1 beside the headline: the same model and batch forward-only (eval, no_grad), rank 0 at N=1
     fwd_only = None
-    if rank == 0 and world == 1 and not args.no_extras and args.workload == 'pose':
+    if args.full and rank == 0 and world == 1 and not args.no_extras and args.workload == 'pose':
         model.eval()
         with torch.no_grad():
             for _ in range(2):
@@ -579,7 +619,7 @@ def main():
     # ---- the mode that meets the north-star 1e-3 gate, with a throughput number beside the headline:
     # the same training step in the fp32-class precisions (same batch, same loss, same optimizer), a short timed sample
     gate_modes = None
-    if rank == 0 and world == 1 and not args.no_extras and args.precision == 'bf16' and args.workload == 'pose':
+    if args.full and rank == 0 and world == 1 and not args.no_extras and args.precision == 'bf16' and args.workload == 'pose':
         gate_modes = {}
         for prec in ('bf16x3', 'fp32'):
             if prec not in M._DTYPES:
@@ -603,7 +643,7 @@ def main():
             torch.cuda.empty_cache()
         model.precision = args.precision
     block = None
-    if rank == 0 and world == 1 and not args.no_extras and args.precision == 'bf16' and args.workload == 'pose':
+    if args.full and rank == 0 and world == 1 and not args.no_extras and args.precision == 'bf16' and args.workload == 'pose':
         torch.cuda.empty_cache()
         try:
             block = bench_block(dev)
@@ -615,7 +655,7 @@ def main():
     # ---- BASELINE config 3 (MB_train_h36m.yaml:10: batch 32): the step issued eagerly (~850 launches from Python) against the
     # same step replayed from one hipGraph (forward + loss + backward + AdamW captured once)
     cfg3 = None
-    if rank == 0 and world == 1 and not args.no_extras and args.precision == 'bf16' and args.workload == 'pose':
+    if args.full and rank == 0 and world == 1 and not args.no_extras and args.precision == 'bf16' and args.workload == 'pose':
         try:
             x3, gt3 = make_batch(32, T, J, 7, dev)
 
@@ -655,7 +695,7 @@ def main():
     # ---- the north-star batch on the FULL model: 256 clips x 243 frames per GPU do not fit with every activation saved
     # (78 GiB at 64 clips -> ~312 GiB); the low-memory mode (model.recompute) rebuilds LayerNorm outputs and MLP post-activations
     full256 = None
-    if rank == 0 and world == 1 and not args.no_extras and args.precision == 'bf16' and args.workload == 'pose':
+    if args.full and rank == 0 and world == 1 and not args.no_extras and args.precision == 'bf16' and args.workload == 'pose':
         try:
             torch.cuda.empty_cache()
             torch.cuda.reset_peak_memory_stats()
@@ -688,7 +728,7 @@ def main():
     # ---- MotionBERT-Lite (the reference's second published architecture: MB_lite.yaml) at the headline batch: the same training step
     # and the no-grad forward on the C = 256 / head-dim-32 kernels (fixtures-tested, never timed before round 4)
     lite = None
-    if rank == 0 and world == 1 and not args.no_extras and args.precision == 'bf16' and args.workload == 'pose':
+    if args.full and rank == 0 and world == 1 and not args.no_extras and args.precision == 'bf16' and args.workload == 'pose':
         try:
             torch.cuda.empty_cache()
             torch.manual_seed(1)
@@ -732,7 +772,7 @@ def main():
     # ---- BASELINE configs 4 and 5 at N = 1 beside the headline; `--workload pretrain|action` times them as
     # the main step (and under --gpus N), these are short samples of the same step functions
     cfg4 = cfg5 = None
-    if rank == 0 and world == 1 and not args.no_extras and args.precision == 'bf16' and args.workload == 'pose':
+    if args.full and rank == 0 and world == 1 and not args.no_extras and args.precision == 'bf16' and args.workload == 'pose':
         try:
             macro, frames, fl4 = make_pretrain(model, model, opt, B, J, rank, dev)
             d4 = time_steps(macro, 6, 2)
@@ -764,7 +804,7 @@ def main():
 
     # ---- one extra instrumented step (untimed): per-kernel HIP-event durations -> roofline of the dominant kernel
     roof, breakdown = None, None
-    if rank == 0:
+    if args.full and rank == 0:
         timed = TimedOps(hip_ops.get())
         for _ in range(2):      # the first pass refills the allocator's pools after empty_cache() (a hipMalloc inside an event pair
             timed.rec.clear()   # once put 25 ms on the LayerNorm-backward line); the second pass is the one reported
@@ -827,7 +867,7 @@ def main():
         'multi_gpu': multi, 'roofline': roof, 'kernel_breakdown_ms': breakdown, 'forward_only': fwd_only, 'gate_1e-3_modes': gate_modes, 'block_b256': block, 'config3_b32': cfg3, 'full_model_b256': full256, 'lite_b64': lite, 'config4_pretrain': cfg4, 'config5_action': cfg5,
     }
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(FULL, T)
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -17,7 +17,8 @@ GPU box, so its inputs/outputs/gradients are committed as small .npz fixtures:
       (lib/utils/learning.py:83-85) after torch.manual_seed(0): per-parameter
       (sum, |sum|) of the initial weights, a [1,27,17,3] input, the fp64 output
       and per-parameter (l2, sum) of the gradients.  The weights themselves are
-      re-created on the test machine from the same seed.
+      re-created on the test machine from the same seed (weights drawn with
+      tests.helpers.portable_erfinv, here and in the tests: the same on every host).
 
   full_1x243.npz / lite_2x81.npz
       the BASELINE.json shapes: the full model on [1,243,17,3] ("trained-like"
@@ -28,6 +29,12 @@ GPU box, so its inputs/outputs/gradients are committed as small .npz fixtures:
       plus the error of the reference ITSELF under torch.autocast(bfloat16)
       against its fp64 run (output, input gradient, global gradient, per tensor): the yardstick
       the bf16 mode of the HIP path is gated against.
+      Their seed-0 weights were drawn with torch's own erfinv on MKL's AVX-512 branch.
+  lite_2x81_init.npz
+      where those weights of lite_2x81 differ from the tests.helpers.portable_erfinv
+      draw (one or two ulps: position gaps + bit-pattern steps), so that
+      tests.helpers.minted_weights rebuilds them bit for bit on any host.  Written
+      on a host whose MKL takes the AVX-512 branch (checked against the fixture).
 
 While generating, the numpy oracle is checked against the reference (fp64
 forward and every gradient); the script aborts if they disagree.
@@ -49,6 +56,7 @@ import torch
 import torch.nn as nn
 
 from oracle import dstformer_oracle as O
+from tests.helpers import portable_erfinv
 
 
 def import_reference(REF=None):
@@ -156,7 +164,8 @@ def seeded(DST, name, dim_feat, mlp_ratio):
     kw = dict(dim_in=3, dim_out=3, dim_feat=dim_feat, dim_rep=512, depth=5, num_heads=8, mlp_ratio=mlp_ratio,
               num_joints=17, maxlen=243)
     torch.manual_seed(0)  # train.py:37,41-44 default seed
-    model = DST(norm_layer=partial(nn.LayerNorm, eps=1e-6), **kw)
+    with portable_erfinv():
+        model = DST(norm_layer=partial(nn.LayerNorm, eps=1e-6), **kw)
     sd32 = {k: v.detach().clone().numpy() for k, v in model.state_dict().items()}
     nparam = sum(v.size for v in sd32.values())
     B, T = 1, 27
@@ -176,6 +185,36 @@ def seeded(DST, name, dim_feat, mlp_ratio):
     save.update({f'cfg.{k}': np.asarray(v) for k, v in kw.items()})
     np.savez_compressed(os.path.join(ROOT, 'tests/golden', f'seed0_{name}.npz'), **save)
     print(f'[{name}] params {nparam:,}; fp32-vs-fp64 output rel-l2 {O.rel_l2(out32, out):.2e}')
+
+
+def init_fixup(name, kw):
+    """tests/golden/<name>_init.npz: where the seed-0 weights the committed <name>.npz was minted with (torch's erfinv on this host)
+    differ from the portable draw: `names` (the tensors that differ) and `count` (how many elements of each), then for every such
+    element in that order `gap_lo` / `gap_hi` (the low / high byte of the gap to the previous differing flat position of the
+    same tensor, the first from -1) and `step` (int8: minted minus portable float32 bit pattern; one or two ulps, never across zero)."""
+    from tests.helpers import build_model
+    with np.load(os.path.join(ROOT, 'tests/golden', f'{name}.npz')) as z:
+        names, w_stats = [str(n) for n in z['names']], z['w_stats']
+    minted = build_model(kw, seed=0).state_dict()
+    got = np.asarray([[minted[k].double().sum().item(), minted[k].double().abs().sum().item()] for k in names])
+    assert np.allclose(got, w_stats, rtol=1e-12, atol=1e-12), f'this host does not draw the weights {name}.npz was minted with'
+    with portable_erfinv():
+        portable = build_model(kw, seed=0).state_dict()
+    diff_names, count, gaps, steps = [], [], [], []
+    for k in names:
+        m, p = minted[k].reshape(-1).numpy(), portable[k].reshape(-1).numpy()
+        pos = np.flatnonzero(m != p)
+        if pos.size == 0:
+            continue
+        step = m[pos].view(np.int32).astype(np.int64) - p[pos].view(np.int32)
+        assert np.abs(step).max() <= 2 and np.array_equal(np.sign(m[pos]), np.sign(p[pos]))
+        gap = np.diff(pos, prepend=-1)
+        assert gap.max() < 65536
+        diff_names.append(k), count.append(pos.size), gaps.append(gap), steps.append(step)
+    gap, step = np.concatenate(gaps), np.concatenate(steps)
+    np.savez_compressed(os.path.join(ROOT, 'tests/golden', f'{name}_init.npz'), names=np.asarray(diff_names), count=np.asarray(count),
+                        gap_lo=(gap & 255).astype(np.uint8), gap_hi=(gap >> 8).astype(np.uint8), step=step.astype(np.int8))
+    print(f'[{name}_init] {gap.size:,} weights one or two ulps off the portable draw')
 
 
 SAMPLE_FULL_BELOW = 16384
@@ -511,7 +550,9 @@ def main():
     if only:      # e.g. `python oracle/make_golden.py lite_2x81 full_1x243` regenerates just those
         for name in only:
             {'pose_loss': pose_loss_fixture, 'loss_2d': loss_2d_fixture, 'actionnet': lambda: actionnet_fixture(DST), 'dropout': lambda: dropout_fixture(DST), 'augment': augment_fixture,
+             'seed0_lite': lambda: seeded(DST, 'lite', 256, 4), 'seed0_full': lambda: seeded(DST, 'full', 512, 2),
              'lite_2x81': lambda: baseline_shape(DST, 'lite_2x81', LITE_KW, 2, 81, None),
+             'lite_2x81_init': lambda: init_fixup('lite_2x81', LITE_KW),
              'full_1x243': lambda: baseline_shape(DST, 'full_1x243', FULL_KW, 1, 243, 5)}[name]()
         return
     tiny(DST, 'default')
@@ -520,6 +561,7 @@ def main():
     seeded(DST, 'full', 512, 2)
     baseline_shape(DST, 'lite_2x81', LITE_KW, 2, 81, None)
     baseline_shape(DST, 'full_1x243', FULL_KW, 1, 243, 5)
+    init_fixup('lite_2x81', LITE_KW)
     pose_loss_fixture()
     loss_2d_fixture()
     actionnet_fixture(DST)

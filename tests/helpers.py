@@ -1,4 +1,5 @@
 """Shared helpers for the test-suite (fixtures loading, model construction)."""
+import contextlib
 import os
 from functools import partial
 
@@ -20,6 +21,44 @@ def build_model(cfg, seed=None):
     if seed is not None:
         torch.manual_seed(seed)
     return DSTformer(norm_layer=partial(nn.LayerNorm, eps=1e-6), **cfg)
+
+
+@contextlib.contextmanager
+def portable_erfinv():
+    """Seeded initial weights that are the same on every host.  trunc_normal_ (DSTformer's weight init, ours and the reference's)
+    draws uniforms and maps them through Tensor.erfinv_, which torch hands to MKL's vector math: its last bit depends on the code
+    branch MKL picks for the host CPU (against the correctly rounded value: 0.7 % of the elements on MKL's AVX-512 branch, 0.015 %
+    on its AVX2 branch), so a fixture minted on one host does not match weights drawn on another.  Inside this context erfinv_ is
+    scipy's float64 erfinv rounded to the tensor's dtype, plain compiled code with no per-CPU branch.  seed0_*.npz are minted
+    inside it too (oracle/make_golden.py); for lite_2x81.npz see minted_weights()."""
+    from scipy.special import erfinv
+    orig = torch.Tensor.erfinv_
+
+    def erfinv_(self):
+        self.copy_(torch.from_numpy(erfinv(self.detach().cpu().double().numpy())))
+        return self
+    torch.Tensor.erfinv_ = erfinv_
+    try:
+        yield
+    finally:
+        torch.Tensor.erfinv_ = orig
+
+
+def minted_weights(model, name):
+    """Turn a portable_erfinv() seed-0 draw into the weights tests/golden/<name>.npz was minted with (torch's erfinv on MKL's
+    AVX-512 branch), bit for bit, from the differences stored in <name>_init.npz (oracle/make_golden.py: init_fixup)."""
+    z = np.load(os.path.join(GOLDEN, name + '_init.npz'))
+    gap = z['gap_lo'].astype(np.int64) + 256 * z['gap_hi'].astype(np.int64)
+    step = z['step'].astype(np.int32)
+    sd, at = model.state_dict(), 0
+    with torch.no_grad():
+        for k, n in zip(z['names'], z['count']):
+            bits = sd[str(k)].view(-1).view(torch.int32)      # (float32 bit patterns of the same storage)
+            pos = torch.from_numpy(np.cumsum(gap[at:at + n]) - 1)
+            bits[pos] += torch.from_numpy(step[at:at + n])
+            at += n
+    assert at == gap.size
+    return model
 
 
 def oracle_cfg(cfg):

@@ -56,9 +56,10 @@ def test_oracle_matches_reference_at_baseline_config0():
     reference's fp64 autograd stored in tests/golden/lite_2x81.npz (full gradients of the small tensors, a fixed
     4096-element sample of every large one, the l2 norm of all 260)."""
     import torch
-    from tests.helpers import build_model, trained_like
+    from tests.helpers import build_model, minted_weights, portable_erfinv, trained_like
     z, cfg = load_golden('lite_2x81')
-    model = build_model(cfg, seed=0)
+    with portable_erfinv():
+        model = minted_weights(build_model(cfg, seed=0), 'lite_2x81')
     if int(z['trained_seed']) >= 0:
         trained_like(model, int(z['trained_seed']))
     P = {k: v.detach().numpy().astype(np.float64) for k, v in model.state_dict().items()}

@@ -4,7 +4,7 @@
 # Every step writes gpurun_out/TAG_<step>.txt (merged back by gpurun) and prints its tail.  Steps:
 #   pytest[:EXPR]        python -m pytest tests -m gpu [-k EXPR]            (EXPR: pytest -k expression, '+' for spaces)
 #   file:PATH[:EXPR]     python -m pytest PATH [-k EXPR]
-#   bench[:ARGS]         python bench.py ARGS                                 (ARGS: '+' for spaces; default: --no-cpu-baseline)
+#   bench[:ARGS]         python bench.py ARGS                                 (ARGS: '+' for spaces; default: --full --no-cpu-baseline)
 #   block | fwd[:CLIPS]  the north-star Block benchmark / forward-only throughput (tools/fwd_bench.py)
 #   mlp[:CLIPS[:C]]      tools/mlp_time.py for the product library and every library in $VARIANTS (names under tools/variants/)
 #   mlpbench | gemm      tools/mlp_bench.py / tools/gemm_bench.py
@@ -22,6 +22,7 @@ n=0
 for step in "$@"; do
   n=$((n + 1)); kind=${step%%:*}; arg=""; [[ "$step" == *:* ]] && arg=${step#*:}
   echo "== [$TAG] $step"
+  [ "$kind" == bench ] && arg=${arg:---full+--no-cpu-baseline}      # without --full bench.py times the headline alone
   case $kind in
     env) export "$(sp "$arg")" ;;
     pytest) timeout 1700 python -m pytest tests -q -m gpu -p no:cacheprovider ${arg:+-k "$(sp "$arg")"} 2>&1 | out pytest$n 8 300 ;;
