@@ -96,25 +96,102 @@ __global__ __launch_bounds__(256) void rows_n_pack_many_kernel(const int64_t* __
     *reinterpret_cast<uint4*>(out + (size_t)frag * 512 + lane * 8) = *reinterpret_cast<const uint4*>(w + (size_t)(32 * nt + i) * K + 16 * kk + 8 * g);
 }
 
-// LDS-DMA with the LDS address as (wave-uniform register + compile-time constant): one scalar register for all ring positions instead of
-// one per position (the peeled last trip doubles their number, and an "s" operand that has been spilled to a VGPR does not assemble)
-__device__ __forceinline__ void rn_glds(const char* base, unsigned voff, unsigned lds_base, int slot_piece) {
-    switch (slot_piece) {      // ring slot * 8 + piece (an asm "n" operand must be a constant at parse time: the switch folds after unrolling)
-#define RG_(p_) case p_: asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff), "s"(base), "s"(lds_base), "n"(p_ * 4096) : "memory", "scc"); break;
-        RG_(0) RG_(1) RG_(2) RG_(3) RG_(4) RG_(5) RG_(6) RG_(7) RG_(8) RG_(9) RG_(10) RG_(11) RG_(12) RG_(13) RG_(14) RG_(15)
-        RG_(16) RG_(17) RG_(18) RG_(19) RG_(20) RG_(21) RG_(22) RG_(23) RG_(24) RG_(25) RG_(26) RG_(27) RG_(28) RG_(29) RG_(30) RG_(31)
-#undef RG_
-        default: break;
-    }
+// LDS-DMA with the LDS address as (wave-uniform register + compile-time constant SP * 4 KiB, SP = ring slot * 8 + piece): one scalar
+// register for all ring positions instead of one per position (the peeled last trip doubles their number, and an "s" operand that has
+// been spilled to a VGPR does not assemble)
+template <int SP> __device__ __forceinline__ void rn_glds(const char* base, unsigned voff, unsigned lds_base) {
+    asm volatile("s_add_u32 m0, %2, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(voff), "s"(base), "s"(lds_base), "n"(SP * 4096) : "memory", "scc");
 }
 template <int N> __device__ __forceinline__ void rn_vmwait() { asm volatile("s_waitcnt vmcnt(%0)" : : "n"(N) : "memory"); }
-// the same with a count that is known only after unrolling (an asm "n" operand must be a constant at parse time: the switch folds)
-__device__ __forceinline__ void rn_vmwait_n(int n) {
-    switch (n) {
-#define RW_(v_) case v_: asm volatile("s_waitcnt vmcnt(" #v_ ")" ::: "memory"); break;
-        RW_(8) RW_(10) RW_(16) RW_(17) RW_(18) RW_(19) RW_(20) RW_(21) RW_(22) RW_(23) RW_(24) RW_(25) RW_(26) RW_(32)
-#undef RW_
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;      // (a count the schedule does not produce: the strongest wait)
+// a token fragment: lane (i, g) = 16 bytes of row i at k = 16 s + 8 g, from a wave-uniform base (the k-step's byte offset added to it)
+// and the lane's 32-bit offset.  Ordered by the counted waits of the stream, not by the compiler (rn_product).
+__device__ __forceinline__ u32x4_t rn_tok(const char* base, unsigned voff) {
+    u32x4_t t;
+    asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(t) : "v"(voff), "s"(base) : "memory");
+    return t;
+}
+
+// ---- the product both kernels share: acc[nt][4 qq + e] = (the wave's 32 rows of `ap`) . (the packed weights)[row i][32 nt + 8 qq + 4 g + e],
+// K = 16 k-steps per trip of TRIP stages (K % 256 == 0).  Slot k of a stage: column tile k % NT, k-step k / NT of the stage's KPS.  Stage u
+// of a trip and slot k are template constants (static_for), so the token ring's indices, the ring offset of every LDS-DMA piece and every
+// counted wait are constants by construction.  The token fragments of k-step ks = KPS (u + LA) + j -- LA stages ahead, RnGeo -- are
+// requested in slot TS0 + 4 j of stage u: from this trip's rows while ks < 16, from the next trip's beyond (not in the LAST trip: a
+// register an asm load writes but nobody reads is dead to the compiler, which hands it to something else -- and the load lands in it later).
+// LAST trip, from slot 27 of stage TRIP - 4 on: the stream has no stage q + 4 / q + 3 left, and the ring slot such a piece would go to is
+// never read again.  Piece n < NPIECE of the EPILOGUE's input goes there instead -- same position in the in-order counter, so no counted
+// wait changes -- by tail(n, sp), n and the ring position sp = slot * 8 + piece as std::integral_constant; n = 0 .. 25 lands in the wave's
+// KiB of ring slot n >> 3, piece n & 7.  Past NPIECE the slot re-reads the last stage.  landed() runs once stage 0 has landed.
+template <int NT, int NPIECE, class Landed, class Tail>
+__device__ __forceinline__ void rn_product(f32x16_t (&acc)[NT], const char* ap, unsigned aoff, const char* wpk, const char* ring, unsigned dlu,
+                                           int K, Landed&& landed, Tail&& tail) {
+    constexpr int PF = 5, KPS = RnGeo<NT>::KPS, TRIP = RnGeo<NT>::TRIP, LA = RnGeo<NT>::LA, TS0 = RnGeo<NT>::TS0;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const unsigned fr = (unsigned)(uintptr_t)(const lds_void_t*)ring + lane * 16;
+    const unsigned wvo = wave * 1024 + lane * 16;
+    const int nstages = K / (16 * KPS);
+    // stage q of the stream (past the end: a harmless re-read of the last stage into a slot nobody reads again)
+    auto stage = [&](int q) { return wpk + (size_t)min(q, nstages - 1) * RN_STAGE; };
+    u32x4_t tok[16];                               // fragment s lives in tok[s & 15]
+    static_for<KPS * LA>([&](auto ks) __attribute__((always_inline)) { tok[ks] = rn_tok(ap + 32 * ks, aoff); });      // the first LA stages
+#pragma unroll
+    for (int q = 0; q < 3; ++q)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) glds16_s(stage(q) + j * 4096, wvo, dlu + q * RN_STAGE + j * 4096);
+    glds16_s(stage(3), wvo, dlu + 3 * RN_STAGE);
+    glds16_s(stage(3) + 4096, wvo, dlu + 3 * RN_STAGE + 4096);
+    static_for<NT>([&](auto t) __attribute__((always_inline)) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
+        asm volatile("" : "+a"(acc[t]));            // zeroed in the accumulator file while the first loads are in flight
+    });
+    rn_vmwait<18>();                               // stage 0 (and, older, the first tokens) has landed
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+    landed();
+    u32x4_t fb[8];
+    static_for<PF>([&](auto k) __attribute__((always_inline)) { fb[k] = lds_read16(fr, k * 1024); });
+    int q0 = 0;
+    auto trip = [&](auto last) __attribute__((always_inline)) {
+        constexpr bool LAST = decltype(last)::value;
+        static_for<TRIP>([&](auto u) __attribute__((always_inline)) {
+            constexpr int U = decltype(u)::value;
+            unsigned st = fr + (U & 3) * RN_STAGE, sn = fr + ((U + 1) & 3) * RN_STAGE;
+            asm volatile("" : "+v"(st), "+v"(sn));
+            const char* const n3 = stage(q0 + U + 3);
+            const char* const n4 = stage(q0 + U + 4);
+            static_for<32>([&](auto k) __attribute__((always_inline)) {
+                constexpr int S = decltype(k)::value;
+                if constexpr (S == 32 - PF) {
+                    rn_vmwait<rn_cnt(KPS, TRIP, LA, TS0, LAST, U)>();
+                    __builtin_amdgcn_sched_barrier(0);
+                    __builtin_amdgcn_s_barrier();
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if constexpr (S + PF < 32) fb[(S + PF) & 7] = lds_read16(st, (S + PF) * 1024);
+                else fb[(S + PF) & 7] = lds_read16(sn, (S + PF - 32) * 1024);
+                asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(acc[S % NT]) : "v"(fb[S & 7]), "v"(tok[(KPS * U + S / NT) & 15]));
+                if constexpr ((S & 3) == 3) {
+                    // weight piece P of stage q + 3 (slots 3 .. 23) or q + 4 (slots 27, 31) into ring position SP; in the LAST trip, where
+                    // that stage lies past the stream (N >= 0), the epilogue's piece N
+                    constexpr int AHEAD = S < 24 ? 3 : 4, P = S < 24 ? (S >> 2) + 2 : (S >> 2) - 6;
+                    constexpr int SP = ((U + AHEAD) & 3) * 8 + P, N = 8 * (U - (TRIP - AHEAD)) + P;
+                    if constexpr (LAST && N >= 0 && N < NPIECE) tail(std::integral_constant<int, N>{}, std::integral_constant<int, SP>{});
+                    else rn_glds<SP>((S < 24 ? n3 : n4) + P * 4096, wvo, dlu);
+                }
+                if constexpr ((S & 3) == 1 && S >= TS0 && S < TS0 + 4 * KPS) {
+                    constexpr int KS = (KPS * (U + LA) + (S - TS0) / 4) & 15;      // the ring index of the k-step this slot requests
+                    if constexpr (U + LA < TRIP) tok[KS] = rn_tok(ap + 32 * KS, aoff);
+                    else if constexpr (!LAST) tok[KS] = rn_tok(ap + 32 * KS + 512, aoff);      // the next trip's first k-steps
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            });
+        });
+        ap += 512;
+    };
+    if (!(MBX_RN_DBG & 2)) {
+        for (; q0 + TRIP < nstages; q0 += TRIP) trip(std::false_type{});
+        trip(std::true_type{});
     }
 }
 
@@ -122,8 +199,7 @@ template <int NT>
 __global__ __launch_bounds__(256, 1) void rows_n_lnbwd_kernel(const bf16_t* __restrict__ dy, const char* __restrict__ wpk,
                                                              const bf16_t* __restrict__ xhat, const float* __restrict__ rstd,
                                                              const bf16_t* __restrict__ dres_t, bf16_t* __restrict__ dx_t, int M, int K) {
-    constexpr int PF = 5;
-    constexpr int RN_N = RnGeo<NT>::N, KPS = RnGeo<NT>::KPS, TRIP = RnGeo<NT>::TRIP, NQ = RnGeo<NT>::NQ, LA = RnGeo<NT>::LA, TS0 = RnGeo<NT>::TS0;
+    constexpr int RN_N = RnGeo<NT>::N, NQ = RnGeo<NT>::NQ;
     extern __shared__ __attribute__((aligned(16))) char ring[];
 #ifdef MBX_RN_TRACE
     long long tsr[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -132,23 +208,17 @@ __global__ __launch_bounds__(256, 1) void rows_n_lnbwd_kernel(const bf16_t* __re
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = lane & 31, g = lane >> 5;
     const int mw = blockIdx.x * RN_BM + 32 * wave;
-    const unsigned fr = (unsigned)(uintptr_t)(const lds_void_t*)ring + lane * 16;
-    const unsigned wvo = wave * 1024 + lane * 16;
-    const unsigned dl = (unsigned)(uintptr_t)(const lds_void_t*)ring + wave * 1024;
-    const int nstages = K / (16 * KPS);
-    // stage q of the stream (past the end: a harmless re-read of the last stage into a slot nobody reads again)
-#define RN_ISSUE(q_, j_) glds16_s(wpk + (size_t)min((q_), nstages - 1) * RN_STAGE + (j_) * 4096, wvo, dl + ((q_) & 3) * RN_STAGE + (j_) * 4096)
-    // token fragments: lane (i, g) = 16 bytes of row i at k = 16 s + 8 g; rows past M repeat row M - 1 (their results are never stored)
+    const unsigned dlu = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(const lds_void_t*)ring + wave * 1024);      // the wave's KiB of a ring stage
+    // token fragments: rows past M repeat row M - 1 (their results are never stored)
     // (round 6: a wave-uniform 64-bit base that moves from trip to trip + ONE 32-bit lane offset, instead of two 64-bit lane pointers --
     // three registers for a loop that has none to spare; the C entries check M K 2 < 2^32)
-    const char* ap = reinterpret_cast<const char*>(dy);
     const unsigned aoff = ((unsigned)min(mw + i, M - 1) * (unsigned)K + 8u * g) * 2u;
     // xhat, the epilogue's first input, is requested DURING the loop, by LDS-DMA (round 6; round 5 loaded it into 128 registers in the
     // last trip and wrote them to LDS after the loop: 2 us per tile in situ, profiles/r06_rn_trace.txt).  Piece n = 8 j + r4 = rows
     // 4 r4 .. 4 r4 + 3 of quarter j (128 columns = 256 bytes per row); lane (xr, xp) fetches the 16-byte piece xp ^ (row & 15) of row
     // 4 r4 + xr, so that piece p of row r lands in slot p ^ (r & 15) of its row.  Pieces 26..31 (quarter 3, r4 = 2..7) go into the wave's
     // fifth buffer HERE -- the oldest vector memory operations of the kernel, so no counted wait below changes; pieces 0..25 take the 26
-    // slots of the last trip in which the stream has nothing left to fetch (RN_TRIP) and land in the wave's KiB of ring slot n >> 3,
+    // slots of the last trip in which the stream has nothing left to fetch (rn_product) and land in the wave's KiB of ring slot n >> 3,
     // piece n & 7 -- each freed by the barrier in front of the slot that refills it.
     const int xr = lane >> 4, xp = lane & 15;
     unsigned xoff[8];                              // byte offset of (row 4 r4 + xr, piece xp ^ (row & 15) of quarter 0) in xhat / dres / dx
@@ -159,86 +229,12 @@ __global__ __launch_bounds__(256, 1) void rows_n_lnbwd_kernel(const bf16_t* __re
 #pragma unroll
         for (int r4 = 2; r4 < 8; ++r4) glds16_s(reinterpret_cast<const char*>(xhat) + 3 * 256, xoff[r4], bdl0 + r4 * 1024);
     }
-#define RN_DP_OK(n_) ((n_) < 8 * NQ)               /* (past xhat's last piece the slot re-reads the last stage, as in round 5) */
-#define RN_DPIECE(n_, sp_) rn_glds(reinterpret_cast<const char*>(xhat) + ((n_) >> 3) * 256, xoff[(n_) & 7], dlu, sp_)
-    u32x4_t tok[16];                               // fragment s lives in tok[s & 15]
-// (the byte offset of the k-step goes into the scalar base -- two SALU instructions per load: inside a template an asm "n" operand is checked
-// at instantiation and must be a constant expression there, which an index of an unrolled loop is not)
-#define RN_TOK(dst_, off_) asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(dst_) : "v"(aoff), "s"(ap + (off_)) : "memory")
-#define RN_TOKN(dst_, off_) RN_TOK(dst_, (off_) + 512)      /* the tokens of the next trip's first half */
-#pragma unroll
-    for (int ks = 0; ks < KPS * LA; ++ks) RN_TOK(tok[ks], 32 * ks);        // the k-steps of the first LA stages
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) RN_ISSUE(q, j);
-    RN_ISSUE(3, 0);
-    RN_ISSUE(3, 1);
     f32x16_t acc[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
-        asm volatile("" : "+a"(acc[t]));            // zeroed in the accumulator file while the first loads are in flight
-    }
-    rn_vmwait<18>();                               // stage 0 (and, older, the first tokens) has landed
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    RN_TS(1);
-    u32x4_t fb[8];
-#pragma unroll
-    for (int k = 0; k < PF; ++k) fb[k] = lds_read16(fr, k * 1024);
-    // ---- the product: trips of TRIP stages = 16 k-steps (the token ring's indices are then static); K % 256 == 0.
-    // Slot k of a stage: column tile k % NT, k-step k / NT of the stage's KPS.  The token fragments of k-step ks = KPS (u + LA) + j -- LA
-    // stages ahead, RnGeo -- are requested in slot TS0 + 4 j of stage u: from this trip's rows while ks < 16, from the next trip's beyond
-    // (not in the LAST trip: a register an asm load writes but nobody reads is dead to the compiler, which hands it to something else --
-    // and the load lands in it later).
-    const unsigned dlu = __builtin_amdgcn_readfirstlane(dl);      // (wave-uniform by construction; said again for the "s" operands below)
-#define RN_KS(u_, k_) (KPS * ((u_) + LA) + ((k_) - TS0) / 4)      /* the k-step whose tokens slot k of stage u requests */
-#define RN_TRIP(LAST_, DP_)                                                                                                 \
-    {                                                                                                                \
-        _Pragma("unroll") for (int u = 0; u < TRIP; ++u) {                                                           \
-            const int q = q0 + u;                                                                                    \
-            unsigned st = fr + (u & 3) * RN_STAGE, sn = fr + ((u + 1) & 3) * RN_STAGE;                               \
-            asm volatile("" : "+v"(st), "+v"(sn));                                                                   \
-            const char* const n3 = wpk + (size_t)min(q + 3, nstages - 1) * RN_STAGE;                                 \
-            const char* const n4 = wpk + (size_t)min(q + 4, nstages - 1) * RN_STAGE;                                 \
-            _Pragma("unroll") for (int k = 0; k < 32; ++k) {                                                         \
-                if (k == 32 - PF) {                                                                                  \
-                    rn_vmwait_n(rn_cnt(KPS, TRIP, LA, TS0, LAST_, u));                                               \
-                    __builtin_amdgcn_sched_barrier(0);                                                               \
-                    __builtin_amdgcn_s_barrier();                                                                    \
-                    __builtin_amdgcn_sched_barrier(0);                                                               \
-                }                                                                                                    \
-                fb[(k + PF) & 7] = k + PF < 32 ? lds_read16(st, (k + PF) * 1024) : lds_read16(sn, (k + PF - 32) * 1024); \
-                asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(acc[k % NT]) : "v"(fb[k & 7]), "v"(tok[(KPS * u + k / NT) & 15])); \
-                if ((k & 3) == 3) {                                                                                  \
-                    /* LAST trip, from slot 27 of stage TRIP - 4 on: the stream has no stage q + 4 / q + 3 left, and the ring slot     \
-                       such a piece would go to is never read again (it used to be a re-read of the last stage, so that the wait     \
-                       counts stay constant).  DP_: piece n = 0..25 of the EPILOGUE's input goes there instead -- same position in   \
-                       the in-order counter, so no counted wait changes -- into the wave's KiB of ring slot n >> 3, piece n & 7 */     \
-                    if (LAST_ && DP_ && k < 24 && u >= TRIP - 3 && RN_DP_OK(8 * (u - (TRIP - 3)) + (k >> 2) + 2))                    \
-                        RN_DPIECE(8 * (u - (TRIP - 3)) + (k >> 2) + 2, ((u + 3) & 3) * 8 + (k >> 2) + 2);                            \
-                    else if (LAST_ && DP_ && k >= 24 && u >= TRIP - 4 && RN_DP_OK(8 * (u - (TRIP - 4)) + (k >> 2) - 6))              \
-                        RN_DPIECE(8 * (u - (TRIP - 4)) + (k >> 2) - 6, ((u + 4) & 3) * 8 + (k >> 2) - 6);                            \
-                    else if (k < 24) rn_glds(n3 + ((k >> 2) + 2) * 4096, wvo, dlu, ((u + 3) & 3) * 8 + (k >> 2) + 2);                \
-                    else rn_glds(n4 + ((k >> 2) - 6) * 4096, wvo, dlu, ((u + 4) & 3) * 8 + (k >> 2) - 6);                             \
-                }                                                                                                    \
-                if ((k & 3) == 1 && k >= TS0 && k < TS0 + 4 * KPS) {                                                 \
-                    if (u + LA < TRIP) RN_TOK(tok[RN_KS(u, k) & 15], 32 * (RN_KS(u, k) & 15));                       \
-                    else if (!LAST_) RN_TOKN(tok[RN_KS(u, k) & 15], 32 * (RN_KS(u, k) & 15));                        \
-                }                                                                                                    \
-                __builtin_amdgcn_sched_barrier(0);                                                                   \
-            }                                                                                                        \
-        }                                                                                                            \
-        ap += 512;                                                                                                   \
-    }
-    int q0 = 0;
-    if (!(MBX_RN_DBG & 2)) {
-        for (; q0 + TRIP < nstages; q0 += TRIP) RN_TRIP(false, false)
-        RN_TRIP(true, true)
-    }
+    // (pieces of xhat past its last -- NT = 8: 16 -- leave the slot to re-read the last stage, as in round 5)
+    rn_product<NT, 8 * NQ>(acc, reinterpret_cast<const char*>(dy), aoff, wpk, ring, dlu, K, [&]() __attribute__((always_inline)) { RN_TS(1); },
+                           [&](auto n, auto sp) __attribute__((always_inline)) {
+                               rn_glds<decltype(sp)::value>(reinterpret_cast<const char*>(xhat) + (n >> 3) * 256, xoff[n & 7], dlu);
+                           });
     RN_TS(2);
     // (no drain of the vector memory counter here: the pieces of xhat requested in the last stages are first-touch loads that are still
     // on their way; pass 1 below waits for them quarter by quarter, by count)
@@ -401,18 +397,12 @@ __global__ __launch_bounds__(256, 1) void rows_n_resid_ln_kernel(const bf16_t* _
                                                                 const float* __restrict__ bias, const float* __restrict__ resid,
                                                                 float* __restrict__ y, bf16_t* __restrict__ xhat_o,
                                                                 float* __restrict__ mean_o, float* __restrict__ rstd_o, float eps, int M, int K) {
-    constexpr int PF = 5;
-    constexpr int RN_N = RnGeo<NT>::N, KPS = RnGeo<NT>::KPS, TRIP = RnGeo<NT>::TRIP, NQ = RnGeo<NT>::NQ, LA = RnGeo<NT>::LA, TS0 = RnGeo<NT>::TS0;
+    constexpr int RN_N = RnGeo<NT>::N, NQ = RnGeo<NT>::NQ;
     extern __shared__ __attribute__((aligned(16))) char ring[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = lane & 31, g = lane >> 5;
     const int mw = blockIdx.x * RN_BM + 32 * wave;
-    const unsigned fr = (unsigned)(uintptr_t)(const lds_void_t*)ring + lane * 16;
-    const unsigned wvo = wave * 1024 + lane * 16;
-    const unsigned dl = (unsigned)(uintptr_t)(const lds_void_t*)ring + wave * 1024;
-    const unsigned dlu = __builtin_amdgcn_readfirstlane(dl);
-    const int nstages = K / (16 * KPS);
-    const char* ap = reinterpret_cast<const char*>(a);
+    const unsigned dlu = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(const lds_void_t*)ring + wave * 1024);
     const unsigned aoff = ((unsigned)min(mw + i, M - 1) * (unsigned)K + 8u * g) * 2u;
     // the wave's copy of the bias (8 floats per lane), requested first -- the oldest vector memory operations of the kernel, so no
     // counted wait below changes -- and parked in the wave's fifth buffer after the loop (the wait there carries the dependence)
@@ -422,29 +412,6 @@ __global__ __launch_bounds__(256, 1) void rows_n_resid_ln_kernel(const bf16_t* _
         asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(bq0) : "v"(bp) : "memory");
         asm volatile("global_load_dwordx4 %0, %1, off offset:16" : "=v"(bq1) : "v"(bp) : "memory");
     }
-    u32x4_t tok[16];
-#pragma unroll
-    for (int ks = 0; ks < KPS * LA; ++ks) RN_TOK(tok[ks], 32 * ks);        // the k-steps of the first LA stages
-#pragma unroll
-    for (int q = 0; q < 3; ++q)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) RN_ISSUE(q, j);
-    RN_ISSUE(3, 0);
-    RN_ISSUE(3, 1);
-    f32x16_t acc[NT];                              // acc[nt][4 qq + e] = out[row i][32 nt + 8 qq + 4 g + e]
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
-        asm volatile("" : "+a"(acc[t]));
-    }
-    rn_vmwait<18>();
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    u32x4_t fb[8];
-#pragma unroll
-    for (int k = 0; k < PF; ++k) fb[k] = lds_read16(fr, k * 1024);
     // (round 6) the 26 slots of the last trip in which the stream has nothing left to fetch request the first 26 KiB of the epilogue's
     // input: KiB m = 16 b + d = rows 2 d, 2 d + 1 of quarter b of resid (fp32, 128 columns = 512 bytes per row; lane l fetches the piece
     // that belongs in slot l & 31 of row 2 d + (l >> 5): piece (l & 31) ^ row), into the wave's KiB of ring slot m >> 3, piece m & 7 --
@@ -452,15 +419,11 @@ __global__ __launch_bounds__(256, 1) void rows_n_resid_ln_kernel(const bf16_t* _
     unsigned doff[16];                             // byte offset of (row 2 d + g, piece i ^ row of quarter 0) in resid and y
 #pragma unroll
     for (int d = 0; d < 16; ++d) doff[d] = (unsigned)min(mw + 2 * d + g, M - 1) * (RN_N * 4) + ((i ^ (2 * d + g)) << 4);
-#undef RN_DPIECE
-#undef RN_DP_OK
-#define RN_DP_OK(n_) true
-#define RN_DPIECE(n_, sp_) rn_glds(reinterpret_cast<const char*>(resid) + ((n_) >> 4) * 512, doff[(n_) & 15], dlu, sp_)
-    int q0 = 0;
-    if (!(MBX_RN_DBG & 2)) {
-        for (; q0 + TRIP < nstages; q0 += TRIP) RN_TRIP(false, false)
-        RN_TRIP(true, true)
-    }
+    f32x16_t acc[NT];                              // acc[nt][4 qq + e] = out[row i][32 nt + 8 qq + 4 g + e]
+    rn_product<NT, 16 * NQ>(acc, reinterpret_cast<const char*>(a), aoff, wpk, ring, dlu, K, [] {},
+                            [&](auto n, auto sp) __attribute__((always_inline)) {
+                                rn_glds<decltype(sp)::value>(reinterpret_cast<const char*>(resid) + (n >> 4) * 512, doff[n & 15], dlu);
+                            });
     // (no drain of the vector memory counter: the KiBs of resid requested in the last stages are still on their way; counted wait below.
     // The bias registers -- the oldest loads of the kernel, landed since the first counted wait of the loop -- take their data dependence here)
     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bq0), "+v"(bq1) : : "memory");
@@ -501,7 +464,7 @@ __global__ __launch_bounds__(256, 1) void rows_n_resid_ln_kernel(const bf16_t* _
     for (int j = 0; j < NQ; ++j) {
         // vector memory operations younger than the last DMA of quarter j, in issue order  R1' (6) | S0 (16) R2 (16) | S1 R3 | S2 | S3
         // (NT = 8: R1' | S0 | S1): the stores of quarter j - 1 and, if there is one, the DMA of quarter j + 1.  Quarter 0: waited for above
-        if (j >= 1) rn_vmwait_n(j + 1 < NQ ? 32 : 16);
+        if (j >= 1) { if (j + 1 < NQ) rn_vmwait<32>(); else rn_vmwait<16>(); }
         char* const rbj = rb_i + (j & 1) * 65536;
 #define RN_RRD(ntl_, qq_) (*reinterpret_cast<const float4*>(rbj + (((8 * (ntl_) + 2 * (qq_) + g_e) << 4) ^ sx)))
 #define RN_BRD(ntl_, qq_) (*reinterpret_cast<const float4*>(bx + (32 * (4 * j + (ntl_)) + 8 * (qq_) + 4 * g_e) * 4))

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <utility>
 #include "../../include/mbx.h"
 
 typedef uint16_t bf16_t;  // raw bfloat16 bits (the C ABI passes void*; T is chosen by `dtype`)
@@ -43,6 +44,16 @@ static inline int mbx_env_int(const char* name, int dflt) { const char* e = gete
 #else
 #define mbx_env_int(name, dflt) (dflt)
 #endif
+
+// ---------------------------------------------------------------- compile-time iteration
+// f(std::integral_constant<int, I>{}) for I = 0 .. N - 1, unrolled by the language rather than by LLVM's unroller (whose size limit
+// `#pragma unroll` silently gives up at): inside the body `constexpr int I = decltype(i)::value;` is a constant expression -- an asm "n"
+// operand, a template argument, an index that keeps a register array out of scratch.  The bodies must be inlined: mark lambdas
+// __attribute__((always_inline)) (an outlined body that takes register arrays by reference puts them in scratch).
+template <class F, int... I> __device__ __forceinline__ void static_for_seq(F& f, std::integer_sequence<int, I...>) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F> __device__ __forceinline__ void static_for(F&& f) { static_for_seq(f, std::make_integer_sequence<int, N>{}); }
 
 // ---------------------------------------------------------------- scalar conversions
 __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((uint32_t)v) << 16); }

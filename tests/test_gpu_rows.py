@@ -123,6 +123,13 @@ def test_rows_gemm_rejects_bad_shapes(ops):
         ops.rows_pack_nk(w)                                  # N % 64
 
 
+def _worst_row(got, ref):
+    """max over rows of |got - ref| / |ref|: a handful of wrong rows among 264,384 does not move a relative L2 over all of them (round 6:
+    a token fragment read before it had landed; the thresholds are those of tools/rows_soak.py)"""
+    g, r = got.float(), ref.float()
+    return float(((g - r).norm(dim=-1) / r.norm(dim=-1)).max())
+
+
 LNBWD_SHAPES = [(128, 512, 512), (4131, 1536, 512), (4131, 1024, 512), (70227, 1536, 512), (33, 512, 512), (2 * 243 * 17, 1024, 512), (129, 1536, 512),
                 (264384, 1024, 512), (300, 768, 512),
                 # dim_feat 256 (MotionBERT-Lite, round 6): dX of qkv (K = 768) and of fc1 (K = 1024), one-trip and ragged cases
@@ -146,6 +153,8 @@ def test_rows_lnbwd_t(ops, M, K, N):
     ref = torch.empty_like(out)
     MockOps().rows_lnbwd_t(dy, w, xhat, rstd, dres, ref)
     check(f'rows_lnbwd_t.{M}x{K}x{N}', out, ref, 4e-3)
+    worst = _worst_row(out, ref)
+    assert worst < 1.2e-2, f'rows_lnbwd_t.{M}x{K}x{N}: worst row {worst:.2e}'
     # the branch alone (dx - dres) against autograd through the plain normalisation of the same rows, with d(xhat) = dy . w^T in fp32:
     # the bf16 xhat the kernel reads differs from the exact one by its rounding, hence 1e-2
     if M <= 8192:
@@ -180,6 +189,9 @@ def test_rows_resid_ln(ops, M, K, N):
     for name, u, v, tol in zip(('y', 'xhat', 'mean', 'rstd'), g, r, (2e-6, 4e-3, 1e-5, 1e-5)):
         assert torch.isfinite(u.float()).all(), name
         check(f'rows_resid_ln.{name}.{tag}', u, v, tol)
+    for name, u, v, tol in zip(('y', 'xhat'), g, r, (1e-5, 1.2e-2)):
+        worst = _worst_row(u, v)
+        assert worst < tol, f'rows_resid_ln.{name}.{tag}: worst row {worst:.2e}'
     ops.gemm_nt(a, w, bias, EPI_RESID, resid=resid, out_f=o[0])
     ops.layernorm_fwd(o[0], None, None, 1e-6, o[1], o[2], o[3])
     check(f'rows_resid_ln.y_vs_tile_kernel.{tag}', g[0], o[0], 2e-6)

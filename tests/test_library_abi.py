@@ -74,9 +74,9 @@ def test_asm_prefetch_registers_are_left_alone(lib, tmp_path):
     MFMAs that consume them, ordered by the kernels' own counted waits.  To the compiler an asm output is valid where the statement
     stands: if register pressure made it copy, spill or reuse one of those registers before the data has landed, the copy would hold
     stale bits (round 5 found both failure modes in the epilogue of an earlier version; round 6 moved the last register prefetch of an
-    epilogue input -- xhat -- to LDS-DMA, which has no register side).  Checked on the disassembly of both kernels: the first instruction
-    that names a destination register of a token load after the load is an MFMA (never a copy, a spill or a VALU operation), and no
-    load of this form exists besides the token loads (8 in the preamble + 16 per trip, two trips in the code)."""
+    epilogue input -- xhat -- to LDS-DMA, which has no register side).  Checked on the disassembly of all four instantiations (16 and 8
+    column tiles per wave): the first instruction that names a destination register of a token load after the load is an MFMA (never a
+    copy, a spill or a VALU operation), and no load of this form exists besides the token loads (32 per kernel, see below)."""
     import re
     import shutil
     import subprocess
@@ -91,25 +91,25 @@ def test_asm_prefetch_registers_are_left_alone(lib, tmp_path):
     for o in [p for p in tmp_path.iterdir() if 'amdgcn' in p.name]:
         asm = subprocess.run([objdump, '-d', '--mcpu=gfx950', str(o)], check=True, capture_output=True, text=True).stdout
         for kern in ('rows_n_lnbwd_kernel', 'rows_n_resid_ln_kernel'):
-            m = re.search(r'^[0-9a-f]+ <_Z\d+' + kern + r'[^>]*>:\n(.*?)s_endpgm', asm, re.S | re.M)
-            if not m:
-                continue
-            seen += 1
-            lines = [l.split('//')[0] for l in m.group(1).split('\n')]
-            loads = []      # (line, registers) of global_load_dwordx4 vdst, voff, s[..]: the SGPR-base form only the token loads use
-            for n, l in enumerate(lines):
-                mm = re.search(r'global_load_dwordx4 v\[(\d+):(\d+)\], v\d+, s\[\d+:\d+\]', l)
-                if mm:
-                    loads.append((n, set(range(int(mm.group(1)), int(mm.group(2)) + 1))))
-            # 8 in the preamble, 16 in the ordinary trip, 8 in the peeled last trip (its second half has no next trip to fetch for)
-            assert len(loads) == 32, (kern, len(loads))
-            for n, regs in loads:
-                for k in range(n + 1, len(lines)):
-                    used = set()
-                    for mm in re.finditer(r'\bv\[(\d+):(\d+)\]|\bv(\d+)\b', lines[k]):
-                        used.update([int(mm.group(3))] if mm.group(3) else range(int(mm.group(1)), int(mm.group(2)) + 1))
-                    if used & regs:
-                        assert 'v_mfma' in lines[k], f'{kern}: "{lines[k].strip()}" touches the registers of the token load in line {n} before an MFMA read them'
-                        break
-    assert seen == 2, 'row-owner kernels not found in the device code'
+            for m in re.finditer(r'^[0-9a-f]+ <(_Z\d+' + kern + r'[^>]*)>:\n(.*?)s_endpgm', asm, re.S | re.M):
+                seen += 1
+                name = m.group(1)
+                lines = [l.split('//')[0] for l in m.group(2).split('\n')]
+                loads = []      # (line, registers) of global_load_dwordx4 vdst, voff, s[..]: the SGPR-base form only the token loads use
+                for n, l in enumerate(lines):
+                    mm = re.search(r'global_load_dwordx4 v\[(\d+):(\d+)\], v\d+, s\[\d+:\d+\]', l)
+                    if mm:
+                        loads.append((n, set(range(int(mm.group(1)), int(mm.group(2)) + 1))))
+                # 16 tiles: 8 in the preamble, 16 in the ordinary trip, 8 in the peeled last trip (its second half has no next trip to
+                # fetch for); 8 tiles: 12 + 16 + 4 (three stages ahead, four k-steps per stage)
+                assert len(loads) == 32, (name, len(loads))
+                for n, regs in loads:
+                    for k in range(n + 1, len(lines)):
+                        used = set()
+                        for mm in re.finditer(r'\bv\[(\d+):(\d+)\]|\bv(\d+)\b', lines[k]):
+                            used.update([int(mm.group(3))] if mm.group(3) else range(int(mm.group(1)), int(mm.group(2)) + 1))
+                        if used & regs:
+                            assert 'v_mfma' in lines[k], f'{name}: "{lines[k].strip()}" touches the registers of the token load in line {n} before an MFMA read them'
+                            break
+    assert seen == 4, 'row-owner kernels (two kernels x two geometries) not found in the device code'
 
