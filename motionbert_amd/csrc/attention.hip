@@ -30,7 +30,7 @@
 //   attn_bwd_fused_kernel<HD>             backward, bf16, 32 < L <= 256: ONE workgroup of 16 waves per problem, Q / K / V / dO
 //                                         staged once, dQ role (8 waves) and dK/dV role (8 waves) concurrently
 //   attn_bwd_dq_kernel / attn_bwd_dkv_kernel   backward, fp32 (tiles twice as large: the four of them do not fit one CU's
-//                                         LDS), and the A/B baseline of -DMBX_ATTN_BWD_TWO_KERNELS builds
+//                                         LDS), dropout, and bf16 beyond the fused kernel's 160 KiB of LDS
 // Outputs never leave a kernel in the accumulator layout (lane = row, 4 consecutive d per register quad: one store
 // instruction would touch 32 rows x 16 bytes).  They are staged through LDS tiles that are dead by then and copied out with
 // eight lanes per 128-byte row segment.
@@ -933,14 +933,11 @@ __global__ __launch_bounds__(1024, 1) void attn_bwd_fused_kernel(const bf16_t* _
     for (int a = 0; a < 2 * (HD / 32); ++a)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[a][r] = 0.f;
-#ifndef MBX_ATTN_SWAP
-#define MBX_ATTN_SWAP 1
-#endif
     // (round 6, measured null: s_setprio 1 around the S / dP clusters, and around all four MFMA clusters of an iteration -- 0.8638 ->
     // 0.8643 / 0.8743 ms; the re-cut "dQ then dV | dK" with every operand row in registers: 0.937 ms -- profiles/r06_attn_trace.txt)
     // which waves take which role: the SIMD issues oldest wave first, and the dK + dV role is the long one (16 MFMAs per 32 x 32 block
-    // against 12, its k / v operand rows re-read from LDS) -- it goes to the OLDER waves (A/B: -DMBX_ATTN_SWAP=0 is round 2's assignment)
-    const bool qrole = MBX_ATTN_SWAP ? wave >= 8 : wave < 8;
+    // against 12, its k / v operand rows re-read from LDS) -- it goes to the OLDER waves (round 2 gave it to waves 8-15)
+    const bool qrole = wave >= 8;
     const int blk = wave & 7, row = blk * 32 + (lane & 31);     // this lane's query (dQ role) or key (dK + dV role)
     if (blk < nfr && !(MBX_ATTN_DBG & 1)) {                       // L <= 256 (check_attn_args): at most eight 32-row blocks, one wave of each role per block
         if (qrole) {
@@ -1010,7 +1007,7 @@ __global__ __launch_bounds__(1024, 1) void attn_bwd_fused_kernel(const bf16_t* _
     int tid2 = threadIdx.x;
     asm volatile("" : "+v"(tid2));         // indices for the epilogue are re-derived here, not carried through the loops (128-VGPR budget)
     const int g2 = (tid2 >> 5) & 1, row2 = blk * 32 + (tid2 & 31);
-    const bool qrole2 = MBX_ATTN_SWAP ? wave >= 8 : wave < 8;
+    const bool qrole2 = wave >= 8;
     if (blk < nfr) {
         if (STATS) {        // each gradient row fragment goes over its own original, whose row dots it takes first
             float p1 = 0.f, p2 = 0.f;
@@ -1185,7 +1182,6 @@ static int attn_bwd_impl(const void* qkv, const void* o, const void* d_o, const 
     const int KP = ((L + 31) / 32) * 32;
     const bool shared = KP > 32;
     hipStream_t s = (hipStream_t)stream;
-#ifndef MBX_ATTN_BWD_TWO_KERNELS      // A/B builds only (tools/build_variants.py): force the dQ + dK/dV kernel pair
     if (shared && dtype == MBX_BF16 && !dr.thresh) {   // dropout: the dQ + dK/dV pair below (this kernel sits at its 128-VGPR budget: the mask hash spills)
         const size_t shm = (size_t)4 * KP * rm_stride<bf16_t>(hd) + 2 * KP * 4 + 3 * hd * 4;      // + the row-dot vectors (stats variant)
         if (shm <= 160 * 1024) {
@@ -1203,7 +1199,6 @@ static int attn_bwd_impl(const void* qkv, const void* o, const void* d_o, const 
 #undef MBX_BWD_FUSED
         }
     }
-#endif
     if (!shared) {
 #define MBX_BWD_SMALL2(TT, HDV, DR)                                                                                   \
     do {                                                                                                              \

@@ -1,36 +1,32 @@
-// MFMA GEMMs of the DSTformer hot path for gfx950 (94 % of the model's FLOPs).
+// fp32 MFMA GEMMs (precision 'fp32', the 1e-3 parity mode) and the C ABI entries mbx_gemm_nt / mbx_gemm_tn / mbx_gemm_*_x3,
+// which hand bf16 and bf16x3 to the kernels of gemm_pipe.hip.
 //
 //   gemm_nt :  acc[M,N] = A[M,K] . W[N,K]^T      every nn.Linear forward and every dX GEMM
 //   gemm_tn :  dW[N,K]  = dY[M,N]^T . A[M,K]     every weight gradient (contraction over the tokens)
 //
 // Both run the same inner product on a 128 x 128 output tile per 256-thread workgroup (4 waves in a
-// 2 x 2 grid, each wave 64 x 64 = 2 x 2 MFMA tiles of 32 x 32):
-//   bf16 : v_mfma_f32_32x32x16_bf16, 16-byte LDS fragment reads (8 bf16 along k per lane)
-//   fp32 : v_mfma_f32_32x32x2_f32,   8-byte LDS fragment reads (exact fp32, the 1e-3 parity mode)
+// 2 x 2 grid, each wave 64 x 64 = 2 x 2 MFMA tiles of 32 x 32) with v_mfma_f32_32x32x2_f32 and 8-byte
+// LDS fragment reads (exact fp32).
 // LDS holds two operand tiles of [128 rows][128 bytes] per stage (k contiguous in a row), double
 // buffered (64 KiB -> 2 workgroups per CU).  A row is eight 16-byte chunks; chunk c of row r lives
-// at physical chunk  c ^ ((r >> 1) & 7)  so that the 16-lane groups of ds_read_b128 hit 16 distinct
-// 16-byte slots of the 256-byte bank row (conflict-free fragment reads) and the 8-lane groups of
-// ds_write_b128 stay conflict-free as well.
+// at physical chunk  c ^ ((r >> 1) & 7)  so that the 8-lane groups of ds_write_b128 are conflict-free
+// (the 8-byte fragment reads are not: see gemm_tn_f32_kernel).
 // The MFMA is issued "transposed" (A-operand = the N-side tile, B-operand = the M-side tile) so
 // that a lane ends up holding 4 consecutive output columns of one output row: the fused epilogue
-// (bias / erf-GELU / residual add / tanh / GELU') then works on 16-byte (fp32) or 8-byte (bf16)
-// vectors straight from the accumulator registers.
+// (bias / erf-GELU / residual add / tanh / GELU') then works on 16-byte vectors straight from the
+// accumulator registers.
 // Workgroup -> tile order is XCD-aware: the 8 XCDs have private L2s and the dispatcher round-robins
 // consecutive workgroup ids over them, so ids are remapped to give each XCD a contiguous run of
 // tiles; consecutive tiles walk N first, i.e. they re-use the same A rows out of that XCD's L2.
-// gemm_tn transposes its operands on the way into LDS (8x8 bf16 / 4x4 fp32 register transposes, the
-// k-major token dimension becomes the contiguous one), splits the token dimension over workgroups
-// and leaves fp32 partial tiles that a deterministic column-sum folds (no atomics); the bias
-// gradient (column sums of dY) rides along in the staging registers.
+// gemm_tn transposes its operands on the way into LDS (4x4 register transposes, the k-major token
+// dimension becomes the contiguous one), splits the token dimension over workgroups and leaves fp32
+// partial tiles that a deterministic column-sum folds (no atomics); the bias gradient (column sums
+// of dY) rides along in the staging registers.  gemm_tn_f32_kernel, the one for multiples of 128,
+// needs no transposes at all.
 #include "mbx_common.h"
 #include "lds_stream.h"
-#include <stdlib.h>
 
-template <typename T> struct GemmT;
-template <> struct GemmT<bf16_t> { static constexpr int BK = 64, EPC = 8; };
-template <> struct GemmT<float>  { static constexpr int BK = 32, EPC = 4; };
-
+static constexpr int G_BK = 32, G_EPC = 4;   // k per stage, floats per 16-byte chunk
 static constexpr int G_BM = 128, G_BN = 128, G_ROWB = 128, G_TILEB = 128 * 128;  // bytes per operand tile
 
 __device__ __forceinline__ int lds_off(int row, int chunk) { return row * G_ROWB + ((chunk ^ ((row >> 1) & 7)) << 4); }
@@ -43,31 +39,7 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 
 // ---- one BK-deep step of the 64x64 wave tile out of LDS ------------------------------------------
 // sA: tile whose rows become accumulator ROWS (MFMA A operand), sB: rows become accumulator COLUMNS.
-template <typename T>
-__device__ __forceinline__ void wave_mma(const char* sA, const char* sB, int rowA0, int rowB0, int lane,
-                                         f32x16_t (&acc)[2][2]);
-template <>
-__device__ __forceinline__ void wave_mma<bf16_t>(const char* sA, const char* sB, int rowA0, int rowB0, int lane,
-                                                 f32x16_t (&acc)[2][2]) {
-    const int i = lane & 31, g = lane >> 5;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        bf16x8_t fa[2], fb[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            fa[t] = *reinterpret_cast<const bf16x8_t*>(sA + lds_off(rowA0 + t * 32 + i, 2 * s + g));
-            fb[t] = *reinterpret_cast<const bf16x8_t*>(sB + lds_off(rowB0 + t * 32 + i, 2 * s + g));
-        }
-#pragma unroll
-        for (int ta = 0; ta < 2; ++ta)
-#pragma unroll
-            for (int tb = 0; tb < 2; ++tb)
-                acc[ta][tb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[ta], fb[tb], acc[ta][tb], 0, 0, 0);
-    }
-}
-template <>
-__device__ __forceinline__ void wave_mma<float>(const char* sA, const char* sB, int rowA0, int rowB0, int lane,
-                                                f32x16_t (&acc)[2][2]) {
+__device__ __forceinline__ void wave_mma(const char* sA, const char* sB, int rowA0, int rowB0, int lane, f32x16_t (&acc)[2][2]) {
     const int i = lane & 31, g = lane >> 5;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
@@ -90,13 +62,13 @@ __device__ __forceinline__ void wave_mma<float>(const char* sA, const char* sB, 
 // ================================================================================================
 // gemm_nt
 // ================================================================================================
-template <typename T, int EPI>
-__global__ __launch_bounds__(256, 2) void gemm_nt_kernel(const T* __restrict__ A, const T* __restrict__ W,
-                                                         const float* __restrict__ bias, T* __restrict__ out_t,
-                                                         T* __restrict__ out2_t, float* __restrict__ out_f,
-                                                         const float* __restrict__ resid, const T* __restrict__ aux,
+template <int EPI>
+__global__ __launch_bounds__(256, 2) void gemm_nt_kernel(const float* __restrict__ A, const float* __restrict__ W,
+                                                         const float* __restrict__ bias, float* __restrict__ out_t,
+                                                         float* __restrict__ out2_t, float* __restrict__ out_f,
+                                                         const float* __restrict__ resid, const float* __restrict__ aux,
                                                          int M, int N, int K, int ntn) {
-    constexpr int BK = GemmT<T>::BK, EPC = GemmT<T>::EPC;
+    constexpr int BK = G_BK, EPC = G_EPC;
     __shared__ __attribute__((aligned(16))) char smem[4 * G_TILEB];  // [stage][A|W]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lid = xcd_remap(blockIdx.x, gridDim.x);
@@ -106,8 +78,8 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(const T* __restrict__ A
     // global -> register staging: 4 x 16 B per operand per thread; thread owns chunk `ch` of rows r0 + 32 i
     const int r0 = tid >> 3, ch = tid & 7;
     const int soff0 = lds_off(r0, ch);  // rows r0 + 32 i share the swizzle term: offset = soff0 + i * 32 * 128
-    const T* pa[4];
-    const T* pw[4];
+    const float* pa[4];
+    const float* pw[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         pa[i] = A + (size_t)min(m0 + r0 + 32 * i, M - 1) * K + ch * EPC;
@@ -156,7 +128,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(const T* __restrict__ A
         if (kt + 1 < nk) NT_GLOAD(kt + 1);
         const char* sa = smem + cur * 2 * G_TILEB;
         // accumulator rows <- W tile rows (n), accumulator columns <- A tile rows (m)
-        wave_mma<T>(sa + G_TILEB, sa, wn * 64, wm * 64, lane, acc);
+        wave_mma(sa + G_TILEB, sa, wn * 64, wm * 64, lane, acc);
         if (kt + 1 < nk) NT_SSTORE(cur ^ 1);
         __syncthreads();
     }
@@ -183,12 +155,12 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(const T* __restrict__ A
                 }
                 const size_t o = (size_t)m * N + n;
                 if (EPI == MBX_EPI_STORE) {
-                    store4<T>(out_t + o, v);
+                    store4<float>(out_t + o, v);
                 } else if (EPI == MBX_EPI_GELU) {
-                    if (out_t) store4<T>(out_t + o, v);   // pre-activation is only needed for backward
+                    if (out_t) store4<float>(out_t + o, v);   // pre-activation is only needed for backward
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = gelu_erf(v[e]);
-                    store4<T>(out2_t + o, v);
+                    store4<float>(out2_t + o, v);
                 } else if (EPI == MBX_EPI_RESID) {
                     float r[4];
                     load4<float>(resid + o, r);
@@ -201,10 +173,10 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(const T* __restrict__ A
                     store4<float>(out_f + o, v);
                 } else if (EPI == MBX_EPI_DGELU) {
                     float u[4];
-                    load4<T>(aux + o, u);
+                    load4<float>(aux + o, u);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] *= gelu_erf_grad(u[e]);
-                    store4<T>(out_t + o, v);
+                    store4<float>(out_t + o, v);
                 }
                 }
             }
@@ -212,15 +184,14 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(const T* __restrict__ A
     }
 }
 
-template <typename T>
 static int launch_gemm_nt(const void* a, const void* w, const float* bias, int epi, void* out_t, void* out2_t,
                           float* out_f, const float* resid, const void* aux, int M, int N, int K, hipStream_t s) {
     const int ntn = (N + G_BN - 1) / G_BN, ntm = (M + G_BM - 1) / G_BM;
     dim3 grid((unsigned)ntn * ntm), block(256);
 #define MBX_NT_CASE(E)                                                                                              \
     case E:                                                                                                         \
-        hipLaunchKernelGGL((gemm_nt_kernel<T, E>), grid, block, 0, s, (const T*)a, (const T*)w, bias, (T*)out_t,    \
-                           (T*)out2_t, out_f, resid, (const T*)aux, M, N, K, ntn);                                  \
+        hipLaunchKernelGGL((gemm_nt_kernel<E>), grid, block, 0, s, (const float*)a, (const float*)w, bias,          \
+                           (float*)out_t, (float*)out2_t, out_f, resid, (const float*)aux, M, N, K, ntn);           \
         break;
     switch (epi) {
         MBX_NT_CASE(MBX_EPI_STORE)
@@ -251,14 +222,12 @@ extern "C" int mbx_gemm_nt(const void* a, const void* w, const float* bias, int 
     }
     hipStream_t s = (hipStream_t)stream;
     if (dtype == MBX_BF16) {
-        MBX_CHECK_ARG(K % GemmT<bf16_t>::BK == 0, "gemm_nt(bf16): K=%d must be a multiple of 64", K);
-        if (!mbx_use_v1_gemm())
-            return mbx_launch_gemm_nt_pipe(a, w, bias, epilogue, out_t, out2_t, out_f, resid, aux_t, M, N, K, s);
-        return launch_gemm_nt<bf16_t>(a, w, bias, epilogue, out_t, out2_t, out_f, resid, aux_t, M, N, K, s);
+        MBX_CHECK_ARG(K % 64 == 0, "gemm_nt(bf16): K=%d must be a multiple of 64", K);
+        return mbx_launch_gemm_nt_pipe(a, w, bias, epilogue, out_t, out2_t, out_f, resid, aux_t, M, N, K, s);
     }
     if (dtype == MBX_F32) {
-        MBX_CHECK_ARG(K % GemmT<float>::BK == 0, "gemm_nt(f32): K=%d must be a multiple of 32", K);
-        return launch_gemm_nt<float>(a, w, bias, epilogue, out_t, out2_t, out_f, resid, aux_t, M, N, K, s);
+        MBX_CHECK_ARG(K % G_BK == 0, "gemm_nt(f32): K=%d must be a multiple of 32", K);
+        return launch_gemm_nt(a, w, bias, epilogue, out_t, out2_t, out_f, resid, aux_t, M, N, K, s);
     }
     return mbx_set_error("gemm_nt: unknown dtype %d", dtype);
 }
@@ -266,58 +235,30 @@ extern "C" int mbx_gemm_nt(const void* a, const void* w, const float* bias, int 
 // ================================================================================================
 // gemm_tn : dW[N,K] = dY[M,N]^T . A[M,K]
 // ================================================================================================
-// register transposes of one 16-byte-wide block: RB rows (tokens) x RB columns -> RB rows of RB tokens
-template <typename T> struct TBlock;
-template <> struct TBlock<bf16_t> {
-    static constexpr int RB = 8;
-    static __device__ __forceinline__ void transpose(const uint4 (&r)[8], uint4 (&o)[8]) {
-        const uint32_t* rw = reinterpret_cast<const uint32_t*>(r);  // rw[row*4 + d]: columns 2d (lo), 2d+1 (hi)
-        uint32_t* ow = reinterpret_cast<uint32_t*>(o);              // ow[col*4 + d]: rows 2d (lo), 2d+1 (hi)
+// register transposes of one 16-byte-wide block: 4 rows (tokens) x 4 columns -> 4 rows of 4 tokens
+static constexpr int TB_RB = 4;
+__device__ __forceinline__ void tblock_transpose(const uint4 (&r)[4], uint4 (&o)[4]) {
+    o[0] = make_uint4(r[0].x, r[1].x, r[2].x, r[3].x);
+    o[1] = make_uint4(r[0].y, r[1].y, r[2].y, r[3].y);
+    o[2] = make_uint4(r[0].z, r[1].z, r[2].z, r[3].z);
+    o[3] = make_uint4(r[0].w, r[1].w, r[2].w, r[3].w);
+}
+__device__ __forceinline__ void tblock_colsum(const uint4 (&r)[4], float (&s)[4]) {
 #pragma unroll
-        for (int c = 0; c < 8; ++c)
-#pragma unroll
-            for (int d = 0; d < 4; ++d) {
-                const uint32_t lo = rw[(2 * d) * 4 + (c >> 1)], hi = rw[(2 * d + 1) * 4 + (c >> 1)];
-                ow[c * 4 + d] = (c & 1) ? ((lo >> 16) | (hi & 0xffff0000u)) : ((lo & 0xffffu) | (hi << 16));
-            }
+    for (int row = 0; row < 4; ++row) {
+        s[0] += __uint_as_float(r[row].x); s[1] += __uint_as_float(r[row].y);
+        s[2] += __uint_as_float(r[row].z); s[3] += __uint_as_float(r[row].w);
     }
-    static __device__ __forceinline__ void colsum(const uint4 (&r)[8], float (&s)[8]) {
-        const uint32_t* rw = reinterpret_cast<const uint32_t*>(r);
-#pragma unroll
-        for (int row = 0; row < 8; ++row)
-#pragma unroll
-            for (int d = 0; d < 4; ++d) {
-                s[2 * d] += __uint_as_float(rw[row * 4 + d] << 16);
-                s[2 * d + 1] += __uint_as_float(rw[row * 4 + d] & 0xffff0000u);
-            }
-    }
-};
-template <> struct TBlock<float> {
-    static constexpr int RB = 4;
-    static __device__ __forceinline__ void transpose(const uint4 (&r)[4], uint4 (&o)[4]) {
-        o[0] = make_uint4(r[0].x, r[1].x, r[2].x, r[3].x);
-        o[1] = make_uint4(r[0].y, r[1].y, r[2].y, r[3].y);
-        o[2] = make_uint4(r[0].z, r[1].z, r[2].z, r[3].z);
-        o[3] = make_uint4(r[0].w, r[1].w, r[2].w, r[3].w);
-    }
-    static __device__ __forceinline__ void colsum(const uint4 (&r)[4], float (&s)[4]) {
-#pragma unroll
-        for (int row = 0; row < 4; ++row) {
-            s[0] += __uint_as_float(r[row].x); s[1] += __uint_as_float(r[row].y);
-            s[2] += __uint_as_float(r[row].z); s[3] += __uint_as_float(r[row].w);
-        }
-    }
-};
+}
 
 // part_w: [splits][N*K] fp32 partial tiles (or dW itself when splits == 1); part_b: [splits][N] or NULL
-template <typename T>
-__global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const T* __restrict__ dY, const T* __restrict__ A,
+__global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const float* __restrict__ dY, const float* __restrict__ A,
                                                          float* __restrict__ part_w, float* __restrict__ part_b, int M,
                                                          int N, int K, int ntk, int chunks_per_split) {
-    constexpr int RB = TBlock<T>::RB;
-    constexpr int BMS = 8 * RB;              // tokens per stage: 64 (bf16) / 32 (fp32) = 128 bytes per LDS row
+    constexpr int RB = TB_RB;
+    constexpr int BMS = 8 * RB;              // tokens per stage: 32 = 128 bytes per LDS row
     constexpr int NBLK = 8 * (128 / RB);     // RB x RB blocks per operand tile
-    constexpr int ITERS = 2 * NBLK / 256;    // blocks per thread per stage: 1 (bf16) / 2 (fp32)
+    constexpr int ITERS = 2 * NBLK / 256;    // blocks per thread per stage: 2
     __shared__ __attribute__((aligned(16))) char smem[4 * G_TILEB];  // [stage][dY^T | A^T]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int tile = blockIdx.x, split = blockIdx.y;
@@ -336,7 +277,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const T* __restrict__ d
 #pragma unroll
         for (int it = 0; it < ITERS; ++it) {
             const int blk = tid + 256 * it, op = blk / NBLK, b = blk % NBLK, mb = b & 7, nb = b >> 3;
-            const T* P = op ? A : dY;
+            const float* P = op ? A : dY;
             const int ld = op ? K : N, col = (op ? k0 : n0) + nb * RB;
             const int mrow = chunk * BMS + mb * RB;
 #pragma unroll
@@ -353,9 +294,9 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const T* __restrict__ d
 #pragma unroll
         for (int it = 0; it < ITERS; ++it) {
             const int blk = tid + 256 * it, op = blk / NBLK, b = blk % NBLK, mb = b & 7, nb = b >> 3;
-            if (want_db && op == 0) TBlock<T>::colsum(reg[it], bsum);
+            if (want_db && op == 0) tblock_colsum(reg[it], bsum);
             uint4 o[RB];
-            TBlock<T>::transpose(reg[it], o);
+            tblock_transpose(reg[it], o);
             char* dst = base + op * G_TILEB;
 #pragma unroll
             for (int j = 0; j < RB; ++j) *reinterpret_cast<uint4*>(dst + lds_off(nb * RB + j, mb)) = o[j];
@@ -380,7 +321,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const T* __restrict__ d
         if (c + 1 < c_end) gload(c + 1);
         const char* base = smem + cur * 2 * G_TILEB;
         // accumulator rows <- dY^T rows (n), accumulator columns <- A^T rows (k)
-        wave_mma<T>(base, base + G_TILEB, wr * 64, wc * 64, lane, acc);
+        wave_mma(base, base + G_TILEB, wr * 64, wc * 64, lane, acc);
         if (c + 1 < c_end) sstore(cur ^ 1);
         __syncthreads();
     }
@@ -408,7 +349,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const T* __restrict__ d
         for (int it = 0; it < ITERS; ++it) {
             const int blk = tid + 256 * it, op = blk / NBLK, b = blk % NBLK, mb = b & 7, nb = b >> 3;
             if (op == 0) {
-                // with ITERS == 2 (fp32) the first iteration is always op 0 and holds the whole sum
+                // with ITERS == 2 the first iteration is always op 0 and holds the whole sum
 #pragma unroll
                 for (int e = 0; e < RB; ++e) red[mb * 128 + nb * RB + e] = bsum[e];
             }
@@ -534,15 +475,12 @@ static int tn_splits(int M, int N, int K, int bms) {
     if (s < 1) s = 1;
     return s;
 }
-bool mbx_use_v1_gemm() {
-    static const bool v1 = mbx_env_int("MBX_GEMM_V1", 0) == 1;
-    return v1;
-}
+// one workspace serves both dtypes: the fp32 kernels' partials (both of them use tn_splits(..., 32)) and the bf16 pipe kernels'
 extern "C" size_t mbx_gemm_tn_ws(int M, int N, int K) {
-    const int s = tn_splits(M, N, K, 32);  // upper bound over both dtypes
-    const size_t v1 = ((size_t)s * N * K + (size_t)s * N) * sizeof(float) + 256;
-    const size_t v2 = mbx_gemm_tn_pipe_ws(M, N, K);
-    return v1 > v2 ? v1 : v2;
+    const int s = tn_splits(M, N, K, 32);
+    const size_t f32 = ((size_t)s * N * K + (size_t)s * N) * sizeof(float) + 256;
+    const size_t bf16 = mbx_gemm_tn_pipe_ws(M, N, K);
+    return f32 > bf16 ? f32 : bf16;
 }
 static int launch_gemm_tn_f32(const void* dy, const void* a, float* dw, float* db, int M, int N, int K, void* ws, hipStream_t s) {
     const int ntn = N / 128, ntk = K / 128;
@@ -561,16 +499,15 @@ static int launch_gemm_tn_f32(const void* dy, const void* a, float* dw, float* d
     }
     return 0;
 }
-template <typename T>
 static int launch_gemm_tn(const void* dy, const void* a, float* dw, float* db, int M, int N, int K, void* ws, hipStream_t s) {
-    constexpr int BMS = 8 * TBlock<T>::RB;
+    constexpr int BMS = 8 * TB_RB;
     const int ntn = (N + 127) / 128, ntk = (K + 127) / 128;
     const int splits = tn_splits(M, N, K, BMS);
     const int nchunks = (M + BMS - 1) / BMS;
     const int cps = (nchunks + splits - 1) / splits;
     float* part_w = splits == 1 ? dw : (float*)ws;
     float* part_b = db ? (splits == 1 ? db : (float*)ws + (size_t)splits * N * K) : nullptr;
-    hipLaunchKernelGGL((gemm_tn_kernel<T>), dim3(ntn * ntk, splits), dim3(256), 0, s, (const T*)dy, (const T*)a, part_w,
+    hipLaunchKernelGGL(gemm_tn_kernel, dim3(ntn * ntk, splits), dim3(256), 0, s, (const float*)dy, (const float*)a, part_w,
                        part_b, M, N, K, ntk, cps);
     MBX_LAUNCH_CHECK("gemm_tn");
     if (splits > 1) {
@@ -585,13 +522,10 @@ extern "C" int mbx_gemm_tn(const void* dy, const void* a, float* dw, float* db, 
     MBX_CHECK_ARG(M > 0 && N > 0 && K > 0 && N % 8 == 0 && K % 8 == 0, "gemm_tn: bad shape M=%d N=%d K=%d (N, K %% 8)", M, N, K);
     MBX_CHECK_ARG((size_t)N * K < ((size_t)1 << 31), "gemm_tn: output too large");
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == MBX_BF16) {
-        if (!mbx_use_v1_gemm()) return mbx_launch_gemm_tn_pipe(dy, a, dw, db, M, N, K, ws, s);
-        return launch_gemm_tn<bf16_t>(dy, a, dw, db, M, N, K, ws, s);
-    }
+    if (dtype == MBX_BF16) return mbx_launch_gemm_tn_pipe(dy, a, dw, db, M, N, K, ws, s);
     if (dtype == MBX_F32)
         return (N % 128 == 0 && K % 128 == 0 && M >= 4 * TF_BT) ? launch_gemm_tn_f32(dy, a, dw, db, M, N, K, ws, s)
-                                                               : launch_gemm_tn<float>(dy, a, dw, db, M, N, K, ws, s);
+                                                               : launch_gemm_tn(dy, a, dw, db, M, N, K, ws, s);
     return mbx_set_error("gemm_tn: unknown dtype %d", dtype);
 }
 

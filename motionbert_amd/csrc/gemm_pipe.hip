@@ -29,8 +29,7 @@
 // (never 0 inside a loop) keep two or three k-tiles in flight across the barriers.  Tile -> workgroup orders are XCD-aware
 // (xcd_remap2: the column tiles of a row block run on CUs that share an L2).
 // The product build has no switches: constants below that read like knobs are closed A/B experiments (numbers in DESIGN.md and
-// profiles/r0*_*.txt); ablation switches (`dbg`), cycle stamps and the round-1 lockstep loop exist in -DMBX_DIAG builds only
-// (tools/build_variants.py diag).
+// profiles/r0*_*.txt); ablation switches (`dbg`) and cycle stamps exist in -DMBX_DIAG builds only (tools/build_variants.py diag).
 #include "mbx_common.h"
 #include "gelu_fast.h"
 #include <stdlib.h>
@@ -370,7 +369,7 @@ constexpr int MBX_LNB_DEPTH = 2;
 }
 
 // ================================================================================================
-// gemm_nt_pipe256: 256 x 256 tile, 8 waves as 2 (M) x 4 (N), each wave 128 x 64 = 4 x 2 MFMA tiles
+// the 256 x 256 NT tile: 8 waves as 2 (M) x 4 (N), each wave 128 x 64 = 4 x 2 MFMA tiles
 // (6 LDS fragment reads per 8 MFMAs instead of 4 per 4), BK = 32, 4-stage ring of 32 KiB (three k-tiles
 // in flight), one workgroup per CU.  Versus the 256 x 128 kernel it moves 1/3 fewer bytes L2 -> LDS and
 // 1/4 fewer bytes LDS -> registers per FLOP; both paths showed up as the limiters of that kernel's loop.
@@ -378,12 +377,9 @@ constexpr int MBX_LNB_DEPTH = 2;
 static constexpr int Q_BM = 256, Q_BN = 256, Q_BK = 32;
 static constexpr int Q_A_BYTES = Q_BM * P_ROWB, Q_W_BYTES = Q_BN * P_ROWB, Q_STAGE = Q_A_BYTES + Q_W_BYTES;  // 32 KiB
 static constexpr int Q_NSTAGE = 4;
-#ifndef MBX_NT_PP_DEFAULT
-#define MBX_NT_PP_DEFAULT 1
-#endif
-#ifndef MBX_NT256_DEFAULT_MASK
-#define MBX_NT256_DEFAULT_MASK ((1 << MBX_EPI_STORE) | (1 << MBX_EPI_GELU) | (1 << MBX_EPI_TANH) | (1 << MBX_EPI_DGELU))
-#endif
+// the epilogues that run on the 256 x 256 kernel (one workgroup per CU) rather than on the 256 x 128 kernel (two per CU): bit e =
+// epilogue e.  Measured (tools/gemm_bench.py, M = 264k, profiles/): see the table in DESIGN.md.
+static constexpr int Q_EPI_MASK = (1 << MBX_EPI_STORE) | (1 << MBX_EPI_GELU) | (1 << MBX_EPI_TANH) | (1 << MBX_EPI_DGELU);
 
 // coalesced epilogue shared by the 256 x 256 kernels.  A wave owns 128 rows x (32 NTN) columns of the tile as
 // acc[tn][tm] (tn: 32-column block, tm: 32-row block; in the transposed MFMA orientation lane (i, g) holds
@@ -645,89 +641,10 @@ __device__ __forceinline__ void nt256_epilogue(f32x16_t (&acc)[2][4], char* smem
         nt_epilogue<EPI, 2, TO>(acc, er, bias, out_t, out2_t, out_f, resid, aux, M, N, row_base, col_base, lane);
 }
 
-#ifdef MBX_DIAG   // the lockstep loop of round 1: kept as the A/B baseline of diagnostic builds only (MBX_NT_PP=0)
-template <int EPI>
-__global__ __launch_bounds__(512, 2) void gemm_nt_pipe256_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ W,
-                                                                 const float* __restrict__ bias, bf16_t* __restrict__ out_t,
-                                                                 bf16_t* __restrict__ out2_t, float* __restrict__ out_f,
-                                                                 const float* __restrict__ resid, const bf16_t* __restrict__ aux,
-                                                                 int M, int N, int K, int ntn) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];  // 4 stages x 32 KiB
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lid = xcd_remap2(blockIdx.x, gridDim.x);
-    const int n0 = (lid % ntn) * Q_BN, m0 = (lid / ntn) * Q_BM;
-    const int wm = wave >> 2, wn = wave & 3;   // wave tile: rows [128 wm, +128), cols [64 wn, +64)
-
-    // LDS-DMA: one instruction = 16 rows x 64 B; wave w fills rows [32 w, 32 w + 32) of A and of W (2 + 2 instr)
-    const int lr = lane >> 2, lp = lane & 3;
-    const bf16_t* srcA[2];
-    const bf16_t* srcW[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int row = wave * 32 + i * 16 + lr;
-        const int sw = (lp ^ ((row >> 2) & 3)) << 3;
-        srcA[i] = A + (size_t)min(m0 + row, M - 1) * K + sw;
-        srcW[i] = W + (size_t)min(n0 + row, N - 1) * K + sw;
-    }
-    char* dstA = smem + wave * 32 * P_ROWB;
-    char* dstW = smem + Q_A_BYTES + wave * 32 * P_ROWB;
-
-    f32x16_t acc[2][4];   // [tn][tm]
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-
-    const int nk = K / Q_BK;
-#define Q_ISSUE(kt_, stage_)                                                           \
-    do {                                                                               \
-        const size_t ko_ = (size_t)(kt_) * Q_BK;                                       \
-        GLDS16(srcA[0] + ko_, dstA + (stage_) * Q_STAGE);                              \
-        GLDS16(srcA[1] + ko_, dstA + (stage_) * Q_STAGE + 1024);                       \
-        GLDS16(srcW[0] + ko_, dstW + (stage_) * Q_STAGE);                              \
-        GLDS16(srcW[1] + ko_, dstW + (stage_) * Q_STAGE + 1024);                       \
-    } while (0)
-
-    Q_ISSUE(0, 0);
-    if (nk > 1) Q_ISSUE(1, 1);
-    if (nk > 2) Q_ISSUE(2, 2);
-    const int i = lane & 31, g = lane >> 5;
-    int stage = 0;
-    for (int kt = 0; kt < nk; ++kt) {
-        const int ahead = nk - 1 - kt;                 // tiles issued after kt that may stay in flight (<= 2)
-        if (ahead >= 2) WAIT_VMCNT(8); else if (ahead == 1) WAIT_VMCNT(4); else WAIT_VMCNT(0);
-        __builtin_amdgcn_s_barrier();                  // tile kt landed for everyone; stage (kt+3)%4 is free
-        if (kt + 3 < nk) Q_ISSUE(kt + 3, (stage + 3) & 3);
-        const char* sA = smem + stage * Q_STAGE;
-        const char* sW = sA + Q_A_BYTES;
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            bf16x8_t fw[2], fa[4];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) fw[t] = *reinterpret_cast<const bf16x8_t*>(sW + sw_off(wn * 64 + t * 32 + i, 2 * s + g));
-#pragma unroll
-            for (int t = 0; t < 4; ++t) fa[t] = *reinterpret_cast<const bf16x8_t*>(sA + sw_off(wm * 128 + t * 32 + i, 2 * s + g));
-#pragma unroll
-            for (int tn = 0; tn < 2; ++tn)
-#pragma unroll
-                for (int tm = 0; tm < 4; ++tm)
-                    acc[tn][tm] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[tn], fa[tm], acc[tn][tm], 0, 0, 0);
-        }
-        stage = (stage + 1) & 3;
-    }
-#undef Q_ISSUE
-
-    nt256_epilogue<EPI>(acc, smem, bias, out_t, out2_t, out_f, resid, aux, M, N, m0, n0, wave, lane);
-}
-
-#endif
-
 // ================================================================================================
-// gemm_nt_pp256: the 256 x 256 tile / 8-wave layout / 4-stage LDS-DMA ring of gemm_nt_pipe256 with a PING-PONG schedule.
-// A 512-thread workgroup puts two waves on every SIMD (waves w and w + 4).  In gemm_nt_pipe256 the two run in lockstep:
-// after every barrier both read their fragments from the LDS at the same time (matrix pipe idle), then both queue MFMAs.
+// gemm_nt_pp256: the 256 x 256 tile / 8-wave layout / 4-stage LDS-DMA ring above with a PING-PONG schedule.
+// A 512-thread workgroup puts two waves on every SIMD (waves w and w + 4).  In the lockstep loop of round 1 the two read their
+// fragments from the LDS at the same time after every barrier (matrix pipe idle), then both queued MFMAs.
 // Here a k-tile is two phases, R = {12 ds_read_b128 of the wave's fragments for the whole k-tile} and M = {16 MFMAs from
 // those registers, with the 4 LDS-DMA issues of tile kt+3 spread between them}, one s_barrier after each phase, and the
 // waves 4-7 ("trailing group") run ONE phase behind waves 0-3: while one wave of a SIMD is in M the other is in R, so the
@@ -915,25 +832,13 @@ static int launch_nt256(const void* a, const void* w, const float* bias, int epi
     dim3 grid((unsigned)ntn * ntm), block(512);
     const size_t shm = Q_NSTAGE * Q_STAGE;
 #ifdef MBX_DIAG
-    static const int pp = mbx_env_int("MBX_NT_PP", MBX_NT_PP_DEFAULT);
-#define MBX_Q_LOCKSTEP(E)                                                                                             \
-        if (!pp) {                                                                                                    \
-            if (st_part != nullptr)                                                                                   \
-                return mbx_set_error("gemm_nt: the lockstep loop (MBX_NT_PP=0, diagnostic builds) has no row-dot epilogue"); \
-            if (set_lds_attr(gemm_nt_pipe256_kernel<E>, shm, "gemm_nt_pipe256")) return 1;                            \
-            hipLaunchKernelGGL((gemm_nt_pipe256_kernel<E>), grid, block, shm, s, (const bf16_t*)a, (const bf16_t*)w, bias, \
-                               (bf16_t*)out_t, (bf16_t*)out2_t, out_f, resid, (const bf16_t*)aux, M, N, K, ntn);      \
-            break;                                                                                                    \
-        }
     static long long* const pptrace = [] { const char* e = getenv("MBX_TRACE_BUF"); return e ? (long long*)strtoull(e, nullptr, 0) : (long long*)nullptr; }();
 #define MBX_Q_TRACE_ARG , pptrace
 #else
-#define MBX_Q_LOCKSTEP(E)
 #define MBX_Q_TRACE_ARG
 #endif
 #define MBX_Q_CASE(E)                                                                                                 \
     case E:                                                                                                           \
-        MBX_Q_LOCKSTEP(E)                                                                                             \
         if (set_lds_attr(gemm_nt_pp256_kernel<E>, shm, "gemm_nt_pp256")) return 1;                                    \
         hipLaunchKernelGGL((gemm_nt_pp256_kernel<E>), grid, block, shm, s, (const bf16_t*)a, (const bf16_t*)w,        \
                            (const bf16_t*)nullptr, (const bf16_t*)nullptr, bias,                                      \
@@ -951,7 +856,6 @@ static int launch_nt256(const void* a, const void* w, const float* bias, int epi
         default: return mbx_set_error("gemm_nt: unknown epilogue %d", epi);
     }
 #undef MBX_Q_CASE
-#undef MBX_Q_LOCKSTEP
 #undef MBX_Q_TRACE_ARG
     MBX_LAUNCH_CHECK("gemm_nt_pp256");
     return 0;
@@ -992,10 +896,7 @@ int mbx_launch_gemm_nt_x3(const void* a_hi, const void* a_lo, const void* w_hi, 
 
 int mbx_launch_gemm_nt_pipe(const void* a, const void* w, const float* bias, int epi, void* out_t, void* out2_t, float* out_f,
                             const float* resid, const void* aux, int M, int N, int K, hipStream_t s) {
-    // Which epilogues run on the 256 x 256 kernel (one workgroup per CU) rather than on the 256 x 128 kernel (two per CU):
-    // bit e = epilogue e.  Measured (tools/gemm_bench.py, M = 264k, profiles/): see the table in DESIGN.md.
-    static const int mask256 = mbx_env_int("MBX_NT256_MASK", MBX_NT256_DEFAULT_MASK);
-    if (((mask256 >> epi) & 1) && N >= 256) return launch_nt256(a, w, bias, epi, out_t, out2_t, out_f, resid, aux, M, N, K, s);
+    if (((Q_EPI_MASK >> epi) & 1) && N >= 256) return launch_nt256(a, w, bias, epi, out_t, out2_t, out_f, resid, aux, M, N, K, s);
     const int ntn = (N + P_BN - 1) / P_BN, ntm = (M + P_BM - 1) / P_BM;
     dim3 grid((unsigned)ntn * ntm), block(512);
     const size_t shm = P_NSTAGE * P_STAGE + (size_t)mbx_env_int("MBX_NTP_LDS_PAD", 0) * 1024;   // diagnostics: padding -> one workgroup per CU
@@ -1520,10 +1421,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_pipe256_kernel(const bf16_t* _
         }
 }
 
-static bool tn_use256(int N, int K) {
-    static const int en = mbx_env_int("MBX_TN256", 1);
-    return en && N >= 256 && K >= 256;
-}
+static bool tn_use256(int N, int K) { return N >= 256 && K >= 256; }
 static int tnp_splits(int M, int N, int K, bool x3 = false) {
     const bool big = tn_use256(N, K);
     const int tiles = big ? ((N + U_BN - 1) / U_BN) * ((K + U_BK - 1) / U_BK) : ((N + T_BN - 1) / T_BN) * ((K + T_BK - 1) / T_BK);

@@ -189,4 +189,3 @@ int mbx_launch_gemm_nt_x3(const void* a_hi, const void* a_lo, const void* w_hi, 
 size_t mbx_gemm_tn_x3_ws(int M, int N, int K);
 int mbx_launch_gemm_tn_x3(const void* dy_hi, const void* dy_lo, const void* a_hi, const void* a_lo, float* dw, float* db, int M, int N,
                           int K, void* ws, hipStream_t s);
-bool mbx_use_v1_gemm();   // MBX_GEMM_V1=1 selects the simple double-buffered kernels of gemm.hip (A/B testing)

@@ -48,14 +48,10 @@
 #ifndef MBX_MLP_DBG
 #define MBX_MLP_DBG 0
 #endif
-// A/B: cache policy of the tile's one-touch activation traffic.  bit 0: non-temporal stores of y in the epilogue; bit 1: non-temporal
-// LDS-DMA loads of o and the residual rows in the prologue.  (The weight stream, 2.5 MiB that all 32 CUs of an XCD re-read every
-// tile, competes with ~20 MiB of activations per tile period for the 4 MiB L2.)
-// Measured in three sessions (profiles/r05_mlp_variants.txt): both bits -1.6 / -2.7 / -2.2 %, either bit alone within noise -> 3.
-#ifndef MBX_MLP_NT
-#define MBX_MLP_NT 3
-#endif
-#define MF_GLDS_ACT(src_, dst_) do { if (MBX_MLP_NT & 2) glds16_nt((src_), (dst_)); else GLDS16((src_), (dst_)); } while (0)
+// The tile's one-touch activation traffic is non-temporal: the stores of y in the epilogue and the LDS-DMA loads of o and the residual
+// rows in the prologue.  (The weight stream, 2.5 MiB that all 32 CUs of an XCD re-read every tile, competes with ~20 MiB of
+// activations per tile period for the 4 MiB L2.)  Measured in three sessions (profiles/r05_mlp_variants.txt): -1.6 / -2.7 / -2.2 %
+// with both, either alone within noise.
 static constexpr int F_BM = 128;               // token rows per workgroup of the throughput shape (4 waves x 32)
 static constexpr int F_STAGE = 32 * 1024;      // one ring stage = 32 fragments of 1 KiB
 static constexpr int F_RING = 4 * F_STAGE;     // 128 KiB
@@ -154,10 +150,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_kernel(const bf16_t* __restr
     constexpr int GSTEPS = 2 / S2;         // GELU micro-steps per fc2 slot (64 per chunk over S2 * 32 slots)
     constexpr int XL = C == 512 ? 4 : 0;   // the last XL fragments of X are kept in LDS and visit registers only around their use (the
                                            // second fc1 stage): the GELU stages, where every VGPR is spoken for, do not carry them
-#ifndef MBX_MLP_PF
-#define MBX_MLP_PF 5
-#endif
-    constexpr int PF = MBX_MLP_PF;         // weight fragments in flight ahead of the MFMA that consumes them (<= 7)
+    constexpr int PF = 5;                  // weight fragments in flight ahead of the MFMA that consumes them (<= 7)
     extern __shared__ __attribute__((aligned(16))) char smem[];   // ring 128 KiB | b1 [hidden] | rsum [hidden] | b2 [C] | XL KiB per wave
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int i = lane & 31, g = lane >> 5;
@@ -196,10 +189,6 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_kernel(const bf16_t* __restr
     float ln_rs = 1.f, ln_k = 0.f;
     f32x16_t acc2[NT2];
     float xsh = 0.f, xs1 = 0.f, xs2 = 0.f;         // from_x: shifted sums over this lane's half row
-#ifndef MBX_MLP_PRO_PIPE
-#define MBX_MLP_PRO_PIPE 1
-#endif
-#if MBX_MLP_PRO_PIPE
     // ---- (round 5) the tile's inputs arrive as a PIPELINE of 16-KiB jobs through two buffers (the halves of the wave's 32 KiB of the
     // ring, which is idle until the weight stream starts): o in column halves (-> X fragments), then the residual rows in quarters of
     // 128 columns (-> four accumulator tiles each, which START from residual + bias so that the epilogue only writes; from_x: also
@@ -220,14 +209,14 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_kernel(const bf16_t* __restr
             for (int jj = 0; jj < 16; ++jj) {
                 const int rb = jj & 3, cs = 4 * h + (jj >> 2);
                 const int row = min(mw + 8 * rb + xr, M - 1);
-                MF_GLDS_ACT(xh + (size_t)row * C + cs * 64 + ((xp ^ x_swz(xr, rb)) << 3), buf + jj * 1024);
+                glds16_nt(xh + (size_t)row * C + cs * 64 + ((xp ^ x_swz(xr, rb)) << 3), buf + jj * 1024);
             }
         };
         auto issue_q = [&](int q, char* buf) {
 #pragma unroll
             for (int r2 = 0; r2 < 16; ++r2) {
                 const int rl = 2 * r2 + (lane >> 5), p = lane & 31;
-                MF_GLDS_ACT(resid + (size_t)min(mw + rl, M - 1) * C + q * 128 + ((p ^ (rl & 15)) << 2), buf + r2 * 1024);
+                glds16_nt(resid + (size_t)min(mw + rl, M - 1) * C + q * 128 + ((p ^ (rl & 15)) << 2), buf + r2 * 1024);
             }
         };
         auto read_o = [&](int h, const char* buf) {
@@ -308,89 +297,6 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_kernel(const bf16_t* __restr
             ln_k = -ln_rs * mu;
         }
     }
-#else
-    if (!from_x) {
-        // the wave's 32 rows of xh -> LDS (wave-private image, whole 128-byte lines per DMA) -> operand fragments
-        char* const ximg = ring + wave * (64 * C);
-        const int xr = lane >> 3, xp = lane & 7;
-#pragma unroll 4
-        for (int j = 0; j < KS; ++j) {             // one instruction = 8 rows x 128 B: row group rb = j & 3, column segment j >> 2
-            const int rb = j & 3, cs = j >> 2;
-            const int row = min(mw + 8 * rb + xr, M - 1);
-            MF_GLDS_ACT(xh + (size_t)row * C + cs * 64 + ((xp ^ x_swz(xr, rb)) << 3), ximg + j * 1024);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int s = 0; s < KS; ++s) {
-            const int rb = i >> 3, r = i & 7, p = 2 * (s & 3) + g;
-            X[s] = *reinterpret_cast<const u32x4_t*>(ximg + ((s >> 2) * 4 + rb) * 1024 + r * 128 + ((p ^ x_swz(r, rb)) << 4));
-        }
-        if (raw_in && !PROJ) {                     // wave-uniform (PROJ: the operand of fc1 and its statistics come from the proj product)
-            float sa = 0.f, sb = 0.f, qa = 0.f, qb = 0.f;
-#pragma unroll
-            for (int s = 0; s < KS; ++s) {
-                sa = dot2_bf16(X[s][0], 0x3f803f80u, sa); qa = dot2_bf16(X[s][0], X[s][0], qa);
-                sb = dot2_bf16(X[s][1], 0x3f803f80u, sb); qb = dot2_bf16(X[s][1], X[s][1], qb);
-                sa = dot2_bf16(X[s][2], 0x3f803f80u, sa); qa = dot2_bf16(X[s][2], X[s][2], qa);
-                sb = dot2_bf16(X[s][3], 0x3f803f80u, sb); qb = dot2_bf16(X[s][3], X[s][3], qb);
-            }
-            const float st = wave_halves<WaveAdd>(sa + sb), qt = wave_halves<WaveAdd>(qa + qb);
-            const float mu = st * (1.0f / (float)C);
-            ln_rs = 1.0f / sqrtf(fmaxf(qt * (1.0f / (float)C) - mu * mu, 0.f) + eps);
-            ln_k = -ln_rs * mu;
-        }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    MF_TS(1);
-    __builtin_amdgcn_s_barrier();                  // the biases are in LDS
-    MF_TS(2);
-
-    // ---- the fc2 accumulators start from residual + bias: y = x + b2 + G . W2^T is then what the MFMAs leave, and the epilogue
-    // only writes.  Per 256-column half the wave's 32 residual rows arrive in its LDS image by LDS-DMA (one instruction = one row's
-    // KiB; 16-byte piece p of row r at p ^ (r & 15), applied to the source address: conflict-free in the accumulator layout -- lane
-    // (i, g): row i, piece 8 ntl + 2 qq + g --, in the operand-fragment layout -- row i, pieces 4 s + 2 g, + 1 -- and row-major), and
-    // each lane takes its accumulator registers from it; from_x: also its operand fragments and its half of the row's statistics.
-    char* const er = ring + wave * 32768;
-#pragma unroll
-    for (int hh = 0; hh < NH; ++hh) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // the image's previous readers (X fragments / first half) are done
-#pragma unroll 4
-        for (int r = 0; r < 32; ++r)
-            MF_GLDS_ACT(resid + (size_t)min(mw + r, M - 1) * C + hh * 256 + ((lane ^ (r & 15)) << 2), er + r * 1024);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int ntl = 0; ntl < 8; ++ntl) {
-            const int nt = hh * 8 + ntl;
-            f32x16_t t;
-#pragma unroll
-            for (int qq = 0; qq < 4; ++qq) {
-                const float4 bb = *reinterpret_cast<const float4*>((PROJ ? bps : b2s) + nt * 32 + 8 * qq + 4 * g);   // (PROJ: bp + b2)
-                const float4 xv = *reinterpret_cast<const float4*>(er + i * 1024 + (((ntl * 8 + 2 * qq + g) ^ (i & 15)) << 4));
-                t[4 * qq] = xv.x + bb.x; t[4 * qq + 1] = xv.y + bb.y; t[4 * qq + 2] = xv.z + bb.z; t[4 * qq + 3] = xv.w + bb.w;
-                if (from_x) {
-                    if (hh == 0 && ntl == 0 && qq == 0) xsh = wave_lower_half(xv.x);      // x[row][0] for both half rows (see below)
-                    const float d0 = xv.x - xsh, d1 = xv.y - xsh, d2 = xv.z - xsh, d3 = xv.w - xsh;
-                    xs1 += (d0 + d1) + (d2 + d3);
-                    xs2 = fmaf(d0, d0, fmaf(d1, d1, fmaf(d2, d2, fmaf(d3, d3, xs2))));
-                }
-            }
-            acc2[nt] = t;
-            asm volatile("s_nop 1" : "+a"(acc2[nt]));             // a whole tile at a time into accumulator registers, where it stays
-        }
-        MF_TS(3 + hh);
-        if (from_x) {
-#pragma unroll
-            for (int sl = 0; sl < 16; ++sl) {                     // k-steps 16 hh + sl: eight consecutive channels of row i per lane
-                const float4 lo = *reinterpret_cast<const float4*>(er + i * 1024 + (((4 * sl + 2 * g) ^ (i & 15)) << 4));
-                const float4 hi = *reinterpret_cast<const float4*>(er + i * 1024 + (((4 * sl + 2 * g + 1) ^ (i & 15)) << 4));
-                // operand = bf16(x - x[row][0]): LayerNorm does not see the shift, and the rounding error then scales with the spread of
-                // the row, not with its magnitude (gemm_rows.hip, FROMX)
-                X[hh * 16 + sl] = u32x4_t{pack_bf2(lo.x - xsh, lo.y - xsh), pack_bf2(lo.z - xsh, lo.w - xsh), pack_bf2(hi.x - xsh, hi.y - xsh),
-                                          pack_bf2(hi.z - xsh, hi.w - xsh)};
-            }
-        }
-    }
-#endif
     if (from_x) {                                  // the row statistics: this lane's half and the partner lane's (lane ^ 32), Chan's formula
         constexpr float nh = (float)(C / 2);
         const float mean_h = xsh + xs1 / nh, m2_h = xs2 - xs1 * xs1 / nh;
@@ -441,18 +347,14 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_kernel(const bf16_t* __restr
     u32x4_t xl[XL > 0 ? XL : 1];                                // the LDS-resident fragments of X, in registers during the second fc1 stage only
     const unsigned fr = (unsigned)(uintptr_t)(const lds_void_t*)ring + lane * 16;   // fragment f of ring slot s: fr + s * F_STAGE + f * 1024
 
-    // Ring schedule (round 5, MBX_MLP_RING_DEEP = 1): the barrier of stage q sits in front of slot 32 - PF = 27 -- the first slot that reads
+    // Ring schedule (round 5): the barrier of stage q sits in front of slot 32 - PF = 27 -- the first slot that reads
     // a fragment of stage q + 1, and the first at which EVERY wave has issued its last read of stage q's buffer (slot 26) -- so that
     // buffer is refilled right away with stage q + 4 (pieces 0, 1 in slots 27 and 31, pieces 2..7 in slots 3..23 of the next stage):
     // three stages (96 KiB) of the stream are in flight and the last-issued piece of a stage has two stage times to land.  Round 4 put
     // the barrier at slot 24 and refilled the buffer of stage q - 1 there, which had been idle for 29 slots by then: one and a half
     // stages in flight, ONE stage time for the last piece -- and a stage took as long as that piece's latency (0.76 us in situ for
     // 32 MFMAs = 0.5 us, with or without the GELU beside them: profiles/r05_mlp_trace_stages.txt).
-#ifndef MBX_MLP_RING_DEEP
-#define MBX_MLP_RING_DEEP 1
-#endif
-    constexpr int RD = MBX_MLP_RING_DEEP ? 1 : 0;               // extra stages of run-ahead
-    constexpr int SYNC_SLOT = RD ? 32 - PF : 24;
+    constexpr int SYNC_SLOT = 32 - PF;
     int q = 0;                                                  // stage sequence number
     {
         const char* const s0 = wpk + seq_off(0);
@@ -463,17 +365,12 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_kernel(const bf16_t* __restr
         for (int d = 0; d < 8; ++d) MF_ISSUE1(s0, 0, d);
 #pragma unroll
         for (int d = 0; d < 8; ++d) MF_ISSUE1(s1, 1, d);
-        if (RD) {
 #pragma unroll
-            for (int d = 0; d < 8; ++d) MF_ISSUE1(s2, 2, d);
-            MF_ISSUE1(s3, 3, 0);
-            MF_ISSUE1(s3, 3, 1);
-        } else {
-            MF_ISSUE1(s2, 2, 0);
-            MF_ISSUE1(s2, 2, 1);
-        }
+        for (int d = 0; d < 8; ++d) MF_ISSUE1(s2, 2, d);
+        MF_ISSUE1(s3, 3, 0);
+        MF_ISSUE1(s3, 3, 1);
     }
-    if (RD) MF_SYNC(18); else MF_SYNC(10);                      // stage 0 is in LDS (younger: stages 1 [, 2] and two pieces)
+    MF_SYNC(18);                                                // stage 0 is in LDS (younger: stages 1, 2 and two pieces)
     MF_TS(6);
 #pragma unroll
     for (int k = 0; k < PF; ++k) fb[k] = lds_read16(fr, k * 1024);
@@ -485,15 +382,15 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_kernel(const bf16_t* __restr
     if (!(MBX_MLP_DBG & 64)) do {                                                                                    \
         unsigned st_ = fr + (q & 3) * F_STAGE, sn_ = fr + ((q + 1) & 3) * F_STAGE;                                   \
         asm volatile("" : "+v"(st_), "+v"(sn_));                                                                     \
-        const char* const n2_ = wpk + seq_off(q + 2 + RD);                                                           \
-        const char* const n3_ = wpk + seq_off(q + 3 + RD);                                                           \
-        const int l2_ = (q + 2 + RD) & 3, l3_ = (q + 3 + RD) & 3;                                                    \
+        const char* const n3_ = wpk + seq_off(q + 3);                                                                \
+        const char* const n4_ = wpk + seq_off(q + 4);                                                                \
+        const int l3_ = (q + 3) & 3, l4_ = (q + 4) & 3;                                                              \
         _Pragma("unroll") for (int k_ = 0; k_ < 32; ++k_) {                                                          \
-            if (k_ == SYNC_SLOT && !(MBX_MLP_DBG & 32)) { if (RD) MF_SYNC(16); else MF_SYNC(8); }                    \
+            if (k_ == SYNC_SLOT && !(MBX_MLP_DBG & 32)) MF_SYNC(16);                                                 \
             if (!(MBX_MLP_DBG & 4))                                                                                  \
                 fb[(k_ + PF) & 7] = k_ + PF < 32 ? lds_read16(st_, (k_ + PF) * 1024) : lds_read16(sn_, (k_ + PF - 32) * 1024); \
             if (!(MBX_MLP_DBG & 16) || (k_ & 15) == 0) MMA_(k_, fb[k_ & 7]);                                         \
-            if ((k_ & 3) == 3 && !(MBX_MLP_DBG & 2)) { if (k_ < 24) MF_ISSUE1(n2_, l2_, (k_ >> 2) + 2); else MF_ISSUE1(n3_, l3_, (k_ >> 2) - 6); } \
+            if ((k_ & 3) == 3 && !(MBX_MLP_DBG & 2)) { if (k_ < 24) MF_ISSUE1(n3_, l3_, (k_ >> 2) + 2); else MF_ISSUE1(n4_, l4_, (k_ >> 2) - 6); } \
             if (!(MBX_MLP_DBG & 1)) HOOK_(k_);                                                                       \
             __builtin_amdgcn_sched_barrier(0);                                                                       \
         }                                                                                                            \
@@ -503,22 +400,15 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_kernel(const bf16_t* __restr
     // ---- GELU of acc1 (+ bias) -> the next generation of G, as 64 micro-steps of ~7 VALU operations: pair j = 0..15 (two accumulator registers), four
     // steps per pair (A&S 7.1.28 as in gelu_fast2: polynomial / polynomial + reciprocal / r^16 / combine + pack).  Pair j: column
     // half tn = j >> 3, register quad qq = (j >> 1) & 3, registers 4 qq + 2 (j & 1) + {0, 1}.
-    mbx_f32x2_t ge_u, ge_a, ge_d;
     float2 ge_b = make_float2(0.f, 0.f), ge_r = make_float2(0.f, 0.f);   // bias / rsum of the next pair, read right after the current pair took its own
     int gc = 0;                                                 // chunk whose GELU runs (bias index)
 #define GE_BIAS(j_) ge_bias_ld(smem + F_RING + 16 * g + (gc * F_CH + ((j_) >> 3) * 32 + 8 * (((j_) >> 1) & 3) + 2 * ((j_) & 1)) * 4)
 #define GE_RSUM(j_) ge_bias_ld(smem + F_RING + 4 * hidden + 16 * g + (gc * F_CH + ((j_) >> 3) * 32 + 8 * (((j_) >> 1) & 3) + 2 * ((j_) & 1)) * 4)
 #define GE_LOAD(j_) do { ge_b = GE_BIAS(j_); ge_r = GE_RSUM(j_); } while (0)
-// (timing probe MBX_MLP_DBG & 128: the first eight GELU pairs run beside the fc1 stages on a dummy source -- what would spreading the
-// GELU over all four stages of a chunk buy?)
-#define GE_SRC(j_, tn_, r_) (((MBX_MLP_DBG & 128) && (j_) < 8) ? ge_dummy : acc1[tn_][r_])
-    float ge_dummy = ln_rs;
-// (scalar since round 5: measured 1-2 % faster than the packed form in two sessions -- packed fp32 VALU beside MFMAs costs more than its
-// two scalar halves, MI355X_MICROARCH.md "price of one filler beside MFMAs"; MBX_MLP_GELU_SCALAR=0 is the A/B switch)
-#ifndef MBX_MLP_GELU_SCALAR
-#define MBX_MLP_GELU_SCALAR 1
-#endif
-#if MBX_MLP_GELU_SCALAR      // A/B form: the same arithmetic on scalar fp32 operations (two interleaved chains, no packed instructions)
+// (timing probe MBX_MLP_DBG & 128: the first eight GELU pairs run beside the fc1 stages -- what would spreading the GELU over all four
+// stages of a chunk buy?)
+// Scalar fp32 operations in two interleaved chains since round 5: measured 1-2 % faster than the packed form in two sessions -- packed
+// fp32 VALU beside MFMAs costs more than its two scalar halves (MI355X_MICROARCH.md "price of one filler beside MFMAs").
     float gu0, gu1, ga0, ga1, gd0, gd1;
 #define GE_STEP(ms_)                                                                                                 \
     do {                                                                                                             \
@@ -542,30 +432,6 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_kernel(const bf16_t* __restr
             G[(tn_ * 2 + (qq_ >> 1) + 4) % 5][2 * (qq_ & 1) + (j_ & 1)] = pack_bf2(o0_, o1_);                        \
         }                                                                                                            \
     } while (0)
-#else
-#define GE_STEP(ms_)                                                                                                 \
-    do {                                                                                                             \
-        const int j_ = (ms_) >> 2, st_ = (ms_) & 3, tn_ = j_ >> 3, qq_ = (j_ >> 1) & 3, r0_ = 4 * qq_ + 2 * (j_ & 1);  /* fold after unrolling */ \
-        if (st_ == 0) {                                                                                              \
-            ge_u = mbx_f32x2_t{fmaf(ln_rs, GE_SRC(j_, tn_, r0_), fmaf(ln_k, ge_r.x, ge_b.x)), fmaf(ln_rs, GE_SRC(j_, tn_, r0_ + 1), fmaf(ln_k, ge_r.y, ge_b.y))}; \
-            if (j_ + 1 < 16) GE_LOAD(j_ + 1);                     /* the next pair's constants: four slots ahead of their use */ \
-            ge_a = mbx_f32x2_t{fabsf(ge_u[0]), fabsf(ge_u[1])};                                                      \
-            ge_d = ge_a * 5.382975e-06f + 4.8890636e-05f;                                                            \
-            ge_d = ge_d * ge_a + 3.8003575e-05f;                                                                     \
-            ge_d = ge_d * ge_a + 3.2776264e-03f;                                                                     \
-        } else if (st_ == 1) {                                                                                       \
-            ge_d = ge_d * ge_a + 2.1141006e-02f;                                                                     \
-            ge_d = ge_d * ge_a + 4.9867347e-02f;                                                                     \
-            ge_d = ge_d * ge_a + 1.0f;                                                                               \
-            ge_d = mbx_f32x2_t{__builtin_amdgcn_rcpf(ge_d[0]), __builtin_amdgcn_rcpf(ge_d[1])};                      \
-        } else if (st_ == 2) {                                                                                       \
-            ge_d = ge_d * ge_d; ge_d = ge_d * ge_d; ge_d = ge_d * ge_d; ge_d = ge_d * ge_d;                          \
-        } else {                                                                                                     \
-            const mbx_f32x2_t o_ = ((ge_u + ge_a) - ge_a * ge_d) * 0.5f;                                             \
-            G[(tn_ * 2 + (qq_ >> 1) + 4) % 5][2 * (qq_ & 1) + (j_ & 1)] = pack_bf2(o_[0], o_[1]);                             \
-        }                                                                                                            \
-    } while (0)
-#endif
 
     // fc1 slot k of the stage's half h: k-step s = 16 h + (k >> 1), column half tn = k & 1
 #define MMA_A0(k_, w_) do { if ((k_) < 2) MFMA_FC1_Z(acc1[(k_) & 1], w_, X[(k_) >> 1]); else MFMA_FC1(acc1[(k_) & 1], w_, X[(k_) >> 1]); } while (0)
@@ -591,29 +457,12 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_kernel(const bf16_t* __restr
 
     if constexpr (PROJ) {
         // ---- proj: acc2 (= resid + bp) += o . Wp^T.  One stage = 32 / NT2 k-steps x NT2 output tiles.
-#ifndef MBX_MLP_PROJ_UNROLL
-#define MBX_MLP_PROJ_UNROLL 1
-#endif
-#if MBX_MLP_PROJ_UNROLL
         // (round 5) every stage written out: the token fragments are then named registers.  The rolled loop of round 4 had to pick
         // them out of X by a chain of compares per stage (X cannot be indexed by a run-time stage counter) and paid a taken branch
         // between two MFMA bursts: 1.47 us per stage in situ where the weight stream allows 0.6 (profiles/r05_mlp_trace_before.txt).
 #define MMA_P(k_, w_) MFMA_FC2(acc2[(k_) % NT2], w_, X[KKS * p + (k_) / NT2])
 #pragma unroll
         for (int p = 0; p < NPS; ++p) MF_STAGE(MMA_P, HOOK_NONE);
-#else
-        u32x4_t xk[KKS];
-#define MMA_P(k_, w_) MFMA_FC2(acc2[(k_) % NT2], w_, xk[(k_) / NT2])
-        for (int p = 0; p < NPS; ++p) {
-#pragma unroll
-            for (int pp = 0; pp < NPS; ++pp)
-                if (p == pp) {
-#pragma unroll
-                    for (int j = 0; j < KKS; ++j) xk[j] = X[KKS * pp + j];
-                }
-            MF_STAGE(MMA_P, HOOK_NONE);
-        }
-#endif
         MF_TS(7);
         // ---- y1 sits in the accumulators: operand fragments and LayerNorm statistics from them.  Lane (i, g) holds columns
         // 32 nt + 8 q + 4 g + e of token i in acc2[nt][4 q + e]; fragment s = 2 nt + h wants its columns 16 s + 8 g + [0, 8): quads
@@ -679,9 +528,6 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_kernel(const bf16_t* __restr
                         asm volatile("s_nop 3" : "+v"(G[0]), "+v"(G[1]), "+v"(G[2]), "+v"(G[3])); } while (0)
     G_ROTATE();
     MF_TS(9);
-#ifdef MBX_MLP_ALIGN_PAD      // A/B: shift the chunk loop's code by 4 bytes (MI355X_MICROARCH.md: hand-placed streams can be sensitive to their 8-byte phase)
-    asm volatile("s_nop 0");
-#endif
 #define MF_CHUNK()                                                                                                   \
     do {                                                                                                             \
         MF_TSC(16);                        /* (trace builds: the four stages of chunk 8, stamped one by one) */      \
@@ -698,9 +544,6 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_kernel(const bf16_t* __restr
         G_ROTATE();                                                                                                  \
     } while (0)
     int c = 1;
-#ifdef MBX_MLP_CHUNK_UNROLL   // A/B: three chunks per loop trip -- a taken branch between two MFMA bursts costs ~0.2 us (stage A0 1.04 us, A1 0.72)
-    for (; c + 2 < nch; ++c) { MF_CHUNK(); ++c; MF_CHUNK(); ++c; MF_CHUNK(); }
-#endif
     for (; c < nch; ++c) MF_CHUNK();
     MF_TS(10);
     MF_STAGE(MMA_B0, HOOK_NONE);           // B(n - 1)
@@ -751,12 +594,8 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_kernel(const bf16_t* __restr
 #pragma unroll 4
         for (int r = 0; r < rows; ++r) {
             const float4 t = *reinterpret_cast<const float4*>(eo + r * 1024 + ((lane_e ^ (r & 15)) << 4));
-            if (MBX_MLP_NT & 1) {
-                typedef float nt_f4 __attribute__((ext_vector_type(4)));
-                __builtin_nontemporal_store(nt_f4{t.x, t.y, t.z, t.w}, reinterpret_cast<nt_f4*>(yrow + (size_t)r * C + lane_e * 4));
-            } else {
-                *reinterpret_cast<float4*>(yrow + (size_t)r * C + lane_e * 4) = t;
-            }
+            typedef float nt_f4 __attribute__((ext_vector_type(4)));
+            __builtin_nontemporal_store(nt_f4{t.x, t.y, t.z, t.w}, reinterpret_cast<nt_f4*>(yrow + (size_t)r * C + lane_e * 4));
             if (yb_out != nullptr)
                 *reinterpret_cast<uint2*>(brow + (size_t)r * C + lane_e * 4) = make_uint2(pack_bf2(t.x, t.y), pack_bf2(t.z, t.w));
         }

@@ -75,15 +75,13 @@ class ModelCfg:
 
 @dataclass(frozen=True)
 class Switches:
-    """The A/B switches of the sequencing: one `MBX_*` environment variable each, every one ON by default except the two marked.
+    """The A/B switches of the sequencing: one `MBX_*` environment variable each, every one ON by default.
     They are read ONCE, when this module is imported (`SWITCHES`); a test or a tool that flips one afterwards calls
     `reload_switches()` (or patches `engine.SWITCHES` with `Switches.from_env({...})`).  What each one selects is described where
     `Engine.__init__` consumes it."""
     x3_planes: bool       # MBX_X3_PLANES      bf16x3: producers write the operand planes themselves (0: every operand through mbx_split_bf16)
     dual_stream: bool     # MBX_DUAL_STREAM    the ts Block of a level on a second HIP stream
-    wgrad_stream: bool    # MBX_WGRAD_STREAM   (default OFF) weight-gradient GEMMs on a third stream
     fold_ln: bool         # MBX_FOLD_LN        LayerNorm folded into the Linear it feeds (bf16)
-    fold_dx_first: bool   # MBX_FOLD_ORDER     (default OFF) the dX GEMM before the weight gradient
     grad_stream: bool     # MBX_GRAD_STREAM    gradient of the residual stream in the operand type between sub-layers
     rows_lnbwd: bool      # MBX_ROWS_LNBWD     row-owner LayerNorm-backward GEMM
     rows_resid_ln: bool   # MBX_ROWS_RESID_LN  row-owner residual GEMM + next LayerNorm
@@ -92,8 +90,8 @@ class Switches:
     rawln: bool           # MBX_RAWLN          no-grad sequencing (raw-operand LayerNorm + fused MLP)
     proj_mlp: bool        # MBX_PROJ_MLP       no-grad: proj + residual inside the MLP kernel
 
-    _ENV: ClassVar[tuple] = (('x3_planes', 'MBX_X3_PLANES', '1'), ('dual_stream', 'MBX_DUAL_STREAM', '1'), ('wgrad_stream', 'MBX_WGRAD_STREAM', '0'),
-            ('fold_ln', 'MBX_FOLD_LN', '1'), ('fold_dx_first', 'MBX_FOLD_ORDER', '0'), ('grad_stream', 'MBX_GRAD_STREAM', '1'),
+    _ENV: ClassVar[tuple] = (('x3_planes', 'MBX_X3_PLANES', '1'), ('dual_stream', 'MBX_DUAL_STREAM', '1'),
+            ('fold_ln', 'MBX_FOLD_LN', '1'), ('grad_stream', 'MBX_GRAD_STREAM', '1'),
             ('rows_lnbwd', 'MBX_ROWS_LNBWD', '1'), ('rows_resid_ln', 'MBX_ROWS_RESID_LN', '1'), ('block_grad_t', 'MBX_BLOCK_GRAD_T', '1'),
             ('gelu_d', 'MBX_GELU_D', '1'), ('rawln', 'MBX_RAWLN', '1'), ('proj_mlp', 'MBX_PROJ_MLP', '1'))
 
@@ -187,10 +185,9 @@ class Engine:
         # MBX_DUAL_STREAM=1 the ts block runs on a second HIP stream so that HBM-bound kernels of one stream
         # (LayerNorm, GEMM epilogues) overlap MFMA-bound kernels of the other.
         self.dual = sw.dual_stream and getattr(ops, 'multi_stream', False)
-        # weight-gradient GEMMs feed nothing downstream in backward: MBX_WGRAD_STREAM=1 issues them on a third stream.  Off by
-        # default: 137.0 -> 136.0 ms per step at 64 clips, but the operands stay alive until that stream catches up
-        # (record_stream), which at 256 clips (231 GiB resident) sends the allocator into retries: 421 -> 37 clips/s.
-        self.wgrad_async = sw.wgrad_stream
+        # (Measured and dropped: the weight-gradient GEMMs on a third stream -- 137.0 -> 136.0 ms per step at 64 clips, but the
+        # operands stay alive until that stream catches up (record_stream), which at 256 clips (231 GiB resident) sends the
+        # allocator into retries: 421 -> 37 clips/s.)
         # LayerNorm folding (round 3, bf16 path; include/mbx.h "LayerNorm folded into the Linear it feeds"): the LayerNorm kernels
         # write the plain normalisation xhat, the affine part lives in the qkv / fc1 weights, and the LayerNorm BACKWARD runs as the
         # epilogue of the dX GEMM from row dots the attention-backward / GELU' kernels emit -- 40 LayerNorm-backward launches and the
@@ -198,7 +195,6 @@ class Engine:
         # fp32-class modes (bf16 kernels only), or by request (model.fold_ln = False / MBX_FOLD_LN=0: the A/B switch).
         self.fold = (sw.fold_ln and not x3 and drop_seed is None and
                      bool(getattr(ops, 'can_fold', lambda *_: False)(tdtype, cfg)))
-        self.fold_dx_first = sw.fold_dx_first
         # Gradient residual stream in the operand type BETWEEN the four sub-layers of a Block (round 4; fp32 at the Block boundaries,
         # fp32 arithmetic in the kernels): the folded LayerNorm-backward GEMM reads its dres as bf16 and writes ONLY the bf16 dx, which
         # is the stream and the next GEMMs' operand at once -- 4 instead of 12 bytes per element and launch.  Numerics:
@@ -245,33 +241,6 @@ class Engine:
         if side is None:
             side = Engine._side_streams[idx] = torch.cuda.Stream(device=idx)
         return torch.cuda.current_stream(idx), side
-
-    _w_streams: Dict[int, Any] = {}
-
-    def _wstream(self):
-        if not (self.wgrad_async and self.dev.type == 'cuda'):
-            return None
-        idx = self.dev.index if self.dev.index is not None else torch.cuda.current_device()
-        ws = Engine._w_streams.get(idx)
-        if ws is None:
-            ws = Engine._w_streams[idx] = torch.cuda.Stream(device=idx)
-        return ws
-
-    def _tn(self, dy_t, a_t, dw, db):
-        """dW / db GEMM, optionally on the weight-gradient stream (call it BEFORE the dX GEMM of the same dy)."""
-        ws = self._wstream()
-        if ws is None:
-            return self.ops.gemm_tn(dy_t, a_t, dw, db)
-        ws.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(ws):
-            self.ops.gemm_tn(dy_t, a_t, dw, db)
-        for t in (dy_t if isinstance(dy_t, tuple) else (dy_t,)) + (a_t if isinstance(a_t, tuple) else (a_t,)):
-            t.record_stream(ws)
-
-    def _join_wgrads(self):
-        ws = self._wstream()
-        if ws is not None:
-            torch.cuda.current_stream().wait_stream(ws)
 
     # ------------------------------------------------------------------ helpers
     def _f(self, *shape):
@@ -647,14 +616,13 @@ class Engine:
                          G['head.weight'], G['head.bias'])
         dxn = self._t(M, C)
         dpre = self._mm(dpre)
-        self._tn(dpre, saved['xn'], G['pre_logits.fc.weight'], G['pre_logits.fc.bias'])
+        ops.gemm_tn(dpre, saved['xn'], G['pre_logits.fc.weight'], G['pre_logits.fc.bias'])
         ops.gemm_nt(dpre, self.Wt['pre_logits.fc'], None, EPI_STORE, out_t=dxn)
         dh = self._f(M, C)
         ops.layernorm_bwd(dxn, saved['h'], saved['mean'], saved['rstd'], P['norm.weight'],
                           None, None, dh, None, G['norm.weight'], G['norm.bias'])
         del dxn, dpre
         if on_ready is not None:
-            self._join_wgrads()
             on_ready(0)
         pair = None      # the two Blocks' input gradients of the level above, T-typed (block_grad_t), instead of their fp32 sum dh
         for i in reversed(range(cfg.depth)):
@@ -713,7 +681,6 @@ class Engine:
             del d_st, d_st_t, d_ts, d_ts_t
             saved['levels'][i] = None  # release this level's activations
             if on_ready is not None:
-                self._join_wgrads()
                 on_ready(cfg.depth - i)
         if self.drop_seed is not None and cfg.drop > 0:
             from .dropmask import site_seed
@@ -725,7 +692,6 @@ class Engine:
         else:
             ops.embed_bwd(dh, saved['x'], P['joints_embed.weight'], G['joints_embed.weight'], G['joints_embed.bias'],
                           G['pos_embed'], G['temp_embed'], dx, B, T, J)
-        self._join_wgrads()
         if on_ready is not None:
             on_ready(cfg.depth + 1)
         return dx
@@ -755,7 +721,7 @@ class Engine:
                 dy_t = self._mm(dy_t)
         elif self.x3 and not isinstance(dy_t, tuple):
             dy_t = self._mm(dy)          # bf16x3: the GEMM operand is the split of the fp32 gradient itself (unless its producer wrote the planes)
-        self._tn(dy_t, sv['o_op'] if 'o_op' in sv else self._mm(sv['o']), G[f'{pre}.{attn}.proj.weight'], G[f'{pre}.{attn}.proj.bias'])
+        ops.gemm_tn(dy_t, sv['o_op'] if 'o_op' in sv else self._mm(sv['o']), G[f'{pre}.{attn}.proj.weight'], G[f'{pre}.{attn}.proj.bias'])
         ops.gemm_nt(dy_t, self.Wt[f'{pre}.{attn}.proj'], None, EPI_STORE, out_t=do)
         dqkv = self._t(M, 3 * C) if self.fold else self._op(M, 3 * C)     # (bf16x3: the attention backward writes the operand planes itself)
         if self.fold:
@@ -776,7 +742,7 @@ class Engine:
         del do
         dxn = self._t(M, C)
         dqkv = self._mm(dqkv)
-        self._tn(dqkv, self._xn(sv, pre, norm), G[f'{pre}.{attn}.qkv.weight'], G.get(f'{pre}.{attn}.qkv.bias'))
+        ops.gemm_tn(dqkv, self._xn(sv, pre, norm), G[f'{pre}.{attn}.qkv.weight'], G.get(f'{pre}.{attn}.qkv.bias'))
         ops.gemm_nt(dqkv, self.Wt[f'{pre}.{attn}.qkv'], None, EPI_STORE, out_t=dxn)
         del dqkv
         dx = self._f(M, C)
@@ -805,7 +771,6 @@ class Engine:
         db = G.get(lin + '.bias')
         if db is None:                     # qkv_bias=False: the column sums of dY are still needed for d(beta)
             db = self._f(dY.shape[1])
-        ws = self._wstream()
         stream = self.gstream and dy_t is not None
         dres = dy_t if stream else dy
 
@@ -820,21 +785,10 @@ class Engine:
                 extra = extra()
             ops.gemm_nt_lnbwd(dY, self.Wt[lin], sv['xn'], rowc, dres, extra, dx, dx_t)
             return dx, dx_t
-        if self.fold_dx_first:       # A/B: the dX GEMM (critical path) before the weight gradient
-            out = dx_gemm(extra)
-        if ws is None:
-            ops.gemm_tn(dY, sv['xn'], G[lin + '.weight'], db)
-            ops.unfold_norm_grads(G[lin + '.weight'], db, P[lin + '.weight'], P[norm + '.weight'], P[norm + '.bias'],
-                                  G[norm + '.weight'], G[norm + '.bias'])
-        else:
-            ws.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(ws):
-                ops.gemm_tn(dY, sv['xn'], G[lin + '.weight'], db)
-                ops.unfold_norm_grads(G[lin + '.weight'], db, P[lin + '.weight'], P[norm + '.weight'], P[norm + '.bias'],
-                                      G[norm + '.weight'], G[norm + '.bias'])
-            for t in (dY, sv['xn'], db):
-                t.record_stream(ws)
-        return out if self.fold_dx_first else dx_gemm(extra)
+        ops.gemm_tn(dY, sv['xn'], G[lin + '.weight'], db)
+        ops.unfold_norm_grads(G[lin + '.weight'], db, P[lin + '.weight'], P[norm + '.weight'], P[norm + '.bias'],
+                              G[norm + '.weight'], G[norm + '.bias'])
+        return dx_gemm(extra)
 
     def _mlp_bwd(self, dy, dy_t, sv, pre, norm, mlp, extra, need_t):
         cfg, ops, P, G = self.cfg, self.ops, self.P, self.grads
@@ -855,7 +809,7 @@ class Engine:
             if dm is not None and dm[0] > 0:
                 ops.dropout(g, g, dm[0], dm[2])
             g = self._mm(g)
-        self._tn(dy_t, g, G[f'{pre}.{mlp}.fc2.weight'], G[f'{pre}.{mlp}.fc2.bias'])
+        ops.gemm_tn(dy_t, g, G[f'{pre}.{mlp}.fc2.weight'], G[f'{pre}.{mlp}.fc2.bias'])
         del g
         if self.fold:
             lin = f'{pre}.{mlp}.fc1'
@@ -879,7 +833,7 @@ class Engine:
             ops.dropout(du, du, dm[0], dm[2])
         dxn = self._t(M, C)
         du = self._mm(du)
-        self._tn(du, self._xn(sv, pre, norm), G[f'{pre}.{mlp}.fc1.weight'], G[f'{pre}.{mlp}.fc1.bias'])
+        ops.gemm_tn(du, self._xn(sv, pre, norm), G[f'{pre}.{mlp}.fc1.weight'], G[f'{pre}.{mlp}.fc1.bias'])
         ops.gemm_nt(du, self.Wt[f'{pre}.{mlp}.fc1'], None, EPI_STORE, out_t=dxn)
         del du
         dx = self._f(M, C)

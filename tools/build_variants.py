@@ -1,6 +1,6 @@
 """Build diagnostic / A-B variants of the kernel library next to the product one.
 
-    python tools/build_variants.py diag                      # -DMBX_DIAG: env switches (MBX_NT256_MASK, MBX_DBG, ...) are live
+    python tools/build_variants.py diag                      # -DMBX_DIAG: env switches (MBX_DBG, MBX_TRACE_BUF, ...) are live
     python tools/build_variants.py name -DFOO=1 -DBAR=2      # any extra compile flags
 
 Output: tools/variants/libmbx_<name>.so (git-ignored, travels to the GPU box with gpurun).  The measurement scripts pick a

@@ -1,7 +1,7 @@
 """GEMM micro-benchmark on the GPU box: the model's GEMM shapes through the C ABI, TF/s per shape
 (HIP events on the launch stream, random data), with a correctness spot check against torch.
 
-    python tools/gemm_bench.py [--batch 64] [--iters 20]       (MBX_GEMM_V1=1 selects the simple kernels)
+    python tools/gemm_bench.py [--batch 64] [--iters 20]
 """
 import argparse
 import json
@@ -123,8 +123,7 @@ def main():
         del dy, a
     out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'gpurun_out')
     os.makedirs(out, exist_ok=True)
-    tag = 'v1' if os.environ.get('MBX_GEMM_V1') == '1' else 'pipe'
-    with open(os.path.join(out, f'gemm_bench_{tag}.json'), 'w') as f:
+    with open(os.path.join(out, 'gemm_bench_pipe.json'), 'w') as f:
         json.dump(res, f, indent=1)
 
 

@@ -1,5 +1,5 @@
 """Diagnostics (MBX_DIAG build): per-phase cycle stamps of the leading and the trailing wave of one workgroup of
-gemm_nt_pp256.   MBX_LIB=tools/variants/libmbx_diag.so MBX_NT_PP=1 python tools/pp_trace.py [N K]"""
+gemm_nt_pp256.   MBX_LIB=tools/variants/libmbx_diag.so python tools/pp_trace.py [N K]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
