@@ -223,7 +223,8 @@ int mbx_gemm_tn_x3(const void* dy_hi, const void* dy_lo, const void* a_hi, const
 
 /* ---- attention core (DSTformer.py:178-200), qkv [M,3C] T with channel order [3][H][hd] --------
  * o [M,C] T (heads concatenated), lse [M,H] f32 = log-sum-exp of the scaled scores.
- * hd = C/H must be 32 or 64; J <= 32; T <= 256. */
+ * hd = C/H must be 32 or 64; J <= 32.  Any T: sequences longer than 256 run the streamed kernels (K / V or Q / dO through LDS in
+ * 64-row tiles) -- every entry below, all forms included; a shape whose launch grid exceeds 2^31 workgroups is refused. */
 int mbx_attn_fwd(const void* qkv, void* o, float* lse, int B, int T, int J, int H, int hd, float scale,
                  int mode, int dtype, void* stream);
 /* mbx_attn_fwd with nn.Dropout(p) on the probabilities (attn_drop, DSTformer.py:96,182,196): o = (mask P / (1 - p)) V with the

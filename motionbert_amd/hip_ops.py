@@ -212,8 +212,8 @@ class HipOps:
         """The folded-LayerNorm kernels exist for bf16 operands; every kernel-side shape constraint of the set is mirrored HERE, because
         the decision is taken before the forward (which then drops the fp32 sub-layer inputs) and a refusal in backward would come too
         late: GELU' row dots per 64-column block and the 64-wide k tiles of the LayerNorm-backward GEMM (hidden % 64, C % 64: K of the dX
-        GEMMs is 3 C / hidden, N is C), attention row dots only in the bf16 kernels with head dim 32 / 64 (sequence length <= 256 is a limit
-        of every attention kernel and raises in forward already)."""
+        GEMMs is 3 C / hidden, N is C), attention row dots in the bf16 kernels with head dim 32 / 64 (every sequence length: the streamed kernels beyond 256
+        frames have the row-dot form too)."""
         return tdtype == torch.bfloat16 and cfg.hidden % 64 == 0 and cfg.C % 64 == 0 and cfg.hd in (32, 64)
 
     def fold_norm_weights(self, P: Dict[str, torch.Tensor], pairs, need_t: bool, tdtype=torch.bfloat16):
