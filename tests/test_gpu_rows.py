@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from motionbert_amd.engine import EPI_RESID
+from tests.localerr import worst_row as _worst_row
 from tests.mock_ops import MockOps
 from tests.test_gpu_kernels import DEV, check, rnd
 
@@ -121,13 +122,6 @@ def test_rows_gemm_rejects_bad_shapes(ops):
     a, w, bias = _operands(64, 96, 256, seed=1)
     with pytest.raises(RuntimeError):
         ops.rows_pack_nk(w)                                  # N % 64
-
-
-def _worst_row(got, ref):
-    """max over rows of |got - ref| / |ref|: a handful of wrong rows among 264,384 does not move a relative L2 over all of them (round 6:
-    a token fragment read before it had landed; the thresholds are those of tools/rows_soak.py)"""
-    g, r = got.float(), ref.float()
-    return float(((g - r).norm(dim=-1) / r.norm(dim=-1)).max())
 
 
 LNBWD_SHAPES = [(128, 512, 512), (4131, 1536, 512), (4131, 1024, 512), (70227, 1536, 512), (33, 512, 512), (2 * 243 * 17, 1024, 512), (129, 1536, 512),
