@@ -345,6 +345,34 @@ int mbx_embed_fwd_tta(const float* x, const int* perm, const float* w, const flo
                       float* h, int B, int T, int J, int Din, int C, void* stream);
 int mbx_flip_average(const float* out2, const int* perm, float* out, int B, int T, int J, int D, void* stream);
 
+/* ---- evaluation on the device: Protocol #1 / #2 errors of train.py:56-153 (csrc/pose_eval.hip) ----------------------------------------
+ * mbx_pose_errors: per frame of pred [N,T,J,3] f32 (the raw network output, normalised image coordinates) against gt [N,T,J,3] f32
+ * (the dataset's joints_2.5d_image), in the reference's order:
+ *   rootrel != 0: pred[:,:,0,:] = 0 (train.py:75-76);   gt_2d != 0: pred[...,:2] = x[...,:2] (train.py:80-81; x [N,T,J,x_channels>=2] f32,
+ *   the model input; read only then);   hw != NULL ([N,2] f32 = (res_w, res_h) per clip, DataReaderH36M.get_hw()): xy = (xy + [1, h/w]) w/2,
+ *   z = z w/2 (datareader_h36m.py:125-136);   factor != NULL ([N,T] f32, 2.5d_factor): pred *= factor (train.py:118-121);
+ *   both poses minus their joint 0 (train.py:124-125);
+ *   e1 = mean_j |p_j - g_j|                                                                   (lib/model/loss.py:8-14   mpjpe)
+ *   e2 = mean_j |a p_j R + t - g_j|, (a, R, t) the optimal similarity transform of p onto g    (lib/model/loss.py:16-51  p_mpjpe)
+ * e1, e2 [N,T] f64; all arithmetic after the f32 loads is f64.  The 3x3 decomposition is a fixed 8 sweeps of cyclic Jacobi on H^T H
+ * with the third singular vectors taken as cross products (planar poses are fine; no data-dependent loop, terminates on NaN input).
+ * 1 < J <= 64.  pred / gt / x need 4-byte alignment only.  A frame whose pred or gt has zero extent (all joints equal) gives e2 = NaN,
+ * the reference's 0/0; a non-finite e1 is dropped by mbx_eval_reduce as the reference's `e1_all[idx] > 0` drops it. */
+int mbx_pose_errors(const float* pred, const float* gt, const float* hw, const float* factor, const float* x, int x_channels, int rootrel,
+                    int gt_2d, double* e1, double* e2, int N, int T, int J, void* stream);
+/* mbx_eval_reduce: the aggregation of train.py:100-149.  e1, e2 [n_err] f64 (n_err = N T slots, slot = clip * T + frame in clip);
+ * CSR over the F test frames: row_ptr [n_row_ptr = F + 1] i32, slots [nnz] i32 = the slots that cover test frame f, in clip order
+ * (the host leaves out the clips of blocked sources, train.py:109-115); action [F] i32 in [0, A).
+ *   frame mean   m(f) = sum over its slots / their number; f is left out when it has no slot or m1(f) is not > 0 (train.py:131-137)
+ *   per_action [2,A] f64 = mean of m1 / m2 over the frames of the action that are left in;  count [A] i32 = their number
+ *   summary [2] f64      = mean of per_action over the A actions (train.py:148-149)
+ * An action without a frame left in gives NaN (np.mean of an empty list), and so does the summary then.  Every sum runs in a fixed
+ * order and there are no floating-point atomics: two calls on the same inputs give the same bits.  Slot indices outside [0, n_err)
+ * and row bounds outside [0, nnz] are ignored, never followed.  ws: >= mbx_eval_reduce_ws(F, A) bytes. */
+size_t mbx_eval_reduce_ws(int F, int A);
+int mbx_eval_reduce(const double* e1, const double* e2, int n_err, const int* row_ptr, int n_row_ptr, const int* slots, int nnz,
+                    const int* action, int F, int A, double* per_action, double* summary, int* count, void* ws, void* stream);
+
 /* ---- "N-resident" row-owner GEMM with the LayerNorm backward as its epilogue (bf16; csrc/gemm_rows_n.hip; round 5) ---------------------
  * The input gradient of a folded (LayerNorm -> Linear) pair INSIDE a Block (DSTformer.py:241-249: norm1 -> attn.qkv :143, norm2 ->
  * mlp.fc1 :80; backward by autograd in the reference) in one launch, without row dots from the producers of dY:

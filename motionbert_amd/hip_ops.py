@@ -93,6 +93,9 @@ SIGNATURES = {
     'mbx_augment2d': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp] + [_f] * 8 + [_i, C.c_uint64, _vp]),
     'mbx_embed_fwd_tta': (_i, [_vp] * 7 + [_i] * 5 + [_vp]),
     'mbx_flip_average': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'mbx_pose_errors': (_i, [_vp] * 5 + [_i] * 3 + [_vp] * 2 + [_i] * 3 + [_vp]),
+    'mbx_eval_reduce_ws': (_sz, [_i, _i]),
+    'mbx_eval_reduce': (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i] + [_vp] * 5),
     'mbx_rows_n_pack_bytes': (_sz, [_i, _i]),
     'mbx_rows_lnbwd_t': (_i, [_vp] * 6 + [_i, _i, _i, _vp]),
     'mbx_rows_n_pack_many': (_i, [_i64p, _i, _i, _i, _vp]),
@@ -129,6 +132,7 @@ class HipOps:
         self.lib = lib or load_library()
         self._ws_cache: Dict[tuple, int] = {}
         self._desc_cache: Dict[tuple, dict] = {}
+        self._desc_held: Dict[int, dict] = {}         # descriptor-table entries a captured hipGraph reads at replay (_hold_if_capturing)
         self.weight_cache: Dict[int, tuple] = {}      # device index -> (key, prepared weights) of the last no-grad forward (engine.prepare_weights)
         self._lock = threading.Lock()
 
@@ -147,6 +151,15 @@ class HipOps:
             n = int(fn(*args))
             self._ws_cache[key] = n
         return torch.empty(max(n, 16), dtype=torch.uint8, device=device)
+
+    def _hold_if_capturing(self, ent: dict):
+        """Called under the lock with the descriptor-table entry a packer is about to read.  A hipGraph under capture records the
+        ADDRESSES of the entry's device tables in its copy nodes and reads them again at every replay, while the tables live in the
+        ordinary allocator pool and belong to `_desc_cache` alone: once `_desc_room` dropped the entry (another model's forward
+        adding the 16th of its kind) the allocator handed the memory on and the replay packed weights from whatever lay there.
+        Entries used during a capture are therefore kept for the life of the provider (a few hundred bytes each)."""
+        if torch.cuda.is_current_stream_capturing():
+            self._desc_held[id(ent)] = ent
 
     # ------------------------------------------------------------------ weights
     def prep_weights(self, P: Dict[str, torch.Tensor], names: List[str], tdtype, need_t: bool, x3: bool = False):
@@ -185,6 +198,7 @@ class HipOps:
                            offs=(torch.tensor(offs, dtype=torch.int64) * torch.empty(0, dtype=tdtype).element_size()).to(dev),
                            offs_host=offs, total=off, max_n=max(w.shape[0] for w in ws), max_k=max(w.shape[1] for w in ws))
                 self._desc_cache[key] = ent
+            self._hold_if_capturing(ent)
         for w in ws:
             if w.dtype != torch.float32 or not w.is_contiguous():
                 raise RuntimeError('libmbx: parameters must be contiguous fp32')
@@ -246,6 +260,7 @@ class HipOps:
                            voffs=(torch.tensor(voffs, dtype=torch.int64) * 4).to(dev), offs_host=offs, voffs_host=voffs, total=off,
                            vtotal=voff, max_n=max(w.shape[0] for w in ws), max_k=max(w.shape[1] for w in ws))
                 self._desc_cache[key] = ent
+            self._hold_if_capturing(ent)
         desc = ent['desc'].clone()
         flat_n = torch.empty(ent['total'], dtype=torch.bfloat16, device=dev)
         flat_t = torch.empty(ent['total'], dtype=torch.bfloat16, device=dev) if need_t else None
@@ -396,6 +411,7 @@ class HipOps:
                 ent = dict(desc=torch.tensor([[w.data_ptr() - base, o, w.shape[1]] for w, o in zip(ws, offs)], dtype=torch.int64).to(dev), offs=offs, total=off,
                            max_k=max(w.shape[1] for w in ws))
                 self._desc_cache[key] = ent
+            self._hold_if_capturing(ent)
         flat = torch.empty(ent['total'], dtype=torch.uint8, device=dev)
         desc = ent['desc'].clone()
         desc[:, 0] += base
@@ -620,6 +636,19 @@ class HipOps:
     def flip_average(self, out2, perm, out):
         B, T, J, D = out.shape
         self._ck(self.lib.mbx_flip_average(_p(out2), _p(perm), _p(out), B, T, J, D, self._stream()))
+
+    # ------------------------------------------------------------------ evaluation (train.py:56-153)
+    def pose_errors(self, pred, gt, hw, factor, x, rootrel, e1, e2):
+        """pred, gt [N,T,J,3] f32; hw [N,2] / factor [N,T] f32 or None; x = the model input [N,T,J,>=2] (gt_2d) or None; e1, e2 [N,T] f64."""
+        N, T, J, _ = pred.shape
+        self._ck(self.lib.mbx_pose_errors(_p(pred), _p(gt), _p(hw), _p(factor), _p(x), 0 if x is None else x.shape[-1], int(bool(rootrel)),
+                                          int(x is not None), _p(e1), _p(e2), N, T, J, self._stream()))
+
+    def eval_reduce(self, e1, e2, row_ptr, slots, action, A, per_action, summary, count):
+        F = action.numel()
+        ws = self._ws(('evr', F, A), self.lib.mbx_eval_reduce_ws, F, A, device=e1.device)
+        self._ck(self.lib.mbx_eval_reduce(_p(e1), _p(e2), e1.numel(), _p(row_ptr), row_ptr.numel(), _p(slots), slots.numel(), _p(action), F, int(A),
+                                          _p(per_action), _p(summary), _p(count), _p(ws), self._stream()))
 
     # ------------------------------------------------------------------ dropout / drop-path (SURVEY 8 a15)
     def dropout(self, x, y, p, seed):
