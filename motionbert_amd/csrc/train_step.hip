@@ -173,7 +173,8 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const
 }
 extern "C" int mbx_adamw_step(float* p, const float* g, float* m, float* v, size_t n, float* state, float beta1, float beta2,
                               float eps, float weight_decay, int tick, void* stream) {
-    MBX_CHECK_ARG(p && g && m && v && state, "adamw_step: null pointer");
+    // an empty range has no storage (torch hands out a null data pointer for it): it only ticks
+    MBX_CHECK_ARG(state && (n == 0 || (p && g && m && v)), "adamw_step: null pointer");
     const size_t mis = (size_t)((uintptr_t)p & 15);
     MBX_CHECK_ARG(mis % 4 == 0 && ((uintptr_t)g & 15) == mis && ((uintptr_t)m & 15) == mis && ((uintptr_t)v & 15) == mis,
                   "adamw_step: p, g, m, v must be 4-byte aligned and share their offset within a 16-byte line (same range of parallel flat buffers)");
@@ -356,7 +357,8 @@ extern "C" int mbx_residual_drop(float* y, const float* x, size_t rows, int C, i
                                  float p_path, uint64_t seed_path, void* stream) {
     MBX_CHECK_ARG(y && x && C > 0 && C % 4 == 0 && rows_per_sample > 0 && p >= 0.f && p < 1.f && p_path >= 0.f && p_path < 1.f,
                   "residual_drop: bad arguments");
-    if (rows == 0) return 0;
+    // p = p_path = 0 is the identity; fma(y - x, 1, x) is not (y - x rounds): leave y as the epilogue wrote it
+    if (rows == 0 || (p == 0.f && p_path == 0.f)) return 0;
     const size_t want = (rows * (C / 4) + 255) / 256;
     const int grid = (int)(want < 4096 ? want : 4096);
     hipLaunchKernelGGL((branch_drop_kernel<float, 0>), dim3(grid), dim3(256), 0, (hipStream_t)stream, y, x, (float*)nullptr, rows, C,
