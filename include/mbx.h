@@ -96,7 +96,11 @@ int mbx_layernorm_bwd_planes(const float* dy, const float* x, const float* mean,
 int mbx_gemm_nt(const void* a, const void* w, const float* bias, int epilogue, void* out_t, void* out2_t,
                 float* out_f, const float* resid, const void* aux_t, int M, int N, int K, int dtype, void* stream);
 /* dw[N,K] = dy[M,N]^T . a[M,K] (f32);  db[N] = column sums of dy (or NULL).  N % 32 == 0, K % 32 == 0.
- * ws: >= mbx_gemm_tn_ws(M,N,K) bytes. */
+ * ws: >= mbx_gemm_tn_ws(M,N,K) bytes: `splits` fp32 partial tiles [N,K] and up to four partial bias rows [N] per split (+ 256), the
+ * larger of the f32 and the bf16 launch plan (one workspace serves either dtype).  The token-split count is at most 64 (f32) or 128
+ * (bf16), except that since round 6 the bf16 / bf16x3 kernel with 1 or 3 output tiles of 256 x 256 searches up to 256 splits: the
+ * workspace, and the rows the column-sum pass reads, can therefore reach 256 (N K + 4 N) floats.  The launcher lays its partials out
+ * by the same plan that this size comes from; a smaller buffer is written past its end. */
 size_t mbx_gemm_tn_ws(int M, int N, int K);
 int mbx_gemm_tn(const void* dy, const void* a, float* dw, float* db, int M, int N, int K, int dtype,
                 void* ws, void* stream);
@@ -217,6 +221,8 @@ int mbx_gemm_nt_x3p(const void* a_hi, const void* a_lo, const void* w_hi, const 
 /* mbx_layernorm_fwd (T = f32) with y written as the operand planes (y_hi, y_lo bf16 [M,C]) of the Linear that follows. */
 int mbx_layernorm_fwd_planes(const float* x, const float* gamma, const float* beta, float eps, void* y_hi, void* y_lo, float* mean,
                              float* rstd, int M, int C, void* stream);
+/* ws of mbx_gemm_tn_x3: exactly splits x (N K + 4 N) floats + 256 bytes, from the launch plan that the launcher follows.  The split
+ * count is bounded as for bf16 (mbx_gemm_tn_ws): up to 128, and up to 256 where the round-6 search runs (1 or 3 output tiles). */
 size_t mbx_gemm_tn_x3_workspace(int M, int N, int K);
 int mbx_gemm_tn_x3(const void* dy_hi, const void* dy_lo, const void* a_hi, const void* a_lo, float* dw, float* db, int M,
                    int N, int K, void* ws, void* stream);

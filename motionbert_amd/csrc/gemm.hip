@@ -188,20 +188,12 @@ static int launch_gemm_nt(const void* a, const void* w, const float* bias, int e
                           float* out_f, const float* resid, const void* aux, int M, int N, int K, hipStream_t s) {
     const int ntn = (N + G_BN - 1) / G_BN, ntm = (M + G_BM - 1) / G_BM;
     dim3 grid((unsigned)ntn * ntm), block(256);
-#define MBX_NT_CASE(E)                                                                                              \
-    case E:                                                                                                         \
-        hipLaunchKernelGGL((gemm_nt_kernel<E>), grid, block, 0, s, (const float*)a, (const float*)w, bias,          \
-                           (float*)out_t, (float*)out2_t, out_f, resid, (const float*)aux, M, N, K, ntn);           \
-        break;
-    switch (epi) {
-        MBX_NT_CASE(MBX_EPI_STORE)
-        MBX_NT_CASE(MBX_EPI_GELU)
-        MBX_NT_CASE(MBX_EPI_RESID)
-        MBX_NT_CASE(MBX_EPI_TANH)
-        MBX_NT_CASE(MBX_EPI_DGELU)
-        default: return mbx_set_error("gemm_nt: unknown epilogue %d", epi);
-    }
-#undef MBX_NT_CASE
+    const int rc = dispatch_epi<MBX_EPI_STORE, MBX_EPI_GELU, MBX_EPI_RESID, MBX_EPI_TANH, MBX_EPI_DGELU>(epi, [&](auto e) {
+        hipLaunchKernelGGL((gemm_nt_kernel<decltype(e)::value>), grid, block, 0, s, (const float*)a, (const float*)w, bias,
+                           (float*)out_t, (float*)out2_t, out_f, resid, (const float*)aux, M, N, K, ntn);
+        return 0;
+    });
+    if (rc < 0) return mbx_set_error("gemm_nt: unknown epilogue %d", epi);
     MBX_LAUNCH_CHECK("gemm_nt");
     return 0;
 }
@@ -475,46 +467,37 @@ static int tn_splits(int M, int N, int K, int bms) {
     if (s < 1) s = 1;
     return s;
 }
-// one workspace serves both dtypes: the fp32 kernels' partials (both of them use tn_splits(..., 32)) and the bf16 pipe kernels'
+// The plan of the two fp32 kernels: gemm_tn_f32_kernel (no transposes, 16-token chunks) for multiples of 128 with at least four chunks,
+// gemm_tn_kernel (32-token chunks) for everything else.  Known property: the split count is clamped by the number of 32-token chunks for
+// BOTH kernels, so one size serves whichever of them runs.
+static TnPlan tn_plan_f32(int M, int N, int K) {
+    TnPlan p{};
+    p.kernel = (N % 128 == 0 && K % 128 == 0 && M >= 4 * TF_BT) ? TN_F32_DIRECT : TN_F32_TRANSPOSING;
+    const int bt = p.kernel == TN_F32_DIRECT ? TF_BT : 8 * TB_RB;
+    p.ntn = (N + 127) / 128, p.ntk = (K + 127) / 128;
+    p.nchunks = (M + bt - 1) / bt;
+    p.splits = tn_splits(M, N, K, 32);
+    p.slots = 1;
+    return tn_plan_layout(p, N, K, 1);
+}
+// one workspace serves both dtypes: the fp32 kernels' partials and the bf16 pipe kernels'
 extern "C" size_t mbx_gemm_tn_ws(int M, int N, int K) {
-    const int s = tn_splits(M, N, K, 32);
-    const size_t f32 = ((size_t)s * N * K + (size_t)s * N) * sizeof(float) + 256;
-    const size_t bf16 = mbx_gemm_tn_pipe_ws(M, N, K);
+    const size_t f32 = tn_plan_f32(M, N, K).ws_bytes, bf16 = mbx_gemm_tn_pipe_ws(M, N, K);
     return f32 > bf16 ? f32 : bf16;
 }
 static int launch_gemm_tn_f32(const void* dy, const void* a, float* dw, float* db, int M, int N, int K, void* ws, hipStream_t s) {
-    const int ntn = N / 128, ntk = K / 128;
-    const int nchunks = (M + TF_BT - 1) / TF_BT;
-    const int splits = tn_splits(M, N, K, 32);                      // the split count the workspace was sized for
-    const int cps = (nchunks + splits - 1) / splits;
-    float* part_w = splits == 1 ? dw : (float*)ws;
-    float* part_b = db ? (splits == 1 ? db : (float*)ws + (size_t)splits * N * K) : nullptr;
-    if (mbx_set_dyn_lds(reinterpret_cast<const void*>(gemm_tn_f32_kernel), TF_NST * TF_STAGE, "gemm_tn")) return 1;
-    hipLaunchKernelGGL(gemm_tn_f32_kernel, dim3(8 * ntn * ntk * ((splits + 7) / 8)), dim3(256), TF_NST * TF_STAGE, s, (const float*)dy,
-                       (const float*)a, part_w, part_b, M, N, K, ntk, cps, splits);
-    MBX_LAUNCH_CHECK("gemm_tn_f32");
-    if (splits > 1) {
-        if (mbx_launch_colsum(part_w, splits, N * K, 0, N * K, dw, s)) return 1;
-        if (db && mbx_launch_colsum(part_b, splits, N, 0, N, db, s)) return 1;
+    const TnPlan p = tn_plan_f32(M, N, K);
+    if (p.kernel == TN_F32_DIRECT) {
+        if (mbx_set_dyn_lds(reinterpret_cast<const void*>(gemm_tn_f32_kernel), TF_NST * TF_STAGE, "gemm_tn")) return 1;
+        hipLaunchKernelGGL(gemm_tn_f32_kernel, dim3(8 * p.tiles * ((p.splits + 7) / 8)), dim3(256), TF_NST * TF_STAGE, s, (const float*)dy,
+                           (const float*)a, p.part_w(ws, dw), p.part_b(ws, db), M, N, K, p.ntk, p.cps, p.splits);
+        MBX_LAUNCH_CHECK("gemm_tn_f32");
+    } else {
+        hipLaunchKernelGGL(gemm_tn_kernel, dim3(p.tiles, p.splits), dim3(256), 0, s, (const float*)dy, (const float*)a, p.part_w(ws, dw),
+                           p.part_b(ws, db), M, N, K, p.ntk, p.cps);
+        MBX_LAUNCH_CHECK("gemm_tn");
     }
-    return 0;
-}
-static int launch_gemm_tn(const void* dy, const void* a, float* dw, float* db, int M, int N, int K, void* ws, hipStream_t s) {
-    constexpr int BMS = 8 * TB_RB;
-    const int ntn = (N + 127) / 128, ntk = (K + 127) / 128;
-    const int splits = tn_splits(M, N, K, BMS);
-    const int nchunks = (M + BMS - 1) / BMS;
-    const int cps = (nchunks + splits - 1) / splits;
-    float* part_w = splits == 1 ? dw : (float*)ws;
-    float* part_b = db ? (splits == 1 ? db : (float*)ws + (size_t)splits * N * K) : nullptr;
-    hipLaunchKernelGGL(gemm_tn_kernel, dim3(ntn * ntk, splits), dim3(256), 0, s, (const float*)dy, (const float*)a, part_w,
-                       part_b, M, N, K, ntk, cps);
-    MBX_LAUNCH_CHECK("gemm_tn");
-    if (splits > 1) {
-        if (mbx_launch_colsum(part_w, splits, N * K, 0, N * K, dw, s)) return 1;
-        if (db && mbx_launch_colsum(part_b, splits, N, 0, N, db, s)) return 1;
-    }
-    return 0;
+    return tn_finalize(p, ws, dw, db, N, K, s);
 }
 extern "C" int mbx_gemm_tn(const void* dy, const void* a, float* dw, float* db, int M, int N, int K, int dtype, void* ws,
                            void* stream) {
@@ -523,9 +506,7 @@ extern "C" int mbx_gemm_tn(const void* dy, const void* a, float* dw, float* db, 
     MBX_CHECK_ARG((size_t)N * K < ((size_t)1 << 31), "gemm_tn: output too large");
     hipStream_t s = (hipStream_t)stream;
     if (dtype == MBX_BF16) return mbx_launch_gemm_tn_pipe(dy, a, dw, db, M, N, K, ws, s);
-    if (dtype == MBX_F32)
-        return (N % 128 == 0 && K % 128 == 0 && M >= 4 * TF_BT) ? launch_gemm_tn_f32(dy, a, dw, db, M, N, K, ws, s)
-                                                               : launch_gemm_tn(dy, a, dw, db, M, N, K, ws, s);
+    if (dtype == MBX_F32) return launch_gemm_tn_f32(dy, a, dw, db, M, N, K, ws, s);
     return mbx_set_error("gemm_tn: unknown dtype %d", dtype);
 }
 

@@ -33,6 +33,7 @@
 #include "mbx_common.h"
 #include "gelu_fast.h"
 #include <stdlib.h>
+#include <tuple>
 #include <type_traits>
 
 typedef __attribute__((address_space(3))) void lds_void_t;
@@ -825,106 +826,87 @@ static int set_lds_attr(K kernel, size_t bytes, const char* who) {
     return mbx_set_dyn_lds(reinterpret_cast<const void*>(kernel), bytes, who);
 }
 
+// The kernels' trailing diagnostic arguments (gemm_nt_pipe_kernel: dbg, trace; gemm_nt_pp256_kernel: trace), made HERE and nowhere else:
+// none in the product build, the MBX_DBG switches and the MBX_TRACE_BUF stamp buffer in a -DMBX_DIAG build (`live` = false: the entries
+// that were never wired to the environment pass 0 / NULL).  launch_diag appends them to the kernel's arguments.
+#ifdef MBX_DIAG
+static long long* diag_trace_buf() {
+    static long long* const buf = [] { const char* e = getenv("MBX_TRACE_BUF"); return e ? (long long*)strtoull(e, nullptr, 0) : (long long*)nullptr; }();
+    return buf;
+}
+static std::tuple<int, long long*> ntp_diag(bool live) {
+    static const int dbg = mbx_env_int("MBX_DBG", 0);
+    return {live ? dbg : 0, live ? diag_trace_buf() : nullptr};
+}
+static std::tuple<long long*> pp256_diag(bool live) { return {live ? diag_trace_buf() : nullptr}; }
+#else
+static std::tuple<> ntp_diag(bool) { return {}; }
+static std::tuple<> pp256_diag(bool) { return {}; }
+#endif
+template <class Kern, class Diag, class... Args>
+static void launch_diag(Kern kernel, dim3 grid, size_t shm, hipStream_t s, const Diag& diag, Args... args) {
+    std::apply([&](auto... d) { hipLaunchKernelGGL(kernel, grid, dim3(512), shm, s, args..., d...); }, diag);
+}
+
+// the 256 x 256 ping-pong kernel, bf16 (lo planes NULL) and X3 (T-typed tensors fp32)
+template <int EPI, bool X3>
+static int launch_pp256(const char* who, const void* a, const void* w, const void* a_lo, const void* w_lo, const float* bias, void* out_t,
+                        void* out2_t, float* out_f, const float* resid, const void* aux, int M, int N, int K, hipStream_t s,
+                        const float* st_bias, const float* st_rsum, float* st_part, void* pl_hi, void* pl_lo) {
+    typedef typename std::conditional<X3, float, bf16_t>::type TO;
+    const int ntn = (N + Q_BN - 1) / Q_BN, ntm = (M + Q_BM - 1) / Q_BM;
+    const size_t shm = Q_NSTAGE * Q_STAGE;
+    if (set_lds_attr(gemm_nt_pp256_kernel<EPI, X3>, shm, who)) return 1;
+    launch_diag(gemm_nt_pp256_kernel<EPI, X3>, dim3((unsigned)ntn * ntm), shm, s, pp256_diag(!X3), (const bf16_t*)a, (const bf16_t*)w,
+                (const bf16_t*)a_lo, (const bf16_t*)w_lo, bias, (TO*)out_t, (TO*)out2_t, out_f, resid, (const TO*)aux, M, N, K, ntn, st_bias,
+                st_rsum, st_part, (bf16_t*)pl_hi, (bf16_t*)pl_lo);
+    MBX_LAUNCH_CHECK(who);
+    return 0;
+}
 static int launch_nt256(const void* a, const void* w, const float* bias, int epi, void* out_t, void* out2_t, float* out_f,
                         const float* resid, const void* aux, int M, int N, int K, hipStream_t s, const float* st_bias = nullptr,
                         const float* st_rsum = nullptr, float* st_part = nullptr) {
-    const int ntn = (N + Q_BN - 1) / Q_BN, ntm = (M + Q_BM - 1) / Q_BM;
-    dim3 grid((unsigned)ntn * ntm), block(512);
-    const size_t shm = Q_NSTAGE * Q_STAGE;
-#ifdef MBX_DIAG
-    static long long* const pptrace = [] { const char* e = getenv("MBX_TRACE_BUF"); return e ? (long long*)strtoull(e, nullptr, 0) : (long long*)nullptr; }();
-#define MBX_Q_TRACE_ARG , pptrace
-#else
-#define MBX_Q_TRACE_ARG
-#endif
-#define MBX_Q_CASE(E)                                                                                                 \
-    case E:                                                                                                           \
-        if (set_lds_attr(gemm_nt_pp256_kernel<E>, shm, "gemm_nt_pp256")) return 1;                                    \
-        hipLaunchKernelGGL((gemm_nt_pp256_kernel<E>), grid, block, shm, s, (const bf16_t*)a, (const bf16_t*)w,        \
-                           (const bf16_t*)nullptr, (const bf16_t*)nullptr, bias,                                      \
-                           (bf16_t*)out_t, (bf16_t*)out2_t, out_f, resid, (const bf16_t*)aux, M, N, K, ntn,          \
-                           st_bias, st_rsum, st_part, (bf16_t*)nullptr, (bf16_t*)nullptr MBX_Q_TRACE_ARG); \
-        break;
-    switch (epi) {
-        MBX_Q_CASE(MBX_EPI_STORE)
-        MBX_Q_CASE(MBX_EPI_GELU)
-        MBX_Q_CASE(MBX_EPI_RESID)
-        MBX_Q_CASE(MBX_EPI_TANH)
-        MBX_Q_CASE(MBX_EPI_DGELU)
-        MBX_Q_CASE(MBX_EPI_GELU_D)
-        MBX_Q_CASE(MBX_EPI_MULAUX)
-        default: return mbx_set_error("gemm_nt: unknown epilogue %d", epi);
-    }
-#undef MBX_Q_CASE
-#undef MBX_Q_TRACE_ARG
-    MBX_LAUNCH_CHECK("gemm_nt_pp256");
-    return 0;
+    const int rc = dispatch_epi<MBX_EPI_STORE, MBX_EPI_GELU, MBX_EPI_RESID, MBX_EPI_TANH, MBX_EPI_DGELU, MBX_EPI_GELU_D, MBX_EPI_MULAUX>(
+        epi, [&](auto e) {
+            return launch_pp256<decltype(e)::value, false>("gemm_nt_pp256", a, w, nullptr, nullptr, bias, out_t, out2_t, out_f, resid, aux, M, N,
+                                                           K, s, st_bias, st_rsum, st_part, nullptr, nullptr);
+        });
+    return rc < 0 ? mbx_set_error("gemm_nt: unknown epilogue %d", epi) : rc;
 }
 
 // fp32-class split-operand GEMM (precision 'bf16x3'): always the 256 x 256 ping-pong kernel; T-typed tensors are fp32
 int mbx_launch_gemm_nt_x3(const void* a_hi, const void* a_lo, const void* w_hi, const void* w_lo, const float* bias, int epi,
                           float* out_t, float* out2_t, float* out_f, const float* resid, const float* aux, int M, int N, int K,
                           hipStream_t s, void* pl_hi, void* pl_lo) {
-    const int ntn = (N + Q_BN - 1) / Q_BN, ntm = (M + Q_BM - 1) / Q_BM;
-    dim3 grid((unsigned)ntn * ntm), block(512);
-    const size_t shm = Q_NSTAGE * Q_STAGE;
-#ifdef MBX_DIAG
-#define MBX_X3_TRACE_ARG , (long long*)nullptr
-#else
-#define MBX_X3_TRACE_ARG
-#endif
-#define MBX_X3_CASE(E)                                                                                                \
-    case E:                                                                                                           \
-        if (set_lds_attr(gemm_nt_pp256_kernel<E, true>, shm, "gemm_nt_x3")) return 1;                                 \
-        hipLaunchKernelGGL((gemm_nt_pp256_kernel<E, true>), grid, block, shm, s, (const bf16_t*)a_hi, (const bf16_t*)w_hi, \
-                           (const bf16_t*)a_lo, (const bf16_t*)w_lo, bias, out_t, out2_t, out_f, resid, aux, M, N, K, ntn, \
-                           (const float*)nullptr, (const float*)nullptr, (float*)nullptr, (bf16_t*)pl_hi, (bf16_t*)pl_lo \
-                           MBX_X3_TRACE_ARG);                                                                        \
-        break;
-    switch (epi) {
-        MBX_X3_CASE(MBX_EPI_STORE)
-        MBX_X3_CASE(MBX_EPI_GELU)
-        MBX_X3_CASE(MBX_EPI_RESID)
-        MBX_X3_CASE(MBX_EPI_TANH)
-        MBX_X3_CASE(MBX_EPI_DGELU)
-        default: return mbx_set_error("gemm_nt_x3: unknown epilogue %d", epi);
-    }
-#undef MBX_X3_CASE
-    MBX_LAUNCH_CHECK("gemm_nt_x3");
-    return 0;
+    const int rc = dispatch_epi<MBX_EPI_STORE, MBX_EPI_GELU, MBX_EPI_RESID, MBX_EPI_TANH, MBX_EPI_DGELU>(epi, [&](auto e) {
+        return launch_pp256<decltype(e)::value, true>("gemm_nt_x3", a_hi, w_hi, a_lo, w_lo, bias, out_t, out2_t, out_f, resid, aux, M, N, K, s,
+                                                      nullptr, nullptr, nullptr, pl_hi, pl_lo);
+    });
+    return rc < 0 ? mbx_set_error("gemm_nt_x3: unknown epilogue %d", epi) : rc;
 }
 
+// the 256 x 128 kernel: the generic epilogues and the two LayerNorm-backward ones (rowc, extra, ln).  env_wired = false is
+// mbx_gemm_nt_lnbwd_t, which never read the environment: in EVERY build it ignores MBX_NTP_LDS_PAD (no LDS padding, product build
+// included), and in a -DMBX_DIAG build it passes dbg = 0 / trace = NULL instead of MBX_DBG / MBX_TRACE_BUF.  Kept as it was.
+template <int EPI>
+static int launch_ntp(const char* who, const void* a, const void* w, const float* bias, void* out_t, void* out2_t, float* out_f,
+                      const float* resid, const void* aux, int M, int N, int K, hipStream_t s, const float* rowc = nullptr,
+                      const float* extra = nullptr, NtLnTail ln = NtLnTail{}, bool env_wired = true) {
+    const int ntn = (N + P_BN - 1) / P_BN, ntm = (M + P_BM - 1) / P_BM;
+    const size_t shm = P_NSTAGE * P_STAGE + (env_wired ? (size_t)mbx_env_int("MBX_NTP_LDS_PAD", 0) * 1024 : 0);   // diagnostics: padding -> one workgroup per CU
+    if (set_lds_attr(gemm_nt_pipe_kernel<EPI>, shm, who)) return 1;
+    launch_diag(gemm_nt_pipe_kernel<EPI>, dim3((unsigned)ntn * ntm), shm, s, ntp_diag(env_wired), (const bf16_t*)a, (const bf16_t*)w, bias,
+                (bf16_t*)out_t, (bf16_t*)out2_t, out_f, resid, (const bf16_t*)aux, M, N, K, ntn, reinterpret_cast<const float4*>(rowc), extra, ln);
+    MBX_LAUNCH_CHECK(who);
+    return 0;
+}
 int mbx_launch_gemm_nt_pipe(const void* a, const void* w, const float* bias, int epi, void* out_t, void* out2_t, float* out_f,
                             const float* resid, const void* aux, int M, int N, int K, hipStream_t s) {
     if (((Q_EPI_MASK >> epi) & 1) && N >= 256) return launch_nt256(a, w, bias, epi, out_t, out2_t, out_f, resid, aux, M, N, K, s);
-    const int ntn = (N + P_BN - 1) / P_BN, ntm = (M + P_BM - 1) / P_BM;
-    dim3 grid((unsigned)ntn * ntm), block(512);
-    const size_t shm = P_NSTAGE * P_STAGE + (size_t)mbx_env_int("MBX_NTP_LDS_PAD", 0) * 1024;   // diagnostics: padding -> one workgroup per CU
-#ifdef MBX_DIAG
-    static const int dbg = mbx_env_int("MBX_DBG", 0);
-    static long long* const trace = [] { const char* e = getenv("MBX_TRACE_BUF"); return e ? (long long*)strtoull(e, nullptr, 0) : (long long*)nullptr; }();
-#define MBX_NTP_DIAG_ARGS , dbg, trace
-#else
-#define MBX_NTP_DIAG_ARGS
-#endif
-#define MBX_NTP_CASE(E)                                                                                               \
-    case E:                                                                                                           \
-        if (set_lds_attr(gemm_nt_pipe_kernel<E>, shm, "gemm_nt_pipe")) return 1;                                      \
-        hipLaunchKernelGGL((gemm_nt_pipe_kernel<E>), grid, block, shm, s, (const bf16_t*)a, (const bf16_t*)w, bias,   \
-                           (bf16_t*)out_t, (bf16_t*)out2_t, out_f, resid, (const bf16_t*)aux, M, N, K, ntn,           \
-                           (const float4*)nullptr, (const float*)nullptr, NtLnTail{} MBX_NTP_DIAG_ARGS);              \
-        break;
-    switch (epi) {
-        MBX_NTP_CASE(MBX_EPI_STORE)
-        MBX_NTP_CASE(MBX_EPI_GELU)
-        MBX_NTP_CASE(MBX_EPI_RESID)
-        MBX_NTP_CASE(MBX_EPI_TANH)
-        MBX_NTP_CASE(MBX_EPI_DGELU)
-        default: return mbx_set_error("gemm_nt: unknown epilogue %d", epi);
-    }
-#undef MBX_NTP_CASE
-    MBX_LAUNCH_CHECK("gemm_nt_pipe");
-    return 0;
+    const int rc = dispatch_epi<MBX_EPI_STORE, MBX_EPI_GELU, MBX_EPI_RESID, MBX_EPI_TANH, MBX_EPI_DGELU>(epi, [&](auto e) {
+        return launch_ntp<decltype(e)::value>("gemm_nt_pipe", a, w, bias, out_t, out2_t, out_f, resid, aux, M, N, K, s);
+    });
+    return rc < 0 ? mbx_set_error("gemm_nt: unknown epilogue %d", epi) : rc;
 }
 
 // ---- round 3: the two GEMM entries of the folded LayerNorm backward (see "LayerNorm folding" in elementwise.hip) --------------
@@ -957,23 +939,7 @@ extern "C" int mbx_gemm_nt_lnbwd(const void* a, const void* w, const void* xhat,
     MBX_CHECK_ARG(a && w && xhat && rowc && dres && dx, "gemm_nt_lnbwd: null pointer");
     MBX_CHECK_ARG(M > 0 && N > 0 && N % 8 == 0 && K > 0 && K % 64 == 0, "gemm_nt_lnbwd: bad shape M=%d N=%d K=%d (N %% 8, K %% 64)", M, N, K);
     MBX_CHECK_ARG((reinterpret_cast<uintptr_t>(rowc) & 15) == 0, "gemm_nt_lnbwd: rowc must be 16-byte aligned");
-    const int ntn = (N + P_BN - 1) / P_BN, ntm = (M + P_BM - 1) / P_BM;
-    const size_t shm = P_NSTAGE * P_STAGE + (size_t)mbx_env_int("MBX_NTP_LDS_PAD", 0) * 1024;
-    hipStream_t s = (hipStream_t)stream;
-#ifdef MBX_DIAG
-    static const int dbg = mbx_env_int("MBX_DBG", 0);
-    static long long* const trace = [] { const char* e = getenv("MBX_TRACE_BUF"); return e ? (long long*)strtoull(e, nullptr, 0) : (long long*)nullptr; }();
-#endif
-    if (set_lds_attr(gemm_nt_pipe_kernel<MBX_EPI_LNBWD>, shm, "gemm_nt_lnbwd")) return 1;
-    hipLaunchKernelGGL((gemm_nt_pipe_kernel<MBX_EPI_LNBWD>), dim3((unsigned)ntn * ntm), dim3(512), shm, s, (const bf16_t*)a, (const bf16_t*)w,
-                       (const float*)nullptr, (bf16_t*)dx_t, (bf16_t*)nullptr, dx, dres, (const bf16_t*)xhat, M, N, K, ntn,
-                       reinterpret_cast<const float4*>(rowc), extra, NtLnTail{}
-#ifdef MBX_DIAG
-                       , dbg, trace
-#endif
-                       );
-    MBX_LAUNCH_CHECK("gemm_nt_lnbwd");
-    return 0;
+    return launch_ntp<MBX_EPI_LNBWD>("gemm_nt_lnbwd", a, w, nullptr, dx_t, nullptr, dx, dres, xhat, M, N, K, (hipStream_t)stream, rowc, extra);
 }
 
 // mbx_gemm_nt_lnbwd with the gradient residual stream in bf16: dres_t bf16 [M,N]; dx f32 or NULL; dx_t bf16 or NULL (at least one)
@@ -982,20 +948,10 @@ extern "C" int mbx_gemm_nt_lnbwd_t(const void* a, const void* w, const void* xha
     MBX_CHECK_ARG(a && w && xhat && rowc && dres_t && (dx || dx_t), "gemm_nt_lnbwd_t: null pointer");
     MBX_CHECK_ARG(M > 0 && N > 0 && N % 8 == 0 && K > 0 && K % 64 == 0, "gemm_nt_lnbwd_t: bad shape M=%d N=%d K=%d (N %% 8, K %% 64)", M, N, K);
     MBX_CHECK_ARG((reinterpret_cast<uintptr_t>(rowc) & 15) == 0, "gemm_nt_lnbwd_t: rowc must be 16-byte aligned");
-    const int ntn = (N + P_BN - 1) / P_BN, ntm = (M + P_BM - 1) / P_BM;
-    const size_t shm = P_NSTAGE * P_STAGE;
-    if (set_lds_attr(gemm_nt_pipe_kernel<MBX_EPI_LNBWD_T>, shm, "gemm_nt_lnbwd_t")) return 1;
     NtLnTail ln{};
     ln.dres_t = (const bf16_t*)dres_t;
-    hipLaunchKernelGGL((gemm_nt_pipe_kernel<MBX_EPI_LNBWD_T>), dim3((unsigned)ntn * ntm), dim3(512), shm, (hipStream_t)stream, (const bf16_t*)a,
-                       (const bf16_t*)w, (const float*)nullptr, (bf16_t*)dx_t, (bf16_t*)nullptr, dx, (const float*)nullptr, (const bf16_t*)xhat,
-                       M, N, K, ntn, reinterpret_cast<const float4*>(rowc), extra, ln
-#ifdef MBX_DIAG
-                       , 0, (long long*)nullptr
-#endif
-                       );
-    MBX_LAUNCH_CHECK("gemm_nt_lnbwd_t");
-    return 0;
+    return launch_ntp<MBX_EPI_LNBWD_T>("gemm_nt_lnbwd_t", a, w, nullptr, dx_t, nullptr, dx, nullptr, xhat, M, N, K, (hipStream_t)stream, rowc, extra,
+                                       ln, false);
 }
 
 // ================================================================================================
@@ -1422,10 +1378,14 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_pipe256_kernel(const bf16_t* _
 }
 
 static bool tn_use256(int N, int K) { return N >= 256 && K >= 256; }
-static int tnp_splits(int M, int N, int K, bool x3 = false) {
-    const bool big = tn_use256(N, K);
-    const int tiles = big ? ((N + U_BN - 1) / U_BN) * ((K + U_BK - 1) / U_BK) : ((N + T_BN - 1) / T_BN) * ((K + T_BK - 1) / T_BK);
-    const int nchunks = (x3 ? 3 : 1) * (big ? (M + U_BMS - 1) / U_BMS : (M + T_BMS - 1) / T_BMS);
+// output tiles and token chunks of the 256 x 256 kernel (k256) or the 256 x 128 one; X3 walks the token range once per operand product
+struct TnGrid { int ntn, ntk, nchunks; };
+static TnGrid tnp_grid(bool k256, int M, int N, int K, bool x3) {
+    const int bn = k256 ? U_BN : T_BN, bk = k256 ? U_BK : T_BK, bms = k256 ? U_BMS : T_BMS;
+    return {(N + bn - 1) / bn, (K + bk - 1) / bk, (x3 ? 3 : 1) * ((M + bms - 1) / bms)};
+}
+// the split rule, for the tiles and chunks the caller names (tn_plan_pipe: `big` = they are the 256 x 256 kernel's)
+static int tnp_splits(int tiles, int nchunks, bool big, int N, int K) {
     // one workgroup per CU: the launch should be an exact number of 256-workgroup waves (measured: 288 blocks
     // cost 1.10 ms where 768 cost 0.77 ms on the QKV weight gradient) and a multiple of the 8 XCDs
     int s = 0;
@@ -1447,79 +1407,57 @@ static int tnp_splits(int M, int N, int K, bool x3 = false) {
     if (s < 1) s = 1;
     return s;
 }
-// partial bias-gradient rows per token split (the k tiles of an n panel share the work: see gemm_tn_pipe256_kernel)
-static int tn_db_slots(int N, int K) {
-    if (!tn_use256(N, K)) return 1;
-    const int ntk = (K + U_BK - 1) / U_BK;
-    return (ntk == 2 || ntk == 4) ? ntk : 1;
+// The plan of the three pipelined paths (TnPlan, mbx_common.h): the 256 x 256 kernel where N, K >= 256 and always for X3, else the
+// 256 x 128 one.  The 256 x 256 kernel leaves ntk partial bias rows per split where ntk is 2 or 4 (the k tiles of an n panel share the
+// work: see gemm_tn_pipe256_kernel, which derives the same number from ntk), every other case one.
+static TnPlan tn_plan_pipe(int M, int N, int K, bool x3) {
+    TnPlan p{};
+    const bool rule256 = tn_use256(N, K);
+    p.kernel = x3 ? TN_X3 : rule256 ? TN_BF16_256 : TN_BF16_SMALL;
+    const bool k256 = p.kernel != TN_BF16_SMALL;
+    const TnGrid g = tnp_grid(k256, M, N, K, x3);
+    // the X3 quirk (TnPlan, mbx_common.h): the split rule is fed the grid of bf16's kernel choice for (N, K), not of the kernel X3 launches;
+    // the two differ only for X3 with N or K < 256
+    const TnGrid r = tnp_grid(rule256, M, N, K, x3);
+    p.ntn = g.ntn, p.ntk = g.ntk, p.nchunks = g.nchunks;
+    p.splits = tnp_splits(r.ntn * r.ntk, r.nchunks, rule256, N, K);
+    p.slots = (k256 && (p.ntk == 2 || p.ntk == 4)) ? p.ntk : 1;
+    return tn_plan_layout(p, N, K, 4);
 }
-size_t mbx_gemm_tn_pipe_ws(int M, int N, int K) {
-    const size_t sp = tnp_splits(M, N, K);
-    return (sp * N * K + sp * 4 * N) * sizeof(float) + 256;
+size_t mbx_gemm_tn_pipe_ws(int M, int N, int K) { return tn_plan_pipe(M, N, K, false).ws_bytes; }
+size_t mbx_gemm_tn_x3_ws(int M, int N, int K) { return tn_plan_pipe(M, N, K, true).ws_bytes; }
+
+// the 256 x 256 kernel: bf16 (lo planes NULL) and the fp32-class split-operand weight gradient (precision 'bf16x3'; N, K >= 256 and
+// multiples of 256 are not required: clamped columns as in the bf16 kernel)
+template <bool X3>
+static int launch_tn256(const TnPlan& p, const void* dy, const void* a, const void* dy_lo, const void* a_lo, float* dw, float* db, int M, int N,
+                        int K, void* ws, hipStream_t s) {
+    const char* who = X3 ? "gemm_tn_x3" : "gemm_tn_pipe256";
+    const size_t shm = 4 * U_STAGE;
+    if (set_lds_attr(gemm_tn_pipe256_kernel<X3>, shm, who)) return 1;
+#ifdef MBX_TN_TRACE
+    if (!X3) {
+        static long long* const tb = [] { const char* e = getenv("MBX_TRACE_BUF"); return e ? (long long*)strtoull(e, nullptr, 0) : (long long*)nullptr; }();
+        (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_tn_trace), &tb, sizeof(tb), 0, hipMemcpyHostToDevice, s);
+    }
+#endif
+    hipLaunchKernelGGL(gemm_tn_pipe256_kernel<X3>, dim3(8 * ((p.splits + 7) / 8) * p.tiles), dim3(512), shm, s, (const bf16_t*)dy, (const bf16_t*)a,
+                       (const bf16_t*)dy_lo, (const bf16_t*)a_lo, p.part_w(ws, dw), p.part_b(ws, db), M, N, K, p.ntk, p.tiles, p.splits, p.cps);
+    MBX_LAUNCH_CHECK(who);
+    return tn_finalize(p, ws, dw, db, N, K, s);
 }
 int mbx_launch_gemm_tn_pipe(const void* dy, const void* a, float* dw, float* db, int M, int N, int K, void* ws, hipStream_t s) {
-    const bool big = tn_use256(N, K);
-    const int ntn = big ? (N + U_BN - 1) / U_BN : (N + T_BN - 1) / T_BN, ntk = big ? (K + U_BK - 1) / U_BK : (K + T_BK - 1) / T_BK;
-    const int splits = tnp_splits(M, N, K);
-    const int nchunks = big ? (M + U_BMS - 1) / U_BMS : (M + T_BMS - 1) / T_BMS;
-    const int cps = (nchunks + splits - 1) / splits;
-    const int slots = tn_db_slots(N, K);
-    float* part_w = splits == 1 ? dw : (float*)ws;
-    float* part_b = db ? (splits * slots == 1 ? db : (float*)ws + (size_t)splits * N * K) : nullptr;
-    if (big) {
-        const size_t shm256 = 4 * U_STAGE;
-        const int ntiles256 = ntn * ntk, groups256 = (splits + 7) / 8;
-        if (set_lds_attr(gemm_tn_pipe256_kernel<false>, shm256, "gemm_tn_pipe256")) return 1;
-#ifdef MBX_TN_TRACE
-        {
-            static long long* const tb = [] { const char* e = getenv("MBX_TRACE_BUF"); return e ? (long long*)strtoull(e, nullptr, 0) : (long long*)nullptr; }();
-            (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_tn_trace), &tb, sizeof(tb), 0, hipMemcpyHostToDevice, s);
-        }
-#endif
-        hipLaunchKernelGGL(gemm_tn_pipe256_kernel<false>, dim3(8 * groups256 * ntiles256), dim3(512), shm256, s, (const bf16_t*)dy,
-                           (const bf16_t*)a, (const bf16_t*)nullptr, (const bf16_t*)nullptr, part_w, part_b, M, N, K, ntk, ntiles256,
-                           splits, cps);
-        MBX_LAUNCH_CHECK("gemm_tn_pipe256");
-        if (splits > 1 && mbx_launch_colsum(part_w, splits, N * K, 0, N * K, dw, s)) return 1;
-        if (db && splits * slots > 1 && mbx_launch_colsum(part_b, splits * slots, N, 0, N, db, s)) return 1;
-        return 0;
-    }
+    const TnPlan p = tn_plan_pipe(M, N, K, false);
+    if (p.kernel == TN_BF16_256) return launch_tn256<false>(p, dy, a, nullptr, nullptr, dw, db, M, N, K, ws, s);
     const size_t shm = 3 * T_STAGE;
     static const int dbg = mbx_env_int("MBX_DBG", 0);
     if (set_lds_attr(gemm_tn_pipe_kernel, shm, "gemm_tn_pipe")) return 1;
-    const int ntiles = ntn * ntk, groups = (splits + 7) / 8;
-    hipLaunchKernelGGL(gemm_tn_pipe_kernel, dim3(8 * groups * ntiles), dim3(512), shm, s, (const bf16_t*)dy, (const bf16_t*)a, part_w,
-                       part_b, M, N, K, ntk, ntiles, splits, cps, dbg);
+    hipLaunchKernelGGL(gemm_tn_pipe_kernel, dim3(8 * ((p.splits + 7) / 8) * p.tiles), dim3(512), shm, s, (const bf16_t*)dy, (const bf16_t*)a,
+                       p.part_w(ws, dw), p.part_b(ws, db), M, N, K, p.ntk, p.tiles, p.splits, p.cps, dbg);
     MBX_LAUNCH_CHECK("gemm_tn_pipe");
-    if (splits > 1) {
-        if (mbx_launch_colsum(part_w, splits, N * K, 0, N * K, dw, s)) return 1;
-        if (db && mbx_launch_colsum(part_b, splits, N, 0, N, db, s)) return 1;
-    }
-    return 0;
-}
-
-// fp32-class split-operand weight gradient (precision 'bf16x3'); N, K >= 256 and multiples of 256 are not required (clamped
-// columns as in the bf16 kernel) but the 256 x 256 kernel is always used.
-size_t mbx_gemm_tn_x3_ws(int M, int N, int K) {
-    const size_t sp = tnp_splits(M, N, K, true);
-    return (sp * N * K + sp * 4 * N) * sizeof(float) + 256;
+    return tn_finalize(p, ws, dw, db, N, K, s);
 }
 int mbx_launch_gemm_tn_x3(const void* dy_hi, const void* dy_lo, const void* a_hi, const void* a_lo, float* dw, float* db, int M, int N,
                           int K, void* ws, hipStream_t s) {
-    const int ntn = (N + U_BN - 1) / U_BN, ntk = (K + U_BK - 1) / U_BK;
-    const int splits = tnp_splits(M, N, K, true);
-    const int nchunks = 3 * ((M + U_BMS - 1) / U_BMS);
-    const int cps = (nchunks + splits - 1) / splits;
-    const int ntk_ = (K + U_BK - 1) / U_BK, slots = (ntk_ == 2 || ntk_ == 4) ? ntk_ : 1;
-    float* part_w = splits == 1 ? dw : (float*)ws;
-    float* part_b = db ? (splits * slots == 1 ? db : (float*)ws + (size_t)splits * N * K) : nullptr;
-    const size_t shm256 = 4 * U_STAGE;
-    if (set_lds_attr(gemm_tn_pipe256_kernel<true>, shm256, "gemm_tn_x3")) return 1;
-    const int ntiles256 = ntn * ntk, groups256 = (splits + 7) / 8;
-    hipLaunchKernelGGL(gemm_tn_pipe256_kernel<true>, dim3(8 * groups256 * ntiles256), dim3(512), shm256, s, (const bf16_t*)dy_hi,
-                       (const bf16_t*)a_hi, (const bf16_t*)dy_lo, (const bf16_t*)a_lo, part_w, part_b, M, N, K, ntk, ntiles256, splits, cps);
-    MBX_LAUNCH_CHECK("gemm_tn_x3");
-    if (splits > 1 && mbx_launch_colsum(part_w, splits, N * K, 0, N * K, dw, s)) return 1;
-    if (db && splits * slots > 1 && mbx_launch_colsum(part_b, splits * slots, N, 0, N, db, s)) return 1;
-    return 0;
+    return launch_tn256<true>(tn_plan_pipe(M, N, K, true), dy_hi, a_hi, dy_lo, a_lo, dw, db, M, N, K, ws, s);
 }

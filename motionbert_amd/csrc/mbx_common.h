@@ -178,6 +178,58 @@ __device__ __forceinline__ float gelu_erf_grad(float u) {
 // out[c] = sum_{p < nparts} part[p * stride + col0 + c],  c < ncols
 int mbx_launch_colsum(const float* part, int nparts, int stride, int col0, int ncols, float* out, hipStream_t s);
 
+// ---------------------------------------------------------------- runtime epilogue -> compile-time epilogue
+// f(std::integral_constant<int, E>{}) for the E among Es that equals `epi`, and its return value (>= 0); -1 if `epi` is not in the list.
+// Every GEMM launcher names the epilogues its kernel is instantiated for and words its own error.
+template <int... Es, class F> static inline int dispatch_epi(int epi, F&& f) {
+    int rc = -1;
+    (void)(... || (epi == Es && ((rc = f(std::integral_constant<int, Es>{})), true)));   // a LEFT fold: the kernels are instantiated in list order
+    return rc;
+}
+
+// ---------------------------------------------------------------- the weight-gradient GEMMs' launch plan
+// dW[N,K] = dY[M,N]^T . A[M,K]: every kernel of the family divides the tokens into `nchunks` chunks, gives `cps` consecutive chunks to each
+// of `splits` workgroups per output tile, and leaves `splits` fp32 partial tiles (+ `splits * slots` partial bias rows) in the workspace for
+// a deterministic column sum.  The plan is the ONE place that decides the split count and the workspace layout: the size functions return
+// its ws_bytes, the launchers pass its fields to the kernel, tn_finalize() issues its column sums.  tn_plan_f32 (gemm.hip) and tn_plan_pipe
+// (gemm_pipe.hip) fill it.  Known properties, kept because the split count fixes the summation order and with it the bits of dW:
+//   - the workspace is [splits][N K] partial tiles, then the partial bias rows; with one split the kernel writes dw itself (direct_w), with
+//     one split AND one slot db itself (direct_b).  Only the 256 x 256 kernel has more than one slot, so for every other kernel
+//     "splits * slots > 1" and "splits > 1" are the same condition.
+//   - ws_bytes reserves ONE bias row per split for fp32 and FOUR for bf16 / X3 (the most slots there are), whatever `slots` is.
+//   - X3 always runs the 256 x 256 kernel with 32-token chunks, but its split count comes from the tile shape bf16 would use for (N, K)
+//     (256 x 128 tiles and 64-token chunks unless N, K >= 256); the fp32 split count is clamped by the 32-token chunks for both fp32
+//     kernels, though the direct one walks 16-token chunks.
+//   - the split count is at most 64 (fp32), 128 (bf16 / X3 whole-round rule and fallback) or 256 (the round-6 search for 1 and 3 tiles).
+enum TnKernel { TN_F32_TRANSPOSING, TN_F32_DIRECT, TN_BF16_SMALL, TN_BF16_256, TN_X3 };
+struct TnPlan {
+    TnKernel kernel;
+    int ntn, ntk, tiles;      // output tiles along n, along k, and their product
+    int nchunks, splits, cps; // token chunks of the kernel, token splits, chunks per split
+    int slots;                // partial bias rows per split
+    size_t off_w, off_b;      // where part_w / part_b start in the workspace, in floats
+    bool direct_w, direct_b;  // the kernel writes dw / db itself: no partials, no column sum
+    size_t ws_bytes;
+    float* part_w(void* ws, float* dw) const { return direct_w ? dw : (float*)ws + off_w; }
+    float* part_b(void* ws, float* db) const { return !db ? nullptr : direct_b ? db : (float*)ws + off_b; }
+};
+// everything that follows from (ntn, ntk, nchunks, splits, slots); bias_rows = the bias rows per split that the size reserves
+static inline TnPlan tn_plan_layout(TnPlan p, int N, int K, int bias_rows) {
+    p.tiles = p.ntn * p.ntk;
+    p.cps = (p.nchunks + p.splits - 1) / p.splits;
+    p.off_w = 0;
+    p.off_b = (size_t)p.splits * N * K;
+    p.direct_w = p.splits == 1;
+    p.direct_b = p.splits * p.slots == 1;
+    p.ws_bytes = (p.off_b + (size_t)p.splits * bias_rows * N) * sizeof(float) + 256;
+    return p;
+}
+static inline int tn_finalize(const TnPlan& p, void* ws, float* dw, float* db, int N, int K, hipStream_t s) {
+    if (!p.direct_w && mbx_launch_colsum((float*)ws + p.off_w, p.splits, N * K, 0, N * K, dw, s)) return 1;
+    if (db && !p.direct_b && mbx_launch_colsum((float*)ws + p.off_b, p.splits * p.slots, N, 0, N, db, s)) return 1;
+    return 0;
+}
+
 // ---------------------------------------------------------------- pipelined bf16 GEMMs (gemm_pipe.hip)
 int mbx_launch_gemm_nt_pipe(const void* a, const void* w, const float* bias, int epi, void* out_t, void* out2_t, float* out_f,
                             const float* resid, const void* aux, int M, int N, int K, hipStream_t s);

@@ -184,7 +184,8 @@ def elementwise_bound(x64, amp64, K, r, lip=1.0, ops=1, eabs=0.0, mag64=None):
 
 
 def tn_splits(M, N, K, x3=False):
-    """Token splits of the weight gradient: a restatement of tnp_splits (gemm_pipe.hip) with its tile constants (256 x 256 tiles and
+    """Token splits of the weight gradient: an independent restatement of the split count in the launch plan of the pipelined kernels
+    (tn_plan_pipe -> tnp_splits, gemm_pipe.hip; TnPlan, mbx_common.h) with its tile constants (256 x 256 tiles and
     32-token chunks where N, K >= 256, else 256 x 128 and 64-token chunks; X3 walks three passes of chunks).  The test checks it against the
     library's workspace size wherever that size determines it."""
     big = N >= 256 and K >= 256          # (tnp_splits takes the tile shape from N, K alone, also for X3)

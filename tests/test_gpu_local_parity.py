@@ -356,7 +356,11 @@ def test_tile128_resid_and_lnbwd(ops, M, N, K):
 # ---------------------------------------------------------------------------------------------- weight gradient (gemm_tn_pipe256 / gemm_tn_pipe)
 @pytest.mark.parametrize('x3', [False, True])
 @pytest.mark.parametrize('M,N,K', [(M_STEP, 1536, 512), (M_STEP, 512, 1024), (M_STEP, 768, 256), (M_STEP + 37, 512, 512), (4131 + 5, 128, 512),
-                                   (4131 + 5, 512, 128), (257, 256, 256)])
+                                   (4131 + 5, 512, 128), (257, 256, 256),
+                                   # branches of the launch plan (TnPlan, csrc/mbx_common.h) that the shapes above do not reach: one chunk and one split
+                                   # (bf16: the kernel writes dw and db itself, no column sum); five tiles through the round-6 search; ntk = 8 with
+                                   # one bias slot; the small tile with its split count clamped to 1
+                                   (17, 256, 256), (4131, 1280, 256), (4131, 512, 2048), (33, 128, 512)])
 def test_weight_gradient(ops, M, N, K, x3):
     dy32, a32 = rows_scaled(M, N, seed=N + 4), rows_scaled(M, K, seed=K + 5)
     dw, db = nan(N, K, dtype=torch.float32), nan(N, dtype=torch.float32)
@@ -377,7 +381,7 @@ def test_weight_gradient(ops, M, N, K, x3):
             x += p[r0:r1].double().t() @ q[r0:r1].double()
             amp += p[r0:r1].double().abs().t() @ q[r0:r1].double().abs()
     # dW: the contraction runs over the M tokens, divided over `splits` workgroups per output tile whose fp32 partial tiles a column-sum pass
-    # adds (mbx_launch_gemm_tn_pipe / _x3): localerr.split_sum_bound.  The split count is localerr.tn_splits (the rule of tnp_splits restated);
+    # adds (tn_finalize): localerr.split_sum_bound.  The split count is localerr.tn_splits (the rule of tnp_splits restated);
     # the library's workspace holds splits x (N K + 4 N) floats + 256 bytes (X3: exactly; bf16: at least -- it is the larger of two kernels')
     splits = LE.tn_splits(M, N, K, x3)
     ws_bytes = int((ops.lib.mbx_gemm_tn_x3_workspace if x3 else ops.lib.mbx_gemm_tn_ws)(M, N, K))
@@ -387,12 +391,17 @@ def test_weight_gradient(ops, M, N, K, x3):
     geo = 'tn256' if N >= 256 and K >= 256 else 'tn'
     gate_once(f'gemm_tn.dw.{tag}', dw, lambda r0, r1: (x[r0:r1], LE.split_sum_bound(x[r0:r1], amp[r0:r1], len(terms) * M, splits)), geo)
     REPORT[f'gemm_tn.dw.{tag}.elementwise']['splits'] = splits
-    # db: column sums of dy (both planes for X3): the same split structure, up to four partial slots per split (tn_db_slots)
+    # db: column sums of dy (both planes for X3): the same split structure, up to four partial slots per split (TnPlan::slots)
     s = sum(c.double().sum(0) for c in col)
     sa = sum(c.double().abs().sum(0) for c in col)
     b = LE.row_abs_rel_check(db, s, (-(-len(col) * M // splits) + 64 + 4 * splits) * U * sa, LE.R_F32)
     note(f'gemm_tn.db.{tag}', 'bound', b['ratio'], 1.0, b['row'], 0)
     assert b['ratio'] <= 1.0, f'gemm_tn.db.{tag}: column {b["row"]} at {b["ratio"]:.2f} x its bound'
+    # without db the plan is the same and the bias sums are simply not taken: dw must not move by a bit
+    dw_nob = nan(N, K, dtype=torch.float32)
+    ops.gemm_tn(*((dyp, ap) if x3 else (dy, a)), dw_nob, None)
+    torch.cuda.synchronize()
+    assert torch.equal(dw_nob.view(torch.int32), dw.view(torch.int32)), f'gemm_tn.dw.{tag}: dw differs between the launches with and without db'
     if M == M_STEP and N == 1536 and not x3:
         thrice(f'gemm_tn.{tag}', lambda: ops.gemm_tn(dy, a, dw, db), [dw, db])
 
