@@ -184,6 +184,27 @@ def test_head(ops, dt, M, R, D):
     check(f'tanh_bwd.{tag}', t1, t2, TOL_T[dt])
 
 
+@pytest.mark.parametrize('numel', [4, 1028])
+def test_split_bf16_bits(ops, numel):
+    """mbx_split_bf16 (every bf16x3 operand that no producer writes as planes) against its restatement in torch, bit for bit:
+    hi == bf16(x), round to nearest even, and lo == bf16(x - hi); the two planes NaN-filled with a guard band behind them -- one float4
+    (no full block) and 257 of them (a second, partial block); values next to bf16 ties, subnormal remainders and exact bf16 included."""
+    from tests import rowerr as RE
+    x = rnd(numel, seed=21, scale=3.0)
+    x[:4] = torch.tensor([1.0 + 2.0 ** -8, 1.0 + 3 * 2.0 ** -8, -0.375, 2.0 ** -120], device=DEV)
+    (hi, hbuf), (lo, lbuf) = RE.guarded((numel,), torch.bfloat16, DEV), RE.guarded((numel,), torch.bfloat16, DEV)
+    ops._ck(ops.lib.mbx_split_bf16(x.data_ptr(), hi.data_ptr(), lo.data_ptr(), numel, ops._stream()))
+    torch.cuda.synchronize()
+    want_hi = x.to(torch.bfloat16)
+    want_lo = (x - want_hi.float()).to(torch.bfloat16)
+    assert RE.same_bits(hi, want_hi) and RE.same_bits(lo, want_lo), 'split_bf16: hi / lo differ from bf16(x) / bf16(x - hi)'
+    assert RE.same_bits(want_hi, RE.split_planes(x)[0]) and RE.same_bits(want_lo, RE.split_planes(x)[1])
+    assert RE.guard_intact(hbuf) and RE.guard_intact(lbuf), 'split_bf16 wrote past a plane'
+    h2, l2 = ops.split(x)       # the wrapper the engine calls
+    assert RE.same_bits(h2, want_hi) and RE.same_bits(l2, want_lo)
+    assert float((hi.double() + lo.double() - x.double()).abs().max()) <= 2.0 ** -16 * float(x.abs().max())
+
+
 @pytest.mark.parametrize('dt', TD)
 @pytest.mark.parametrize('numel', [64, 4131 * 1024, 1000 * 384 + 4])
 def test_gelu_fwd(ops, dt, numel):
