@@ -300,6 +300,17 @@ int mbx_tanh_bwd(const float* drep, const float* rep, void* dpre_t, size_t n, in
 size_t mbx_pose_loss_ws(int B, int T);
 int mbx_pose_loss(const float* pred, const float* gt, float lambda_scale, float lambda_velocity, float* losses, float* dpred,
                   float grad_scale, int B, int T, int J, void* ws, void* stream);
+/* All seven 3D losses of train.py:177-199 and the weighted total of :185-191:
+ *   total = loss_mpjpe + lambda_scale * n_mpjpe + lambda_velocity * loss_velocity + lambda_lv * loss_limb_var
+ *           + lambda_lg * loss_limb_gt + lambda_a * loss_angle + lambda_av * loss_angle_velocity    (lib/model/loss.py:98-203)
+ * losses[8] = {mpjpe, n_mpjpe, velocity, lv, lg, angle, angle_velocity, total}, the reference's log order; dpred (or NULL) =
+ * grad_scale * d total / d pred.  J must be 17: the 16 limbs and 18 limb pairs are those of the H36M skeleton.  The first three terms are
+ * the arithmetic of mbx_pose_loss: with the four new lambdas 0, losses[{0,1,2,7}] and dpred equal its outputs bit for bit.
+ * ws: >= mbx_pose_loss_full_ws(B,T) bytes. */
+size_t mbx_pose_loss_full_ws(int B, int T);
+int mbx_pose_loss_full(const float* pred, const float* gt, float lambda_scale, float lambda_velocity, float lambda_lv, float lambda_lg,
+                       float lambda_a, float lambda_av, float* losses, float* dpred, float grad_scale, int B, int T, int J, void* ws,
+                       void* stream);
 /* 2D re-projection loss of the pre-training's 2D branch (lib/model/loss.py:72-77 loss_2d_weighted, train.py:200-203):
  * loss[1] = mean |(pred_xy - target_xy) * conf| and, if dpred != NULL, dpred [B,T,J,3] = grad_scale * d loss / d pred (z row 0).
  * pred [B,T,J,3] f32; target: x, y at target[tok * target_stride + {0,1}]; conf at conf[tok * conf_stride] -- with strides 3 / 3

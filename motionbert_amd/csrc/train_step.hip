@@ -20,12 +20,10 @@
 // ---------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float norm3(float x, float y, float z) { return sqrtf(fmaf(x, x, fmaf(y, y, z * z))); }
 
-__global__ __launch_bounds__(256) void pose_loss_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
-                                                        float* __restrict__ part, float* __restrict__ dpred, float ls, float lv,
-                                                        float gscale, int B, int T, int J) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int frame = blockIdx.x * 4 + wave;
-    if (frame >= B * T) return;                      // whole waves only: the reductions below need all 64 lanes
+// the three terms of one frame: this lane's gradient of mpjpe + ls n_mpjpe + lv velocity (not yet scaled by grad_scale) and the frame's
+// three partial sums.  Shared by pose_loss_kernel and pose_loss_full_kernel: one arithmetic, the same bits.  All 64 lanes must be active.
+__device__ __forceinline__ void pose_base_frame(const float* __restrict__ pred, const float* __restrict__ gt, int frame, int lane, float ls,
+                                                float lv, int B, int T, int J, float (&grad)[3], float& s1, float& s2, float& s3) {
     const int t = frame % T;
     const bool on = lane < J;
     const size_t o = ((size_t)frame * J + (on ? lane : 0)) * 3;
@@ -39,7 +37,7 @@ __global__ __launch_bounds__(256) void pose_loss_kernel(const float* __restrict_
     const float r0 = p[0] - g[0], r1 = p[1] - g[1], r2 = p[2] - g[2];
     const float n1 = on ? norm3(r0, r1, r2) : 0.f;
     const float i1 = n1 > 0.f ? 1.0f / n1 : 0.f;
-    float grad[3] = {r0 * i1 * inv_n, r1 * i1 * inv_n, r2 * i1 * inv_n};
+    grad[0] = r0 * i1 * inv_n; grad[1] = r1 * i1 * inv_n; grad[2] = r2 * i1 * inv_n;
     // ---- n_mpjpe
     const float a = wave_sum(g[0] * p[0] + g[1] * p[1] + g[2] * p[2]);
     const float b = wave_sum(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
@@ -72,14 +70,26 @@ __global__ __launch_bounds__(256) void pose_loss_kernel(const float* __restrict_
             grad[0] -= d0 * i3; grad[1] -= d1 * i3; grad[2] -= d2 * i3;
         }
     }
-    if (on && dpred) {
+    s1 = wave_sum(n1) * inv_n; s2 = wave_sum(n2) * inv_n; s3 = wave_sum(n3) * inv_nv;
+}
+__device__ __forceinline__ float pose_base_total(float s1, float s2, float s3, float ls, float lv) { return s1 + ls * s2 + lv * s3; }
+
+__global__ __launch_bounds__(256) void pose_loss_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                        float* __restrict__ part, float* __restrict__ dpred, float ls, float lv,
+                                                        float gscale, int B, int T, int J) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int frame = blockIdx.x * 4 + wave;
+    if (frame >= B * T) return;                      // whole waves only: the reductions below need all 64 lanes
+    float grad[3], s1, s2, s3;
+    pose_base_frame(pred, gt, frame, lane, ls, lv, B, T, J, grad, s1, s2, s3);
+    if (lane < J && dpred) {
+        const size_t o = ((size_t)frame * J + lane) * 3;
 #pragma unroll
         for (int cc = 0; cc < 3; ++cc) dpred[o + cc] = gscale * grad[cc];
     }
-    const float s1 = wave_sum(n1) * inv_n, s2 = wave_sum(n2) * inv_n, s3 = wave_sum(n3) * inv_nv;
     if (lane == 0) {
         float* pr = part + (size_t)frame * 4;
-        pr[0] = s1; pr[1] = s2; pr[2] = s3; pr[3] = s1 + ls * s2 + lv * s3;
+        pr[0] = s1; pr[1] = s2; pr[2] = s3; pr[3] = pose_base_total(s1, s2, s3, ls, lv);
     }
 }
 extern "C" size_t mbx_pose_loss_ws(int B, int T) { return (size_t)B * T * 4 * sizeof(float) + 256; }
@@ -92,6 +102,235 @@ extern "C" int mbx_pose_loss(const float* pred, const float* gt, float lambda_sc
                        lambda_velocity, grad_scale, B, T, J);
     MBX_LAUNCH_CHECK("pose_loss");
     return mbx_launch_colsum((const float*)ws, B * T, 4, 0, 4, losses, s);   // fixed order, no atomics: deterministic
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// All seven losses of train.py:177-199: the three above plus the limb and angle terms of lib/model/loss.py:98-203 on the H36M skeleton.
+//   limb l   v_l = x[a_l] - x[b_l],  len = |v|                                   d len / d v = v / len (0 where len = 0)
+//   lv       mean_{b,l} var_t(len_p)  (unbiased; 0 for T <= 1)                   d / d len_{b,t,l} = 2 (len - mean_t len) / ((T-1) B 16)
+//   lg       mean |len_p - len_g|                                                sign(0) = 0
+//   angle k  theta = acos(clamp(cos, -1+1e-7, 1-1e-7)),  cos = uh . wh,  uh = u / max(|u|, 1e-8)   (F.cosine_similarity of two limbs)
+//            d theta / d cos = -1 / sqrt((1-cos)(1+cos)) inside the clamp, 0 outside;   d cos / d u = (wh - cos uh) / |u|
+//            (|u| < 1e-8: the clamp of the norm is active, d cos / d u = wh / 1e-8, as autograd gives)
+//   angle    mean |theta_p - theta_g|
+//   av       mean_{b,t>=1,k} |(theta_p,t - theta_p,t-1) - (theta_g,t - theta_g,t-1)|  (0 for T <= 1; never across a clip boundary)
+// Three launches and a column sum, all on the caller's stream, nothing read back:
+//   limb_angle_kernel      one wave per frame: len_p [F,16], theta_p, theta_g [F,18] to the workspace
+//   limb_mean_kernel       one wave per clip: mean_t len_p [B,16], a fixed-order sum
+//   pose_loss_full_kernel  one wave per frame: the eight partial sums and d total / d pred.  d / d theta and d / d len become per-limb vector
+//                          gradients through LDS: the angle lanes leave their two limb contributions in slots, limb lane l adds the slots
+//                          incident to limb l, joint lane j adds the signed limbs incident to joint j -- fixed lists, fixed order.
+// Gathers are plain loads and ordinary LDS reads (a frame is 204 bytes): no lane shuffles.
+// ---------------------------------------------------------------------------------------------------------------
+struct SkelTables {
+    int la[16], lb[16];         // limb l = x[la] - x[lb]                       (loss.py:103-108)
+    int ai[18], aj[18];         // angle k between the limbs ai and aj          (loss.py:159-176)
+    int limb_slot[16][4];       // limb l <- the angle slots 2 k + side that name it; 36 = the slot that holds zeros
+    int joint_limb[17][4];      // joint j <- the limbs that end in it; 16 = the slot that holds zeros
+    float joint_sign[17][4];    // +1 where j = la, -1 where j = lb
+};
+constexpr SkelTables make_skel_tables() {
+    constexpr int L[16][2] = {{0, 1}, {1, 2}, {2, 3}, {0, 4}, {4, 5}, {5, 6}, {0, 7}, {7, 8}, {8, 9}, {9, 10}, {8, 11}, {11, 12}, {12, 13},
+                              {8, 14}, {14, 15}, {15, 16}};
+    constexpr int A[18][2] = {{0, 3}, {0, 6}, {3, 6}, {0, 1}, {1, 2}, {3, 4}, {4, 5}, {6, 7}, {7, 10}, {7, 13}, {8, 13}, {10, 13}, {7, 8},
+                              {8, 9}, {10, 11}, {11, 12}, {13, 14}, {14, 15}};
+    SkelTables s{};
+    int nl[16] = {}, nj[17] = {};
+    for (int l = 0; l < 16; ++l) {
+        s.la[l] = L[l][0]; s.lb[l] = L[l][1];
+        for (int q = 0; q < 4; ++q) s.limb_slot[l][q] = 36;
+    }
+    for (int j = 0; j < 17; ++j)
+        for (int q = 0; q < 4; ++q) { s.joint_limb[j][q] = 16; s.joint_sign[j][q] = 0.f; }
+    for (int k = 0; k < 18; ++k) {
+        s.ai[k] = A[k][0]; s.aj[k] = A[k][1];
+        for (int side = 0; side < 2; ++side) { const int l = A[k][side]; s.limb_slot[l][nl[l]++] = 2 * k + side; }
+    }
+    for (int l = 0; l < 16; ++l)
+        for (int side = 0; side < 2; ++side) {
+            const int j = L[l][side];
+            s.joint_limb[j][nj[j]] = l; s.joint_sign[j][nj[j]++] = side == 0 ? 1.f : -1.f;
+        }
+    return s;
+}
+__constant__ SkelTables SKEL = make_skel_tables();
+#define MBX_ANGLE_CLAMP 0.9999999f      // 1 - 1e-7 in fp32 (1 - 2^-23), what torch's clamp compares an fp32 tensor with
+#define MBX_COS_EPS 1e-8f
+
+__device__ __forceinline__ float sign0(float x) { return (x > 0.f ? 1.f : 0.f) - (x < 0.f ? 1.f : 0.f); }
+// limb (lane < 16 ? lane : 0) of frame f: its vector in pred and in gt, and the two lengths
+__device__ __forceinline__ void limb_vectors(const float* __restrict__ pred, const float* __restrict__ gt, int f, int lane, float (&vp)[3],
+                                             float (&vg)[3], float& lp, float& lg) {
+    const int l = lane < 16 ? lane : 0;
+    const size_t a = (size_t)f * 51 + SKEL.la[l] * 3, b = (size_t)f * 51 + SKEL.lb[l] * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { vp[c] = pred[a + c] - pred[b + c]; vg[c] = gt[a + c] - gt[b + c]; }
+    lp = norm3(vp[0], vp[1], vp[2]); lg = norm3(vg[0], vg[1], vg[2]);
+}
+// the angle between the limbs i and j of v [16][3] (LDS), and what its gradient needs: the unit vectors, 1 / max(|.|, eps), the cosine
+// where the norm's clamp passes a gradient (else 0), d theta / d cos
+__device__ __forceinline__ float limb_angle(const float* v, int i, int j, float (&uh)[3], float (&wh)[3], float& iu, float& iw, float& pu,
+                                            float& pw, float& dth) {
+    const float u0 = v[i * 3], u1 = v[i * 3 + 1], u2 = v[i * 3 + 2], w0 = v[j * 3], w1 = v[j * 3 + 1], w2 = v[j * 3 + 2];
+    const float nu = norm3(u0, u1, u2), nw = norm3(w0, w1, w2);
+    iu = 1.0f / fmaxf(nu, MBX_COS_EPS); iw = 1.0f / fmaxf(nw, MBX_COS_EPS);
+    uh[0] = u0 * iu; uh[1] = u1 * iu; uh[2] = u2 * iu;
+    wh[0] = w0 * iw; wh[1] = w1 * iw; wh[2] = w2 * iw;
+    const float cs = uh[0] * wh[0] + uh[1] * wh[1] + uh[2] * wh[2];
+    const float cl = fminf(fmaxf(cs, -MBX_ANGLE_CLAMP), MBX_ANGLE_CLAMP);
+    pu = nu >= MBX_COS_EPS ? cs : 0.f; pw = nw >= MBX_COS_EPS ? cs : 0.f;
+    dth = (cs >= -MBX_ANGLE_CLAMP && cs <= MBX_ANGLE_CLAMP) ? -1.0f / sqrtf((1.0f - cl) * (1.0f + cl)) : 0.f;
+    return acosf(cl);
+}
+
+// blocks of 4 waves, one frame each; a wave past the last frame repeats it and writes nothing (every wave reaches the barriers)
+__global__ __launch_bounds__(256) void limb_angle_kernel(const float* __restrict__ pred, const float* __restrict__ gt, float* __restrict__ lenp,
+                                                         float* __restrict__ thp, float* __restrict__ thg, int F) {
+    __shared__ float sv[4][2][16 * 3];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int frame = blockIdx.x * 4 + wave;
+    const bool valid = frame < F;
+    const int f = valid ? frame : F - 1;
+    float vp[3], vg[3], lp, lg;
+    limb_vectors(pred, gt, f, lane, vp, vg, lp, lg);
+    if (lane < 16) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { sv[wave][0][lane * 3 + c] = vp[c]; sv[wave][1][lane * 3 + c] = vg[c]; }
+        if (valid) lenp[(size_t)f * 16 + lane] = lp;
+    }
+    __syncthreads();
+    const int k = lane < 18 ? lane : 0;
+    const int i = SKEL.ai[k], j = SKEL.aj[k];
+    float uh[3], wh[3], iu, iw, pu, pw, dth;
+    const float tp = limb_angle(sv[wave][0], i, j, uh, wh, iu, iw, pu, pw, dth);
+    const float tg = limb_angle(sv[wave][1], i, j, uh, wh, iu, iw, pu, pw, dth);
+    if (valid && lane < 18) { thp[(size_t)f * 18 + lane] = tp; thg[(size_t)f * 18 + lane] = tg; }
+}
+// one wave per clip: lane = 16 q + l sums len_p[b, t, l] over t = q, q + 4, ..; the four phases are added as (0 + 1) + (2 + 3)
+__global__ __launch_bounds__(64) void limb_mean_kernel(const float* __restrict__ lenp, float* __restrict__ mean, int T) {
+    __shared__ float red[4][16];
+    const int b = blockIdx.x, l = threadIdx.x & 15, q = threadIdx.x >> 4;
+    float s = 0.f;
+    for (int t = q; t < T; t += 4) s += lenp[((size_t)b * T + t) * 16 + l];
+    red[q][l] = s;
+    __syncthreads();
+    if (threadIdx.x < 16) mean[(size_t)b * 16 + l] = ((red[0][l] + red[1][l]) + (red[2][l] + red[3][l])) / (float)T;
+}
+__global__ __launch_bounds__(256) void pose_loss_full_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
+                                                             const float* __restrict__ lenp, const float* __restrict__ thp,
+                                                             const float* __restrict__ thg, const float* __restrict__ mean,
+                                                             float* __restrict__ part, float* __restrict__ dpred, float ls, float lv, float llv,
+                                                             float llg, float la, float lav, float gscale, int B, int T) {
+    constexpr int J = 17;
+    __shared__ float sv[4][16 * 3];       // pred's limb vectors
+    __shared__ float sa[4][37 * 3];       // angle slots: 2 k + side, and the zero slot
+    __shared__ float sl[4][17 * 3];       // limb gradients, and the zero slot
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int frame = blockIdx.x * 4 + wave;
+    const bool valid = frame < B * T;
+    const int f = valid ? frame : B * T - 1;
+    const int t = f % T, b = f / T;
+    float grad[3], s1, s2, s3;
+    pose_base_frame(pred, gt, f, lane, ls, lv, B, T, J, grad, s1, s2, s3);
+    const float inv_l = 1.0f / ((float)B * T * 16), inv_var = T > 1 ? 1.0f / ((float)(T - 1) * B * 16) : 0.f;
+    const float inv_a = 1.0f / ((float)B * T * 18), inv_av = T > 1 ? 1.0f / ((float)B * (T - 1) * 18) : 0.f;
+    const bool limb = lane < 16, ang = lane < 18;
+    const int l = limb ? lane : 0, k = ang ? lane : 0;
+    // ---- limb lengths: the variance over the clip and the distance to gt's
+    float vp[3], vg[3], lp, lg;
+    limb_vectors(pred, gt, f, lane, vp, vg, lp, lg);
+    const float lps = lenp[(size_t)f * 16 + l];
+    const float dm = lps - mean[(size_t)b * 16 + l], dlg = lps - lg;
+    // ---- angles of this frame and of its neighbours in the clip
+    const size_t ao = (size_t)f * 18 + k;
+    const float tp = thp[ao], tg = thg[ao];
+    const float da = tp - tg;
+    float dprev = 0.f, dnext = 0.f;
+    if (t >= 1) dprev = (tp - thp[ao - 18]) - (tg - thg[ao - 18]);
+    if (t + 1 < T) dnext = (thp[ao + 18] - tp) - (thg[ao + 18] - tg);
+    const float s4 = wave_sum(limb ? dm * dm : 0.f) * inv_var, s5 = wave_sum(limb ? fabsf(dlg) : 0.f) * inv_l;
+    const float s6 = wave_sum(ang ? fabsf(da) : 0.f) * inv_a, s7 = wave_sum(ang ? fabsf(dprev) : 0.f) * inv_av;
+    if (dpred) {
+        // the four new lambdas all 0: the gradient is mbx_pose_loss's, bit for bit (nothing is added, not even a zero)
+        if (llv != 0.f || llg != 0.f || la != 0.f || lav != 0.f) {
+            if (limb) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) sv[wave][lane * 3 + c] = vp[c];
+            }
+            if (lane == 63) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) { sa[wave][36 * 3 + c] = 0.f; sl[wave][16 * 3 + c] = 0.f; }
+            }
+            __syncthreads();
+            // d total / d theta -> d / d cos -> the two limbs of the angle
+            float uh[3], wh[3], iu, iw, pu, pw, dth;
+            limb_angle(sv[wave], SKEL.ai[k], SKEL.aj[k], uh, wh, iu, iw, pu, pw, dth);
+            const float gc = (la * inv_a * sign0(da) + lav * inv_av * (sign0(dprev) - sign0(dnext))) * dth;
+            if (ang) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    sa[wave][(2 * lane) * 3 + c] = gc * (wh[c] - pu * uh[c]) * iu;
+                    sa[wave][(2 * lane + 1) * 3 + c] = gc * (uh[c] - pw * wh[c]) * iw;
+                }
+            }
+            __syncthreads();
+            // d total / d len along the limb, plus the angle slots that name this limb
+            const float il = lp > 0.f ? 1.0f / lp : 0.f;
+            const float gl = (llv * inv_var * 2.0f * dm + llg * inv_l * sign0(dlg)) * il;
+            float acc[3] = {gl * vp[0], gl * vp[1], gl * vp[2]};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int s = SKEL.limb_slot[l][q];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) acc[c] += sa[wave][s * 3 + c];
+            }
+            if (limb) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) sl[wave][lane * 3 + c] = acc[c];
+            }
+            __syncthreads();
+            const int jn = lane < J ? lane : 0;
+            float e[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int m = SKEL.joint_limb[jn][q];
+                const float sg = SKEL.joint_sign[jn][q];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) e[c] += sg * sl[wave][m * 3 + c];
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) grad[c] += e[c];
+        }
+        if (valid && lane < J) {
+            const size_t o = ((size_t)f * J + lane) * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) dpred[o + c] = gscale * grad[c];
+        }
+    }
+    if (valid && lane == 0) {
+        float* pr = part + (size_t)f * 8;
+        pr[0] = s1; pr[1] = s2; pr[2] = s3; pr[3] = s4; pr[4] = s5; pr[5] = s6; pr[6] = s7;
+        pr[7] = pose_base_total(s1, s2, s3, ls, lv) + llv * s4 + llg * s5 + la * s6 + lav * s7;
+    }
+}
+// workspace, in floats: part [F,8] | len_p [F,16] | theta_p [F,18] | theta_g [F,18] | mean_t len_p [B,16]
+extern "C" size_t mbx_pose_loss_full_ws(int B, int T) { return ((size_t)B * T * 60 + (size_t)B * 16) * sizeof(float) + 256; }
+extern "C" int mbx_pose_loss_full(const float* pred, const float* gt, float lambda_scale, float lambda_velocity, float lambda_lv,
+                                  float lambda_lg, float lambda_a, float lambda_av, float* losses, float* dpred, float grad_scale, int B,
+                                  int T, int J, void* ws, void* stream) {
+    MBX_CHECK_ARG(pred && gt && losses && ws, "pose_loss_full: null pointer");
+    MBX_CHECK_ARG(J == 17, "pose_loss_full: J=%d, the limb and angle losses are defined on the 17-joint H36M skeleton", J);
+    MBX_CHECK_ARG(B > 0 && T > 0 && (long long)B * T <= (1 << 24), "pose_loss_full: bad shape B=%d T=%d (B T <= 2^24)", B, T);
+    hipStream_t s = (hipStream_t)stream;
+    const int F = B * T;
+    float* part = (float*)ws;
+    float *lenp = part + (size_t)F * 8, *thp = lenp + (size_t)F * 16, *thg = thp + (size_t)F * 18, *mean = thg + (size_t)F * 18;
+    hipLaunchKernelGGL(limb_angle_kernel, dim3((F + 3) / 4), dim3(256), 0, s, pred, gt, lenp, thp, thg, F);
+    hipLaunchKernelGGL(limb_mean_kernel, dim3(B), dim3(64), 0, s, lenp, mean, T);
+    hipLaunchKernelGGL(pose_loss_full_kernel, dim3((F + 3) / 4), dim3(256), 0, s, pred, gt, lenp, thp, thg, mean, part, dpred, lambda_scale,
+                       lambda_velocity, lambda_lv, lambda_lg, lambda_a, lambda_av, grad_scale, B, T);
+    MBX_LAUNCH_CHECK("pose_loss_full");
+    return mbx_launch_colsum(part, F, 8, 0, 8, losses, s);   // fixed order, no atomics: deterministic
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -83,6 +83,8 @@ SIGNATURES = {
     'mbx_tanh_bwd': (_i, [_vp, _vp, _vp, _sz, _i, _vp]),
     'mbx_pose_loss_ws': (_sz, [_i, _i]),
     'mbx_pose_loss': (_i, [_vp, _vp, _f, _f, _vp, _vp, _f, _i, _i, _i, _vp, _vp]),
+    'mbx_pose_loss_full_ws': (_sz, [_i, _i]),
+    'mbx_pose_loss_full': (_i, [_vp, _vp] + [_f] * 6 + [_vp, _vp, _f, _i, _i, _i, _vp, _vp]),
     'mbx_loss_2d_weighted_ws': (_sz, [_i, _i]),
     'mbx_loss_2d_weighted': (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _f, _i, _i, _i, _vp, _vp]),
     'mbx_pool_rep_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, C.c_uint64, _vp]),
@@ -680,6 +682,17 @@ class HipOps:
         ws = self._ws(('pl', B, T), self.lib.mbx_pose_loss_ws, B, T, device=pred.device)
         self._ck(self.lib.mbx_pose_loss(_p(pred), _p(gt), float(lambda_scale), float(lambda_velocity), _p(losses), _p(dpred),
                                         float(grad_scale), B, T, J, _p(ws), self._stream()))
+
+    def pose_loss_full(self, pred, gt, lambdas6, losses, dpred, grad_scale=1.0):
+        """lambdas6 = (lambda_scale, lambda_velocity, lambda_lv, lambda_lg, lambda_a, lambda_av); losses [8] =
+        [mpjpe, n_mpjpe, velocity, lv, lg, angle, angle_velocity, total]; dpred [B,T,17,3] or None."""
+        B, T, J, D = pred.shape
+        if D != 3 or gt.shape != pred.shape or len(lambdas6) != 6:
+            raise RuntimeError(f'libmbx: pose_loss_full needs pred, gt [B,T,17,3] and six lambdas, got {tuple(pred.shape)} / {tuple(gt.shape)} / '
+                               f'{len(lambdas6)} lambdas')
+        ws = self._ws(('plf', B, T), self.lib.mbx_pose_loss_full_ws, B, T, device=pred.device)
+        self._ck(self.lib.mbx_pose_loss_full(_p(pred), _p(gt), *[float(v) for v in lambdas6], _p(losses), _p(dpred), float(grad_scale),
+                                             B, T, J, _p(ws), self._stream()))
 
     def loss_2d_weighted(self, pred, target, conf, loss, dpred, grad_scale=1.0):
         """pred [B,T,J,3]; target [B,T,J,>=2] (x, y first) and conf [B,T,J] or [B,T,J,1] may be strided VIEWS of one [B,T,J,3]

@@ -6,6 +6,9 @@ backbone itself runs in tens of milliseconds those pieces show, so they are part
 
   pose_loss(pred, gt, ...)   loss_mpjpe + lambda_scale * n_mpjpe + lambda_velocity * loss_velocity and its gradient in ONE
                              kernel pass (`mbx_pose_loss`); the four loss values stay on the device.
+  pose_loss_full(pred, gt, ...)  all seven losses of train.py:177-199 -- the three above plus loss_limb_var, loss_limb_gt, loss_angle and
+                             loss_angle_velocity -- their weighted total and its gradient (`mbx_pose_loss_full`); the eight values the
+                             reference logs stay on the device.  `PretrainStepFull` / `GraphedTrainStepFull` are the steps built on it.
   FlatAdamW                  the model's parameters re-laid into ONE flat fp32 buffer in backward-completion order -- the
                              same order in which the backbone's backward writes its single flat gradient buffer -- so that
                              `step()` is one launch of `mbx_adamw_step` over 42.5 M elements (and, under data parallelism,
@@ -54,6 +57,40 @@ def pose_loss(pred: torch.Tensor, gt: torch.Tensor, lambda_scale: float = 0.5, l
     return _PoseLossFn.apply(ops, pred, gt, float(lambda_scale), float(lambda_velocity))
 
 
+class _PoseLossFullFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ops, pred, gt, lambdas6):
+        pred_c, gt_c = pred.contiguous().float(), gt.contiguous().float()
+        losses = torch.empty(8, dtype=torch.float32, device=pred.device)
+        dpred = torch.empty_like(pred_c) if ctx.needs_input_grad[1] else None
+        ops.pose_loss_full(pred_c, gt_c, lambdas6, losses, dpred)
+        ctx.dpred = dpred
+        ctx.mark_non_differentiable(losses)
+        return losses[7].clone(), losses
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dtotal, _dlosses):
+        d = ctx.dpred
+        ctx.dpred = None
+        return None, (d * dtotal if d is not None else None), None, None
+
+
+def pose_loss_full(pred: torch.Tensor, gt: torch.Tensor, lambda_scale: float = 0.5, lambda_velocity: float = 20.0, lambda_lv: float = 0.,
+                   lambda_lg: float = 0., lambda_a: float = 0., lambda_av: float = 0., ops=None):
+    """`(total, losses)` with `losses = [mpjpe, n_mpjpe, velocity, lv, lg, angle, angle_velocity, total]` (device tensor, no host sync;
+    the order of the reference's log, train.py:192-199) for pred, gt [B,T,17,3]: the three terms of `pose_loss` plus
+    `lambda_lv * loss_limb_var + lambda_lg * loss_limb_gt + lambda_a * loss_angle + lambda_av * loss_angle_velocity`
+    (lib/model/loss.py:98-203 combined as train.py:185-191).  `total` is differentiable with respect to `pred`.  With the four new
+    lambdas at 0 the total and the gradient are `pose_loss`'s bit for bit and the four extra values are still computed: the
+    reference's log without a single `.item()`."""
+    if ops is None:
+        from . import hip_ops
+        ops = hip_ops.get()
+    lambdas6 = tuple(float(v) for v in (lambda_scale, lambda_velocity, lambda_lv, lambda_lg, lambda_a, lambda_av))
+    return _PoseLossFullFn.apply(ops, pred, gt, lambdas6)
+
+
 class _Loss2DFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ops, pred, target, conf):
@@ -91,7 +128,7 @@ class PretrainStep:
         losses = step(batch_2d, batch_2d, has_3d=False, has_gt=...)            # 2D batches  [B,81|30,17,3], target = input
 
     has_3d: pose losses `loss_mpjpe + lambda_scale * n_mpjpe + lambda_3d_velocity * loss_velocity` (the other lambdas are 0
-    in every shipped config and are refused otherwise) -> `losses` = [mpjpe, n_mpjpe, velocity, total];
+    in every shipped config and are refused here: `PretrainStepFull` takes them) -> `losses` = [mpjpe, n_mpjpe, velocity, total];
     not has_3d: `loss_2d_weighted(pred, batch_gt, conf)` with conf = the input's third channel BEFORE augmentation
     (train.py:163-164) -> `losses` = [0, 0, 0, 2d_proj].  `rootrel`: batch_gt -= batch_gt[:, :, 0:1] (train.py:165-166), else the
     depth of the first frame's root is moved to 0 (:168).  `aug.augment2D(batch_input, noise=noise and has_gt, mask=mask)`
@@ -103,7 +140,7 @@ class PretrainStep:
                  lambda_scale: float = 0.5, lambda_velocity: float = 20.0, lambda_lv=0.0, lambda_lg=0.0, lambda_a=0.0, lambda_av=0.0):
         if any(float(v) != 0.0 for v in (lambda_lv, lambda_lg, lambda_a, lambda_av)):
             raise NotImplementedError('limb / angle losses (lambda_lv, lambda_lg, lambda_a, lambda_av) are 0 in every shipped config; '
-                                      'only loss_mpjpe + n_mpjpe + loss_velocity are fused')
+                                      'only loss_mpjpe + n_mpjpe + loss_velocity are fused here; PretrainStepFull computes all seven')
         if (mask or noise) and aug is None:
             raise ValueError('mask / noise need an Augmenter2D (motionbert_amd.augment.Augmenter2D(args))')
         self.net, self.opt, self.aug = net, optimizer, aug
@@ -132,6 +169,46 @@ class PretrainStep:
             total = loss_2d_weighted(pred, batch_gt, conf)
             z = total.detach() * 0
             losses = torch.stack([z, z, z, total.detach()])
+        total.backward()
+        self.opt.step()
+        return losses
+
+
+class PretrainStepFull(PretrainStep):
+    """`PretrainStep` with all seven 3D losses of train.py:177-199: the same constructor, and nonzero `lambda_lv`, `lambda_lg`,
+    `lambda_a`, `lambda_av` are accepted.  3D batches return the eight values of the reference's log,
+    `losses` = [mpjpe, n_mpjpe, velocity, lv, lg, angle, angle_velocity, total] (`pose_loss_full`); 2D batches [0] * 7 + [2d_proj].
+    With the four lambdas at 0 the parameters move exactly as under `PretrainStep`."""
+    def __init__(self, net, optimizer, aug=None, rootrel: bool = True, mask: bool = True, noise: bool = True, no_conf: bool = False,
+                 lambda_scale: float = 0.5, lambda_velocity: float = 20.0, lambda_lv=0.0, lambda_lg=0.0, lambda_a=0.0, lambda_av=0.0):
+        super().__init__(net, optimizer, aug=aug, rootrel=rootrel, mask=mask, noise=noise, no_conf=no_conf, lambda_scale=lambda_scale,
+                         lambda_velocity=lambda_velocity)
+        self.lambdas4 = tuple(float(v) for v in (lambda_lv, lambda_lg, lambda_a, lambda_av))
+
+    def __call__(self, batch_input: torch.Tensor, batch_gt: torch.Tensor, has_3d: bool, has_gt: bool = True, seed=None) -> torch.Tensor:
+        # PretrainStep.__call__ with the eight-value loss in the 3D branch (PretrainStep itself stays as it is: its four-value
+        # `losses` is what its callers index)
+        with torch.no_grad():
+            conf = None
+            if self.no_conf:
+                batch_input = batch_input[..., :2]
+            if not has_3d:
+                conf = batch_input[..., 2:]
+            if self.rootrel:
+                batch_gt = batch_gt - batch_gt[:, :, 0:1, :]
+            else:
+                batch_gt = batch_gt.clone()
+                batch_gt[..., 2] = batch_gt[..., 2] - batch_gt[:, 0:1, 0:1, 2]
+            if self.mask or self.noise:
+                batch_input = self.aug.augment2D(batch_input, noise=(self.noise and has_gt), mask=self.mask, seed=seed)
+        pred = self.net(batch_input)
+        self.opt.zero_grad(set_to_none=True)
+        if has_3d:
+            total, losses = pose_loss_full(pred, batch_gt, self.ls, self.lv, *self.lambdas4)
+        else:
+            total = loss_2d_weighted(pred, batch_gt, conf)
+            z = total.detach() * 0
+            losses = torch.stack([z] * 7 + [total.detach()])
         total.backward()
         self.opt.step()
         return losses
@@ -436,3 +513,23 @@ class GraphedTrainStep:
         self.gt.copy_(gt)
         self.graph.replay()
         return self.losses.clone()
+
+
+class GraphedTrainStepFull(GraphedTrainStep):
+    """`GraphedTrainStep` with the eight-loss step captured: forward + `pose_loss_full` + backward + FlatAdamW update as one hipGraph.
+
+        step = GraphedTrainStepFull(model, opt, x_example, gt_example, lambda_lv=..., lambda_lg=..., lambda_a=..., lambda_av=...)
+        losses = step(x, gt)            # device tensor [mpjpe, n_mpjpe, velocity, lv, lg, angle, angle_velocity, total]"""
+
+    def __init__(self, model, optimizer: FlatAdamW, x: torch.Tensor, gt: torch.Tensor, lambda_scale: float = 0.5,
+                 lambda_velocity: float = 20.0, lambda_lv: float = 0., lambda_lg: float = 0., lambda_a: float = 0., lambda_av: float = 0.,
+                 warmup: int = 2):
+        self.lambdas4 = tuple(float(v) for v in (lambda_lv, lambda_lg, lambda_a, lambda_av))      # (read by _one during the capture)
+        super().__init__(model, optimizer, x, gt, lambda_scale=lambda_scale, lambda_velocity=lambda_velocity, warmup=warmup)
+
+    def _one(self):
+        self.opt.zero_grad(set_to_none=True)
+        total, losses = pose_loss_full(self.model(self.x), self.gt, self.ls, self.lv, *self.lambdas4)
+        total.backward()
+        self.opt.step()
+        return losses
