@@ -31,6 +31,7 @@ as row constants in its epilogue (mbx_rows_gemm_nk_ln), the MLP as ONE kernel (m
 """
 from __future__ import annotations
 
+from collections import namedtuple
 from dataclasses import dataclass
 from typing import Any, ClassVar, Dict, List, Optional
 
@@ -120,28 +121,36 @@ ORDER = {
 }
 
 
+STREAMS = (('blocks_st', 'st'), ('blocks_ts', 'ts'))      # (module list, Block flavour) of the two streams
+LINEARS = {'attn': ('qkv', 'proj'), 'mlp': ('fc1', 'fc2')}      # (Linear-in, Linear-out) of a sub-layer
+
+
+def sublayers(cfg: ModelCfg):
+    """(prefix, level, sub, typ, norm, mod, mode) of every sub-layer in execution order: stream by stream, level by level, ORDER."""
+    for stream, kind in STREAMS:
+        for i in range(cfg.depth):
+            for sub, (typ, norm, mod, mode) in enumerate(ORDER[kind]):
+                yield f'{stream}.{i}', i, sub, typ, norm, mod, mode
+
+
 def linear_names(cfg: ModelCfg) -> List[str]:
     """Every nn.Linear whose weight runs through the MFMA GEMM (prefix without '.weight')."""
     names = []
-    for stream in ('blocks_st', 'blocks_ts'):
-        for i in range(cfg.depth):
-            for a in ('attn_s', 'attn_t'):
-                names += [f'{stream}.{i}.{a}.qkv', f'{stream}.{i}.{a}.proj']
-            for m in ('mlp_s', 'mlp_t'):
-                names += [f'{stream}.{i}.{m}.fc1', f'{stream}.{i}.{m}.fc2']
-    names.append('pre_logits.fc')
-    return names
+    for pre, _, sub, *_ in sublayers(cfg):
+        if sub == 0:      # per Block in this order, whatever its flavour: the flat gradient layout follows it
+            for mod in ('attn_s', 'attn_t', 'mlp_s', 'mlp_t'):
+                names += [f'{pre}.{mod}.{lin}' for lin in LINEARS[mod[:-2]]]
+    return names + ['pre_logits.fc']
 
 
 def folded_pairs(cfg: ModelCfg) -> List[tuple]:
     """(linear, norm) pairs whose LayerNorm is folded into the Linear it feeds (bf16 path): every norm1 -> qkv and norm2 -> fc1
     of every Block (DSTformer.py:241-249).  The final `norm` -> pre_logits.fc keeps the plain kernels."""
     pairs = []
-    for stream in ('blocks_st', 'blocks_ts'):
-        for i in range(cfg.depth):
-            for sfx in ('s', 't'):
-                pairs.append((f'{stream}.{i}.attn_{sfx}.qkv', f'{stream}.{i}.norm1_{sfx}'))
-                pairs.append((f'{stream}.{i}.mlp_{sfx}.fc1', f'{stream}.{i}.norm2_{sfx}'))
+    for pre, _, sub, *_ in sublayers(cfg):
+        if sub == 0:      # per Block the spatial pairs first, whatever its flavour: the descriptor tables follow this order
+            for mod, norm in (('attn_s', 'norm1_s'), ('mlp_s', 'norm2_s'), ('attn_t', 'norm1_t'), ('mlp_t', 'norm2_t')):
+                pairs.append((f'{pre}.{mod}.{LINEARS[mod[:-2]][0]}', f'{pre}.{norm}'))
     return pairs
 
 
@@ -153,6 +162,13 @@ def grad_bucket(name: str, depth: int) -> int:
     if name.startswith(('blocks_st.', 'blocks_ts.', 'ts_attn.')):
         return depth - int(name.split('.')[1])
     return depth + 1
+
+
+class Drops(namedtuple('Drops', 'p seed_branch seed_act p_path seed_path p_attn seed_attn')):
+    """Active dropout of one sub-layer (`Engine._drops`): rates and mask seeds of proj_drop / the MLP drops (on the branch output, after
+    the activation), of DropPath and of the dropout on the attention probabilities."""
+    branch = property(lambda d: d.p > 0 or d.p_path > 0)      # dropout or DropPath on the branch output (DSTformer.py:84,148-149,241-242)
+    attn = property(lambda d: (d.p_attn, d.seed_attn) if d.p_attn > 0 else None)      # `drop` of the attention kernels (mask applied inside)
 
 
 class Engine:
@@ -193,8 +209,7 @@ class Engine:
         # epilogue of the dX GEMM from row dots the attention-backward / GELU' kernels emit -- 40 LayerNorm-backward launches and the
         # saved fp32 sub-layer inputs disappear.  Off with dropout (the masks sit between the producer and the row dots), in the
         # fp32-class modes (bf16 kernels only), or by request (model.fold_ln = False / MBX_FOLD_LN=0: the A/B switch).
-        self.fold = (sw.fold_ln and not x3 and drop_seed is None and
-                     bool(getattr(ops, 'can_fold', lambda *_: False)(tdtype, cfg)))
+        self.fold = sw.fold_ln and not x3 and drop_seed is None and self._can('can_fold')
         # Gradient residual stream in the operand type BETWEEN the four sub-layers of a Block (round 4; fp32 at the Block boundaries,
         # fp32 arithmetic in the kernels): the folded LayerNorm-backward GEMM reads its dres as bf16 and writes ONLY the bf16 dx, which
         # is the stream and the next GEMMs' operand at once -- 4 instead of 12 bytes per element and launch.  Numerics:
@@ -207,13 +222,13 @@ class Engine:
         # epilogue of a row-owner GEMM that takes both row means from its own accumulators (mbx_rows_lnbwd_t): the producers of dY --
         # attention backward, the GELU' GEMM -- run WITHOUT their row dots there, and no row-constant launch is needed.  The first
         # sub-layer of a Block (fp32 out, the other block's gradient added) keeps the tile kernel.  MBX_ROWS_LNBWD=0: the A/B switch.
-        self.rows_lnbwd = (sw.rows_lnbwd and bool(getattr(ops, 'can_rows_lnbwd', lambda *_: False)(tdtype, cfg)))
+        self.rows_lnbwd = sw.rows_lnbwd and self._can('can_rows_lnbwd')
         self.Pn: Dict[str, torch.Tensor] = {}       # transposed folded weights in the fragment order of mbx_rows_lnbwd_t
         # Round 5: the FORWARD residual GEMM (proj / fc2) of a sub-layer that is followed by a LayerNorm runs on the same row-owner shape
         # and leaves the plain normalisation of its output rows with them (mbx_rows_resid_ln): three of the four LayerNorm launches of a
         # Block -- each a second read of the fp32 rows -- disappear.  Folded sequencing only (the kernel writes xhat, not gamma xhat +
         # beta), no dropout on the branch.  MBX_ROWS_RESID_LN=0: the A/B switch.
-        self.rows_resid_ln = (sw.rows_resid_ln and bool(getattr(ops, 'can_rows_resid_ln', lambda *_: False)(tdtype, cfg)))
+        self.rows_resid_ln = sw.rows_resid_ln and self._can('can_rows_resid_ln')
         self.Pf: Dict[str, torch.Tensor] = {}       # proj / fc2 weights of those sub-layers in the fragment order of the row-owner kernels
         # Round 5: the gradient of the residual stream stays in the operand type ACROSS Block boundaries too: the first
         # sub-layer of a Block then also takes the row-owner LayerNorm backward (no row dots, no row constants, bf16 out), and the fusion
@@ -224,7 +239,7 @@ class Engine:
         # Round 5: with the row means taken by that kernel the GELU' epilogue no longer has to produce the dot of
         # du with the pre-activation, so fc1's forward epilogue saves gelu'(u) -- taken from the fp32 accumulator -- INSTEAD of u (same
         # bytes) and the backward epilogue is one multiply (mbx_gemm_nt_gelu_d / mbx_gemm_nt_mul).  MBX_GELU_D=0: the A/B switch.
-        self.gelu_d = (sw.gelu_d and self.rows_lnbwd and bool(getattr(ops, 'can_gelu_d', lambda *_: False)(tdtype, cfg)))
+        self.gelu_d = sw.gelu_d and self.rows_lnbwd and self._can('can_gelu_d')
         # no-grad sequencing of a Block (decided per forward): raw-operand LayerNorm + fused MLP, see the module docstring
         self.rawln = False
         self.rawln_allowed = sw.rawln      # A/B switch: 0 = the training sequencing without saves
@@ -249,12 +264,15 @@ class Engine:
     def _t(self, *shape):
         return torch.empty(shape, dtype=self.T, device=self.dev)
 
-    def _bias(self, name):
-        return self.P.get(name + '.bias')
+    def _can(self, name: str) -> bool:      # capability probe of the kernel provider (none: no)
+        return bool(getattr(self.ops, name, lambda *_: False)(self.T, self.cfg))
 
-    def _drops(self, pre: str, sub: int):
-        """Active dropout of sub-layer `sub` of block `pre` ('blocks_st.3'): None, or (p, seed_branch, seed_act, p_path, seed_path,
-        p_attn, seed_attn)."""
+    @staticmethod
+    def _await(extra):      # dual-stream backward: the other block's input gradient, awaited only now
+        return extra() if callable(extra) else extra
+
+    def _drops(self, pre: str, sub: int) -> Optional[Drops]:
+        """Active dropout of sub-layer `sub` of block `pre` ('blocks_st.3'), or None."""
         if self.drop_seed is None:
             return None
         from .dropmask import site_seed
@@ -264,16 +282,21 @@ class Engine:
         if cfg.drop <= 0 and pp <= 0 and cfg.attn_drop <= 0:
             return None
         ss = lambda kind: site_seed(self.drop_seed, level, stream, sub, kind)
-        return (cfg.drop, ss(1), ss(2), pp, ss(3), cfg.attn_drop, ss(0))
+        return Drops(cfg.drop, ss(1), ss(2), pp, ss(3), cfg.attn_drop, ss(0))
 
     def _xn(self, sv, pre, norm):
         """The normalised GEMM operand of a sub-layer in backward: the saved one, or (recompute mode) LayerNorm of the saved input."""
-        if sv['xn'] is not None:
-            return sv['xn']
-        cfg, P = self.cfg, self.P
-        xn, mean, rstd = self._op(self.M, cfg.C), self._f(self.M), self._f(self.M)
-        self.ops.layernorm_fwd(sv['x'], P[f'{pre}.{norm}.weight'], P[f'{pre}.{norm}.bias'], cfg.eps, xn, mean, rstd)
-        return self._mm(xn)
+        return sv['xn'] if sv['xn'] is not None else self._mm(self._layernorm(sv['x'], f'{pre}.{norm}')[0])
+
+    def _layernorm(self, x, norm):      # -> (xn, mean, rstd): LayerNorm `norm` of x, or (None) its plain normalisation xhat
+        xn, mean, rstd = self._op(self.M, self.cfg.C), self._f(self.M), self._f(self.M)
+        self.ops.layernorm_fwd(x, self.P[norm + '.weight'] if norm else None, self.P[norm + '.bias'] if norm else None, self.cfg.eps, xn, mean, rstd)
+        return xn, mean, rstd
+
+    def _norm_in(self, x, pre, norm, ln):
+        """(GEMM operand, mean, rstd) of a sub-layer's LayerNorm; `ln` when LayerNorm(x) came with x from its producer."""
+        xn, mean, rstd = ln if ln is not None else self._layernorm(x, None if self.fold else f'{pre}.{norm}')
+        return self._mm(xn), mean, rstd
 
     def _mm(self, t):
         """GEMM operand form of a T-typed tensor: itself, or its (hi, lo) bf16 planes in bf16x3 mode (already planes: unchanged)."""
@@ -333,37 +356,29 @@ class Engine:
             self.Wt.update(ft)
             if self.rows_resid_ln and not self.rawln:
                 # proj / fc2 of the first three sub-layers of every Block (the fourth feeds the fusion, not a LayerNorm)
-                lins = [f'{stream}.{i}.{m}.' + ('proj' if typ == 'attn' else 'fc2') for stream, kind in (('blocks_st', 'st'), ('blocks_ts', 'ts'))
-                        for i in range(cfg.depth) for typ, _norm, m, _mode in ORDER[kind][:-1]]
+                lins = [f'{pre}.{mod}.{LINEARS[typ][1]}' for pre, _, sub, typ, _, mod, _ in sublayers(cfg) if sub < 3]
                 self.Pf = dict(zip(lins, ops.rows_n_pack_many([self.Wn[lin] for lin in lins])))
             if need_grad and self.rows_lnbwd and self.gstream_allowed:
                 # (not for the first sub-layer of a Block whose input gradient leaves in fp32 with the other stream's gradient added --
                 # MBX_BLOCK_GRAD_T=0: the tile kernel's epilogue)
-                first = {f'{stream}.{i}.{ORDER[kind][0][2]}.qkv' for stream, kind in (('blocks_st', 'st'), ('blocks_ts', 'ts')) for i in range(cfg.depth)
-                         if not (self.block_grad_t and cfg.att_fuse)}
+                first = {f'{pre}.{mod}.qkv' for pre, _, sub, _, _, mod, _ in sublayers(cfg) if sub == 0 and not (self.block_grad_t and cfg.att_fuse)}
                 lins = [lin for lin, _ in pairs if lin not in first]
                 self.Pn = dict(zip(lins, ops.rows_n_pack_many([ft[lin] for lin in lins])))
             if self.rawln:
-                for stream, kind in (('blocks_st', 'st'), ('blocks_ts', 'ts')):
-                    for i in range(cfg.depth):
-                        order = ORDER[kind]
-                        for sub, (typ, _norm, m, _mode) in enumerate(order):
-                            if typ != 'mlp':
-                                continue
-                            pre = f'{stream}.{i}.{m}'
-                            # the proj that runs in front of this MLP in the same kernel: the attention right before it in ORDER
-                            a = order[sub - 1][2] if sub > 0 and order[sub - 1][0] == 'attn' else None
-                            if self.proj_mlp and a is not None:
-                                self.Pk_proj[pre] = f'{stream}.{i}.{a}.proj'
-                                self.Pk[pre] = ops.proj_mlp_pack_weights(self.Wn[self.Pk_proj[pre]], self.Wn[pre + '.fc1'], self.Wn[pre + '.fc2'])
-                            else:
-                                self.Pk[pre] = ops.mlp_pack_weights(self.Wn[pre + '.fc1'], self.Wn[pre + '.fc2'])
-                        for a in ('attn_s', 'attn_t'):
-                            lin = f'{stream}.{i}.{a}.qkv'
-                            self.Pk[lin] = ops.rows_pack_nk(self.Wn[lin])
+                before = None      # the sub-layer in front of the current one in its Block: (typ, module)
+                for blk, _, sub, typ, _, m, _ in sublayers(cfg):
+                    pre = f'{blk}.{m}'
+                    if typ == 'mlp' and self.proj_mlp and before is not None and before[0] == 'attn':
+                        # the proj that runs in front of this MLP in the same kernel: the attention right before it in ORDER
+                        self.Pk_proj[pre] = f'{blk}.{before[1]}.proj'
+                        self.Pk[pre] = ops.proj_mlp_pack_weights(self.Wn[self.Pk_proj[pre]], self.Wn[pre + '.fc1'], self.Wn[pre + '.fc2'])
+                    elif typ == 'mlp':
+                        self.Pk[pre] = ops.mlp_pack_weights(self.Wn[pre + '.fc1'], self.Wn[pre + '.fc2'])
+                    before = (typ, m) if sub < 3 else None
+                    for a in ('attn_s', 'attn_t') if sub == 3 else ():      # the Block is complete: its two qkv
+                        self.Pk[f'{blk}.{a}.qkv'] = ops.rows_pack_nk(self.Wn[f'{blk}.{a}.qkv'])
         else:
-            self.Wn, self.Wt = (ops.prep_weights(P, linear_names(cfg), self.T, need_grad, x3=True) if self.x3 else
-                                ops.prep_weights(P, linear_names(cfg), self.T, need_grad))
+            self.Wn, self.Wt = ops.prep_weights(P, linear_names(cfg), self.T, need_grad, x3=self.x3)
 
     # ------------------------------------------------------------------ forward
     def forward(self, x: torch.Tensor, return_rep, need_grad: bool, tta_perm=None):
@@ -379,8 +394,7 @@ class Engine:
             B = 2 * B
         M, C = B * T * J, cfg.C
         self.B, self.Tlen, self.M = B, T, M
-        self.rawln = (not need_grad and self.fold and self.drop_seed is None and self.rawln_allowed and
-                      bool(getattr(ops, 'can_fuse_mlp', lambda *_: False)(self.T, cfg)))
+        self.rawln = not need_grad and self.fold and self.drop_seed is None and self.rawln_allowed and self._can('can_fuse_mlp')
         self.prepare_weights(need_grad)
         h = self._f(M, C)
         if tta_perm is not None:
@@ -397,10 +411,7 @@ class Engine:
         if self.fold and not self.rawln:
             # folded: both Blocks of a level read the SAME plain normalisation of h (their gamma / beta live in their own weights) -- one
             # launch for level 0 too, as the fusion kernel provides one xhat for the later levels
-            xn0, mean0, rstd0 = self._op(M, C), self._f(M), self._f(M)
-            ops.layernorm_fwd(h, None, None, cfg.eps, xn0, mean0, rstd0)
-            ln_st = ln_ts = (xn0, mean0, rstd0)
-            del xn0, mean0, rstd0
+            ln_st = ln_ts = self._layernorm(h, None)
         for i in range(cfg.depth):
             if side is not None:
                 side.wait_stream(main)
@@ -418,22 +429,17 @@ class Engine:
                 # level (one mean / rstd for the two), or the final `norm` after the last level
                 alpha, mean, rstd = self._f(M, 2), self._f(M), self._f(M)
                 last = i + 1 == cfg.depth
-                n1 = 'norm' if last else f"blocks_st.{i + 1}.{ORDER['st'][0][1]}"
-                n2 = None if last else f"blocks_ts.{i + 1}.{ORDER['ts'][0][1]}"
-                if self.fold and not last:      # ONE plain normalisation serves both blocks of the next level
-                    xn1 = self._t(M, C)
-                    ops.fuse_ln_fwd(x_st, x_ts, P[f'ts_attn.{i}.weight'], P[f'ts_attn.{i}.bias'], hn, alpha,
-                                    None, None, xn1, None, None, None, cfg.eps, mean, rstd)
-                    ln_st = ln_ts = (xn1, mean, rstd)
+                # (folded, not last: ONE plain normalisation -- no gamma / beta -- serves both blocks of the next level)
+                n1, n2 = (('norm', None) if last else (None, None) if self.fold else
+                          (f"blocks_st.{i + 1}.{ORDER['st'][0][1]}", f"blocks_ts.{i + 1}.{ORDER['ts'][0][1]}"))
+                xn1, xn2 = self._t(M, C), (self._t(M, C) if n2 else None)
+                gb = [P[f'{n}.{k}'] if n else None for n in (n1, n2) for k in ('weight', 'bias')]
+                ops.fuse_ln_fwd(x_st, x_ts, P[f'ts_attn.{i}.weight'], P[f'ts_attn.{i}.bias'], hn, alpha,
+                                gb[0], gb[1], xn1, gb[2], gb[3], xn2, cfg.eps, mean, rstd)
+                if last:
+                    ln_tail = (xn1, mean, rstd)
                 else:
-                    xn1, xn2 = self._t(M, C), (None if last else self._t(M, C))
-                    ops.fuse_ln_fwd(x_st, x_ts, P[f'ts_attn.{i}.weight'], P[f'ts_attn.{i}.bias'], hn, alpha,
-                                    P[n1 + '.weight'], P[n1 + '.bias'], xn1, P[n2 + '.weight'] if n2 else None, P[n2 + '.bias'] if n2 else None, xn2,
-                                    cfg.eps, mean, rstd)
-                    if last:
-                        ln_tail = (xn1, mean, rstd)
-                    else:
-                        ln_st, ln_ts = (xn1, mean, rstd), (xn2, mean, rstd)
+                    ln_st, ln_ts = (xn1, mean, rstd), (xn2 if n2 else xn1, mean, rstd)
             elif cfg.att_fuse:
                 alpha = self._f(M, 2)
                 ops.fuse_fwd(x_st, x_ts, P[f'ts_attn.{i}.weight'], P[f'ts_attn.{i}.bias'], hn, alpha)
@@ -446,8 +452,7 @@ class Engine:
         if ln_tail is not None:
             xn, mean, rstd = ln_tail
         else:
-            xn, mean, rstd = self._op(M, C), self._f(M), self._f(M)
-            ops.layernorm_fwd(h, P['norm.weight'], P['norm.bias'], cfg.eps, xn, mean, rstd)
+            xn, mean, rstd = self._layernorm(h, 'norm')
         xn = self._mm(xn)
         # the returned tensor is allocated in its final 4-D shape (the kernels see [M, .] views of it): autograd refuses
         # in-place writes into an output that is itself a view (callers do `out[:, :, 0, :] = 0`, train.py:76)
@@ -495,14 +500,15 @@ class Engine:
         row-owner kernel ran (it owns whole rows, so LayerNorm's statistics cost it nothing), else None."""
         cfg, ops, P = self.cfg, self.ops, self.P
         y = self._f(self.M, cfg.C)
+        drop = dm is not None and dm.branch      # proj_drop / MLP drop + DropPath on the branch (DSTformer.py:84,148-149,241-242)
         # (the kernel addresses its 2-KiB rows with 32-bit offsets: beyond 2^21 rows the tile kernel + LayerNorm take over)
-        if self.fold and nxt is not None and lin in self.Pf and self.M < (1 << 21) and not (dm is not None and (dm[0] > 0 or dm[3] > 0)):
+        if self.fold and nxt is not None and lin in self.Pf and self.M < (1 << 21) and not drop:
             xn, mean, rstd = self._op(self.M, cfg.C), self._f(self.M), self._f(self.M)
             ops.rows_resid_ln(a, self.Pf[lin], P[lin + '.bias'], x, y, xn, mean, rstd, cfg.eps)
             return y, (xn, mean, rstd)
         ops.gemm_nt(a, self.Wn[lin], P[lin + '.bias'], EPI_RESID, resid=x, out_f=y)
-        if (not self.rawln) and dm is not None and (dm[0] > 0 or dm[3] > 0):      # proj_drop / MLP drop + DropPath on the branch (DSTformer.py:84,148-149,241-242)
-            ops.residual_drop(y, x, cfg.J, dm[0], dm[1], dm[3], dm[4])
+        if drop and not self.rawln:
+            ops.residual_drop(y, x, cfg.J, dm.p, dm.seed_branch, dm.p_path, dm.seed_path)
         return y, None
 
     def _attn_fwd(self, x, pre, norm, attn, mode, need_grad, sub=0, ln=None, nxt=None, defer_proj=False):
@@ -514,39 +520,30 @@ class Engine:
             xn = mean = rstd = None
             ops.rows_gemm_nk_ln(x, self.Pk[lin], self.Bf[lin], self.Rs[lin], cfg.eps, qkv)
         else:
-            if ln is not None:   # LayerNorm(x) came with x from its producer
-                xn, mean, rstd = ln
-            else:
-                xn, mean, rstd = self._op(M, C), self._f(M), self._f(M)
-                if self.fold:
-                    ops.layernorm_fwd(x, None, None, cfg.eps, xn, mean, rstd)
-                else:
-                    ops.layernorm_fwd(x, P[f'{pre}.{norm}.weight'], P[f'{pre}.{norm}.bias'], cfg.eps, xn, mean, rstd)
-            xn = self._mm(xn)
-            ops.gemm_nt(xn, self.Wn[lin], self.Bf[lin] if self.fold else self._bias(lin), EPI_STORE, out_t=qkv)
+            xn, mean, rstd = self._norm_in(x, pre, norm, ln)
+            ops.gemm_nt(xn, self.Wn[lin], self.Bf[lin] if self.fold else P.get(lin + '.bias'), EPI_STORE, out_t=qkv)
         dm = self._drops(pre, sub)
         o, lse = self._t(M, C), self._f(M, cfg.H)
-        if dm is not None and dm[5] > 0:      # attn_drop: the counter-based mask is applied to the probabilities inside the kernel
-            ops.attn_fwd(qkv, o, lse, self.B, self.Tlen, cfg.J, cfg.H, cfg.scale, mode, drop=(dm[5], dm[6]))
-        else:
-            ops.attn_fwd(qkv, o, lse, self.B, self.Tlen, cfg.J, cfg.H, cfg.scale, mode)
+        ops.attn_fwd(qkv, o, lse, self.B, self.Tlen, cfg.J, cfg.H, cfg.scale, mode, drop=dm.attn if dm else None)
         if defer_proj:      # no-grad: proj + residual run inside the MLP kernel that follows
             return x, None, None, dict(o=o, proj=f'{pre}.{attn}.proj')
         o_op = self._mm(o)      # (bf16x3: the operand planes are kept for the weight gradient too -- o itself stays fp32 for the attention backward)
         y, ln_y = self._resid_gemm(o_op, f'{pre}.{attn}.proj', x, dm, pre, nxt)
-        if self.fold:      # backward needs xhat and rstd only: the fp32 sub-layer input is not kept
-            sv = dict(x=None, mean=None, rstd=rstd, xn=xn, qkv=qkv, o=o, lse=lse, dm=dm) if need_grad else None
-        else:
-            sv = dict(x=x, mean=mean, rstd=rstd, xn=None if self.recompute else xn, qkv=qkv, o=o, lse=lse, dm=dm) if need_grad else None
+        sv = self._saved(x, xn, mean, rstd, dm, qkv=qkv, o=o, lse=lse) if need_grad else None
         if sv is not None and self.x3 and self.x3_planes and not self.recompute:
             sv['o_op'] = o_op
         return y, sv, ln_y, None
 
+    def _saved(self, x, xn, mean, rstd, dm, **core):
+        if self.fold:      # backward needs xhat and rstd only: the fp32 sub-layer input is not kept
+            return dict(x=None, mean=None, rstd=rstd, xn=xn, dm=dm, **core)
+        return dict(x=x, mean=mean, rstd=rstd, xn=None if self.recompute else xn, dm=dm, **core)
+
     def _mlp_fwd(self, x, pre, norm, mlp, need_grad, sub=1, ln=None, nxt=None, pending_proj=None):
         cfg, ops, P = self.cfg, self.ops, self.P
         M, C = self.M, cfg.C
+        lin = f'{pre}.{mlp}.fc1'
         if self.rawln:                # no-grad: the whole sub-layer is one kernel; the hidden never reaches HBM, the operand is bf16(x) made in the kernel
-            lin = f'{pre}.{mlp}.fc1'
             y = self._f(M, C)
             if pending_proj is not None:      # x + proj(o) first, in the same kernel
                 if self.Pk_proj.get(f'{pre}.{mlp}') != pending_proj['proj']:
@@ -557,36 +554,24 @@ class Engine:
                 ops.mlp_fused_fwd(None, True, self.Pk[f'{pre}.{mlp}'], self.Bf[lin], P[f'{pre}.{mlp}.fc2.bias'], self.Rs[lin], x, y, None,
                                   cfg.eps, None, None)
             return y, None, None
-        if ln is not None:            # LayerNorm(x) came with x from the residual GEMM of the previous sub-layer
-            xn, mean, rstd = ln
-        else:
-            xn, mean, rstd = self._op(M, C), self._f(M), self._f(M)
-            if self.fold:
-                ops.layernorm_fwd(x, None, None, cfg.eps, xn, mean, rstd)
-            else:
-                ops.layernorm_fwd(x, P[f'{pre}.{norm}.weight'], P[f'{pre}.{norm}.bias'], cfg.eps, xn, mean, rstd)
-        xn = self._mm(xn)
+        xn, mean, rstd = self._norm_in(x, pre, norm, ln)
         dm = self._drops(pre, sub)
-        mlp_drop = dm is not None and dm[0] > 0
+        mlp_drop = dm is not None and dm.p > 0
         # u only feeds GELU' in backward; g is only fc2's operand (and the weight gradient's) unless the MLP dropout touches it first
         u, g = (self._t(M, cfg.hidden) if need_grad else None), (self._t(M, cfg.hidden) if mlp_drop else self._op(M, cfg.hidden))
         # the derivative instead of the pre-activation where backward will run the row-owner tail (every MLP of a Block does: never the
         # first sub-layer, so bf16 gradient in and out and no second summand)
         save_d = bool(need_grad and self.fold and self.gelu_d and self.gstream_allowed and not self.recompute and not mlp_drop
-                      and f'{pre}.{mlp}.fc1' in self.Pn and self.M < (1 << 22))
+                      and lin in self.Pn and self.M < (1 << 22))
         if save_d:
-            ops.gemm_nt_gelu_d(xn, self.Wn[f'{pre}.{mlp}.fc1'], self.Bf[f'{pre}.{mlp}.fc1'], u, g)
+            ops.gemm_nt_gelu_d(xn, self.Wn[lin], self.Bf[lin], u, g)
         else:
-            ops.gemm_nt(xn, self.Wn[f'{pre}.{mlp}.fc1'], self.Bf[f'{pre}.{mlp}.fc1'] if self.fold else P[f'{pre}.{mlp}.fc1.bias'],
-                        EPI_GELU, out_t=u, out2_t=g)
-        if dm is not None and dm[0] > 0:                      # MLP drop after the activation (DSTformer.py:82)
-            ops.dropout(g, g, dm[0], dm[2])
+            ops.gemm_nt(xn, self.Wn[lin], self.Bf[lin] if self.fold else P[lin + '.bias'], EPI_GELU, out_t=u, out2_t=g)
+        if mlp_drop:                                          # MLP drop after the activation (DSTformer.py:82)
+            ops.dropout(g, g, dm.p, dm.seed_act)
         g = self._mm(g)
         y, ln_y = self._resid_gemm(g, f'{pre}.{mlp}.fc2', x, dm, pre, nxt)
-        if self.fold:
-            sv = dict(x=None, mean=None, rstd=rstd, xn=xn, u=None if save_d else u, d=u if save_d else None, g=None if self.recompute else g, dm=dm) if need_grad else None
-        else:
-            sv = dict(x=x, mean=mean, rstd=rstd, xn=None if self.recompute else xn, u=u, g=None if self.recompute else g, dm=dm) if need_grad else None
+        sv = self._saved(x, xn, mean, rstd, dm, u=None if save_d else u, d=u if save_d else None, g=None if self.recompute else g) if need_grad else None
         return y, sv, ln_y
 
     # ----------------------------------------------------------------- backward
@@ -642,7 +627,7 @@ class Engine:
             pair = dh = None
             # this level's Blocks hand their input gradients down T-typed when the row-owner tail can take their first sub-layer
             out_t = bool(self.block_grad_t and self.gstream and cfg.att_fuse and (i > 0 or self.drop_seed is None) and self.M < (1 << 22)
-                         and all(f'{st}.{i}.{ORDER[kind][0][2]}.qkv' in self.Pn for st, kind in (('blocks_st', 'st'), ('blocks_ts', 'ts'))))
+                         and all(f'{st}.{i}.{ORDER[kind][0][2]}.qkv' in self.Pn for st, kind in STREAMS))
             main, side = self._streams()
             if out_t:
                 if side is not None:
@@ -697,60 +682,68 @@ class Engine:
         return dx
 
     def _block_bwd(self, dy, dy_t, svs, pre, kind, extra_last, last_needs_t):
-        order = ORDER[kind]
         for idx in reversed(range(4)):
-            typ, norm, mod, mode = order[idx]
+            typ, norm, mod, mode = ORDER[kind][idx]
             extra = extra_last if idx == 0 else None
             need_t = True if idx > 0 else last_needs_t
-            if typ == 'attn':
-                dy, dy_t = self._attn_bwd(dy, dy_t, svs[idx], pre, norm, mod, mode, extra, need_t)
-            else:
-                dy, dy_t = self._mlp_bwd(dy, dy_t, svs[idx], pre, norm, mod, extra, need_t)
+            dy, dy_t = self._sub_bwd(typ, dy, dy_t, svs[idx], pre, norm, mod, mode, extra, need_t)
             svs[idx] = None
         return dy, dy_t
 
-    def _attn_bwd(self, dy, dy_t, sv, pre, norm, attn, mode, extra, need_t):
-        cfg, ops, P, G = self.cfg, self.ops, self.P, self.grads
-        M, C = self.M, cfg.C
-        do = self._t(M, C)
-        dm = sv.get('dm')
-        if dm is not None and (dm[0] > 0 or dm[3] > 0):      # gradient entering the dropped branch; the residual path keeps dy
-            dy_t = self._t(M, C)
-            ops.grad_drop(dy, dy_t, cfg.J, dm[0], dm[1], dm[3], dm[4])
-            if self.x3:
-                dy_t = self._mm(dy_t)
-        elif self.x3 and not isinstance(dy_t, tuple):
-            dy_t = self._mm(dy)          # bf16x3: the GEMM operand is the split of the fp32 gradient itself (unless its producer wrote the planes)
-        ops.gemm_tn(dy_t, sv['o_op'] if 'o_op' in sv else self._mm(sv['o']), G[f'{pre}.{attn}.proj.weight'], G[f'{pre}.{attn}.proj.bias'])
-        ops.gemm_nt(dy_t, self.Wt[f'{pre}.{attn}.proj'], None, EPI_STORE, out_t=do)
-        dqkv = self._t(M, 3 * C) if self.fold else self._op(M, 3 * C)     # (bf16x3: the attention backward writes the operand planes itself)
+    def _sub_bwd(self, typ, dy, dy_t, sv, pre, norm, mod, mode, extra, need_t):
+        """One sub-layer: branch gradient, the core back to the Linear-in's output gradient dY, and a tail: returns (dx, dx_t)."""
+        ops, G = self.ops, self.grads
+        lin = f'{pre}.{mod}.{LINEARS[typ][0]}'
+        dy_t = self._branch_grad(dy, dy_t, sv.get('dm'))
+        if dy_t is None and sv.get('d') is not None:
+            dy_t = dy.to(self.T)
+        # the row-owner tail takes its row means itself: the core then runs without its row dots (part = None)
+        rows = self.fold and self._rows_tail_ok(lin, dy_t, extra, need_t)
+        dY, part = self._attn_bwd(dy_t, sv, pre, mod, mode, rows) if typ == 'attn' else self._mlp_bwd(dy_t, sv, pre, mod, rows)
         if self.fold:
-            lin = f'{pre}.{attn}.qkv'
-            if self._rows_tail_ok(lin, dy_t, extra, need_t):      # the consumer takes its row means itself: plain attention backward
-                ops.attn_bwd(sv['qkv'], sv['o'], do, sv['lse'], dqkv, self.B, self.Tlen, cfg.J, cfg.H, cfg.scale, mode)
-                del do
-                return self._fold_tail(dqkv, None, sv, lin, f'{pre}.{norm}', dy, dy_t, extra, need_t)
+            return self._fold_tail(dY, part, sv, lin, f'{pre}.{norm}', dy, dy_t, extra, need_t)
+        dxn = self._t(self.M, self.cfg.C)
+        dY = self._mm(dY)
+        ops.gemm_tn(dY, self._xn(sv, pre, norm), G[lin + '.weight'], G.get(lin + '.bias'))
+        ops.gemm_nt(dY, self.Wt[lin], None, EPI_STORE, out_t=dxn)
+        del dY      # (the largest tensor of the sub-layer: released before the tail allocates)
+        return self._plain_tail(dxn, sv, pre, norm, dy, extra, need_t)
+
+    def _branch_grad(self, dy, dy_t, dm):
+        """GEMM operand of the gradient that enters a sub-layer's branch (the residual path keeps dy)."""
+        if dm is not None and dm.branch:      # gradient entering the dropped branch
+            dy_t = self._t(self.M, self.cfg.C)
+            self.ops.grad_drop(dy, dy_t, self.cfg.J, dm.p, dm.seed_branch, dm.p_path, dm.seed_path)
+            return self._mm(dy_t)
+        if self.x3 and not isinstance(dy_t, tuple):
+            return self._mm(dy)          # bf16x3: the GEMM operand is the split of the fp32 gradient itself (unless its producer wrote the planes)
+        return dy_t
+
+    def _attn_bwd(self, dy_t, sv, pre, attn, mode, rows):      # -> (dqkv, its row dots for the folded tile tail or None)
+        cfg, ops, G = self.cfg, self.ops, self.grads
+        M, C = self.M, cfg.C
+        lin, proj = f'{pre}.{attn}.qkv', f'{pre}.{attn}.proj'
+        do = self._t(M, C)
+        ops.gemm_tn(dy_t, sv['o_op'] if 'o_op' in sv else self._mm(sv['o']), G[proj + '.weight'], G[proj + '.bias'])
+        ops.gemm_nt(dy_t, self.Wt[proj], None, EPI_STORE, out_t=do)
+        dqkv = self._t(M, 3 * C) if self.fold else self._op(M, 3 * C)     # (bf16x3: the attention backward writes the operand planes itself)
+        dims = (self.B, self.Tlen, cfg.J, cfg.H, cfg.scale, mode)
+        if self.fold and not rows:
             part = self._f(2 * cfg.H, M, 2)       # block-major; per head: the q columns, the k + v columns
-            ops.attn_bwd_stats(sv['qkv'], sv['o'], do, sv['lse'], dqkv, self.Bf[lin], self.Rs[lin], part, self.B, self.Tlen, cfg.J, cfg.H,
-                               cfg.scale, mode)
-            del do
-            return self._fold_tail(dqkv, part, sv, lin, f'{pre}.{norm}', dy, dy_t, extra, need_t)
-        if dm is not None and dm[5] > 0:
-            ops.attn_bwd(sv['qkv'], sv['o'], do, sv['lse'], dqkv, self.B, self.Tlen, cfg.J, cfg.H, cfg.scale, mode, drop=(dm[5], dm[6]))
-        else:
-            ops.attn_bwd(sv['qkv'], sv['o'], do, sv['lse'], dqkv, self.B, self.Tlen, cfg.J, cfg.H, cfg.scale, mode)
-        del do
-        dxn = self._t(M, C)
-        dqkv = self._mm(dqkv)
-        ops.gemm_tn(dqkv, self._xn(sv, pre, norm), G[f'{pre}.{attn}.qkv.weight'], G.get(f'{pre}.{attn}.qkv.bias'))
-        ops.gemm_nt(dqkv, self.Wt[f'{pre}.{attn}.qkv'], None, EPI_STORE, out_t=dxn)
-        del dqkv
+            ops.attn_bwd_stats(sv['qkv'], sv['o'], do, sv['lse'], dqkv, self.Bf[lin], self.Rs[lin], part, *dims)
+            return dqkv, part
+        dm = sv.get('dm')
+        ops.attn_bwd(sv['qkv'], sv['o'], do, sv['lse'], dqkv, *dims, drop=dm.attn if dm else None)
+        return dqkv, None
+
+    def _plain_tail(self, dxn, sv, pre, norm, dy, extra, need_t):
+        """The counterpart of `_fold_tail`: (dx, dx_t), dx = dy [+ extra] + LayerNorm'(dxn) (dx_t -- bf16x3: operand planes -- if need_t)."""
+        P, G = self.P, self.grads
+        M, C = self.M, self.cfg.C
         dx = self._f(M, C)
-        dx_t = (self._t(M, C) if not self.x3 else (self._op(M, C) if self.x3_planes else None)) if need_t else None      # bf16x3: operand planes
-        if callable(extra):      # dual-stream backward: the other block's input gradient, awaited only now
-            extra = extra()
-        ops.layernorm_bwd(dxn, sv['x'], sv['mean'], sv['rstd'], P[f'{pre}.{norm}.weight'], dy, extra,
-                          dx, dx_t, G[f'{pre}.{norm}.weight'], G[f'{pre}.{norm}.bias'])
+        dx_t = (self._t(M, C) if not self.x3 else (self._op(M, C) if self.x3_planes else None)) if need_t else None
+        self.ops.layernorm_bwd(dxn, sv['x'], sv['mean'], sv['rstd'], P[f'{pre}.{norm}.weight'], dy, self._await(extra),
+                               dx, dx_t, G[f'{pre}.{norm}.weight'], G[f'{pre}.{norm}.bias'])
         return dx, dx_t
 
     def _rows_tail_ok(self, lin, dy_t, extra, need_t) -> bool:
@@ -773,73 +766,46 @@ class Engine:
             db = self._f(dY.shape[1])
         stream = self.gstream and dy_t is not None
         dres = dy_t if stream else dy
-
-        def dx_gemm(extra):
-            if rows:
-                dx_t = self._t(M, C)
-                ops.rows_lnbwd_t(dY, self.Pn[lin], sv['xn'], sv['rstd'], dres, dx_t)
-                return None, dx_t
-            dx = None if (stream and need_t) else self._f(M, C)
-            dx_t = self._t(M, C) if need_t else None
-            if callable(extra):      # dual-stream backward: the other block's input gradient, awaited only now
-                extra = extra()
-            ops.gemm_nt_lnbwd(dY, self.Wt[lin], sv['xn'], rowc, dres, extra, dx, dx_t)
-            return dx, dx_t
         ops.gemm_tn(dY, sv['xn'], G[lin + '.weight'], db)
         ops.unfold_norm_grads(G[lin + '.weight'], db, P[lin + '.weight'], P[norm + '.weight'], P[norm + '.bias'],
                               G[norm + '.weight'], G[norm + '.bias'])
-        return dx_gemm(extra)
+        if rows:
+            dx_t = self._t(M, C)
+            ops.rows_lnbwd_t(dY, self.Pn[lin], sv['xn'], sv['rstd'], dres, dx_t)
+            return None, dx_t
+        dx = None if (stream and need_t) else self._f(M, C)
+        dx_t = self._t(M, C) if need_t else None
+        ops.gemm_nt_lnbwd(dY, self.Wt[lin], sv['xn'], rowc, dres, self._await(extra), dx, dx_t)
+        return dx, dx_t
 
-    def _mlp_bwd(self, dy, dy_t, sv, pre, norm, mlp, extra, need_t):
-        cfg, ops, P, G = self.cfg, self.ops, self.P, self.grads
-        M, C = self.M, cfg.C
+    def _mlp_bwd(self, dy_t, sv, pre, mlp, rows):      # -> (du, its row dots for the folded tile tail or None)
+        cfg, ops, G = self.cfg, self.ops, self.grads
+        M = self.M
+        lin, fc2 = f'{pre}.{mlp}.fc1', f'{pre}.{mlp}.fc2'
         du = self._t(M, cfg.hidden)
         dm = sv.get('dm')
-        if dm is not None and (dm[0] > 0 or dm[3] > 0):
-            dy_t = self._t(M, C)
-            ops.grad_drop(dy, dy_t, cfg.J, dm[0], dm[1], dm[3], dm[4])
-            if self.x3:
-                dy_t = self._mm(dy_t)
-        elif self.x3 and not isinstance(dy_t, tuple):
-            dy_t = self._mm(dy)
+        act_drop = dm is not None and dm.p > 0      # the MLP's drop after the activation
         g = sv['g']
         if g is None:                                         # recompute mode: post-activation from the saved pre-activation
             g = self._t(M, cfg.hidden)
             ops.gelu_fwd(sv['u'], g)
-            if dm is not None and dm[0] > 0:
-                ops.dropout(g, g, dm[0], dm[2])
+            if act_drop:
+                ops.dropout(g, g, dm.p, dm.seed_act)
             g = self._mm(g)
-        ops.gemm_tn(dy_t, g, G[f'{pre}.{mlp}.fc2.weight'], G[f'{pre}.{mlp}.fc2.bias'])
+        ops.gemm_tn(dy_t, g, G[fc2 + '.weight'], G[fc2 + '.bias'])
         del g
-        if self.fold:
-            lin = f'{pre}.{mlp}.fc1'
-            if sv.get('d') is not None:                           # forward saved gelu'(u): one multiply, then the row-owner tail
-                if dy_t is None:
-                    dy_t = dy.to(self.T)
-                if not self._rows_tail_ok(lin, dy_t, extra, need_t):
-                    raise RuntimeError(f'{lin}: the derivative was saved for the row-owner LayerNorm backward, which cannot run here')
-                ops.gemm_nt_mul(dy_t, self.Wt[f'{pre}.{mlp}.fc2'], sv['d'], du)
-                return self._fold_tail(du, None, sv, lin, f'{pre}.{norm}', dy, dy_t, extra, need_t)
-            if self._rows_tail_ok(lin, dy_t, extra, need_t):      # the consumer takes its row means itself: plain GELU' epilogue
-                ops.gemm_nt(dy_t, self.Wt[f'{pre}.{mlp}.fc2'], None, EPI_DGELU, out_t=du, aux_t=sv['u'])
-                return self._fold_tail(du, None, sv, lin, f'{pre}.{norm}', dy, dy_t, extra, need_t)
+        if sv.get('d') is not None:                           # forward saved gelu'(u): one multiply, then the row-owner tail
+            if not rows:
+                raise RuntimeError(f'{lin}: the derivative was saved for the row-owner LayerNorm backward, which cannot run here')
+            ops.gemm_nt_mul(dy_t, self.Wt[fc2], sv['d'], du)
+            return du, None
+        if self.fold and not rows:
             part = self._f(cfg.hidden // 64, M, 2)
-            ops.gemm_nt_dgelu_stats(dy_t, self.Wt[f'{pre}.{mlp}.fc2'], du, sv['u'], self.Bf[lin], self.Rs[lin], part)
-            return self._fold_tail(du, part, sv, lin, f'{pre}.{norm}', dy, dy_t, extra, need_t)
-        if self.x3 and not (dm is not None and dm[0] > 0):
+            ops.gemm_nt_dgelu_stats(dy_t, self.Wt[fc2], du, sv['u'], self.Bf[lin], self.Rs[lin], part)
+            return du, part
+        if self.x3 and not act_drop:
             du = self._op(M, cfg.hidden)                      # bf16x3: the GELU' epilogue writes the operand planes itself
-        ops.gemm_nt(dy_t, self.Wt[f'{pre}.{mlp}.fc2'], None, EPI_DGELU, out_t=du, aux_t=sv['u'])
-        if dm is not None and dm[0] > 0:                      # backward of the drop after the activation (commutes with GELU')
-            ops.dropout(du, du, dm[0], dm[2])
-        dxn = self._t(M, C)
-        du = self._mm(du)
-        ops.gemm_tn(du, self._xn(sv, pre, norm), G[f'{pre}.{mlp}.fc1.weight'], G[f'{pre}.{mlp}.fc1.bias'])
-        ops.gemm_nt(du, self.Wt[f'{pre}.{mlp}.fc1'], None, EPI_STORE, out_t=dxn)
-        del du
-        dx = self._f(M, C)
-        dx_t = (self._t(M, C) if not self.x3 else (self._op(M, C) if self.x3_planes else None)) if need_t else None      # bf16x3: operand planes
-        if callable(extra):      # dual-stream backward: the other block's input gradient, awaited only now
-            extra = extra()
-        ops.layernorm_bwd(dxn, sv['x'], sv['mean'], sv['rstd'], P[f'{pre}.{norm}.weight'], dy, extra,
-                          dx, dx_t, G[f'{pre}.{norm}.weight'], G[f'{pre}.{norm}.bias'])
-        return dx, dx_t
+        ops.gemm_nt(dy_t, self.Wt[fc2], None, EPI_DGELU, out_t=du, aux_t=sv['u'])
+        if act_drop:                                          # backward of the drop after the activation (commutes with GELU')
+            ops.dropout(du, du, dm.p, dm.seed_act)
+        return du, None

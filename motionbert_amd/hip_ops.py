@@ -10,6 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import threading
+from itertools import accumulate
 from typing import Dict, List, Optional
 
 import torch
@@ -181,26 +182,29 @@ class HipOps:
             for k in stale:
                 del self._desc_cache[k]
 
+    def _desc_entry(self, kind: str, key: tuple, build) -> dict:
+        """The descriptor-cache protocol of the three packers: the entry of `(kind,) + key`; where it is missing, room is made and
+        `build()` makes it (`desc`: the device table without the addresses that change from call to call, filled into a clone)."""
+        with self._lock:
+            ent = self._desc_cache.get((kind,) + key)
+            if ent is None:
+                self._desc_room(kind)
+                ent = self._desc_cache[(kind,) + key] = build()
+            self._hold_if_capturing(ent)
+        return ent
+
     def _prep_weights(self, P, names, tdtype, need_t, lo):
         ws = [P[n + '.weight'] for n in names]
         dev = ws[0].device
         dt = _DT[tdtype]
-        key = ('prep', tuple((w.data_ptr(), tuple(w.shape)) for w in ws), dt, dev.index)
-        with self._lock:
-            ent = self._desc_cache.get(key)
-            if ent is None:
-                offs, rows, off = [], [], 0
-                for w in ws:
-                    N, K = w.shape
-                    rows.append([w.data_ptr(), 0, 0, N, K])
-                    offs.append(off)
-                    off += N * K
-                self._desc_room('prep')
-                ent = dict(desc=torch.tensor(rows, dtype=torch.int64).to(dev),
-                           offs=(torch.tensor(offs, dtype=torch.int64) * torch.empty(0, dtype=tdtype).element_size()).to(dev),
-                           offs_host=offs, total=off, max_n=max(w.shape[0] for w in ws), max_k=max(w.shape[1] for w in ws))
-                self._desc_cache[key] = ent
-            self._hold_if_capturing(ent)
+
+        def build():
+            offs = list(accumulate((w.numel() for w in ws), initial=0))      # element offsets into the flat buffers, the total last
+            return dict(desc=torch.tensor([[w.data_ptr(), 0, 0, *w.shape] for w in ws], dtype=torch.int64).to(dev),
+                        offs=(torch.tensor(offs[:-1], dtype=torch.int64) * torch.empty(0, dtype=tdtype).element_size()).to(dev),
+                        offs_host=offs[:-1], total=offs[-1], max_n=max(w.shape[0] for w in ws), max_k=max(w.shape[1] for w in ws))
+        key = (tuple((w.data_ptr(), tuple(w.shape)) for w in ws), dt, dev.index)
+        ent = self._desc_entry('prep', key, build)
         for w in ws:
             if w.dtype != torch.float32 or not w.is_contiguous():
                 raise RuntimeError('libmbx: parameters must be contiguous fp32')
@@ -237,32 +241,22 @@ class HipOps:
         Bf[linear] = b + W beta (fp32 [N]), Rs[linear] = row sums of the rounded folded weights (fp32 [N]).  One call, two launches."""
         if tdtype != torch.bfloat16:
             raise RuntimeError('libmbx: fold_norm_weights is a bf16 path')
-        ws = [P[l + '.weight'] for l, _ in pairs]
+        ps = [(P[l + '.weight'], P.get(l + '.bias'), P[n + '.weight'], P[n + '.bias']) for l, n in pairs]      # W, b, gamma, beta
+        ws = [p[0] for p in ps]
         dev = ws[0].device
-        key = ('fold', tuple((w.data_ptr(), tuple(w.shape), P[n + '.weight'].data_ptr(), P[n + '.bias'].data_ptr(),
-                              0 if P.get(l + '.bias') is None else P[l + '.bias'].data_ptr()) for (l, n), w in zip(pairs, ws)), dev.index)
-        with self._lock:
-            ent = self._desc_cache.get(key)
-            if ent is None:
-                rows, offs, voffs, off, voff = [], [], [], 0, 0
-                for (l, n), w in zip(pairs, ws):
-                    N, K = w.shape
-                    b = P.get(l + '.bias')
-                    for t in (w, P[n + '.weight'], P[n + '.bias']) + ((b,) if b is not None else ()):
-                        if t.dtype != torch.float32 or not t.is_contiguous():
-                            raise RuntimeError('libmbx: parameters must be contiguous fp32')
-                    rows.append([w.data_ptr(), 0 if b is None else b.data_ptr(), P[n + '.weight'].data_ptr(), P[n + '.bias'].data_ptr(),
-                                 0, 0, 0, 0, N, K])
-                    offs.append(off)
-                    voffs.append(voff)
-                    off += N * K
-                    voff += N
-                self._desc_room('fold')
-                ent = dict(desc=torch.tensor(rows, dtype=torch.int64).to(dev), offs=(torch.tensor(offs, dtype=torch.int64) * 2).to(dev),
-                           voffs=(torch.tensor(voffs, dtype=torch.int64) * 4).to(dev), offs_host=offs, voffs_host=voffs, total=off,
-                           vtotal=voff, max_n=max(w.shape[0] for w in ws), max_k=max(w.shape[1] for w in ws))
-                self._desc_cache[key] = ent
-            self._hold_if_capturing(ent)
+
+        def build():
+            for t in (t for p in ps for t in p if t is not None):
+                if t.dtype != torch.float32 or not t.is_contiguous():
+                    raise RuntimeError('libmbx: parameters must be contiguous fp32')
+            offs = list(accumulate((w.numel() for w in ws), initial=0))      # element offsets of the weights, the total last
+            voffs = list(accumulate((w.shape[0] for w in ws), initial=0))      # ... of the [N] vectors
+            rows = [[w.data_ptr(), _p(b) or 0, g.data_ptr(), bt.data_ptr(), 0, 0, 0, 0, *w.shape] for w, b, g, bt in ps]
+            return dict(desc=torch.tensor(rows, dtype=torch.int64).to(dev), offs=(torch.tensor(offs[:-1], dtype=torch.int64) * 2).to(dev),
+                        voffs=(torch.tensor(voffs[:-1], dtype=torch.int64) * 4).to(dev), offs_host=offs[:-1], voffs_host=voffs[:-1],
+                        total=offs[-1], vtotal=voffs[-1], max_n=max(w.shape[0] for w in ws), max_k=max(w.shape[1] for w in ws))
+        key = (tuple((w.data_ptr(), tuple(w.shape), g.data_ptr(), bt.data_ptr(), _p(b) or 0) for w, b, g, bt in ps), dev.index)
+        ent = self._desc_entry('fold', key, build)
         desc = ent['desc'].clone()
         flat_n = torch.empty(ent['total'], dtype=torch.bfloat16, device=dev)
         flat_t = torch.empty(ent['total'], dtype=torch.bfloat16, device=dev) if need_t else None
@@ -401,19 +395,13 @@ class HipOps:
         store = ws[0].untyped_storage().data_ptr()
         if any(w.untyped_storage().data_ptr() != store for w in ws):
             base = 0
-        key = ('rnpack', base == 0, N, tuple((w.data_ptr() - base, w.shape[1]) for w in ws), dev.index)
-        with self._lock:
-            ent = self._desc_cache.get(key)
-            if ent is None:
-                offs, off = [], 0
-                for w in ws:
-                    offs.append(off)
-                    off += N * w.shape[1] * 2
-                self._desc_room('rnpack')
-                ent = dict(desc=torch.tensor([[w.data_ptr() - base, o, w.shape[1]] for w, o in zip(ws, offs)], dtype=torch.int64).to(dev), offs=offs, total=off,
-                           max_k=max(w.shape[1] for w in ws))
-                self._desc_cache[key] = ent
-            self._hold_if_capturing(ent)
+
+        def build():
+            offs = list(accumulate((N * w.shape[1] * 2 for w in ws), initial=0))      # byte offsets into the flat buffer, the total last
+            rows = [[w.data_ptr() - base, o, w.shape[1]] for w, o in zip(ws, offs)]
+            return dict(desc=torch.tensor(rows, dtype=torch.int64).to(dev), offs=offs[:-1], total=offs[-1], max_k=max(w.shape[1] for w in ws))
+        key = (base == 0, N, tuple((w.data_ptr() - base, w.shape[1]) for w in ws), dev.index)
+        ent = self._desc_entry('rnpack', key, build)
         flat = torch.empty(ent['total'], dtype=torch.uint8, device=dev)
         desc = ent['desc'].clone()
         desc[:, 0] += base
