@@ -417,6 +417,29 @@ int mbx_rows_lnbwd_t(const void* dy, const void* packed, const void* xhat, const
 int mbx_rows_resid_ln(const void* a, const void* packed, const float* bias, const float* resid, float* y, void* xhat, float* mean,
                       float* rstd, float eps, int M, int N, int K, void* stream);
 
+/* ---- one-shot action recognition (csrc/oneshot.hip; train_action_1shot.py:58-69,186-198, lib/model/loss_supcon.py:57-98) ----------------
+ * mbx_supcon_loss: SupConLoss.forward(features, labels) with contrast_mode 'all' and its gradient in one call.  feat f32
+ * [bsz, n_views, D], labels i32 [bsz]; A = bsz * n_views anchors, row r carries labels[r / n_views].  With S_ij = x_i . x_j / tau,
+ * m_i = max_j S_ij (diagonal included), lse_i = log sum_{j != i} exp(S_ij - m_i), P(i) = {j != i : label_j = label_i}, n_i = |P(i)|:
+ *     loss[0] = mean_i -(tau / tau_b) (1 / n_i) sum_{j in P(i)} (S_ij - m_i - lse_i)
+ *     dfeat   = grad_scale * d loss / d feat   (NULL: not computed; the loss has the same bits either way)
+ * normalize != 0: feat is the embedding BEFORE F.normalize; x = z / max(|z|, 1e-12) and dfeat is the gradient with respect to z.
+ * An anchor without a positive gives NaN in the loss and in every element of dfeat, as the reference's 0 / 0 does.
+ * 2 <= A <= 128, D >= 1, temperatures > 0 (checked).  fp32 arithmetic, fixed summation order, no floating-point atomics.
+ * ws: >= mbx_supcon_loss_ws(A, D) bytes. */
+size_t mbx_supcon_loss_ws(int A, int D);
+int mbx_supcon_loss(const float* feat, const int* labels, int bsz, int n_views, int D, float temperature, float base_temperature,
+                    int normalize, float grad_scale, float* loss, float* dfeat, void* ws, void* stream);
+/* mbx_nn_cosine: for every test row t [N,D] the exemplar a [M,D] of the largest (a . t) / (max(|a|, 1e-8) max(|t|, 1e-8)); ties go to
+ * the lowest index and NaN counts as maximal, the first NaN winning (torch.argmax).  pred_label[t] = anchor_labels[argmax] (i32),
+ * best_sim[t] (f32, may be NULL), hits[0] += #(pred_label == test_labels) (i64, integer atomic; test_labels may be NULL).
+ * Any M >= 1 (exemplars are streamed in tiles), any D >= 1, N = 0 is a no-op.
+ * There is no workspace argument, so the norms are not kept between workgroups: a workgroup (32 test rows) forms the norm of an exemplar
+ * once per exemplar tile and the norms of its test rows once per tile, from the elements it stages for the dots anyway (one fma per staged
+ * element); with M > 32 it reads its test rows once per tile of 32 exemplars. */
+int mbx_nn_cosine(const float* anchors, const int* anchor_labels, int M, const float* test, const int* test_labels, int N, int D,
+                  int* pred_label, float* best_sim, long long* hits, void* stream);
+
 /* ---- measurement aid (bench.py `roofline.sustained_mfma_tflops`; not part of the model) --------------------------------------------
  * The bf16 MFMA rate the part sustains under its power cap with nothing but v_mfma_f32_32x32x16_bf16 in the loop (pseudo-random
  * operands; n_wg workgroups of 4 waves, `iters` x 16 MFMAs per wave).  ws: >= mbx_mfma_probe_ws(n_wg) bytes = a float sink

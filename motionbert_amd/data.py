@@ -229,3 +229,33 @@ class PackedMotion3D:
             th.join()
             if pending is not None and pending[3] is not None:
                 pending[3].synchronize()                   # an H2D copy still reading a pinned slot must finish before it is freed
+
+
+def m_per_class_batches(labels, m: int, batch_size: int, length: Optional[int] = None, seed: int = 0):
+    """Index batches for one-shot training (train_action_1shot.py:145: `MPerClassSampler(labels, m=n_views, batch_size, length_before_new_iter)`
+    of pytorch_metric_learning, which this package does not depend on).  Returns a list of `length // batch_size` int64 arrays (a
+    `batch_sampler` for a DataLoader); `length` defaults to len(labels).
+
+    Every batch holds `batch_size / m` DISTINCT classes with exactly `m` samples each, laid out class by class; a class with fewer than
+    `m` samples is sampled with repetition, a larger one without.  With m >= 2 no anchor of the supervised-contrastive loss is ever
+    without a positive -- the guarantee MPerClassSampler is used for (a lonely anchor makes the loss NaN).  The draw order of that
+    library is NOT reproduced: the batches are a function of (labels, m, batch_size, length, seed) alone."""
+    labels = np.asarray(labels).reshape(-1)
+    if m < 2:
+        raise ValueError(f'm = {m}: an anchor needs at least one positive in its batch (m >= 2)')
+    if batch_size < m or batch_size % m:
+        raise ValueError(f'batch_size {batch_size} must be a positive multiple of m = {m}')
+    classes, inverse = np.unique(labels, return_inverse=True)
+    per_batch = batch_size // m
+    if len(classes) < per_batch:
+        raise ValueError(f'{len(classes)} classes cannot fill {per_batch} distinct classes per batch')
+    members = [np.flatnonzero(inverse == c) for c in range(len(classes))]
+    length = len(labels) if length is None else int(length)
+    rng = np.random.default_rng(seed)
+    batches = []
+    for _ in range(length // batch_size):
+        out = []
+        for c in rng.choice(len(classes), size=per_batch, replace=False):
+            out.append(rng.choice(members[c], size=m, replace=len(members[c]) < m))
+        batches.append(np.concatenate(out).astype(np.int64))
+    return batches

@@ -99,6 +99,9 @@ SIGNATURES = {
     'mbx_pose_errors': (_i, [_vp] * 5 + [_i] * 3 + [_vp] * 2 + [_i] * 3 + [_vp]),
     'mbx_eval_reduce_ws': (_sz, [_i, _i]),
     'mbx_eval_reduce': (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i] + [_vp] * 5),
+    'mbx_supcon_loss_ws': (_sz, [_i, _i]),
+    'mbx_supcon_loss': (_i, [_vp, _vp, _i, _i, _i, _f, _f, _i, _f, _vp, _vp, _vp, _vp]),
+    'mbx_nn_cosine': (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     'mbx_rows_n_pack_bytes': (_sz, [_i, _i]),
     'mbx_rows_lnbwd_t': (_i, [_vp] * 6 + [_i, _i, _i, _vp]),
     'mbx_rows_n_pack_many': (_i, [_i64p, _i, _i, _i, _vp]),
@@ -639,6 +642,47 @@ class HipOps:
         ws = self._ws(('evr', F, A), self.lib.mbx_eval_reduce_ws, F, A, device=e1.device)
         self._ck(self.lib.mbx_eval_reduce(_p(e1), _p(e2), e1.numel(), _p(row_ptr), row_ptr.numel(), _p(slots), slots.numel(), _p(action), F, int(A),
                                           _p(per_action), _p(summary), _p(count), _p(ws), self._stream()))
+
+    # ------------------------------------------------------------------ one-shot recognition (train_action_1shot.py)
+    @staticmethod
+    def _dense(what, dtype, numel, dev, **tensors):
+        """every named tensor (None allowed) is contiguous, of `dtype`, of `numel` elements (None: any) and on device `dev`: the kernels
+        take raw pointers, so a strided view or a tensor of another size would be read or written with the wrong layout"""
+        for name, t in tensors.items():
+            if t is not None and (t.dtype != dtype or not t.is_contiguous() or t.device != dev or (numel is not None and t.numel() != numel)):
+                raise RuntimeError(f'libmbx: {what}: {name} must be a contiguous {dtype} tensor' + (f' of {numel} elements' if numel is not None else '') +
+                                   f' on {dev}, got {tuple(t.shape)} {t.dtype} strides {t.stride()} on {t.device}')
+
+    def supcon_loss(self, feat, labels, temperature, base_temperature, normalize, loss, dfeat, grad_scale=1.0):
+        """feat [bsz,n_views,D] f32, labels [bsz] i32, loss [1] f32, dfeat like feat or None; all contiguous, on the device of feat."""
+        if feat.dim() != 3:
+            raise RuntimeError(f'libmbx: supcon_loss needs feat [bsz,n_views,D], got {tuple(feat.shape)}')
+        bsz, n_views, D = feat.shape
+        self._dense('supcon_loss', torch.float32, bsz * n_views * D, feat.device, feat=feat, dfeat=dfeat)
+        self._dense('supcon_loss', torch.float32, 1, feat.device, loss=loss)
+        self._dense('supcon_loss', torch.int32, bsz, feat.device, labels=labels)
+        A = bsz * n_views
+        ws = self._ws(('supcon', A, D), self.lib.mbx_supcon_loss_ws, A, D, device=feat.device)
+        self._ck(self.lib.mbx_supcon_loss(_p(feat), _p(labels), bsz, n_views, D, float(temperature), float(base_temperature),
+                                          int(bool(normalize)), float(grad_scale), _p(loss), _p(dfeat), _p(ws), self._stream()))
+
+    def nn_cosine(self, anchors, anchor_labels, test, test_labels, pred_label, best_sim, hits):
+        """anchors [M,D] / test [N,D] f32, labels i32, pred_label [N] i32, best_sim [N] f32 or None, hits [1] i64 (accumulated); all
+        contiguous, on the device of anchors."""
+        if anchors.dim() != 2 or test.dim() != 2 or test.shape[1] != anchors.shape[1]:
+            raise RuntimeError(f'libmbx: nn_cosine needs anchors [M,D] and test [N,D], got {tuple(anchors.shape)} / {tuple(test.shape)}')
+        M, D = anchors.shape
+        N = test.shape[0]
+        dev = anchors.device
+        self._dense('nn_cosine', torch.float32, None, dev, anchors=anchors, test=test)
+        self._dense('nn_cosine', torch.float32, N, dev, best_sim=best_sim)
+        self._dense('nn_cosine', torch.int32, M, dev, anchor_labels=anchor_labels)
+        self._dense('nn_cosine', torch.int32, N, dev, pred_label=pred_label, test_labels=test_labels)
+        self._dense('nn_cosine', torch.int64, 1, dev, hits=hits)
+        if test_labels is not None and hits is None:
+            raise RuntimeError('libmbx: nn_cosine: test labels without a hit counter')
+        self._ck(self.lib.mbx_nn_cosine(_p(anchors), _p(anchor_labels), M, _p(test), _p(test_labels), N, D, _p(pred_label), _p(best_sim),
+                                        _p(hits), self._stream()))
 
     # ------------------------------------------------------------------ dropout / drop-path (SURVEY 8 a15)
     def dropout(self, x, y, p, seed):
