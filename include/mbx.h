@@ -440,6 +440,48 @@ int mbx_supcon_loss(const float* feat, const int* labels, int bsz, int n_views, 
 int mbx_nn_cosine(const float* anchors, const int* anchor_labels, int M, const float* test, const int* test_labels, int N, int D,
                   int* pred_label, float* best_sim, long long* hits, void* stream);
 
+/* ---- mesh recovery around a user-supplied SMPL layer (csrc/mesh.hip; lib/model/model_mesh.py:57-79, loss_mesh.py:49-68, ------------------
+ *      lib/utils/utils_mesh.py) -- mbx_version() >= 110
+ * mbx_rot6d_theta_fwd: the head's rotation chain for M joints, one thread per joint, fp32.  x6 [M,6] f32, row = the reference's
+ * view(-1,3,2): (a1x, a2x, a1y, a2y, a1z, a2z).
+ *   rotmat [M,9] (row-major 3x3, or NULL) = rot6d_to_rotmat (utils_mesh.py:316-330): b1 = a1 / max(|a1|, 1e-6),
+ *       b2 = u / max(|u|, 1e-6) with u = a2 - (b1 . a2) b1, b3 = b1 x b2, R = [b1 b2 b3] by columns;
+ *   aa [M,3] (or NULL) = rotation_matrix_to_angle_axis(rotmat) (:54-83) along the reference's own path: the TRANSPOSED matrix of
+ *       rotation_matrix_to_quaternion, its four mask cases with eps = 1e-6, q = 0.5 q_case / sqrt(t_case), then quaternion_to_angle_axis:
+ *       2 theta = 2 atan2(-sin, -cos) where cos < 0 and 2 atan2(sin, cos) otherwise, k = 2 theta / sin, k = 2 where sin^2 == 0, NaN -> 0.
+ * mbx_rot6d_theta_bwd: dx6 [M,6] = the cotangents drotmat [M,9] and daa [M,3] (either may be NULL: zero) pulled back to x6.  The forward
+ * is recomputed in registers.  It is the gradient autograd gives the reference: through the selected quaternion case only and through
+ * both normalisations (above and below their clamp).  ONE deviation: where sin^2 == 0 (an exact identity) the reference's autograd
+ * returns NaN for the whole joint (0 * inf through the unselected 2 theta / sin); here the continuous extension d aa = 2 d q_xyz is used.
+ * An element of aa that the NaN rule set to 0 passes no gradient.  dx6 must not alias x6.  Rows need 4-byte alignment only. */
+int mbx_rot6d_theta_fwd(const float* x6, float* rotmat, float* aa, int M, void* stream);
+int mbx_rot6d_theta_bwd(const float* x6, const float* drotmat, const float* daa, float* dx6, int M, void* stream);
+/* mbx_mesh_param_loss: the three parameter terms of MeshLoss.forward (loss_mesh.py:49-68) and their gradient in one call.  pred_theta,
+ * gt_theta [F,82] f32 = 24 axis-angle joints | 10 shape coefficients.  loss_type 0 = MSE, 1 = L1 (the shipped configs).
+ *   losses[0] loss_pose  = mean over F*24*9 of (R_p - R_g)^2 or |R_p - R_g|, R = batch_rodrigues (utils_mesh.py:8-51: |a + 1e-8| as the
+ *                          angle, the quaternion normalised once more in quat2mat) of both pose vectors
+ *   losses[1] loss_shape = mean over F*10 of the shape difference, by the same loss_type
+ *   losses[2] loss_norm  = mean over frames of |pred_theta|_2 (all 82 elements)
+ *   losses[3]            = lambda_pose * loss_pose + lambda_shape * loss_shape + lambda_norm * loss_norm
+ *   dtheta [F,82] (or NULL) = grad_scale * d losses[3] / d pred_theta; the L1 subgradient at a zero difference is 0 (torch's sign)
+ * It takes theta rather than rotation matrices because the evaluation feeds it flip-averaged thetas.  fp32; a workgroup leaves three
+ * partial sums and one finishing launch adds them in workgroup order.  ws: >= mbx_mesh_param_loss_ws(F) bytes. */
+size_t mbx_mesh_param_loss_ws(int F);
+int mbx_mesh_param_loss(const float* pred_theta, const float* gt_theta, int loss_type, float lambda_pose, float lambda_shape,
+                        float lambda_norm, float grad_scale, float* losses, float* dtheta, int F, void* ws, void* stream);
+/* mbx_mesh_errors: per frame, in the order of compute_error / evaluate_mesh (utils_mesh.py:333-438), fp64 after the f32 loads.
+ * verts_p, verts_g [F,V,3] f32 (both NULL: row 0 is NaN, for callers that only have joints), kp_p, kp_g [F,17,3] f32, err [5,F] f64:
+ *   err[0] MPVE            mean over vertices of |(v_p - kp_p[0]) - (v_g - kp_g[0])|
+ *   err[1] MPJPE, 17 joints, both sides minus their joint 0          ('mpjpe_17j')
+ *   err[2] MPJPE, the 14 joints h36m_17_to_14 = (1..6, 8, 10..16)    ('mpjpe')
+ *   err[3] PA-MPJPE, 17 joints: after rigid_align's similarity transform of the prediction onto the target   ('pa_mpjpe_17j')
+ *   err[4] PA-MPJPE, 14 joints                                       ('pa_mpjpe')
+ * One workgroup per frame streams the vertices with 4-byte loads (frame bases need no more alignment).  The 3x3 decomposition is the
+ * fixed-sweep Jacobi of mbx_pose_errors (csrc/pose_solve.h).  A frame whose predicted joints have zero extent gives NaN in rows 3 / 4
+ * as the reference's 0 / 0 does; a target of zero extent alone gives the reference's scale 0.  1 <= V. */
+int mbx_mesh_errors(const float* verts_p, const float* verts_g, const float* kp_p, const float* kp_g, double* err, int F, int V,
+                    void* stream);
+
 /* ---- measurement aid (bench.py `roofline.sustained_mfma_tflops`; not part of the model) --------------------------------------------
  * The bf16 MFMA rate the part sustains under its power cap with nothing but v_mfma_f32_32x32x16_bf16 in the loop (pseudo-random
  * operands; n_wg workgroups of 4 waves, `iters` x 16 MFMAs per wave).  ws: >= mbx_mfma_probe_ws(n_wg) bytes = a float sink

@@ -5,6 +5,7 @@
 //   mbx_eval_reduce : mean over the clips that cover a test frame, mean over the frames of an action, mean over the actions,
 //                     in a fixed summation order (no floating-point atomics): two runs give the same bits.
 #include "mbx_common.h"
+#include "pose_solve.h"
 
 // ---------------------------------------------------------------------------------------------------------------
 // pose errors.  A workgroup is ONE wave and owns 64 consecutive frames.  Their 64 * 3J floats of pred and of gt are one
@@ -24,30 +25,6 @@
 // A frame whose pred or gt has zero extent divides 0 by 0 as the reference does: e2 is NaN there.
 // ---------------------------------------------------------------------------------------------------------------
 #define PE_FRAMES 64
-
-// one Jacobi rotation of the symmetric 3x3 matrix in the (p, q) plane; r is the third index.  V's columns p and q follow.
-__device__ __forceinline__ void pe_jacobi(double& app, double& aqq, double& apq, double& apr, double& aqr, double& v0p, double& v0q,
-                                          double& v1p, double& v1q, double& v2p, double& v2q) {
-    const double theta = (aqq - app) / (2.0 * apq);
-    double t = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0));
-    t = theta < 0.0 ? -t : t;
-    t = apq == 0.0 ? 0.0 : t;              // nothing to annihilate (theta = +-inf or NaN)
-    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-    app -= t * apq;
-    aqq += t * apq;
-    apq = 0.0;
-    const double pr = apr, qr = aqr;
-    apr = c * pr - s * qr;
-    aqr = s * pr + c * qr;
-    double a, b;
-    a = v0p; b = v0q; v0p = c * a - s * b; v0q = s * a + c * b;
-    a = v1p; b = v1q; v1p = c * a - s * b; v1q = s * a + c * b;
-    a = v2p; b = v2q; v2p = c * a - s * b; v2q = s * a + c * b;
-}
-__device__ __forceinline__ void pe_swap_if(bool sw, double& a, double& b) {
-    const double x = sw ? b : a, y = sw ? a : b;
-    a = x; b = y;
-}
 
 // copy the run [beg, end) (element indices into src) to LDS rows of `stride` words, 3J elements per row
 __device__ __forceinline__ void pe_stage(const float* __restrict__ src, const float* __restrict__ x2d, int xs, long long beg, long long end,
@@ -159,47 +136,14 @@ __global__ __launch_bounds__(PE_FRAMES) void pose_errors_kernel(const float* __r
     const double h00 = m00 * hs, h01 = m01 * hs, h02 = m02 * hs, h10 = m10 * hs, h11 = m11 * hs, h12 = m12 * hs, h20 = m20 * hs,
                  h21 = m21 * hs, h22 = m22 * hs;
 
-    // ---- A = H^T H = V S^2 V^T by cyclic Jacobi; V = (v_ij), column j the j-th right singular vector
-    double a00 = h00 * h00 + h10 * h10 + h20 * h20, a01 = h00 * h01 + h10 * h11 + h20 * h21, a02 = h00 * h02 + h10 * h12 + h20 * h22;
-    double a11 = h01 * h01 + h11 * h11 + h21 * h21, a12 = h01 * h02 + h11 * h12 + h21 * h22, a22 = h02 * h02 + h12 * h12 + h22 * h22;
-    double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
-#pragma unroll
-    for (int sweep = 0; sweep < 8; ++sweep) {
-        pe_jacobi(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);
-        pe_jacobi(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);
-        pe_jacobi(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);
-    }
-    // the two largest eigenvalues first (a compare with NaN swaps nothing)
-    bool sw = a00 < a11;
-    pe_swap_if(sw, a00, a11); pe_swap_if(sw, v00, v01); pe_swap_if(sw, v10, v11); pe_swap_if(sw, v20, v21);
-    sw = a00 < a22;
-    pe_swap_if(sw, a00, a22); pe_swap_if(sw, v00, v02); pe_swap_if(sw, v10, v12); pe_swap_if(sw, v20, v22);
-    sw = a11 < a22;
-    pe_swap_if(sw, a11, a22); pe_swap_if(sw, v01, v02); pe_swap_if(sw, v11, v12); pe_swap_if(sw, v21, v22);
-    // v0, v1 unit and orthogonal to rounding; v2 = v0 x v1
-    v02 = v10 * v21 - v20 * v11;
-    v12 = v20 * v01 - v00 * v21;
-    v22 = v00 * v11 - v10 * v01;
-    // u0 = H v0 / s0,  u1 = H v1 / s1 (orthogonalised against u0),  u2 = u0 x u1
-    double u00 = h00 * v00 + h01 * v10 + h02 * v20, u10 = h10 * v00 + h11 * v10 + h12 * v20, u20 = h20 * v00 + h21 * v10 + h22 * v20;
-    const double sv0 = sqrt(u00 * u00 + u10 * u10 + u20 * u20);
-    u00 /= sv0; u10 /= sv0; u20 /= sv0;
-    double u01 = h00 * v01 + h01 * v11 + h02 * v21, u11 = h10 * v01 + h11 * v11 + h12 * v21, u21 = h20 * v01 + h21 * v11 + h22 * v21;
-    const double dot = u00 * u01 + u10 * u11 + u20 * u21;
-    u01 -= dot * u00; u11 -= dot * u10; u21 -= dot * u20;
-    const double sv1 = sqrt(u01 * u01 + u11 * u11 + u21 * u21);
-    u01 /= sv1; u11 /= sv1; u21 /= sv1;
-    const double u02 = u10 * u21 - u20 * u11, u12 = u20 * u01 - u00 * u21, u22 = u00 * u11 - u10 * u01;
-    const double w0 = h00 * v02 + h01 * v12 + h02 * v22, w1 = h10 * v02 + h11 * v12 + h12 * v22, w2 = h20 * v02 + h21 * v12 + h22 * v22;
-    const double sv2 = u02 * w0 + u12 * w1 + u22 * w2;     // signed: negative when the best orthogonal map is a reflection
-    const double scale = (sv0 + sv1 + sv2) * normx / normy;
-    // a R,  R = V U^T:  R[i][k] = sum_m v_im u_km
-    const double r00 = scale * (v00 * u00 + v01 * u01 + v02 * u02), r01 = scale * (v00 * u10 + v01 * u11 + v02 * u12),
-                 r02 = scale * (v00 * u20 + v01 * u21 + v02 * u22);
-    const double r10 = scale * (v10 * u00 + v11 * u01 + v12 * u02), r11 = scale * (v10 * u10 + v11 * u11 + v12 * u12),
-                 r12 = scale * (v10 * u20 + v11 * u21 + v12 * u22);
-    const double r20 = scale * (v20 * u00 + v21 * u01 + v22 * u02), r21 = scale * (v20 * u10 + v21 * u11 + v22 * u12),
-                 r22 = scale * (v20 * u20 + v21 * u21 + v22 * u22);
+    // ---- R = V U^T and the signed sum of the singular values (pose_solve.h)
+    double ssum, q00, q01, q02, q10, q11, q12, q20, q21, q22;
+    pe_rotation(h00, h01, h02, h10, h11, h12, h20, h21, h22, ssum, q00, q01, q02, q10, q11, q12, q20, q21, q22);
+    const double scale = ssum * normx / normy;
+    // a R
+    const double r00 = scale * q00, r01 = scale * q01, r02 = scale * q02;
+    const double r10 = scale * q10, r11 = scale * q11, r12 = scale * q12;
+    const double r20 = scale * q20, r21 = scale * q21, r22 = scale * q22;
 
     // ---- pass 3: Protocol #2
     double s2 = 0.0;

@@ -102,6 +102,11 @@ SIGNATURES = {
     'mbx_supcon_loss_ws': (_sz, [_i, _i]),
     'mbx_supcon_loss': (_i, [_vp, _vp, _i, _i, _i, _f, _f, _i, _f, _vp, _vp, _vp, _vp]),
     'mbx_nn_cosine': (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    'mbx_rot6d_theta_fwd': (_i, [_vp, _vp, _vp, _i, _vp]),
+    'mbx_rot6d_theta_bwd': (_i, [_vp, _vp, _vp, _vp, _i, _vp]),
+    'mbx_mesh_param_loss_ws': (_sz, [_i]),
+    'mbx_mesh_param_loss': (_i, [_vp, _vp, _i, _f, _f, _f, _f, _vp, _vp, _i, _vp, _vp]),
+    'mbx_mesh_errors': (_i, [_vp] * 5 + [_i, _i, _vp]),
     'mbx_rows_n_pack_bytes': (_sz, [_i, _i]),
     'mbx_rows_lnbwd_t': (_i, [_vp] * 6 + [_i, _i, _i, _vp]),
     'mbx_rows_n_pack_many': (_i, [_i64p, _i, _i, _i, _vp]),
@@ -683,6 +688,68 @@ class HipOps:
             raise RuntimeError('libmbx: nn_cosine: test labels without a hit counter')
         self._ck(self.lib.mbx_nn_cosine(_p(anchors), _p(anchor_labels), M, _p(test), _p(test_labels), N, D, _p(pred_label), _p(best_sim),
                                         _p(hits), self._stream()))
+
+    # ------------------------------------------------------------------ mesh recovery (train_mesh.py, lib/model/model_mesh.py, loss_mesh.py)
+    def rot6d_theta_fwd(self, x6, rotmat, aa):
+        """x6 [M,6] f32 -> rotmat [M,9] (or [M,3,3]) and aa [M,3] f32, either None; all contiguous, on the device of x6."""
+        if x6.dim() != 2 or x6.shape[1] != 6 or (rotmat is None and aa is None):
+            raise RuntimeError(f'libmbx: rot6d_theta_fwd needs x6 [M,6] and at least one output, got {tuple(x6.shape)}')
+        M = x6.shape[0]
+        self._dense('rot6d_theta_fwd', torch.float32, M * 6, x6.device, x6=x6)
+        self._dense('rot6d_theta_fwd', torch.float32, M * 9, x6.device, rotmat=rotmat)
+        self._dense('rot6d_theta_fwd', torch.float32, M * 3, x6.device, aa=aa)
+        self._ck(self.lib.mbx_rot6d_theta_fwd(_p(x6), _p(rotmat), _p(aa), M, self._stream()))
+
+    def rot6d_theta_bwd(self, x6, drotmat, daa, dx6):
+        """dx6 [M,6] = the cotangents drotmat [M,9] / daa [M,3] (either None: zero) pulled back to x6 [M,6]."""
+        if x6.dim() != 2 or x6.shape[1] != 6:
+            raise RuntimeError(f'libmbx: rot6d_theta_bwd needs x6 [M,6], got {tuple(x6.shape)}')
+        M = x6.shape[0]
+        if dx6 is None or dx6.data_ptr() == x6.data_ptr() and M:
+            raise RuntimeError('libmbx: rot6d_theta_bwd needs dx6, which must not alias x6')
+        self._dense('rot6d_theta_bwd', torch.float32, M * 6, x6.device, x6=x6, dx6=dx6)
+        self._dense('rot6d_theta_bwd', torch.float32, M * 9, x6.device, drotmat=drotmat)
+        self._dense('rot6d_theta_bwd', torch.float32, M * 3, x6.device, daa=daa)
+        self._ck(self.lib.mbx_rot6d_theta_bwd(_p(x6), _p(drotmat), _p(daa), _p(dx6), M, self._stream()))
+
+    def mesh_param_loss(self, pred_theta, gt_theta, loss_type, lambdas3, losses, dtheta, grad_scale=1.0):
+        """pred_theta, gt_theta [F,82] f32; loss_type 0 (MSE) / 1 (L1); lambdas3 = (lambda_pose, lambda_shape, lambda_norm);
+        losses [4] f32 = [loss_pose, loss_shape, loss_norm, weighted sum]; dtheta like pred_theta or None."""
+        if pred_theta.dim() != 2 or pred_theta.shape[1] != 82 or pred_theta.shape[0] < 1 or gt_theta.shape != pred_theta.shape or len(lambdas3) != 3:
+            raise RuntimeError(f'libmbx: mesh_param_loss needs pred_theta, gt_theta [F >= 1, 82] and three lambdas, got {tuple(pred_theta.shape)} / '
+                               f'{tuple(gt_theta.shape)} / {len(lambdas3)} lambdas')
+        if int(loss_type) not in (0, 1):
+            raise RuntimeError(f'libmbx: mesh_param_loss: loss_type {loss_type} (0 = MSE, 1 = L1)')
+        F = pred_theta.shape[0]
+        dev = pred_theta.device
+        self._dense('mesh_param_loss', torch.float32, F * 82, dev, pred_theta=pred_theta, gt_theta=gt_theta, dtheta=dtheta)
+        self._dense('mesh_param_loss', torch.float32, 4, dev, losses=losses)
+        if losses is None:
+            raise RuntimeError('libmbx: mesh_param_loss: losses [4] is required')
+        ws = self._ws(('mpl', F), self.lib.mbx_mesh_param_loss_ws, F, device=dev)
+        self._ck(self.lib.mbx_mesh_param_loss(_p(pred_theta), _p(gt_theta), int(loss_type), *[float(v) for v in lambdas3], float(grad_scale),
+                                              _p(losses), _p(dtheta), F, _p(ws), self._stream()))
+
+    def mesh_errors(self, verts_p, verts_g, kp_p, kp_g, err):
+        """verts_p, verts_g [F,V,3] f32 (both None: the MPVE row is NaN), kp_p, kp_g [F,17,3] f32, err [5,F] f64 =
+        [mpve, mpjpe_17j, mpjpe (14 joints), pa_mpjpe_17j, pa_mpjpe (14 joints)] per frame."""
+        if kp_p.dim() != 3 or tuple(kp_p.shape[1:]) != (17, 3) or kp_g.shape != kp_p.shape:
+            raise RuntimeError(f'libmbx: mesh_errors needs kp_p, kp_g [F,17,3], got {tuple(kp_p.shape)} / {tuple(kp_g.shape)}')
+        F = kp_p.shape[0]
+        dev = kp_p.device
+        if (verts_p is None) != (verts_g is None):
+            raise RuntimeError('libmbx: mesh_errors: verts_p and verts_g must both be given or both be None')
+        V = 1
+        if verts_p is not None:
+            if verts_p.dim() != 3 or verts_p.shape[0] != F or verts_p.shape[2] != 3 or verts_p.shape[1] < 1 or verts_g.shape != verts_p.shape:
+                raise RuntimeError(f'libmbx: mesh_errors needs verts_p, verts_g [{F},V >= 1,3], got {tuple(verts_p.shape)} / {tuple(verts_g.shape)}')
+            V = verts_p.shape[1]
+        self._dense('mesh_errors', torch.float32, F * 51, dev, kp_p=kp_p, kp_g=kp_g)
+        self._dense('mesh_errors', torch.float32, F * V * 3, dev, verts_p=verts_p, verts_g=verts_g)
+        self._dense('mesh_errors', torch.float64, 5 * F, dev, err=err)
+        if err is None:
+            raise RuntimeError('libmbx: mesh_errors: err [5,F] is required')
+        self._ck(self.lib.mbx_mesh_errors(_p(verts_p), _p(verts_g), _p(kp_p), _p(kp_g), _p(err), F, V, self._stream()))
 
     # ------------------------------------------------------------------ dropout / drop-path (SURVEY 8 a15)
     def dropout(self, x, y, p, seed):

@@ -1,0 +1,427 @@
+"""Mesh recovery on the device (reference `train_mesh.py`, `lib/model/model_mesh.py`, `lib/model/loss_mesh.py`, `lib/utils/utils_mesh.py`;
+configs `configs/mesh/*.yaml`).  The SMPL layer stays what it is in the reference -- a module the user supplies (`smplx` and the SMPL model
+files are not part of this project); everything around it is here:
+
+    rot6d_to_rotmat_theta(x6)       the head's rotation chain 6D -> rotation matrix -> quaternion -> axis-angle as ONE kernel forward and ONE
+                                    backward (`mbx_rot6d_theta_fwd / _bwd`; about 120 small torch kernels each way in the reference).
+    SMPLRegressor / MeshRegressor   model_mesh.py:9-101 with the reference's parameter and buffer names; `smpl`, `init_pose`, `init_shape` and
+                                    `J_regressor` are injected.
+    MeshLoss(loss_type, lambdas)    loss_mesh.py:7-68: the reference's dict of ten losses as 0-dim device tensors; the seven joint terms from
+                                    one `mbx_pose_loss_full`, the three parameter terms from one `mbx_mesh_param_loss`.
+    MeshStep(model, ...)            the optimizer step of train_mesh.py:165-203 without a host synchronisation; the ten losses, the total and
+                                    the step's MPJPE / MPVE stay in a device log tensor.
+    MeshEvaluator()                 `update(output, batch_gt)` per test batch (`mbx_mesh_errors` into device buffers), `finish()` returns
+                                    `evaluate_mesh`'s dict and is the only host synchronisation: no vertex ever goes to the host.
+    compute_error / compute_error_frames   the reference's signatures (utils_mesh.py:357-393) on the same kernel.
+
+Not here: an SMPL layer, `flip_thetas_batch`, translation estimation, rendering, a DDP variant of the step.
+
+There is no CPU path: without an injected kernel provider (`ops=`), tensors that are not on a ROCm device raise.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+
+LOSS_KEYS = ('loss_3d_pos', 'loss_3d_scale', 'loss_3d_velocity', 'loss_lv', 'loss_lg', 'loss_a', 'loss_av', 'loss_shape', 'loss_pose', 'loss_norm')
+LAMBDA_NAMES = ('lambda_3d', 'lambda_scale', 'lambda_3dv', 'lambda_lv', 'lambda_lg', 'lambda_a', 'lambda_av', 'lambda_shape', 'lambda_pose',
+                'lambda_norm')      # train_mesh.py:180-189, in the order of LOSS_KEYS
+ERROR_KEYS = ('mpve', 'mpjpe_17j', 'mpjpe', 'pa_mpjpe_17j', 'pa_mpjpe')      # rows of mbx_mesh_errors; 'mpjpe' / 'pa_mpjpe' use the 14 joints
+LOSS_TYPES = {'MSE': 0, 'L1': 1}
+
+
+def _provider(ops, what: str, *tensors):
+    if ops is not None:
+        return ops
+    for t in tensors:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f'motionbert_amd.mesh.{what} runs on the ROCm device (move the tensors first); there is no CPU path')
+    from . import hip_ops
+    return hip_ops.get()
+
+
+# ---------------------------------------------------------------------------------------------------------------- rotation chain
+class _Rot6dFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ops, x6):
+        x = x6.detach().contiguous().float()
+        M = x.shape[0]
+        rotmat = torch.empty(M, 9, dtype=torch.float32, device=x.device)
+        aa = torch.empty(M, 3, dtype=torch.float32, device=x.device)
+        if M:
+            ops.rot6d_theta_fwd(x, rotmat, aa)
+        ctx.ops, ctx.x = ops, x
+        ctx.set_materialize_grads(False)
+        return rotmat.view(M, 3, 3), aa
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, drotmat, daa):
+        x = ctx.x
+        dx = torch.zeros_like(x)
+        if x.shape[0] and (drotmat is not None or daa is not None):
+            dr = None if drotmat is None else drotmat.contiguous().float().reshape(-1, 9)
+            da = None if daa is None else daa.contiguous().float()
+            ctx.ops.rot6d_theta_bwd(x, dr, da, dx)
+        return None, dx
+
+
+def rot6d_to_rotmat_theta(x6: torch.Tensor, ops=None):
+    """`(rotmat [M,3,3], aa [M,3])` of x6 [M,6] (or [..., 6k], flattened as the reference's `view(-1, 3, 2)` flattens it):
+    `rot6d_to_rotmat(x6)` and `rotation_matrix_to_angle_axis(rotmat)` of utils_mesh.py, differentiable with respect to x6 through
+    either output.  The gradient is autograd's of the reference, except at an exact identity (sin^2 == 0), where the reference gives
+    NaN and this the continuous extension `d aa = 2 d q_xyz` (include/mbx.h)."""
+    if x6.numel() % 6 != 0:
+        raise ValueError(f'rot6d_to_rotmat_theta needs a multiple of 6 elements, got {tuple(x6.shape)}')
+    if not x6.dtype.is_floating_point:
+        raise ValueError(f'rot6d_to_rotmat_theta needs a floating-point tensor, got {x6.dtype}')
+    ops = _provider(ops, 'rot6d_to_rotmat_theta', x6)
+    return _Rot6dFn.apply(ops, x6.reshape(-1, 6))
+
+
+# ---------------------------------------------------------------------------------------------------------------- model
+class SMPLRegressor(nn.Module):
+    """model_mesh.py:9-80 with the SMPL layer injected.  `smpl`: any nn.Module called as `smpl(betas=, body_pose=, global_orient=,
+    pose2rot=False)` that returns an object with `.vertices` [F,V,3] in metres; `init_pose` [1,144] / `init_shape` [1,10]: the mean
+    parameters (`smpl_mean_params`); `J_regressor` [17,V]: `smpl.J_regressor_h36m`.  Parameter and buffer names are the reference's
+    (`fc1 / fc2 / bn1 / bn2 / head_pose / head_shape`, `init_pose`, `init_shape`, `smpl.*`): with the reference's `SMPL` injected its
+    checkpoints load with `strict=True`.  `J_regressor` is a plain attribute as in the reference (it is `smpl`'s buffer there).
+    The Linear / BatchNorm layers are torch modules; the rotation chain is `rot6d_to_rotmat_theta`."""
+
+    def __init__(self, smpl, init_pose, init_shape, J_regressor, dim_rep=512, num_joints=17, hidden_dim=2048, dropout_ratio=0., ops=None):
+        super().__init__()
+        param_pose_dim = 24 * 6
+        self.dropout = nn.Dropout(p=dropout_ratio)
+        self.fc1 = nn.Linear(num_joints * dim_rep, hidden_dim)
+        self.pool2 = nn.AdaptiveAvgPool2d((None, 1))
+        self.fc2 = nn.Linear(num_joints * dim_rep, hidden_dim)
+        self.bn1 = nn.BatchNorm1d(hidden_dim, momentum=0.1)
+        self.bn2 = nn.BatchNorm1d(hidden_dim, momentum=0.1)
+        self.relu1 = nn.ReLU(inplace=True)
+        self.relu2 = nn.ReLU(inplace=True)
+        self.head_pose = nn.Linear(hidden_dim, param_pose_dim)
+        self.head_shape = nn.Linear(hidden_dim, 10)
+        nn.init.xavier_uniform_(self.head_pose.weight, gain=0.01)
+        nn.init.xavier_uniform_(self.head_shape.weight, gain=0.01)
+        self.smpl = smpl
+        init_pose, init_shape = torch.as_tensor(init_pose), torch.as_tensor(init_shape)
+        if init_pose.numel() != param_pose_dim or init_shape.numel() != 10:
+            raise ValueError(f'init_pose needs 144 elements and init_shape 10, got {tuple(init_pose.shape)} / {tuple(init_shape.shape)}')
+        self.register_buffer('init_pose', init_pose.reshape(1, param_pose_dim).clone())
+        self.register_buffer('init_shape', init_shape.reshape(1, 10).float().clone())
+        J_regressor = torch.as_tensor(J_regressor)
+        if J_regressor.dim() != 2 or J_regressor.shape[0] != 17:
+            raise ValueError(f'J_regressor needs to be [17, V], got {tuple(J_regressor.shape)}')
+        self.J_regressor = J_regressor
+        self.ops = ops
+
+    def forward(self, feat, init_pose=None, init_shape=None):
+        N, T, J, C = feat.shape
+        NT = N * T
+        feat = feat.reshape(N, T, -1)
+        feat_pose = self.relu1(self.bn1(self.fc1(self.dropout(feat.reshape(NT, -1)))))          # (NT, hidden)
+        feat_shape = self.pool2(feat.permute(0, 2, 1)).reshape(N, -1)                           # mean over T: (N, J*C)
+        feat_shape = self.relu2(self.bn2(self.fc2(self.dropout(feat_shape))))                   # (N, hidden)
+        pred_pose = self.head_pose(feat_pose) + self.init_pose.expand(NT, -1)
+        pred_shape = self.head_shape(feat_shape) + self.init_shape.expand(N, -1)
+        pred_shape = pred_shape.expand(T, N, -1).permute(1, 0, 2).reshape(NT, -1)
+        rotmat, aa = rot6d_to_rotmat_theta(pred_pose.float(), ops=self.ops)
+        rotmat, aa = rotmat.to(pred_pose.dtype), aa.to(pred_pose.dtype)                         # (the kernels are fp32)
+        pred_rotmat = rotmat.view(NT, 24, 3, 3)
+        pred_output = self.smpl(betas=pred_shape, body_pose=pred_rotmat[:, 1:], global_orient=pred_rotmat[:, 0].unsqueeze(1), pose2rot=False)
+        pred_vertices = pred_output.vertices * 1000.0
+        if self.J_regressor.device != pred_vertices.device or self.J_regressor.dtype != pred_vertices.dtype:
+            self.J_regressor = self.J_regressor.to(pred_vertices)         # once, not per forward as the reference moves it: a host copy per step
+        pred_joints = torch.matmul(self.J_regressor[None].expand(NT, -1, -1), pred_vertices)
+        return [{'theta': torch.cat([aa.reshape(NT, 72), pred_shape], dim=1),       # (N*T, 72+10)
+                 'verts': pred_vertices,                                            # (N*T, V, 3)
+                 'kp_3d': pred_joints}]                                             # (N*T, 17, 3)
+
+
+class MeshRegressor(nn.Module):
+    """model_mesh.py:82-101: `MeshRegressor(backbone, head)` with a ready `SMPLRegressor`, or `MeshRegressor(backbone, smpl=, init_pose=,
+    init_shape=, J_regressor=, dim_rep=, num_joints=, hidden_dim=, dropout_ratio=)` (the reference's default dropout_ratio 0.5).
+    forward: x [N,T,17,3] -> a list with one dict `theta` [N,T,82] / `verts` [N,T,V,3] / `kp_3d` [N,T,17,3]."""
+
+    def __init__(self, backbone, head=None, dim_rep=512, num_joints=17, hidden_dim=2048, dropout_ratio=0.5, **head_args):
+        super().__init__()
+        self.backbone = backbone
+        self.feat_J = num_joints
+        if head is None:
+            head = SMPLRegressor(dim_rep=dim_rep, num_joints=num_joints, hidden_dim=hidden_dim, dropout_ratio=dropout_ratio, **head_args)
+        elif head_args:
+            raise ValueError(f'MeshRegressor: a ready head and head arguments {sorted(head_args)} exclude each other')
+        self.head = head
+
+    def forward(self, x, init_pose=None, init_shape=None, n_iter=3):
+        N, T, J, C = x.shape
+        feat = self.backbone.get_representation(x).reshape([N, T, self.feat_J, -1])
+        smpl_output = self.head(feat)
+        for s in smpl_output:
+            s['theta'] = s['theta'].reshape(N, T, -1)
+            s['verts'] = s['verts'].reshape(N, T, -1, 3)
+            s['kp_3d'] = s['kp_3d'].reshape(N, T, -1, 3)
+        return smpl_output
+
+
+# ---------------------------------------------------------------------------------------------------------------- loss
+def _joint_call(ops, kp, gt, lam6, want_grad):
+    losses = torch.empty(8, dtype=torch.float32, device=kp.device)
+    d = torch.empty_like(kp) if want_grad else None
+    ops.pose_loss_full(kp, gt, lam6, losses, d)
+    return losses, d
+
+
+def _param_call(ops, loss_type, theta, gt_theta, lam3, want_grad):
+    losses = torch.empty(4, dtype=torch.float32, device=theta.device)
+    d = torch.empty_like(theta) if want_grad else None
+    ops.mesh_param_loss(theta, gt_theta, loss_type, lam3, losses, d)
+    return losses, d
+
+
+def _log10(joint, param):
+    """the ten values in the order of LOSS_KEYS from mbx_pose_loss_full's [8] and mbx_mesh_param_loss's [4] = pose, shape, norm, sum"""
+    return torch.cat([joint[:7], param[1:2], param[0:1], param[2:3]])
+
+
+class _MeshTotalFn(torch.autograd.Function):
+    """total = sum lambda_i loss_i and the log; both cotangents come out of the two forward calls"""
+
+    @staticmethod
+    def forward(ctx, ops, kp, gt_kp, theta, gt_theta, lam10, loss_type):
+        l3d, lam6 = lam10[0], lam10[1:7]
+        lam3 = (lam10[8], lam10[7], lam10[9])                         # the kernel's order: pose, shape, norm
+        gk, gth = ctx.needs_input_grad[1], ctx.needs_input_grad[3]
+        if l3d != 0.0:
+            # mbx_pose_loss_full fixes the weight of loss_mpjpe at 1: the other six lambdas are divided by lambda_3d and the total and
+            # the cotangent multiplied by it
+            joint, dk = _joint_call(ops, kp, gt_kp, tuple(v / l3d for v in lam6), gk)
+            jtotal = joint[7] * l3d
+            if dk is not None:
+                dk = dk * l3d
+        else:
+            # lambda_3d == 0: (mpjpe + sum lambda_k term_k) - mpjpe, two calls
+            joint, dk = _joint_call(ops, kp, gt_kp, lam6, gk)
+            if dk is not None:
+                dk = dk - _joint_call(ops, kp, gt_kp, (0.0,) * 6, True)[1]
+            jtotal = joint[7] - joint[0]
+        param, dth = _param_call(ops, loss_type, theta, gt_theta, lam3, gth)
+        ctx.dk, ctx.dth = dk, dth
+        log = _log10(joint, param)
+        ctx.mark_non_differentiable(log)
+        return jtotal + param[3], log
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dtotal, _dlog):
+        dk, dth = ctx.dk, ctx.dth
+        ctx.dk = ctx.dth = None
+        return None, (dk * dtotal if dk is not None else None), None, (dth * dtotal if dth is not None else None), None, None, None
+
+
+class _MeshTermsFn(torch.autograd.Function):
+    """the ten losses as ten differentiable outputs: backward runs one kernel call per output that received a cotangent (the joint terms
+    2 .. 7 one more, shared: the kernel's total always carries loss_mpjpe with weight 1, which is subtracted again)"""
+
+    @staticmethod
+    def forward(ctx, ops, kp, gt_kp, theta, gt_theta, loss_type):
+        joint, _ = _joint_call(ops, kp, gt_kp, (0.0,) * 6, False)
+        param, _ = _param_call(ops, loss_type, theta, gt_theta, (0.0, 0.0, 0.0), False)
+        ctx.ops, ctx.loss_type = ops, loss_type
+        ctx.save_for_backward(kp, gt_kp, theta, gt_theta)
+        ctx.set_materialize_grads(False)
+        return tuple(_log10(joint, param).unbind(0))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *g):
+        kp, gt_kp, theta, gt_theta = ctx.saved_tensors
+        ops = ctx.ops
+        dk = dth = None
+        if ctx.needs_input_grad[1] and any(v is not None for v in g[:7]):
+            base = _joint_call(ops, kp, gt_kp, (0.0,) * 6, True)[1]
+            dk = base * g[0] if g[0] is not None else torch.zeros_like(kp)
+            for k in range(1, 7):
+                if g[k] is not None:
+                    e = tuple(1.0 if i == k - 1 else 0.0 for i in range(6))
+                    dk = dk + (_joint_call(ops, kp, gt_kp, e, True)[1] - base) * g[k]
+        if ctx.needs_input_grad[3] and any(v is not None for v in g[7:]):
+            dth = torch.zeros_like(theta)
+            for slot, k in ((0, 8), (1, 7), (2, 9)):             # kernel slot (pose, shape, norm) <- position in LOSS_KEYS
+                if g[k] is not None:
+                    e = tuple(1.0 if i == slot else 0.0 for i in range(3))
+                    dth = dth + _param_call(ops, ctx.loss_type, theta, gt_theta, e, True)[1] * g[k]
+        return None, dk, None, dth, None, None
+
+
+def _lambdas10(lambdas):
+    if isinstance(lambdas, dict):
+        return tuple(float(lambdas[n]) for n in LAMBDA_NAMES)
+    return tuple(float(getattr(lambdas, n)) for n in LAMBDA_NAMES)
+
+
+class MeshLoss(nn.Module):
+    """loss_mesh.py:7-68.  `forward(smpl_output, data_gt)` returns the reference's dict of ten 0-dim device tensors (`loss_3d_pos`,
+    `loss_3d_scale`, `loss_3d_velocity`, `loss_lv`, `loss_lg`, `loss_a`, `loss_av`, `loss_shape`, `loss_pose`, `loss_norm`) from
+    `smpl_output[-1]['theta' / 'kp_3d']` [N,T,82] / [N,T,17,3] and `data_gt['theta' / 'kp_3d']`.
+
+    With `lambdas` (an object or dict carrying `lambda_3d, lambda_scale, lambda_3dv, lambda_lv, lambda_lg, lambda_a, lambda_av, lambda_shape,
+    lambda_pose, lambda_norm` as train_mesh.py:180-189 reads them) the dict also has `total`, the trainer's weighted sum.  Only `total` is
+    differentiable then: its gradient comes out of the same two kernel calls that computed the values, and the ten entries are the log.
+    `mbx_pose_loss_full` fixes the weight of `loss_3d_pos` at 1; `lambda_3d` is honoured by handing the kernel the six other joint
+    lambdas divided by `lambda_3d` and multiplying its total and its cotangent by `lambda_3d`.  With `lambda_3d == 0` the kernel is
+    called twice (with the lambdas, and with all of them 0) and the `loss_3d_pos` part is subtracted.
+
+    Without `lambdas` every entry is individually differentiable, so the reference's own weighting line works unchanged; backward
+    then costs one kernel call per entry that is used."""
+
+    def __init__(self, loss_type='MSE', lambdas=None, device='cuda', ops=None):
+        super().__init__()
+        if loss_type not in LOSS_TYPES:
+            raise ValueError(f"loss_type must be 'MSE' or 'L1', got {loss_type!r}")
+        self.loss_type, self.device, self.ops = loss_type, device, ops
+        self.lambdas = None if lambdas is None else _lambdas10(lambdas)
+
+    def forward(self, smpl_output, data_gt):
+        preds = smpl_output[-1]
+        theta, kp = preds['theta'], preds['kp_3d']
+        gt_theta, gt_kp = data_gt['theta'], data_gt['kp_3d']
+        if theta.dim() != 3 or theta.shape[-1] != 82 or theta.shape[0] * theta.shape[1] < 1 or tuple(gt_theta.shape) != tuple(theta.shape):
+            raise ValueError(f'theta [N,T,82] expected for prediction and target, got {tuple(theta.shape)} / {tuple(gt_theta.shape)}')
+        if tuple(kp.shape) != tuple(theta.shape[:2]) + (17, 3) or tuple(gt_kp.shape) != tuple(kp.shape):
+            raise ValueError(f'kp_3d [N,T,17,3] expected for prediction and target, got {tuple(kp.shape)} / {tuple(gt_kp.shape)}')
+        ops = _provider(self.ops, 'MeshLoss', theta, kp, gt_theta, gt_kp)
+        kp_local = (kp - kp[:, :, 0:1, :]).float().contiguous()                    # loss_mesh.py:36-37
+        gt_local = (gt_kp - gt_kp[:, :, 0:1, :]).detach().float().contiguous()
+        th = theta.reshape(-1, 82).float().contiguous()
+        gth = gt_theta.reshape(-1, 82).detach().float().contiguous()
+        t = LOSS_TYPES[self.loss_type]
+        if self.lambdas is None:
+            return dict(zip(LOSS_KEYS, _MeshTermsFn.apply(ops, kp_local, gt_local, th, gth, t)))
+        total, log = _MeshTotalFn.apply(ops, kp_local, gt_local, th, gth, self.lambdas, t)
+        out = dict(zip(LOSS_KEYS, log.unbind(0)))
+        out['total'] = total
+        return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- errors
+def _frames(output, target):
+    out = output[0] if isinstance(output, (list, tuple)) else output
+    kp_p, kp_g = out['kp_3d'], target['kp_3d']
+    if kp_p.shape[-2:] != (17, 3) or tuple(kp_g.shape) != tuple(kp_p.shape):
+        raise ValueError(f'kp_3d [...,17,3] expected for prediction and target, got {tuple(kp_p.shape)} / {tuple(kp_g.shape)}')
+    vp, vg = out.get('verts'), target.get('verts')
+    if (vp is None) != (vg is None):
+        raise ValueError('verts must be given for prediction and target, or for neither')
+    F = kp_p.numel() // 51
+    if vp is not None:
+        if vp.shape[-1] != 3 or tuple(vg.shape) != tuple(vp.shape) or vp.numel() % (3 * max(F, 1)) != 0 or (F and vp.numel() == 0):
+            raise ValueError(f'verts [...,V,3] with the frames of kp_3d expected for prediction and target, got {tuple(vp.shape)} / {tuple(vg.shape)}')
+        V = vp.shape[-2]
+        vp, vg = vp.detach().reshape(-1, V, 3).float().contiguous(), vg.detach().reshape(-1, V, 3).float().contiguous()
+        if vp.shape[0] != F:
+            raise ValueError(f'verts have {vp.shape[0]} frames, kp_3d {F}')
+    return vp, vg, kp_p.detach().reshape(-1, 17, 3).float().contiguous(), kp_g.detach().reshape(-1, 17, 3).float().contiguous()
+
+
+def mesh_errors(output, target, ops=None) -> torch.Tensor:
+    """err [5,F] float64 on the device, rows ERROR_KEYS, for `output` (the model's list, or its dict) and `target` (dict): `verts`
+    [...,V,3] (optional on both) and `kp_3d` [...,17,3].  Without `verts` the `mpve` row is NaN."""
+    vp, vg, kp, kg = _frames(output, target)
+    ops = _provider(ops, 'mesh_errors', vp, vg, kp, kg)
+    err = torch.empty(5, kp.shape[0], dtype=torch.float64, device=kp.device)
+    if kp.shape[0]:
+        ops.mesh_errors(vp, vg, kp, kg, err)
+    return err
+
+
+def compute_error_frames(output, target, ops=None):
+    """utils_mesh.py:376-393: `(mpjpes [F], mpves [F])`, the 17-joint MPJPE and the MPVE per frame -- float64 tensors on the device (the
+    reference returns fp32 on the host, which is a synchronisation)."""
+    err = mesh_errors(output, target, ops)
+    return err[1], err[0]
+
+
+def compute_error(output, target, ops=None):
+    """utils_mesh.py:357-374: `(mpjpe, mpve)` as 0-dim device tensors, the means of `compute_error_frames`."""
+    mpjpes, mpves = compute_error_frames(output, target, ops)
+    return mpjpes.mean(), mpves.mean()
+
+
+class MeshEvaluator:
+    """`evaluate_mesh` (utils_mesh.py:395-438) accumulated on the device.
+
+        ev = MeshEvaluator()
+        for batch_input, batch_gt in test_loader: ev.update(model(batch_input.cuda()), batch_gt)      # batch_gt's tensors on the device
+        errors = ev.finish()       # {'mpve', 'mpjpe', 'pa_mpjpe', 'mpjpe_17j', 'pa_mpjpe_17j'}: the one host synchronisation
+
+    `update` runs `mbx_mesh_errors` on the batch and keeps its [5, frames] float64 result on the device (40 bytes per frame where the
+    reference keeps 165 KB per frame on the host); it returns that result.  `finish` averages every row over all frames seen."""
+
+    def __init__(self, ops=None):
+        if ops is None and not torch.cuda.is_available():
+            raise RuntimeError('motionbert_amd.mesh.MeshEvaluator runs on the ROCm device; there is no CPU path')
+        self.ops = ops
+        self.reset()
+
+    def reset(self):
+        self.rows = []
+        self.count = 0
+
+    def update(self, output, batch_gt) -> torch.Tensor:
+        err = mesh_errors(output, batch_gt, self.ops)
+        self.rows.append(err)
+        self.count += err.shape[1]
+        return err
+
+    def frames(self) -> torch.Tensor:
+        """[5, frames seen] on the device"""
+        if not self.rows:
+            raise RuntimeError('no update() yet')
+        return torch.cat(self.rows, dim=1)
+
+    def finish(self) -> dict:
+        if self.count == 0:
+            raise RuntimeError('finish() before any update()')
+        mean = self.frames().mean(dim=1).cpu().tolist()
+        return {k: mean[ERROR_KEYS.index(k)] for k in ('mpve', 'mpjpe', 'pa_mpjpe', 'mpjpe_17j', 'pa_mpjpe_17j')}
+
+
+# ---------------------------------------------------------------------------------------------------------------- step
+LOG_KEYS = LOSS_KEYS + ('total', 'mpjpe', 'mpve')
+
+
+class MeshStep:
+    """One optimizer step of train_mesh.py:165-203: forward, `MeshLoss` with the trainer's lambdas, `compute_error`, backward, and the two
+    AdamW groups of :316-321 -- backbone at `lr_backbone`, head at `lr_head` -- as two flat one-launch optimizers; `decay()` is the per-epoch
+    StepLR(gamma=lr_decay).  `batch_gt`: dict with `theta` [N,T,82], `kp_3d` [N,T,17,3], `verts` [N,T,V,3] on the device.
+    Returns the log: a device tensor [13] in the order of LOG_KEYS (the ten losses, the weighted total, the step's mean 17-joint MPJPE and
+    MPVE); nothing is synchronised with the host (the reference ends every step with eleven `.item()` calls and a `.cpu()`).
+    Single-process only."""
+
+    def __init__(self, model, lr_backbone: float = 5e-5, lr_head: float = 5e-4, weight_decay: float = 0.01, lambdas=None,
+                 loss_type: str = 'L1', ops=None):
+        from .train import FlatAdamW
+        if lambdas is None:
+            raise ValueError('MeshStep needs the trainer\'s lambdas (lambda_3d ... lambda_norm)')
+        self.model, self.ops = model, ops
+        self.criterion = MeshLoss(loss_type=loss_type, lambdas=lambdas, ops=ops)
+        self.opt_backbone = FlatAdamW(model.backbone, lr=lr_backbone, weight_decay=weight_decay)
+        self.opt_head = FlatAdamW([('head.' + n, p) for n, p in model.head.named_parameters() if p.requires_grad], lr=lr_head,
+                                  weight_decay=weight_decay)
+
+    def __call__(self, batch_input: torch.Tensor, batch_gt: dict) -> torch.Tensor:
+        output = self.model(batch_input)
+        self.opt_backbone.zero_grad(set_to_none=True)
+        self.opt_head.zero_grad(set_to_none=True)
+        losses = self.criterion(output, batch_gt)
+        with torch.no_grad():
+            mpjpe, mpve = compute_error(output, batch_gt, self.ops)
+        losses['total'].backward()
+        self.opt_backbone.step()
+        self.opt_head.step()
+        return torch.cat([torch.stack([losses[k].detach() for k in LOSS_KEYS + ('total',)]).double(), torch.stack([mpjpe, mpve])])
+
+    def decay(self, gamma: float):
+        self.opt_backbone.lr = self.opt_backbone.lr * gamma
+        self.opt_head.lr = self.opt_head.lr * gamma
