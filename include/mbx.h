@@ -482,6 +482,31 @@ int mbx_mesh_param_loss(const float* pred_theta, const float* gt_theta, int loss
 int mbx_mesh_errors(const float* verts_p, const float* verts_g, const float* kp_p, const float* kp_g, double* err, int F, int V,
                     void* stream);
 
+/* ---- the SMPL body model (csrc/smpl.hip; linear blend skinning as smplx.lbs.lbs evaluates it) -- mbx_version() >= 120 -------------------
+ * Model (all f32 on the device but `parents`): v_template [V,3], shapedirs [V,3,10], posedirs [207,3V] (column 3v+c; rows = the row-major
+ * flattening of R_1..R_23 - I), Jt [24,3] = J_regressor . v_template and Jd [24,3,10] = J_regressor . shapedirs (folded by the caller),
+ * parents: 24 ints ON THE HOST, parents[0] = -1 and 0 <= parents[j] < j, lbs_weights [V,24], Q [K,V] (a joint regressor, K <= 32, or NULL
+ * with K = 0), packed_t [3V,224] from mbx_smpl_pack = [posedirs^T | shapedirs | 0].
+ * Forward, per frame (betas [F,10], rotmat [F,24,9] row-major, global orientation first):
+ *   J_j = Jt_j + Jd_j beta;  Grot_0 = R_0, Gt_0 = J_0;  Grot_j = Grot_p R_j, Gt_j = Grot_p (J_j - J_p) + Gt_p;  A_j = [Grot_j | Gt_j - Grot_j J_j]
+ *   vp_v = v_template_v + shapedirs_v beta + posedirs[:, 3v:3v+3]^T vec(R_1 - I, ..., R_23 - I);  T_v = sum_j w_vj A_j;  x_v = T_v [vp_v; 1]
+ *   verts [F,V,3] = scale x;  kp [F,K,3] = scale Q x;  joints [F,24,3] = scale Gt.   Each output may be NULL (not all three).
+ * Backward: dverts [F,V,3], dkp [F,K,3], djoints [F,24,3] (each may be NULL: zero) pulled back to drotmat [F,24,9] and dbetas [F,10]; only
+ * betas and rotmat are read again, every per-vertex value is recomputed.  Nothing of size [F,V,...] but verts touches global memory.
+ * fp32, fixed summation order, no float atomics (tile / split partials and finishing launches).  ws: >= mbx_smpl_fwd_ws(F, V, K with kp,
+ * else 0) / mbx_smpl_bwd_ws(F, V, K) bytes, 16-byte aligned; ws_bytes is checked.  F = 0 is a no-op.  Refused: V < 1, K > 32, parents that
+ * are not a forward-ordered tree, an undersized workspace. */
+int mbx_smpl_pack(const float* shapedirs, const float* posedirs, float* packed_t, int V, void* stream);
+size_t mbx_smpl_fwd_ws(int F, int V, int K);
+size_t mbx_smpl_bwd_ws(int F, int V, int K);
+int mbx_smpl_fwd(const float* v_template, const float* shapedirs, const float* posedirs, const float* Jt, const float* Jd,
+                 const int* parents, const float* lbs_weights, const float* Q, int K, const float* betas, const float* rotmat,
+                 float scale, float* verts, float* kp, float* joints, int F, int V, void* ws, size_t ws_bytes, void* stream);
+int mbx_smpl_bwd(const float* v_template, const float* shapedirs, const float* posedirs, const float* packed_t, const float* Jt,
+                 const float* Jd, const int* parents, const float* lbs_weights, const float* Q, int K, const float* betas,
+                 const float* rotmat, float scale, const float* dverts, const float* dkp, const float* djoints, float* drotmat,
+                 float* dbetas, int F, int V, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- measurement aid (bench.py `roofline.sustained_mfma_tflops`; not part of the model) --------------------------------------------
  * The bf16 MFMA rate the part sustains under its power cap with nothing but v_mfma_f32_32x32x16_bf16 in the loop (pseudo-random
  * operands; n_wg workgroups of 4 waves, `iters` x 16 MFMAs per wave).  ws: >= mbx_mfma_probe_ws(n_wg) bytes = a float sink

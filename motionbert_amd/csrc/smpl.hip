@@ -1,0 +1,572 @@
+// The SMPL body model on the device: linear blend skinning as smplx.lbs.lbs evaluates it, forward and hand-written backward (include/mbx.h).
+//   mbx_smpl_pack     : the transposed model table PT [3V,224] = [posedirs^T | shapedirs | 0] the backward reads with one lane per column.
+//   mbx_smpl_fwd      : chain kernel (one thread per frame: joints, the 24 transforms A_j [F,24,12], pf [F,207]) -> vertex kernel (64
+//                       vertices x 32 frames per workgroup; lane = vertex, wave = 8 frames; pose blend, skinning, the tile's share of
+//                       Q x) -> keypoint finalize (tile partials added in tile order).
+//   mbx_smpl_bwd      : chain kernel again (nothing but betas and rotmat is saved) -> vertex backward (64 vertices x 16 frames per step;
+//                       phase 1, lane = vertex: vp, T, g, dvp recomputed into LDS; phase 2, lane = output column: d pf / d beta and d A
+//                       accumulated in registers over the workgroup's vertex tiles) -> split sum -> chain backward (one thread per frame).
+// Nothing of size [F,V,...] but verts exists in global memory: no transform tensor, no pose offsets, no v_posed.
+// fp32 FMAs on the vector unit (the fp32 MFMA of gfx950 runs at the same rate), fixed summation order, no floating-point atomics: two
+// calls on the same inputs give the same bits.  Frame-uniform operands (pf, A, betas, dkp) are read through wave-uniform addresses.
+#include "mbx_common.h"
+
+#define SM_J 24
+#define SM_PF 207          // 23 * 9
+#define SM_PFS 208         // row stride of the pf workspace
+#define SM_A 288           // 24 * 12
+#define SM_PT 224          // columns of PT: 207 posedirs rows, 10 shapedirs, 7 zero
+#define SM_COLS 512        // partial / sum record per frame: [0,224) the PT columns, [224,512) d A
+#define SM_VT 64           // vertices per tile
+#define SM_FW 8            // forward: frames per wave (32 per workgroup)
+#define SM_BW 4            // backward: frames per wave (16 per workgroup)
+#define SM_BF (4 * SM_BW)
+#define SM_ZS 20           // LDS row stride of the phase-1 values: 16 frames + 4 pad (16-byte aligned, conflict-free b128 writes)
+#define SM_SPLITS 8
+
+struct SmplTree { int p[SM_J]; };
+
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void smpl_pack_kernel(const float* __restrict__ shapedirs, const float* __restrict__ posedirs,
+                                                        float* __restrict__ pt, int V) {
+    const size_t n = (size_t)3 * V * SM_PT;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        const size_t row = i / SM_PT;
+        const int col = (int)(i % SM_PT);
+        float v = 0.0f;
+        if (col < SM_PF) v = posedirs[(size_t)col * 3 * V + row];
+        else if (col < SM_PF + 10) v = shapedirs[row * 10 + (col - SM_PF)];
+        pt[i] = v;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// chain.  G: per-thread scratch [288][F] (frame-minor: coalesced), first [Grot_j | Gt_j], read back by the same thread for the children.
+// ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void smpl_joint(const float* __restrict__ Jt, const float* __restrict__ Jd, const float (&b)[10], int j, float (&J)[3]) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float s = Jt[j * 3 + c];
+#pragma unroll
+        for (int k = 0; k < 10; ++k) s += Jd[(j * 3 + c) * 10 + k] * b[k];
+        J[c] = s;
+    }
+}
+
+__global__ __launch_bounds__(64) void smpl_chain_fwd_kernel(const float* __restrict__ betas, const float* __restrict__ rotmat,
+                                                            const float* __restrict__ Jt, const float* __restrict__ Jd, SmplTree tree, float scale,
+                                                            float* __restrict__ Aws, float* __restrict__ PFws, float* G, float* __restrict__ joints,
+                                                            int F) {
+    const int f = blockIdx.x * 64 + threadIdx.x;
+    if (f >= F) return;
+    float b[10];
+#pragma unroll
+    for (int k = 0; k < 10; ++k) b[k] = betas[(size_t)f * 10 + k];
+    const float* R = rotmat + (size_t)f * 216;
+    for (int k = 0; k < SM_PF; ++k) PFws[(size_t)f * SM_PFS + k] = R[9 + k] - (((k % 9) % 4 == 0) ? 1.0f : 0.0f);
+    PFws[(size_t)f * SM_PFS + SM_PF] = 0.0f;
+#define SM_G(j, e) G[(size_t)((j) * 12 + (e)) * F + f]
+    for (int j = 0; j < SM_J; ++j) {
+        float J[3], r[9];
+        smpl_joint(Jt, Jd, b, j, J);
+#pragma unroll
+        for (int e = 0; e < 9; ++e) r[e] = R[j * 9 + e];
+        if (j == 0) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+#pragma unroll
+                for (int d = 0; d < 3; ++d) SM_G(0, c * 4 + d) = r[c * 3 + d];
+                SM_G(0, c * 4 + 3) = J[c];
+            }
+        } else {
+            const int p = tree.p[j];
+            float Jp[3], P[12], rel[3];
+            smpl_joint(Jt, Jd, b, p, Jp);
+#pragma unroll
+            for (int e = 0; e < 12; ++e) P[e] = SM_G(p, e);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) rel[c] = J[c] - Jp[c];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+#pragma unroll
+                for (int d = 0; d < 3; ++d) SM_G(j, c * 4 + d) = P[c * 4] * r[d] + P[c * 4 + 1] * r[3 + d] + P[c * 4 + 2] * r[6 + d];
+                SM_G(j, c * 4 + 3) = P[c * 4] * rel[0] + P[c * 4 + 1] * rel[1] + P[c * 4 + 2] * rel[2] + P[c * 4 + 3];
+            }
+        }
+    }
+    for (int j = 0; j < SM_J; ++j) {
+        float J[3], g[12];
+        smpl_joint(Jt, Jd, b, j, J);
+#pragma unroll
+        for (int e = 0; e < 12; ++e) g[e] = SM_G(j, e);
+        float* A = Aws + (size_t)f * SM_A + j * 12;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+#pragma unroll
+            for (int d = 0; d < 3; ++d) A[c * 4 + d] = g[c * 4 + d];
+            A[c * 4 + 3] = g[c * 4 + 3] - (g[c * 4] * J[0] + g[c * 4 + 1] * J[1] + g[c * 4 + 2] * J[2]);
+            if (joints) joints[(size_t)f * 72 + j * 3 + c] = scale * g[c * 4 + 3];
+        }
+    }
+#undef SM_G
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// the per-vertex values both directions need, lane = vertex, NF frames of the wave in registers
+// ---------------------------------------------------------------------------------------------------------------
+template <int NF>
+__device__ __forceinline__ void smpl_vposed(const float* __restrict__ vt, const float* __restrict__ sd, const float* __restrict__ pd,
+                                            const float* __restrict__ betas, const float* __restrict__ PFws, const int (&fi)[NF], int v, int V,
+                                            float (&vp)[NF][3]) {
+    // the offsets are summed from zero and the template is added last: 217 additions into a running value of template size would
+    // each round at the template's ulp, and (vp - J) is what the skinning and its gradient see
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int i = 0; i < NF; ++i) vp[i][c] = 0.0f;
+    for (int k = 0; k < 10; ++k) {
+        const float s0 = sd[(size_t)v * 30 + k], s1 = sd[(size_t)v * 30 + 10 + k], s2 = sd[(size_t)v * 30 + 20 + k];
+#pragma unroll
+        for (int i = 0; i < NF; ++i) {
+            const float bv = betas[(size_t)fi[i] * 10 + k];
+            vp[i][0] += s0 * bv; vp[i][1] += s1 * bv; vp[i][2] += s2 * bv;
+        }
+    }
+    const float* col = pd + (size_t)3 * v;
+#pragma unroll 3
+    for (int k = 0; k < SM_PF; ++k) {
+        const float* row = col + (size_t)k * 3 * V;
+        const float p0 = row[0], p1 = row[1], p2 = row[2];
+#pragma unroll
+        for (int i = 0; i < NF; ++i) {
+            const float pf = PFws[(size_t)fi[i] * SM_PFS + k];
+            vp[i][0] += p0 * pf; vp[i][1] += p1 * pf; vp[i][2] += p2 * pf;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float t = vt[(size_t)v * 3 + c];
+#pragma unroll
+        for (int i = 0; i < NF; ++i) vp[i][c] += t;
+    }
+}
+
+// T = sum_j w_j A_j over the joints some lane of the wave has a weight on (mask); a skipped term is an exact + 0
+__device__ __forceinline__ void smpl_blend(const float (&w)[SM_J], unsigned mask, const float* __restrict__ A, float (&T)[12]) {
+#pragma unroll
+    for (int e = 0; e < 12; ++e) T[e] = 0.0f;
+#pragma unroll
+    for (int j = 0; j < SM_J; ++j) {
+        if (mask & (1u << j)) {
+#pragma unroll
+            for (int e = 0; e < 12; ++e) T[e] += w[j] * A[j * 12 + e];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void smpl_verts_fwd_kernel(const float* __restrict__ vt, const float* __restrict__ sd, const float* __restrict__ pd,
+                                                             const float* __restrict__ lbsw, const float* __restrict__ Q,
+                                                             const float* __restrict__ betas, const float* __restrict__ Aws,
+                                                             const float* __restrict__ PFws, float scale, float* __restrict__ verts,
+                                                             float* __restrict__ kpart, int F, int V, int K) {
+    __shared__ float qs[32 * 65];
+    __shared__ float xs[4][3][64];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int v0 = blockIdx.x * SM_VT;
+    const bool live = v0 + lane < V;
+    const int v = live ? v0 + lane : V - 1;
+    const int f0 = blockIdx.y * (4 * SM_FW) + wave * SM_FW;
+    if (kpart) {
+        for (int idx = tid; idx < K * 64; idx += 256) {
+            const int k = idx >> 6, l = idx & 63;
+            qs[k * 65 + l] = (v0 + l < V) ? Q[(size_t)k * V + v0 + l] : 0.0f;
+        }
+    }
+    float w[SM_J];
+    unsigned mask = 0;
+#pragma unroll
+    for (int j = 0; j < SM_J; ++j) {
+        w[j] = lbsw[(size_t)v * SM_J + j];
+        if (__ballot(w[j] != 0.0f) != 0ull) mask |= 1u << j;
+    }
+    int fi[SM_FW];
+#pragma unroll
+    for (int i = 0; i < SM_FW; ++i) fi[i] = min(f0 + i, F - 1);
+    float vp[SM_FW][3];
+    smpl_vposed<SM_FW>(vt, sd, pd, betas, PFws, fi, v, V, vp);
+    __syncthreads();
+    const int nout = 3 * K;
+#pragma unroll
+    for (int i = 0; i < SM_FW; ++i) {
+        const bool fl = f0 + i < F;
+        float T[12], x[3];
+        smpl_blend(w, mask, Aws + (size_t)fi[i] * SM_A, T);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) x[c] = T[c * 4] * vp[i][0] + T[c * 4 + 1] * vp[i][1] + T[c * 4 + 2] * vp[i][2] + T[c * 4 + 3];
+        if (verts && live && fl) {
+            float* o = verts + ((size_t)fi[i] * V + v) * 3;
+            o[0] = scale * x[0]; o[1] = scale * x[1]; o[2] = scale * x[2];
+        }
+        if (kpart) {
+            xs[wave][0][lane] = x[0]; xs[wave][1][lane] = x[1]; xs[wave][2][lane] = x[2];
+            __syncthreads();
+            for (int o = lane; o < nout; o += 64) {
+                const int k = o / 3, c = o - 3 * k;
+                float s = 0.0f;
+                for (int l = 0; l < 64; ++l) s += qs[k * 65 + l] * xs[wave][c][l];
+                if (fl) kpart[((size_t)blockIdx.x * F + fi[i]) * nout + o] = s;
+            }
+            __syncthreads();
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void smpl_kp_finish_kernel(const float* __restrict__ kpart, int nvt, float scale, float* __restrict__ kp,
+                                                             size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float s = 0.0f;
+    for (int t = 0; t < nvt; ++t) s += kpart[(size_t)t * n + i];
+    kp[i] = scale * s;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// vertex backward.  zs[(val * 64 + vertex) * 20 + frame]: val 0 .. 2 g, 3 .. 5 vp, 6 .. 8 dvp of the 16 frames of the workgroup.
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void smpl_verts_bwd_kernel(const float* __restrict__ vt, const float* __restrict__ sd, const float* __restrict__ pd,
+                                                             const float* __restrict__ pt, const float* __restrict__ lbsw,
+                                                             const float* __restrict__ Q, const float* __restrict__ betas,
+                                                             const float* __restrict__ Aws, const float* __restrict__ PFws,
+                                                             const float* __restrict__ dverts, const float* __restrict__ dkp, float scale,
+                                                             float* __restrict__ part, int F, int V, int K, int nvt, int S) {
+    __shared__ __attribute__((aligned(16))) float zs[9 * 64 * SM_ZS];
+    __shared__ float wl[64 * 25];
+    __shared__ float qs[32 * 64];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int split = blockIdx.x;
+    const int f0 = blockIdx.y * SM_BF;
+    const int kcol = min(tid, SM_PT - 1);
+    const int ja = tid >> 3, fa = tid & 7;
+    float accP[SM_BF];
+    float accA[2][12];
+#pragma unroll
+    for (int i = 0; i < SM_BF; ++i) accP[i] = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int e = 0; e < 12; ++e) accA[r][e] = 0.0f;
+    int fi[SM_BW];
+#pragma unroll
+    for (int i = 0; i < SM_BW; ++i) fi[i] = min(f0 + wave * SM_BW + i, F - 1);
+
+    for (int t = split; t < nvt; t += S) {
+        const int v0 = t * SM_VT;
+        const bool live = v0 + lane < V;
+        const int v = live ? v0 + lane : V - 1;
+        __syncthreads();                                  // the previous tile's phase 2 is through with zs / wl / qs
+        for (int idx = tid; idx < 64 * SM_J; idx += 256) {
+            const int l = idx / SM_J, j = idx - l * SM_J;
+            wl[l * 25 + j] = lbsw[(size_t)min(v0 + l, V - 1) * SM_J + j];
+        }
+        if (dkp) {
+            for (int idx = tid; idx < K * 64; idx += 256) {
+                const int k = idx >> 6, l = idx & 63;
+                qs[idx] = (v0 + l < V) ? Q[(size_t)k * V + v0 + l] : 0.0f;
+            }
+        }
+        __syncthreads();
+        // ---- phase 1: lane = vertex, the wave's 4 frames
+        {
+            float w[SM_J];
+            unsigned mask = 0;
+#pragma unroll
+            for (int j = 0; j < SM_J; ++j) {
+                w[j] = wl[lane * 25 + j];
+                if (__ballot(w[j] != 0.0f) != 0ull) mask |= 1u << j;
+            }
+            float vp[SM_BW][3], g[SM_BW][3], dvp[SM_BW][3];
+            smpl_vposed<SM_BW>(vt, sd, pd, betas, PFws, fi, v, V, vp);
+#pragma unroll
+            for (int i = 0; i < SM_BW; ++i) {
+                float T[12];
+                smpl_blend(w, mask, Aws + (size_t)fi[i] * SM_A, T);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) g[i][c] = dverts ? dverts[((size_t)fi[i] * V + v) * 3 + c] : 0.0f;
+                if (dkp) {
+                    const float* dk = dkp + (size_t)fi[i] * K * 3;
+                    for (int k = 0; k < K; ++k) {
+                        const float q = qs[k * 64 + lane];
+                        g[i][0] += q * dk[3 * k]; g[i][1] += q * dk[3 * k + 1]; g[i][2] += q * dk[3 * k + 2];
+                    }
+                }
+#pragma unroll
+                for (int c = 0; c < 3; ++c) g[i][c] = live ? scale * g[i][c] : 0.0f;
+#pragma unroll
+                for (int d = 0; d < 3; ++d) dvp[i][d] = T[d] * g[i][0] + T[4 + d] * g[i][1] + T[8 + d] * g[i][2];
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                *reinterpret_cast<float4*>(&zs[((0 + c) * 64 + lane) * SM_ZS + wave * SM_BW]) = make_float4(g[0][c], g[1][c], g[2][c], g[3][c]);
+                *reinterpret_cast<float4*>(&zs[((3 + c) * 64 + lane) * SM_ZS + wave * SM_BW]) = make_float4(vp[0][c], vp[1][c], vp[2][c], vp[3][c]);
+                *reinterpret_cast<float4*>(&zs[((6 + c) * 64 + lane) * SM_ZS + wave * SM_BW]) =
+                    make_float4(dvp[0][c], dvp[1][c], dvp[2][c], dvp[3][c]);
+            }
+        }
+        __syncthreads();
+        // ---- phase 2, columns of PT: thread = column, 16 frames in registers, the tile's 192 (vertex, coordinate) rows in order
+        {
+            const int rows = min(3 * SM_VT, 3 * V - 3 * v0);
+            const float* ptc = pt + (size_t)3 * v0 * SM_PT + kcol;
+            for (int vc = 0; vc < rows; ++vc) {
+                const float pv = ptc[(size_t)vc * SM_PT];
+                const int l = vc / 3, c = vc - 3 * l;
+                const float4* z = reinterpret_cast<const float4*>(&zs[((6 + c) * 64 + l) * SM_ZS]);
+                const float4 d0 = z[0], d1 = z[1], d2 = z[2], d3 = z[3];
+                accP[0] += pv * d0.x; accP[1] += pv * d0.y; accP[2] += pv * d0.z; accP[3] += pv * d0.w;
+                accP[4] += pv * d1.x; accP[5] += pv * d1.y; accP[6] += pv * d1.z; accP[7] += pv * d1.w;
+                accP[8] += pv * d2.x; accP[9] += pv * d2.y; accP[10] += pv * d2.z; accP[11] += pv * d2.w;
+                accP[12] += pv * d3.x; accP[13] += pv * d3.y; accP[14] += pv * d3.z; accP[15] += pv * d3.w;
+            }
+        }
+        // ---- phase 2, d A: thread = (joint, frame mod 8), two frames, the tile's vertices in order
+        if (ja < SM_J) {
+            for (int l = 0; l < SM_VT; ++l) {
+                const float wv = wl[l * 25 + ja];
+#pragma unroll
+                for (int r = 0; r < 2; ++r) {
+                    const int fo = r * 8 + fa;
+                    const float p0 = zs[(3 * 64 + l) * SM_ZS + fo], p1 = zs[(4 * 64 + l) * SM_ZS + fo], p2 = zs[(5 * 64 + l) * SM_ZS + fo];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        const float gw = wv * zs[(c * 64 + l) * SM_ZS + fo];
+                        accA[r][c * 4] += gw * p0; accA[r][c * 4 + 1] += gw * p1; accA[r][c * 4 + 2] += gw * p2; accA[r][c * 4 + 3] += gw;
+                    }
+                }
+            }
+        }
+    }
+    if (tid < SM_PT) {
+#pragma unroll
+        for (int i = 0; i < SM_BF; ++i)
+            if (f0 + i < F) part[((size_t)split * F + f0 + i) * SM_COLS + tid] = accP[i];
+    }
+    if (ja < SM_J) {
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int f = f0 + r * 8 + fa;
+            if (f < F) {
+                float* o = part + ((size_t)split * F + f) * SM_COLS + SM_PT + ja * 12;
+#pragma unroll
+                for (int e = 0; e < 12; ++e) o[e] = accA[r][e];
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void smpl_split_sum_kernel(const float* __restrict__ part, int S, float* __restrict__ sums, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float s = 0.0f;
+    for (int t = 0; t < S; ++t) s += part[(size_t)t * n + i];
+    sums[i] = s;
+}
+
+// chain backward, one thread per frame.  D: scratch [288][F] (d Grot_j [9], d Gt_j [3]); DJ: scratch [72][F] (d J_j).
+__global__ __launch_bounds__(64) void smpl_chain_bwd_kernel(const float* __restrict__ betas, const float* __restrict__ rotmat,
+                                                            const float* __restrict__ Jt, const float* __restrict__ Jd, SmplTree tree, float scale,
+                                                            const float* __restrict__ Aws, const float* __restrict__ sums,
+                                                            const float* __restrict__ djoints, float* D, float* DJ, float* __restrict__ drot,
+                                                            float* __restrict__ dbetas, int F) {
+    const int f = blockIdx.x * 64 + threadIdx.x;
+    if (f >= F) return;
+    float b[10];
+#pragma unroll
+    for (int k = 0; k < 10; ++k) b[k] = betas[(size_t)f * 10 + k];
+    const float* R = rotmat + (size_t)f * 216;
+    const float* A = Aws + (size_t)f * SM_A;
+    const float* sm = sums + (size_t)f * SM_COLS;
+#define SM_D(j, e) D[(size_t)((j) * 12 + (e)) * F + f]
+#define SM_DJ(j, c) DJ[(size_t)((j) * 3 + (c)) * F + f]
+    for (int j = 0; j < SM_J; ++j) {
+        float J[3], dA[12];
+        smpl_joint(Jt, Jd, b, j, J);
+#pragma unroll
+        for (int e = 0; e < 12; ++e) dA[e] = sm[SM_PT + j * 12 + e];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+#pragma unroll
+            for (int d = 0; d < 3; ++d) SM_D(j, c * 3 + d) = dA[c * 4 + d] - dA[c * 4 + 3] * J[d];
+            SM_D(j, 9 + c) = dA[c * 4 + 3] + (djoints ? scale * djoints[(size_t)f * 72 + j * 3 + c] : 0.0f);
+        }
+#pragma unroll
+        for (int m = 0; m < 3; ++m) SM_DJ(j, m) = -(A[j * 12 + m] * dA[3] + A[j * 12 + 4 + m] * dA[7] + A[j * 12 + 8 + m] * dA[11]);
+    }
+    float* dR = drot + (size_t)f * 216;
+    for (int j = SM_J - 1; j >= 1; --j) {
+        const int p = tree.p[j];
+        float J[3], Jp[3], rel[3], r[9], dG[9], dt[3], Gp[9];
+        smpl_joint(Jt, Jd, b, j, J);
+        smpl_joint(Jt, Jd, b, p, Jp);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) rel[c] = J[c] - Jp[c];
+#pragma unroll
+        for (int e = 0; e < 9; ++e) { r[e] = R[j * 9 + e]; dG[e] = SM_D(j, e); Gp[e] = A[p * 12 + (e / 3) * 4 + (e % 3)]; }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) dt[c] = SM_D(j, 9 + c);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+#pragma unroll
+            for (int m = 0; m < 3; ++m)
+                SM_D(p, c * 3 + m) = SM_D(p, c * 3 + m) + (dG[c * 3] * r[m * 3] + dG[c * 3 + 1] * r[m * 3 + 1] + dG[c * 3 + 2] * r[m * 3 + 2]) + dt[c] * rel[m];
+            SM_D(p, 9 + c) = SM_D(p, 9 + c) + dt[c];
+        }
+#pragma unroll
+        for (int m = 0; m < 3; ++m) {
+#pragma unroll
+            for (int d = 0; d < 3; ++d)
+                dR[j * 9 + m * 3 + d] = (Gp[m] * dG[d] + Gp[3 + m] * dG[3 + d] + Gp[6 + m] * dG[6 + d]) + sm[(j - 1) * 9 + m * 3 + d];
+            const float drel = Gp[m] * dt[0] + Gp[3 + m] * dt[1] + Gp[6 + m] * dt[2];
+            SM_DJ(j, m) = SM_DJ(j, m) + drel;
+            SM_DJ(p, m) = SM_DJ(p, m) - drel;
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 9; ++e) dR[e] = SM_D(0, e);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) SM_DJ(0, c) = SM_DJ(0, c) + SM_D(0, 9 + c);
+    float db[10];
+#pragma unroll
+    for (int k = 0; k < 10; ++k) db[k] = sm[SM_PF + k];
+    for (int j = 0; j < SM_J; ++j) {
+#pragma unroll
+        for (int m = 0; m < 3; ++m) {
+            const float dj = SM_DJ(j, m);
+#pragma unroll
+            for (int k = 0; k < 10; ++k) db[k] += Jd[(j * 3 + m) * 10 + k] * dj;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 10; ++k) dbetas[(size_t)f * 10 + k] = db[k];
+#undef SM_D
+#undef SM_DJ
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// host
+// ---------------------------------------------------------------------------------------------------------------
+static inline int sm_tiles(int V) { return (V + SM_VT - 1) / SM_VT; }
+static inline int sm_splits(int V) { const int t = sm_tiles(V); return t < SM_SPLITS ? t : SM_SPLITS; }
+static inline bool sm_dims_ok(int F, int V, int K) { return F >= 0 && F <= (1 << 20) && V >= 1 && V <= (1 << 20) && K >= 0 && K <= 32; }
+// float offsets: A [F,288] | pf [F,208] | scratch [288,F] | (fwd) keypoint partials [tiles,F,3K]
+//                                                         | (bwd) d J scratch [72,F] | partials [S,F,512] | sums [F,512]
+static inline size_t sm_common_floats(int F) { return (size_t)F * (SM_A + SM_PFS + SM_A); }
+
+extern "C" size_t mbx_smpl_fwd_ws(int F, int V, int K) {
+    if (!sm_dims_ok(F, V, K) || F < 1) return 0;
+    return (sm_common_floats(F) + (size_t)sm_tiles(V) * F * 3 * K) * sizeof(float) + 256;
+}
+
+extern "C" size_t mbx_smpl_bwd_ws(int F, int V, int K) {
+    if (!sm_dims_ok(F, V, K) || F < 1) return 0;
+    return (sm_common_floats(F) + (size_t)F * 72 + (size_t)(sm_splits(V) + 1) * F * SM_COLS) * sizeof(float) + 256;
+}
+
+extern "C" int mbx_smpl_pack(const float* shapedirs, const float* posedirs, float* packed_t, int V, void* stream) {
+    MBX_CHECK_ARG(V >= 1 && V <= (1 << 20), "smpl_pack: bad vertex count V=%d", V);
+    MBX_CHECK_ARG(shapedirs && posedirs && packed_t, "smpl_pack: null pointer");
+    MBX_CHECK_ARG((((uintptr_t)shapedirs | (uintptr_t)posedirs | (uintptr_t)packed_t) & 3) == 0, "smpl_pack: pointers must be 4-byte aligned");
+    const size_t n = (size_t)3 * V * SM_PT;
+    const int blocks = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
+    hipLaunchKernelGGL(smpl_pack_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, shapedirs, posedirs, packed_t, V);
+    MBX_LAUNCH_CHECK("smpl_pack");
+    return 0;
+}
+
+static int sm_tree(const int* parents, SmplTree& tree, const char* who) {
+    MBX_CHECK_ARG(parents, "%s: null parents", who);
+    MBX_CHECK_ARG(parents[0] == -1, "%s: parents[0] must be -1, got %d", who, parents[0]);
+    tree.p[0] = -1;
+    for (int j = 1; j < SM_J; ++j) {
+        MBX_CHECK_ARG(parents[j] >= 0 && parents[j] < j, "%s: parents[%d] = %d is not a forward-ordered tree (0 <= parents[j] < j)", who, j, parents[j]);
+        tree.p[j] = parents[j];
+    }
+    return 0;
+}
+
+extern "C" int mbx_smpl_fwd(const float* v_template, const float* shapedirs, const float* posedirs, const float* Jt, const float* Jd,
+                            const int* parents, const float* lbs_weights, const float* Q, int K, const float* betas, const float* rotmat,
+                            float scale, float* verts, float* kp, float* joints, int F, int V, void* ws, size_t ws_bytes, void* stream) {
+    MBX_CHECK_ARG(sm_dims_ok(F, V, K), "smpl_fwd: bad sizes F=%d V=%d K=%d (V >= 1, K <= 32)", F, V, K);
+    SmplTree tree;
+    if (sm_tree(parents, tree, "smpl_fwd")) return 1;
+    if (F == 0) return 0;
+    MBX_CHECK_ARG(v_template && shapedirs && posedirs && Jt && Jd && lbs_weights && betas && rotmat && ws, "smpl_fwd: null pointer");
+    MBX_CHECK_ARG(verts || kp || joints, "smpl_fwd: no output");
+    MBX_CHECK_ARG(!kp || (Q && K >= 1), "smpl_fwd: kp needs a regressor Q [K,V] with K >= 1");
+    MBX_CHECK_ARG(ws_bytes >= mbx_smpl_fwd_ws(F, V, kp ? K : 0), "smpl_fwd: workspace of %zu bytes, %zu needed", ws_bytes,
+                  mbx_smpl_fwd_ws(F, V, kp ? K : 0));
+    MBX_CHECK_ARG((((uintptr_t)v_template | (uintptr_t)shapedirs | (uintptr_t)posedirs | (uintptr_t)Jt | (uintptr_t)Jd | (uintptr_t)lbs_weights |
+                    (uintptr_t)Q | (uintptr_t)betas | (uintptr_t)rotmat | (uintptr_t)verts | (uintptr_t)kp | (uintptr_t)joints) & 3) == 0 &&
+                      ((uintptr_t)ws & 15) == 0,
+                  "smpl_fwd: pointers must be 4-byte aligned, the workspace 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    float* Aws = (float*)ws;
+    float* PFws = Aws + (size_t)F * SM_A;
+    float* G = PFws + (size_t)F * SM_PFS;
+    float* kpart = G + (size_t)F * SM_A;
+    hipLaunchKernelGGL(smpl_chain_fwd_kernel, dim3((F + 63) / 64), dim3(64), 0, s, betas, rotmat, Jt, Jd, tree, scale, Aws, PFws, G, joints, F);
+    MBX_LAUNCH_CHECK("smpl_fwd (chain)");
+    if (!verts && !kp) return 0;
+    const int nvt = sm_tiles(V);
+    hipLaunchKernelGGL(smpl_verts_fwd_kernel, dim3(nvt, (F + 4 * SM_FW - 1) / (4 * SM_FW)), dim3(256), 0, s, v_template, shapedirs, posedirs,
+                       lbs_weights, Q, betas, (const float*)Aws, (const float*)PFws, scale, verts, kp ? kpart : (float*)nullptr, F, V, kp ? K : 0);
+    MBX_LAUNCH_CHECK("smpl_fwd (vertices)");
+    if (kp) {
+        const size_t n = (size_t)F * 3 * K;
+        hipLaunchKernelGGL(smpl_kp_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)kpart, nvt, scale, kp, n);
+        MBX_LAUNCH_CHECK("smpl_fwd (keypoints)");
+    }
+    return 0;
+}
+
+extern "C" int mbx_smpl_bwd(const float* v_template, const float* shapedirs, const float* posedirs, const float* packed_t, const float* Jt,
+                            const float* Jd, const int* parents, const float* lbs_weights, const float* Q, int K, const float* betas,
+                            const float* rotmat, float scale, const float* dverts, const float* dkp, const float* djoints, float* drotmat,
+                            float* dbetas, int F, int V, void* ws, size_t ws_bytes, void* stream) {
+    MBX_CHECK_ARG(sm_dims_ok(F, V, K), "smpl_bwd: bad sizes F=%d V=%d K=%d (V >= 1, K <= 32)", F, V, K);
+    SmplTree tree;
+    if (sm_tree(parents, tree, "smpl_bwd")) return 1;
+    if (F == 0) return 0;
+    MBX_CHECK_ARG(v_template && shapedirs && posedirs && packed_t && Jt && Jd && lbs_weights && betas && rotmat && drotmat && dbetas && ws,
+                  "smpl_bwd: null pointer");
+    MBX_CHECK_ARG(!dkp || (Q && K >= 1), "smpl_bwd: dkp needs a regressor Q [K,V] with K >= 1");
+    MBX_CHECK_ARG(ws_bytes >= mbx_smpl_bwd_ws(F, V, K), "smpl_bwd: workspace of %zu bytes, %zu needed", ws_bytes, mbx_smpl_bwd_ws(F, V, K));
+    MBX_CHECK_ARG(drotmat != rotmat && dbetas != betas, "smpl_bwd: a gradient must not alias its input");
+    MBX_CHECK_ARG((((uintptr_t)v_template | (uintptr_t)shapedirs | (uintptr_t)posedirs | (uintptr_t)packed_t | (uintptr_t)Jt | (uintptr_t)Jd |
+                    (uintptr_t)lbs_weights | (uintptr_t)Q | (uintptr_t)betas | (uintptr_t)rotmat | (uintptr_t)dverts | (uintptr_t)dkp |
+                    (uintptr_t)djoints | (uintptr_t)drotmat | (uintptr_t)dbetas) & 3) == 0 && ((uintptr_t)ws & 15) == 0,
+                  "smpl_bwd: pointers must be 4-byte aligned, the workspace 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const int nvt = sm_tiles(V), S = sm_splits(V);
+    float* Aws = (float*)ws;
+    float* PFws = Aws + (size_t)F * SM_A;
+    float* G = PFws + (size_t)F * SM_PFS;
+    float* DJ = G + (size_t)F * SM_A;
+    float* part = DJ + (size_t)F * 72;
+    float* sums = part + (size_t)S * F * SM_COLS;
+    hipLaunchKernelGGL(smpl_chain_fwd_kernel, dim3((F + 63) / 64), dim3(64), 0, s, betas, rotmat, Jt, Jd, tree, scale, Aws, PFws, G,
+                       (float*)nullptr, F);
+    MBX_LAUNCH_CHECK("smpl_bwd (chain)");
+    hipLaunchKernelGGL(smpl_verts_bwd_kernel, dim3(S, (F + SM_BF - 1) / SM_BF), dim3(256), 0, s, v_template, shapedirs, posedirs, packed_t,
+                       lbs_weights, Q, betas, (const float*)Aws, (const float*)PFws, dverts, dkp, scale, part, F, V, dkp ? K : 0, nvt, S);
+    MBX_LAUNCH_CHECK("smpl_bwd (vertices)");
+    const size_t n = (size_t)F * SM_COLS;
+    hipLaunchKernelGGL(smpl_split_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)part, S, sums, n);
+    MBX_LAUNCH_CHECK("smpl_bwd (split sum)");
+    hipLaunchKernelGGL(smpl_chain_bwd_kernel, dim3((F + 63) / 64), dim3(64), 0, s, betas, rotmat, Jt, Jd, tree, scale, (const float*)Aws,
+                       (const float*)sums, djoints, G, DJ, drotmat, dbetas, F);
+    MBX_LAUNCH_CHECK("smpl_bwd (chain backward)");
+    return 0;
+}

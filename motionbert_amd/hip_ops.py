@@ -107,6 +107,11 @@ SIGNATURES = {
     'mbx_mesh_param_loss_ws': (_sz, [_i]),
     'mbx_mesh_param_loss': (_i, [_vp, _vp, _i, _f, _f, _f, _f, _vp, _vp, _i, _vp, _vp]),
     'mbx_mesh_errors': (_i, [_vp] * 5 + [_i, _i, _vp]),
+    'mbx_smpl_pack': (_i, [_vp, _vp, _vp, _i, _vp]),
+    'mbx_smpl_fwd_ws': (_sz, [_i, _i, _i]),
+    'mbx_smpl_bwd_ws': (_sz, [_i, _i, _i]),
+    'mbx_smpl_fwd': (_i, [_vp] * 5 + [C.POINTER(C.c_int)] + [_vp, _vp, _i, _vp, _vp, _f, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
+    'mbx_smpl_bwd': (_i, [_vp] * 6 + [C.POINTER(C.c_int)] + [_vp, _vp, _i, _vp, _vp, _f] + [_vp] * 5 + [_i, _i, _vp, _sz, _vp]),
     'mbx_rows_n_pack_bytes': (_sz, [_i, _i]),
     'mbx_rows_lnbwd_t': (_i, [_vp] * 6 + [_i, _i, _i, _vp]),
     'mbx_rows_n_pack_many': (_i, [_i64p, _i, _i, _i, _vp]),
@@ -750,6 +755,108 @@ class HipOps:
         if err is None:
             raise RuntimeError('libmbx: mesh_errors: err [5,F] is required')
         self._ck(self.lib.mbx_mesh_errors(_p(verts_p), _p(verts_g), _p(kp_p), _p(kp_g), _p(err), F, V, self._stream()))
+
+    # ------------------------------------------------------------------ SMPL body model (csrc/smpl.hip; motionbert_amd/smpl.py)
+    def _smpl_model(self, what, m, need_packed):
+        """m: dict of the model tensors (smpl.SMPLModel.tensors()): checked dense f32 on one device; returns (V, device, host parents)"""
+        vt = m['v_template']
+        if vt.dim() != 2 or vt.shape[1] != 3 or vt.shape[0] < 1:
+            raise RuntimeError(f'libmbx: {what} needs v_template [V >= 1, 3], got {tuple(vt.shape)}')
+        V, dev = vt.shape[0], vt.device
+        self._dense(what, torch.float32, V * 3, dev, v_template=vt)
+        self._dense(what, torch.float32, V * 30, dev, shapedirs=m['shapedirs'])
+        self._dense(what, torch.float32, 207 * 3 * V, dev, posedirs=m['posedirs'])
+        self._dense(what, torch.float32, 72, dev, Jt=m['Jt'])
+        self._dense(what, torch.float32, 720, dev, Jd=m['Jd'])
+        self._dense(what, torch.float32, V * 24, dev, lbs_weights=m['lbs_weights'])
+        if need_packed:
+            if m.get('packed_t') is None:
+                raise RuntimeError(f'libmbx: {what} needs packed_t [3V,224] (smpl_pack)')
+            self._dense(what, torch.float32, 3 * V * 224, dev, packed_t=m['packed_t'])
+        parents = [int(p) for p in m['parents']]
+        if len(parents) != 24:
+            raise RuntimeError(f'libmbx: {what} needs 24 parents, got {len(parents)}')
+        return V, dev, (C.c_int * 24)(*parents)
+
+    @staticmethod
+    def _smpl_frames(what, betas, rotmat):
+        if betas.dim() != 2 or betas.shape[1] != 10 or rotmat.dim() not in (3, 4) or rotmat.shape[0] != betas.shape[0] or rotmat.numel() != betas.shape[0] * 216:
+            raise RuntimeError(f'libmbx: {what} needs betas [F,10] and rotmat [F,24,9] (or [F,24,3,3]), got {tuple(betas.shape)} / {tuple(rotmat.shape)}')
+        return betas.shape[0]
+
+    def smpl_pack(self, shapedirs, posedirs, packed_t):
+        """packed_t [3V,224] f32 = [posedirs^T | shapedirs | 0] of shapedirs [V,3,10] and posedirs [207,3V]"""
+        if shapedirs.dim() != 3 or tuple(shapedirs.shape[1:]) != (3, 10) or shapedirs.shape[0] < 1:
+            raise RuntimeError(f'libmbx: smpl_pack needs shapedirs [V >= 1,3,10], got {tuple(shapedirs.shape)}')
+        V, dev = shapedirs.shape[0], shapedirs.device
+        self._dense('smpl_pack', torch.float32, V * 30, dev, shapedirs=shapedirs)
+        self._dense('smpl_pack', torch.float32, 207 * 3 * V, dev, posedirs=posedirs)
+        self._dense('smpl_pack', torch.float32, 3 * V * 224, dev, packed_t=packed_t)
+        if posedirs is None or packed_t is None:
+            raise RuntimeError('libmbx: smpl_pack: posedirs and packed_t are required')
+        self._ck(self.lib.mbx_smpl_pack(_p(shapedirs), _p(posedirs), _p(packed_t), V, self._stream()))
+
+    def smpl_fwd_ws(self, F, V, K, device):
+        return self._ws(('smplf', F, V, K), self.lib.mbx_smpl_fwd_ws, F, V, K, device=device)
+
+    def smpl_bwd_ws(self, F, V, K, device):
+        return self._ws(('smplb', F, V, K), self.lib.mbx_smpl_bwd_ws, F, V, K, device=device)
+
+    def smpl_fwd(self, model, Q, betas, rotmat, scale, verts, kp, joints, ws=None):
+        """model: dict v_template [V,3], shapedirs [V,3,10], posedirs [207,3V], Jt [24,3], Jd [24,3,10], lbs_weights [V,24] f32 on the device
+        and parents (24 host ints); Q [K,V] f32 or None; betas [F,10], rotmat [F,24,9] f32; outputs verts [F,V,3] / kp [F,K,3] /
+        joints [F,24,3] f32, each may be None; ws: a uint8 workspace of smpl_fwd_ws(F, V, K with kp else 0) (allocated when None)."""
+        V, dev, parents = self._smpl_model('smpl_fwd', model, False)
+        F = self._smpl_frames('smpl_fwd', betas, rotmat)
+        if verts is None and kp is None and joints is None:
+            raise RuntimeError('libmbx: smpl_fwd: no output')
+        K = 0
+        if Q is not None:
+            if Q.dim() != 2 or Q.shape[1] != V or not 1 <= Q.shape[0] <= 32:
+                raise RuntimeError(f'libmbx: smpl_fwd needs Q [1 <= K <= 32, {V}], got {tuple(Q.shape)}')
+            K = Q.shape[0]
+        if kp is not None and Q is None:
+            raise RuntimeError('libmbx: smpl_fwd: kp needs the regressor Q')
+        self._dense('smpl_fwd', torch.float32, K * V, dev, Q=Q)
+        self._dense('smpl_fwd', torch.float32, F * 10, dev, betas=betas)
+        self._dense('smpl_fwd', torch.float32, F * 216, dev, rotmat=rotmat)
+        self._dense('smpl_fwd', torch.float32, F * V * 3, dev, verts=verts)
+        self._dense('smpl_fwd', torch.float32, F * K * 3, dev, kp=kp)
+        self._dense('smpl_fwd', torch.float32, F * 72, dev, joints=joints)
+        if ws is None:
+            ws = self.smpl_fwd_ws(F, V, K if kp is not None else 0, dev)
+        self._dense('smpl_fwd', torch.uint8, None, dev, ws=ws)
+        self._ck(self.lib.mbx_smpl_fwd(_p(model['v_template']), _p(model['shapedirs']), _p(model['posedirs']), _p(model['Jt']), _p(model['Jd']),
+                                       parents, _p(model['lbs_weights']), _p(Q), K, _p(betas), _p(rotmat), float(scale), _p(verts), _p(kp),
+                                       _p(joints), F, V, _p(ws), ws.numel(), self._stream()))
+
+    def smpl_bwd(self, model, Q, betas, rotmat, scale, dverts, dkp, djoints, drotmat, dbetas, ws=None):
+        """the cotangents dverts [F,V,3] / dkp [F,K,3] / djoints [F,24,3] (each may be None: zero) pulled back to drotmat [F,24,9] and
+        dbetas [F,10]; model as smpl_fwd plus packed_t [3V,224]."""
+        V, dev, parents = self._smpl_model('smpl_bwd', model, True)
+        F = self._smpl_frames('smpl_bwd', betas, rotmat)
+        K = 0
+        if Q is not None:
+            if Q.dim() != 2 or Q.shape[1] != V or not 1 <= Q.shape[0] <= 32:
+                raise RuntimeError(f'libmbx: smpl_bwd needs Q [1 <= K <= 32, {V}], got {tuple(Q.shape)}')
+            K = Q.shape[0]
+        if dkp is not None and Q is None:
+            raise RuntimeError('libmbx: smpl_bwd: dkp needs the regressor Q')
+        if drotmat is None or dbetas is None:
+            raise RuntimeError('libmbx: smpl_bwd: drotmat and dbetas are required')
+        self._dense('smpl_bwd', torch.float32, K * V, dev, Q=Q)
+        self._dense('smpl_bwd', torch.float32, F * 10, dev, betas=betas, dbetas=dbetas)
+        self._dense('smpl_bwd', torch.float32, F * 216, dev, rotmat=rotmat, drotmat=drotmat)
+        self._dense('smpl_bwd', torch.float32, F * V * 3, dev, dverts=dverts)
+        self._dense('smpl_bwd', torch.float32, F * K * 3, dev, dkp=dkp)
+        self._dense('smpl_bwd', torch.float32, F * 72, dev, djoints=djoints)
+        if ws is None:
+            ws = self.smpl_bwd_ws(F, V, K, dev)
+        self._dense('smpl_bwd', torch.uint8, None, dev, ws=ws)
+        self._ck(self.lib.mbx_smpl_bwd(_p(model['v_template']), _p(model['shapedirs']), _p(model['posedirs']), _p(model['packed_t']),
+                                       _p(model['Jt']), _p(model['Jd']), parents, _p(model['lbs_weights']), _p(Q), K, _p(betas), _p(rotmat),
+                                       float(scale), _p(dverts), _p(dkp), _p(djoints), _p(drotmat), _p(dbetas), F, V, _p(ws), ws.numel(),
+                                       self._stream()))
 
     # ------------------------------------------------------------------ dropout / drop-path (SURVEY 8 a15)
     def dropout(self, x, y, p, seed):

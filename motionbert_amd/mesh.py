@@ -1,6 +1,6 @@
 """Mesh recovery on the device (reference `train_mesh.py`, `lib/model/model_mesh.py`, `lib/model/loss_mesh.py`, `lib/utils/utils_mesh.py`;
-configs `configs/mesh/*.yaml`).  The SMPL layer stays what it is in the reference -- a module the user supplies (`smplx` and the SMPL model
-files are not part of this project); everything around it is here:
+configs `configs/mesh/*.yaml`).  The SMPL layer is injected as in the reference: the project's own `motionbert_amd.smpl.SMPLLayer` (fused device
+skinning, built from the user's SMPL arrays) or any module with the reference's call signature (`smplx`); everything around it is here:
 
     rot6d_to_rotmat_theta(x6)       the head's rotation chain 6D -> rotation matrix -> quaternion -> axis-angle as ONE kernel forward and ONE
                                     backward (`mbx_rot6d_theta_fwd / _bwd`; about 120 small torch kernels each way in the reference).
@@ -13,8 +13,11 @@ files are not part of this project); everything around it is here:
     MeshEvaluator()                 `update(output, batch_gt)` per test batch (`mbx_mesh_errors` into device buffers), `finish()` returns
                                     `evaluate_mesh`'s dict and is the only host synchronisation: no vertex ever goes to the host.
     compute_error / compute_error_frames   the reference's signatures (utils_mesh.py:357-393) on the same kernel.
+    flip_thetas_batch(thetas)       utils_mesh.py:486-513 on a tensor, bit for bit.
+    flip_average(model, smpl, x)    the flip evaluation of train_mesh.py:83-108: the mean of the model's output and the flipped-back output of
+                                    the flipped input, for `MeshEvaluator.update`.
 
-Not here: an SMPL layer, `flip_thetas_batch`, translation estimation, rendering, a DDP variant of the step.
+Not here: the 49-joint map of `utils_smpl.SMPL`, translation estimation, rendering, `infer_wild_mesh.py`, a DDP variant of the step.
 
 There is no CPU path: without an injected kernel provider (`ops=`), tensors that are not on a ROCm device raise.
 """
@@ -22,6 +25,8 @@ from __future__ import annotations
 
 import torch
 import torch.nn as nn
+
+from .smpl import SMPLLayer, rodrigues
 
 LOSS_KEYS = ('loss_3d_pos', 'loss_3d_scale', 'loss_3d_velocity', 'loss_lv', 'loss_lg', 'loss_a', 'loss_av', 'loss_shape', 'loss_pose', 'loss_norm')
 LAMBDA_NAMES = ('lambda_3d', 'lambda_scale', 'lambda_3dv', 'lambda_lv', 'lambda_lg', 'lambda_a', 'lambda_av', 'lambda_shape', 'lambda_pose',
@@ -115,6 +120,11 @@ class SMPLRegressor(nn.Module):
         self.J_regressor = J_regressor
         self.ops = ops
 
+    def _regressor(self, device, dtype):
+        if self.J_regressor.device != device or self.J_regressor.dtype != dtype:
+            self.J_regressor = self.J_regressor.to(device=device, dtype=dtype)    # once, not per forward as the reference moves it: a host copy per step
+        return self.J_regressor
+
     def forward(self, feat, init_pose=None, init_shape=None):
         N, T, J, C = feat.shape
         NT = N * T
@@ -128,11 +138,14 @@ class SMPLRegressor(nn.Module):
         rotmat, aa = rot6d_to_rotmat_theta(pred_pose.float(), ops=self.ops)
         rotmat, aa = rotmat.to(pred_pose.dtype), aa.to(pred_pose.dtype)                         # (the kernels are fp32)
         pred_rotmat = rotmat.view(NT, 24, 3, 3)
+        if isinstance(self.smpl, SMPLLayer):
+            # the project's own layer: vertices in millimetres and the 17 regressed joints from one fused launch (no [NT,V,3] product
+            # with 1000 and no batched [17,V] matmul; their gradients come back through mbx_smpl_bwd)
+            verts, kp = self.smpl.forward_kp(pred_shape, pred_rotmat, self._regressor(pred_shape.device, torch.float32), 1000.0, ops=self.ops)
+            return [{'theta': torch.cat([aa.reshape(NT, 72), pred_shape], dim=1), 'verts': verts.to(pred_pose.dtype), 'kp_3d': kp.to(pred_pose.dtype)}]
         pred_output = self.smpl(betas=pred_shape, body_pose=pred_rotmat[:, 1:], global_orient=pred_rotmat[:, 0].unsqueeze(1), pose2rot=False)
         pred_vertices = pred_output.vertices * 1000.0
-        if self.J_regressor.device != pred_vertices.device or self.J_regressor.dtype != pred_vertices.dtype:
-            self.J_regressor = self.J_regressor.to(pred_vertices)         # once, not per forward as the reference moves it: a host copy per step
-        pred_joints = torch.matmul(self.J_regressor[None].expand(NT, -1, -1), pred_vertices)
+        pred_joints = torch.matmul(self._regressor(pred_vertices.device, pred_vertices.dtype)[None].expand(NT, -1, -1), pred_vertices)
         return [{'theta': torch.cat([aa.reshape(NT, 72), pred_shape], dim=1),       # (N*T, 72+10)
                  'verts': pred_vertices,                                            # (N*T, V, 3)
                  'kp_3d': pred_joints}]                                             # (N*T, 17, 3)
@@ -385,6 +398,52 @@ class MeshEvaluator:
             raise RuntimeError('finish() before any update()')
         mean = self.frames().mean(dim=1).cpu().tolist()
         return {k: mean[ERROR_KEYS.index(k)] for k in ('mpve', 'mpjpe', 'pa_mpjpe', 'mpjpe_17j', 'pa_mpjpe_17j')}
+
+
+# ---------------------------------------------------------------------------------------------------------------- flip evaluation
+THETA_FLIP_PERM = (0, 2, 1, 3, 5, 4, 6, 8, 7, 9, 11, 10, 12, 14, 13, 15, 17, 16, 19, 18, 21, 20, 23, 22)     # utils_mesh.py:503, as a permutation
+JOINT_FLIP_PERM = (0, 4, 5, 6, 1, 2, 3, 7, 8, 9, 10, 14, 15, 16, 11, 12, 13)                                   # flip_data, utils_data.py:61-65
+
+
+def flip_thetas_batch(thetas: torch.Tensor) -> torch.Tensor:
+    """utils_mesh.py:486-513: thetas [N,F,72] axis-angle -> the pose of the mirrored body: the y and z components of every joint negated,
+    left and right joints swapped.  A new tensor; bit-equal to the reference's."""
+    if thetas.dim() != 3 or thetas.shape[-1] != 72:
+        raise ValueError(f'thetas [N,F,72] expected, got {tuple(thetas.shape)}')
+    t = thetas.reshape(*thetas.shape[:2], 24, 3)
+    sign = torch.tensor([1.0, -1.0, -1.0], dtype=thetas.dtype, device=thetas.device)
+    return (t * sign).index_select(2, torch.tensor(THETA_FLIP_PERM, device=thetas.device)).reshape(*thetas.shape[:2], 72)
+
+
+def flip_input(x: torch.Tensor) -> torch.Tensor:
+    """`flip_data` (utils_data.py:54-66) of [..., 17, D]: x negated, left and right joints swapped; a new tensor"""
+    f = x.index_select(-2, torch.tensor(JOINT_FLIP_PERM, device=x.device)).clone()
+    f[..., 0] = -f[..., 0]
+    return f
+
+
+def flip_average(model, smpl, batch_input: torch.Tensor, output=None):
+    """train_mesh.py:83-108 (`args.flip`): the model on the flipped input, its thetas flipped back, SMPL with `pose2rot=True`, the joint
+    regression, and per key the mean with the model's output on the input itself (`output`: that output where the caller already has it).
+    Returns the list with one dict `theta` [N,T,82] / `verts` [N,T,V,3] / `kp_3d` [N,T,17,3] that `MeshEvaluator.update` takes.  With an
+    `SMPLLayer` the vertices and joints of the flipped pass come from one fused launch; any other `smpl` is called as the reference calls it."""
+    with torch.no_grad():
+        if output is None:
+            output = model(batch_input)
+        N, T = batch_input.shape[:2]
+        flipped = model(flip_input(batch_input))[0]
+        pose = flip_thetas_batch(flipped['theta'][:, :, :72]).reshape(-1, 72)
+        shape = flipped['theta'][:, :, 72:].reshape(-1, 10)
+        Q = smpl.J_regressor_h36m
+        if isinstance(smpl, SMPLLayer):
+            rot = rodrigues(pose.reshape(-1, 3).float()).view(N * T, 24, 3, 3)
+            verts, kp = smpl.forward_kp(shape.float().contiguous(), rot, Q, 1000.0)
+        else:
+            verts = smpl(betas=shape, body_pose=pose[:, 3:], global_orient=pose[:, :3], pose2rot=True).vertices.detach() * 1000.0
+            kp = torch.matmul(Q.to(verts)[None].expand(verts.shape[0], -1, -1), verts)
+        back = {'theta': torch.cat([pose.reshape(N, T, -1), shape.reshape(N, T, -1)], dim=-1), 'verts': verts.reshape(N, T, -1, 3),
+                'kp_3d': kp.reshape(N, T, -1, 3)}
+        return [{k: (output[0][k] + back[k].to(output[0][k].dtype)) * 0.5 for k in flipped}]
 
 
 # ---------------------------------------------------------------------------------------------------------------- step

@@ -1,0 +1,306 @@
+"""The SMPL body model on the device (csrc/smpl.hip): linear blend skinning as `smplx.lbs.lbs` evaluates it, as one fused forward and one
+hand-written backward.  `smplx` is not imported; the model arrays come from the user's files or module.
+
+    SMPLModel                   the arrays: v_template [V,3], shapedirs [V,3,10], posedirs [207,3V], J_regressor [24,V], parents [24],
+                                lbs_weights [V,24] and, where present, J_regressor_h36m [17,V].  `from_npz(path)`, `from_module(m)` (duck-typed:
+                                a `smplx.SMPL` or the reference's `lib.utils.utils_smpl.SMPL` converts), `synthetic(V, seed)` for tests.
+    SMPLLayer(model)            nn.Module called as the reference calls its layer: `layer(betas=, body_pose=, global_orient=, pose2rot=False)`
+                                -> an object with `.vertices` [F,V,3] in metres and `.joints` [F,24,3]; differentiable in betas and the
+                                rotations through one autograd.Function (`mbx_smpl_fwd` / `mbx_smpl_bwd`).  `forward_kp(betas, rotmat, Q, scale)`
+                                -> `(verts, kp)` = `(scale x, scale Q x)` from the same launch.
+    rodrigues(aa)               smplx's axis-angle form (angle = |r + 1e-8|), plain torch operations: 24 matrices per frame.
+
+Not here: the 49-joint map of `utils_smpl.SMPL` (`J_regressor_extra`, `joint_map`); no caller in the reference reads it.
+
+There is no CPU path: without an injected kernel provider (`ops=`), tensors that are not on a ROCm device raise.  A layer keeps one workspace
+per call shape and is meant to be driven from one stream at a time."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+SMPL_PARENTS = (-1, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16, 17, 18, 19, 20, 21)      # the public SMPL kinematic tree
+NUM_JOINTS, NUM_BETAS, POSE_FEATS, PACK_COLS, MAX_K = 24, 10, 207, 224, 32
+
+
+def _provider(ops, what: str, *tensors):
+    if ops is not None:
+        return ops
+    for t in tensors:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f'motionbert_amd.smpl.{what} runs on the ROCm device (move the module and the tensors first); there is no CPU path')
+    from . import hip_ops
+    return hip_ops.get()
+
+
+def _dense64(a):
+    if hasattr(a, 'todense'):                      # scipy sparse J_regressor of the original model files
+        a = a.todense()
+    if torch.is_tensor(a):
+        a = a.detach().cpu().numpy()
+    return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+
+
+class SMPLModel:
+    """The arrays of one SMPL model, validated, as float32 CPU tensors (`parents`: a tuple of ints).  `Jt` [24,3] = J_regressor . v_template
+    and `Jd` [24,3,10] = J_regressor . shapedirs are folded here in float64 (from the stored fp32 arrays) and stored in float32."""
+
+    def __init__(self, v_template, shapedirs, posedirs, J_regressor, parents, lbs_weights, J_regressor_h36m=None):
+        vt, sd, pd = _dense64(v_template), _dense64(shapedirs), _dense64(posedirs)
+        jr, w = _dense64(J_regressor), _dense64(lbs_weights)
+        if vt.ndim != 2 or vt.shape[1] != 3 or vt.shape[0] < 1:
+            raise ValueError(f'v_template needs to be [V >= 1, 3], got {vt.shape}')
+        V = vt.shape[0]
+        if sd.ndim != 3 or sd.shape[:2] != (V, 3) or sd.shape[2] < NUM_BETAS:
+            raise ValueError(f'shapedirs needs to be [{V}, 3, >= {NUM_BETAS}], got {sd.shape}')
+        sd = np.ascontiguousarray(sd[:, :, :NUM_BETAS])                     # the reference uses the first ten shape components
+        if pd.shape == (V, 3, POSE_FEATS):                                  # the layout of the model files; smplx: reshape(-1, 207).T
+            pd = np.ascontiguousarray(pd.reshape(-1, POSE_FEATS).T)
+        if pd.shape != (POSE_FEATS, 3 * V):
+            raise ValueError(f'posedirs needs to be [{POSE_FEATS}, {3 * V}] (or [{V}, 3, {POSE_FEATS}]), got {pd.shape}')
+        if jr.shape != (NUM_JOINTS, V):
+            raise ValueError(f'J_regressor needs to be [{NUM_JOINTS}, {V}], got {jr.shape}')
+        if w.shape != (V, NUM_JOINTS):
+            raise ValueError(f'lbs_weights needs to be [{V}, {NUM_JOINTS}], got {w.shape}')
+        parents = tuple(int(p) for p in np.asarray(parents.detach().cpu() if torch.is_tensor(parents) else parents).reshape(-1))
+        if len(parents) != NUM_JOINTS:
+            raise ValueError(f'parents needs {NUM_JOINTS} entries, got {len(parents)}')
+        parents = (-1,) + parents[1:]                                        # the files store 2^32 - 1 for the root
+        for j in range(1, NUM_JOINTS):
+            if not 0 <= parents[j] < j:
+                raise ValueError(f'parents[{j}] = {parents[j]} is not a forward-ordered tree (0 <= parents[j] < j)')
+        for name, a in (('v_template', vt), ('shapedirs', sd), ('posedirs', pd), ('J_regressor', jr), ('lbs_weights', w)):
+            if not np.isfinite(a).all():
+                raise ValueError(f'{name} has non-finite entries')
+        vt, sd, pd, jr, w = (a.astype(np.float32).astype(np.float64) for a in (vt, sd, pd, jr, w))      # fold from the fp32 bits that are stored
+        self.V = V
+        self.parents = parents
+        self.v_template, self.shapedirs, self.posedirs = (torch.from_numpy(a).float() for a in (vt, sd, pd))
+        self.J_regressor, self.lbs_weights = torch.from_numpy(jr).float(), torch.from_numpy(w).float()
+        self.Jt = torch.from_numpy(jr @ vt).float()
+        self.Jd = torch.from_numpy(np.einsum('jv,vck->jck', jr, sd)).float().contiguous()
+        self.J_regressor_h36m = None
+        if J_regressor_h36m is not None:
+            q = _dense64(J_regressor_h36m)
+            if q.ndim != 2 or q.shape[1] != V or not 1 <= q.shape[0] <= MAX_K:
+                raise ValueError(f'J_regressor_h36m needs to be [1 <= K <= {MAX_K}, {V}], got {q.shape}')
+            self.J_regressor_h36m = torch.from_numpy(q).float()
+
+    @classmethod
+    def from_npz(cls, path):
+        """an .npz with `v_template, shapedirs, posedirs, J_regressor, lbs_weights` (or `weights`), `parents` (or `kintree_table` [2,24]) and
+        optionally `J_regressor_h36m`: what `to_npz` writes, and what the arrays of the SMPL model files are called"""
+        with np.load(path, allow_pickle=False) as z:
+            keys = set(z.files)
+            missing = [k for k in ('v_template', 'shapedirs', 'posedirs', 'J_regressor') if k not in keys]
+            if missing or not ({'lbs_weights', 'weights'} & keys) or not ({'parents', 'kintree_table'} & keys):
+                raise ValueError(f'{path}: missing arrays (have {sorted(keys)})')
+            parents = z['parents'] if 'parents' in keys else np.asarray(z['kintree_table'])[0].astype(np.int64)
+            return cls(z['v_template'], z['shapedirs'], z['posedirs'], z['J_regressor'], parents,
+                       z['lbs_weights'] if 'lbs_weights' in keys else z['weights'], z['J_regressor_h36m'] if 'J_regressor_h36m' in keys else None)
+
+    def to_npz(self, path):
+        arrays = dict(v_template=self.v_template.numpy(), shapedirs=self.shapedirs.numpy(), posedirs=self.posedirs.numpy(),
+                      J_regressor=self.J_regressor.numpy(), parents=np.asarray(self.parents, np.int64), lbs_weights=self.lbs_weights.numpy())
+        if self.J_regressor_h36m is not None:
+            arrays['J_regressor_h36m'] = self.J_regressor_h36m.numpy()
+        np.savez(path, **arrays)
+
+    @classmethod
+    def from_module(cls, m):
+        """from any object with `v_template / shapedirs / posedirs / J_regressor / parents / lbs_weights` (and `J_regressor_h36m` where
+        present): a `smplx.SMPL`, or the reference's subclass of it"""
+        missing = [k for k in ('v_template', 'shapedirs', 'posedirs', 'J_regressor', 'parents', 'lbs_weights') if not hasattr(m, k)]
+        if missing:
+            raise ValueError(f'{type(m).__name__} has no {missing}')
+        return cls(m.v_template, m.shapedirs, m.posedirs, m.J_regressor, m.parents, m.lbs_weights, getattr(m, 'J_regressor_h36m', None))
+
+    @classmethod
+    def synthetic(cls, V, seed, dense_weights=False):
+        """a model for tests: the SMPL kinematic tree, a random template of about body size, shape directions of 2 cm and pose directions of
+        1 cm per unit, weight rows with at most 4 non-zeros (dense_weights: all 24) summing to 1, regressor rows non-negative summing to 1"""
+        g = torch.Generator().manual_seed(int(seed))
+        vt = 0.3 * torch.randn(V, 3, generator=g, dtype=torch.float64)
+        sd = 0.02 * torch.randn(V, 3, NUM_BETAS, generator=g, dtype=torch.float64)
+        pd = 0.01 * torch.randn(POSE_FEATS, 3 * V, generator=g, dtype=torch.float64)
+        logits = 2.0 * torch.randn(V, NUM_JOINTS, generator=g, dtype=torch.float64)
+        if not dense_weights:
+            keep = torch.rand(V, NUM_JOINTS, generator=g).argsort(dim=1)[:, :4]
+            mask = torch.zeros(V, NUM_JOINTS, dtype=torch.bool).scatter_(1, keep, True)
+            logits = logits.masked_fill(~mask, -float('inf'))
+        w = torch.softmax(logits, dim=1)
+        jr = torch.softmax(2.0 * torch.randn(NUM_JOINTS, V, generator=g, dtype=torch.float64), dim=1)
+        q = torch.softmax(2.0 * torch.randn(17, V, generator=g, dtype=torch.float64), dim=1)
+        return cls(vt, sd, pd, jr, SMPL_PARENTS, w, q)
+
+    def tensors(self, device=None):
+        """the dict the kernel provider takes (without packed_t)"""
+        d = dict(v_template=self.v_template, shapedirs=self.shapedirs, posedirs=self.posedirs, Jt=self.Jt, Jd=self.Jd, lbs_weights=self.lbs_weights)
+        d = {k: (v.to(device) if device is not None else v).contiguous() for k, v in d.items()}
+        d['parents'] = self.parents
+        return d
+
+
+def rodrigues(rot_vecs: torch.Tensor) -> torch.Tensor:
+    """[M,3] axis-angle -> [M,3,3], smplx's `batch_rodrigues`: angle = |r + 1e-8|, R = I + sin K + (1 - cos) K^2"""
+    angle = torch.norm(rot_vecs + 1e-8, dim=1, keepdim=True)
+    d = rot_vecs / angle
+    cos, sin = torch.cos(angle)[:, None], torch.sin(angle)[:, None]
+    rx, ry, rz = d[:, 0], d[:, 1], d[:, 2]
+    zeros = torch.zeros_like(rx)
+    K = torch.stack([zeros, -rz, ry, rz, zeros, -rx, -ry, rx, zeros], dim=1).view(-1, 3, 3)
+    ident = torch.eye(3, dtype=rot_vecs.dtype, device=rot_vecs.device)[None]
+    return ident + sin * K + (1 - cos) * torch.bmm(K, K)
+
+
+class SMPLOutput:
+    """what the layer returns: `.vertices` [F,V,3] (metres), `.joints` [F,24,3] (the posed joints of the kinematic chain)"""
+
+    def __init__(self, vertices, joints):
+        self.vertices, self.joints = vertices, joints
+
+
+class _SMPLFn(torch.autograd.Function):
+    """mode 'layer': (verts, joints); mode 'kp': (verts, kp).  Saves betas and rotmat; the backward recomputes the rest."""
+
+    @staticmethod
+    def forward(ctx, layer, ops, mode, Q, scale, betas, rotmat):
+        b = betas.detach().contiguous().float()
+        r = rotmat.detach().contiguous().float().reshape(-1, NUM_JOINTS, 9)
+        F, V, dev = b.shape[0], layer.v_template.shape[0], b.device
+        model = layer.model_tensors()
+        verts = torch.empty(F, V, 3, dtype=torch.float32, device=dev)
+        if mode == 'kp':
+            second = torch.empty(F, Q.shape[0], 3, dtype=torch.float32, device=dev)
+            if F:
+                ops.smpl_fwd(model, Q, b, r, scale, verts, second, None, ws=layer.workspace(ops, 'fwd', F, Q.shape[0], dev))
+        else:
+            second = torch.empty(F, NUM_JOINTS, 3, dtype=torch.float32, device=dev)
+            if F:
+                ops.smpl_fwd(model, None, b, r, scale, verts, None, second, ws=layer.workspace(ops, 'fwd', F, 0, dev))
+        ctx.layer, ctx.ops, ctx.mode, ctx.Q, ctx.scale = layer, ops, mode, Q, scale
+        ctx.save_for_backward(b, r)
+        ctx.set_materialize_grads(False)
+        return verts, second
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dverts, dsecond):
+        b, r = ctx.saved_tensors
+        layer, ops, F = ctx.layer, ctx.ops, b.shape[0]
+        db, dr = torch.zeros_like(b), torch.zeros_like(r)
+        if F and (dverts is not None or dsecond is not None):
+            dv = None if dverts is None else dverts.contiguous().float()
+            d2 = None if dsecond is None else dsecond.contiguous().float()
+            K = ctx.Q.shape[0] if ctx.mode == 'kp' else 0
+            model = layer.model_tensors(packed=ops)
+            ws = layer.workspace(ops, 'bwd', F, K, b.device)
+            if ctx.mode == 'kp':
+                ops.smpl_bwd(model, ctx.Q, b, r, ctx.scale, dv, d2, None, dr, db, ws=ws)
+            else:
+                ops.smpl_bwd(model, None, b, r, ctx.scale, dv, None, d2, dr, db, ws=ws)
+        return None, None, None, None, None, db, dr.view(F, NUM_JOINTS, 3, 3)
+
+
+class SMPLLayer(nn.Module):
+    """`SMPLLayer(model, ops=None)`; see the module docstring.  The model arrays are buffers (`v_template, shapedirs, posedirs, J_regressor,
+    lbs_weights, parents`, and `J_regressor_h36m` where the model has it), so `.to()` and `state_dict` work; `Jt`, `Jd` and the packed table
+    of the backward are derived, not saved, and rebuilt after `load_state_dict`."""
+
+    def __init__(self, model: SMPLModel, ops=None):
+        super().__init__()
+        if not isinstance(model, SMPLModel):
+            raise TypeError('SMPLLayer needs an SMPLModel (SMPLModel.from_npz / from_module / synthetic)')
+        for name in ('v_template', 'shapedirs', 'posedirs', 'J_regressor', 'lbs_weights'):
+            self.register_buffer(name, getattr(model, name).clone().contiguous())
+        self.register_buffer('parents', torch.tensor(model.parents, dtype=torch.long))
+        if model.J_regressor_h36m is not None:
+            self.register_buffer('J_regressor_h36m', model.J_regressor_h36m.clone().contiguous())
+        else:
+            self.J_regressor_h36m = None
+        self.register_buffer('Jt', model.Jt.clone(), persistent=False)
+        self.register_buffer('Jd', model.Jd.clone(), persistent=False)
+        self.register_buffer('packed_t', torch.empty(0), persistent=False)
+        self._parents = model.parents
+        self.ops = ops
+        self._ws = {}
+        self.register_load_state_dict_post_hook(lambda module, _keys: module._refresh())
+
+    def _refresh(self):
+        """after load_state_dict: validate the arrays again and rebuild what is derived from them"""
+        m = SMPLModel(self.v_template, self.shapedirs, self.posedirs, self.J_regressor, self.parents, self.lbs_weights, self.J_regressor_h36m)
+        self._parents = m.parents
+        self.Jt, self.Jd = m.Jt.to(self.v_template.device), m.Jd.to(self.v_template.device)
+        self.packed_t = torch.empty(0, device=self.v_template.device)
+
+    @property
+    def num_vertices(self):
+        return self.v_template.shape[0]
+
+    def model_tensors(self, packed=None):
+        """the provider's model dict; packed: the provider that builds the backward's table [3V,224] on first use"""
+        d = dict(v_template=self.v_template, shapedirs=self.shapedirs, posedirs=self.posedirs, Jt=self.Jt, Jd=self.Jd, lbs_weights=self.lbs_weights,
+                 parents=self._parents)
+        if packed is not None:
+            if self.packed_t.numel() != 3 * self.num_vertices * PACK_COLS or self.packed_t.device != self.posedirs.device:
+                t = torch.empty(3 * self.num_vertices, PACK_COLS, dtype=torch.float32, device=self.posedirs.device)
+                packed.smpl_pack(self.shapedirs, self.posedirs, t)
+                self.packed_t = t
+            d['packed_t'] = self.packed_t
+        return d
+
+    def workspace(self, ops, kind, F, K, device):
+        """one workspace per (direction, F, K, device), kept: a captured graph replays with the addresses of its capture"""
+        key = (kind, F, K, str(device))
+        ws = self._ws.get(key)
+        if ws is None:
+            if len(self._ws) >= 16:
+                self._ws.clear()
+            ws = self._ws[key] = (ops.smpl_fwd_ws if kind == 'fwd' else ops.smpl_bwd_ws)(F, self.num_vertices, K, device)
+        return ws
+
+    def prepare(self, F, K=0):
+        """allocate the workspaces of a call shape and the packed table now (before a graph capture that has had no warm-up)"""
+        ops = _provider(self.ops, 'SMPLLayer', self.v_template)
+        self.model_tensors(packed=ops)
+        for kind, k in (('fwd', K), ('bwd', K), ('fwd', 0), ('bwd', 0)):
+            self.workspace(ops, kind, F, k, self.v_template.device)
+
+    def _check(self, betas, rotmat):
+        if betas.dim() != 2 or betas.shape[1] != NUM_BETAS:
+            raise ValueError(f'betas [F,{NUM_BETAS}] expected, got {tuple(betas.shape)}')
+        if rotmat.shape[0] != betas.shape[0] or rotmat.numel() != betas.shape[0] * NUM_JOINTS * 9:
+            raise ValueError(f'24 rotation matrices per frame expected for {betas.shape[0]} frames, got {tuple(rotmat.shape)}')
+        if betas.device != self.v_template.device or rotmat.device != self.v_template.device:
+            raise ValueError(f'the layer is on {self.v_template.device}, betas on {betas.device}, the rotations on {rotmat.device}')
+
+    def forward(self, betas, body_pose, global_orient, pose2rot=False, **_unused):
+        F = betas.shape[0]
+        n = 3 if pose2rot else 9
+        if global_orient.numel() != F * n or body_pose.numel() != F * 23 * n:
+            raise ValueError(('axis-angle global_orient [F,3] and body_pose [F,69]' if pose2rot else '24 rotation matrices per frame: global_orient '
+                              '[F,1,3,3] and body_pose [F,23,3,3]') + f' expected, got {tuple(global_orient.shape)} / {tuple(body_pose.shape)}')
+        if pose2rot:
+            aa = torch.cat([global_orient.reshape(F, 1, 3), body_pose.reshape(F, 23, 3)], dim=1)
+            rotmat = rodrigues(aa.reshape(-1, 3)).view(F, NUM_JOINTS, 3, 3)
+        else:
+            rotmat = torch.cat([global_orient.reshape(F, 1, 3, 3), body_pose.reshape(F, 23, 3, 3)], dim=1)
+        self._check(betas, rotmat)
+        ops = _provider(self.ops, 'SMPLLayer', betas, rotmat, self.v_template)
+        verts, joints = _SMPLFn.apply(self, ops, 'layer', None, 1.0, betas, rotmat)
+        return SMPLOutput(verts.to(betas.dtype), joints.to(betas.dtype))
+
+    def forward_kp(self, betas, rotmat, Q=None, scale=1.0, ops=None):
+        """`(verts [F,V,3], kp [F,K,3]) = (scale x, scale Q x)` of betas [F,10] and rotmat [F,24,3,3] from the fused launch; Q [K,V]
+        (default: the model's J_regressor_h36m), fp32 outputs"""
+        Q = self.J_regressor_h36m if Q is None else Q
+        if Q is None:
+            raise ValueError('forward_kp needs a regressor Q [K,V] (the model has no J_regressor_h36m)')
+        if Q.dim() != 2 or Q.shape[1] != self.num_vertices or not 1 <= Q.shape[0] <= MAX_K:
+            raise ValueError(f'Q [1 <= K <= {MAX_K}, {self.num_vertices}] expected, got {tuple(Q.shape)}')
+        self._check(betas, rotmat)
+        ops = _provider(ops if ops is not None else self.ops, 'SMPLLayer.forward_kp', betas, rotmat, self.v_template)
+        if Q.device != betas.device or Q.dtype != torch.float32 or not Q.is_contiguous():
+            Q = Q.to(device=betas.device, dtype=torch.float32).contiguous()
+        return _SMPLFn.apply(self, ops, 'kp', Q.detach(), float(scale), betas, rotmat)
