@@ -24,14 +24,10 @@ from typing import Dict, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import hip_ops
+
 #: train.py:109-111: test sources left out of both protocols
 BLOCK_LIST = ('s_09_act_05_subact_02', 's_09_act_10_subact_02', 's_09_act_13_subact_01')
-
-
-def _device_only(what: str, *tensors):
-    for t in tensors:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError(f'motionbert_amd.evaluate.{what} runs on the ROCm device (move the tensors first); there is no CPU path')
 
 
 def _f32(t: Optional[torch.Tensor]):
@@ -63,10 +59,7 @@ def pose_errors(pred: torch.Tensor, gt: torch.Tensor, *, hw: Optional[torch.Tens
         raise ValueError(f'factor must be [N,T], got {tuple(factor.shape)}')
     if gt_2d_input is not None and (gt_2d_input.dim() != 4 or tuple(gt_2d_input.shape[:3]) != (N, T, J) or gt_2d_input.shape[-1] < 2):
         raise ValueError(f'gt_2d_input must be [N,T,J,>=2], got {tuple(gt_2d_input.shape)}')
-    if ops is None:
-        _device_only('pose_errors', pred, gt, hw, factor, gt_2d_input)
-        from . import hip_ops
-        ops = hip_ops.get()
+    ops = hip_ops.provider(ops, 'motionbert_amd.evaluate.pose_errors', pred, gt, hw, factor, gt_2d_input)
     if out is None:
         e1 = torch.empty(N, T, dtype=torch.float64, device=pred.device)
         e2 = torch.empty(N, T, dtype=torch.float64, device=pred.device)
@@ -116,16 +109,7 @@ class H36MEvaluator:
 
     def __init__(self, gt_clips, factor_clips, frame_clips, hw_clips, actions, sources, *, rootrel: bool, flip: bool, gt_2d: bool = False,
                  no_conf: bool = False, block_list: Sequence[str] = BLOCK_LIST, ops=None, device=None):
-        if ops is None:
-            if not torch.cuda.is_available():
-                raise RuntimeError('motionbert_amd.evaluate.H36MEvaluator runs on the ROCm device; there is no CPU path')
-            from . import hip_ops
-            ops = hip_ops.get()
-            device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-            if device.type != 'cuda':
-                raise RuntimeError('motionbert_amd.evaluate.H36MEvaluator runs on the ROCm device; there is no CPU path')
-        else:
-            device = torch.device('cpu' if device is None else device)      # an injected provider decides where its tensors live
+        ops, device = hip_ops.evaluator_provider(ops, device, 'motionbert_amd.evaluate.H36MEvaluator')
         self.ops, self.device = ops, device
         self.rootrel, self.flip, self.gt_2d, self.no_conf = bool(rootrel), bool(flip), bool(gt_2d), bool(no_conf)
         gt_clips = np.asarray(gt_clips)
@@ -165,7 +149,7 @@ class H36MEvaluator:
         """Forward of the next len(batch_input) clips (flip test-time augmentation when `flip`), their errors into the slots of
         those clips.  Returns the raw network output of the batch (a fresh tensor the caller may write into)."""
         if self.device.type == 'cuda':
-            _device_only('H36MEvaluator.update', batch_input)
+            hip_ops.provider(None, 'motionbert_amd.evaluate.H36MEvaluator.update', batch_input)
         n0, n1 = self.cursor, self.cursor + batch_input.shape[0]
         if n1 > self.n_clips:
             raise ValueError(f'update() was given clips {n0}..{n1 - 1} of a split of {self.n_clips}')
@@ -212,10 +196,7 @@ def evaluate(args, model_pos, test_loader, datareader):
     the end; the reference additionally leaves the 2.5D factor multiplied into the clips of unblocked sources, a side effect of
     `pred *= factor` on a view (train.py:120-121), which is not reproduced.  The per-action numbers are not printed: use
     H36MEvaluator.finish() for them."""
-    params = list(model_pos.parameters())
-    if not params or not params[0].is_cuda:
-        raise RuntimeError('motionbert_amd.evaluate.evaluate runs on the ROCm device (move the model first); there is no CPU path')
-    device = params[0].device
+    device = hip_ops.model_device(model_pos, 'motionbert_amd.evaluate.evaluate')
     model_pos.eval()
     _, split_id_test = datareader.get_split_id()
     test = datareader.dt_dataset['test']

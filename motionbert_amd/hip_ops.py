@@ -935,6 +935,38 @@ def get() -> HipOps:
     return _OPS
 
 
+def provider(ops, where: str, *tensors, move: str = 'the tensors'):
+    """The kernel provider of a task-layer call made as `where` (its full dotted name): an injected `ops` as it is (it decides where
+    its tensors live); otherwise the process-wide instance, once every tensor is on the ROCm device.  The check comes first: a host
+    tensor raises without loading libmbx.so."""
+    if ops is not None:
+        return ops
+    for t in tensors:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f'{where} runs on the ROCm device (move {move} first); there is no CPU path')
+    return get()
+
+
+def model_device(model, where: str) -> torch.device:
+    """The ROCm device of `model`'s first parameter, for a drop-in evaluation called as `where`; a model on the host, or one without
+    parameters, raises."""
+    p = next(iter(model.parameters()), None) if hasattr(model, 'parameters') else None
+    if p is None or not p.is_cuda:
+        raise RuntimeError(f'{where} runs on the ROCm device (move the model first); there is no CPU path')
+    return p.device
+
+
+def evaluator_provider(ops, device, where: str):
+    """`(ops, device)` of an evaluator's constructor: an injected `ops` with `device` (default: the host); otherwise the process-wide
+    instance with a ROCm `device` (default: the current one)."""
+    if ops is not None:
+        return ops, torch.device('cpu' if device is None else device)
+    device = None if device is None else torch.device(device)
+    if not torch.cuda.is_available() or (device is not None and device.type != 'cuda'):
+        raise RuntimeError(f'{where} runs on the ROCm device; there is no CPU path')
+    return get(), torch.device('cuda', torch.cuda.current_device()) if device is None else device
+
+
 def peek() -> Optional[HipOps]:
     """The process-wide instance if one has been created, else None (never loads the library: model.train() on a CPU box)."""
     return _OPS

@@ -8,7 +8,7 @@ skinning, built from the user's SMPL arrays) or any module with the reference's 
                                     `J_regressor` are injected.
     MeshLoss(loss_type, lambdas)    loss_mesh.py:7-68: the reference's dict of ten losses as 0-dim device tensors; the seven joint terms from
                                     one `mbx_pose_loss_full`, the three parameter terms from one `mbx_mesh_param_loss`.
-    MeshStep(model, ...)            the optimizer step of train_mesh.py:165-203 without a host synchronisation; the ten losses, the total and
+    MeshStep(model, ...)            the optimizer step of train_mesh.py:165-203 (a `train.TwoGroupStep`), no host synchronisation; the ten losses, the total and
                                     the step's MPJPE / MPVE stay in a device log tensor.
     MeshEvaluator()                 `update(output, batch_gt)` per test batch (`mbx_mesh_errors` into device buffers), `finish()` returns
                                     `evaluate_mesh`'s dict and is the only host synchronisation: no vertex ever goes to the host.
@@ -26,23 +26,15 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
+from . import hip_ops
 from .smpl import SMPLLayer, rodrigues
+from .train import TwoGroupStep
 
 LOSS_KEYS = ('loss_3d_pos', 'loss_3d_scale', 'loss_3d_velocity', 'loss_lv', 'loss_lg', 'loss_a', 'loss_av', 'loss_shape', 'loss_pose', 'loss_norm')
 LAMBDA_NAMES = ('lambda_3d', 'lambda_scale', 'lambda_3dv', 'lambda_lv', 'lambda_lg', 'lambda_a', 'lambda_av', 'lambda_shape', 'lambda_pose',
                 'lambda_norm')      # train_mesh.py:180-189, in the order of LOSS_KEYS
 ERROR_KEYS = ('mpve', 'mpjpe_17j', 'mpjpe', 'pa_mpjpe_17j', 'pa_mpjpe')      # rows of mbx_mesh_errors; 'mpjpe' / 'pa_mpjpe' use the 14 joints
 LOSS_TYPES = {'MSE': 0, 'L1': 1}
-
-
-def _provider(ops, what: str, *tensors):
-    if ops is not None:
-        return ops
-    for t in tensors:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError(f'motionbert_amd.mesh.{what} runs on the ROCm device (move the tensors first); there is no CPU path')
-    from . import hip_ops
-    return hip_ops.get()
 
 
 # ---------------------------------------------------------------------------------------------------------------- rotation chain
@@ -80,7 +72,7 @@ def rot6d_to_rotmat_theta(x6: torch.Tensor, ops=None):
         raise ValueError(f'rot6d_to_rotmat_theta needs a multiple of 6 elements, got {tuple(x6.shape)}')
     if not x6.dtype.is_floating_point:
         raise ValueError(f'rot6d_to_rotmat_theta needs a floating-point tensor, got {x6.dtype}')
-    ops = _provider(ops, 'rot6d_to_rotmat_theta', x6)
+    ops = hip_ops.provider(ops, 'motionbert_amd.mesh.rot6d_to_rotmat_theta', x6)
     return _Rot6dFn.apply(ops, x6.reshape(-1, 6))
 
 
@@ -303,7 +295,7 @@ class MeshLoss(nn.Module):
             raise ValueError(f'theta [N,T,82] expected for prediction and target, got {tuple(theta.shape)} / {tuple(gt_theta.shape)}')
         if tuple(kp.shape) != tuple(theta.shape[:2]) + (17, 3) or tuple(gt_kp.shape) != tuple(kp.shape):
             raise ValueError(f'kp_3d [N,T,17,3] expected for prediction and target, got {tuple(kp.shape)} / {tuple(gt_kp.shape)}')
-        ops = _provider(self.ops, 'MeshLoss', theta, kp, gt_theta, gt_kp)
+        ops = hip_ops.provider(self.ops, 'motionbert_amd.mesh.MeshLoss', theta, kp, gt_theta, gt_kp)
         kp_local = (kp - kp[:, :, 0:1, :]).float().contiguous()                    # loss_mesh.py:36-37
         gt_local = (gt_kp - gt_kp[:, :, 0:1, :]).detach().float().contiguous()
         th = theta.reshape(-1, 82).float().contiguous()
@@ -341,7 +333,7 @@ def mesh_errors(output, target, ops=None) -> torch.Tensor:
     """err [5,F] float64 on the device, rows ERROR_KEYS, for `output` (the model's list, or its dict) and `target` (dict): `verts`
     [...,V,3] (optional on both) and `kp_3d` [...,17,3].  Without `verts` the `mpve` row is NaN."""
     vp, vg, kp, kg = _frames(output, target)
-    ops = _provider(ops, 'mesh_errors', vp, vg, kp, kg)
+    ops = hip_ops.provider(ops, 'motionbert_amd.mesh.mesh_errors', vp, vg, kp, kg)
     err = torch.empty(5, kp.shape[0], dtype=torch.float64, device=kp.device)
     if kp.shape[0]:
         ops.mesh_errors(vp, vg, kp, kg, err)
@@ -372,9 +364,8 @@ class MeshEvaluator:
     reference keeps 165 KB per frame on the host); it returns that result.  `finish` averages every row over all frames seen."""
 
     def __init__(self, ops=None):
-        if ops is None and not torch.cuda.is_available():
-            raise RuntimeError('motionbert_amd.mesh.MeshEvaluator runs on the ROCm device; there is no CPU path')
-        self.ops = ops
+        hip_ops.evaluator_provider(ops, None, 'motionbert_amd.mesh.MeshEvaluator')
+        self.ops = ops                      # (stays None without an injected provider: every update() then checks where its tensors are)
         self.reset()
 
     def reset(self):
@@ -450,37 +441,27 @@ def flip_average(model, smpl, batch_input: torch.Tensor, output=None):
 LOG_KEYS = LOSS_KEYS + ('total', 'mpjpe', 'mpve')
 
 
-class MeshStep:
+class MeshStep(TwoGroupStep):
     """One optimizer step of train_mesh.py:165-203: forward, `MeshLoss` with the trainer's lambdas, `compute_error`, backward, and the two
-    AdamW groups of :316-321 -- backbone at `lr_backbone`, head at `lr_head` -- as two flat one-launch optimizers; `decay()` is the per-epoch
-    StepLR(gamma=lr_decay).  `batch_gt`: dict with `theta` [N,T,82], `kp_3d` [N,T,17,3], `verts` [N,T,V,3] on the device.
+    AdamW groups of `train.TwoGroupStep` (:316-321).  `batch_gt`: dict with `theta` [N,T,82], `kp_3d` [N,T,17,3], `verts` [N,T,V,3] on the device.
     Returns the log: a device tensor [13] in the order of LOG_KEYS (the ten losses, the weighted total, the step's mean 17-joint MPJPE and
     MPVE); nothing is synchronised with the host (the reference ends every step with eleven `.item()` calls and a `.cpu()`).
     Single-process only."""
 
     def __init__(self, model, lr_backbone: float = 5e-5, lr_head: float = 5e-4, weight_decay: float = 0.01, lambdas=None,
                  loss_type: str = 'L1', ops=None):
-        from .train import FlatAdamW
         if lambdas is None:
             raise ValueError('MeshStep needs the trainer\'s lambdas (lambda_3d ... lambda_norm)')
-        self.model, self.ops = model, ops
+        self.ops = ops
         self.criterion = MeshLoss(loss_type=loss_type, lambdas=lambdas, ops=ops)
-        self.opt_backbone = FlatAdamW(model.backbone, lr=lr_backbone, weight_decay=weight_decay)
-        self.opt_head = FlatAdamW([('head.' + n, p) for n, p in model.head.named_parameters() if p.requires_grad], lr=lr_head,
-                                  weight_decay=weight_decay)
+        super().__init__(model, lr_backbone, lr_head, weight_decay)
 
     def __call__(self, batch_input: torch.Tensor, batch_gt: dict) -> torch.Tensor:
         output = self.model(batch_input)
-        self.opt_backbone.zero_grad(set_to_none=True)
-        self.opt_head.zero_grad(set_to_none=True)
+        self.zero_grad()
         losses = self.criterion(output, batch_gt)
         with torch.no_grad():
             mpjpe, mpve = compute_error(output, batch_gt, self.ops)
         losses['total'].backward()
-        self.opt_backbone.step()
-        self.opt_head.step()
+        self.step()
         return torch.cat([torch.stack([losses[k].detach() for k in LOSS_KEYS + ('total',)]).double(), torch.stack([mpjpe, mpve])])
-
-    def decay(self, gamma: float):
-        self.opt_backbone.lr = self.opt_backbone.lr * gamma
-        self.opt_head.lr = self.opt_head.lr * gamma

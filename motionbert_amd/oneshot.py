@@ -6,7 +6,7 @@ builds the `[M, N, hidden]` broadcast for `F.cosine_similarity` -- M * N * 2048 
 
     supcon_loss(features, labels, ...)   SupConLoss.forward with contrast_mode 'all' and its gradient in one call of `mbx_supcon_loss`,
                                          optionally through the head's L2 normalisation; the loss stays on the device.
-    OneShotStep(model, ...)              the optimizer step of train_action_1shot.py:186-198, shaped like `train.ActionStep`.
+    OneShotStep(model, ...)              the optimizer step of train_action_1shot.py:186-198, a `train.TwoGroupStep` like `train.ActionStep`.
     OneShotEvaluator(...)                exemplars once, then `update(model, batch, labels)` per test batch (`mbx_nn_cosine` into device
                                          buffers); `finish()` returns the accuracy and is the only host synchronisation.
     validate(anchor_loader, test_loader, model)   the reference's signature and return value.
@@ -14,7 +14,7 @@ builds the `[M, N, hidden]` broadcast for `F.cosine_similarity` -- M * N * 2048 
 `mask=` and `contrast_mode='one'` of the reference's loss are not offered (the trainer uses neither).  The step is single-process: the
 reference computes the loss over the gathered batch, and a per-rank loss would be a different objective.
 
-There is no CPU path: without an injected kernel provider, tensors that are not on a ROCm device raise.
+There is no CPU path: without an injected kernel provider, tensors that are not on a ROCm device raise (`hip_ops.provider`).
 """
 from __future__ import annotations
 
@@ -22,33 +22,8 @@ from typing import Optional
 
 import torch
 
-
-def _provider(ops, what: str, *tensors):
-    if ops is not None:
-        return ops
-    for t in tensors:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError(f'motionbert_amd.oneshot.{what} runs on the ROCm device (move the tensors first); there is no CPU path')
-    from . import hip_ops
-    return hip_ops.get()
-
-
-class _SupConFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, ops, feat, labels, temperature, base_temperature, normalize):
-        feat_c = feat.contiguous().float()
-        loss = torch.empty(1, dtype=torch.float32, device=feat.device)
-        dfeat = torch.empty_like(feat_c) if ctx.needs_input_grad[1] else None
-        ops.supcon_loss(feat_c, labels, temperature, base_temperature, normalize, loss, dfeat)
-        ctx.dfeat = dfeat
-        return loss[0]
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dloss):
-        d = ctx.dfeat
-        ctx.dfeat = None
-        return None, (d * dloss if d is not None else None), None, None, None, None
+from . import hip_ops
+from .train import TwoGroupStep, _FusedLossFn
 
 
 def supcon_loss(features: torch.Tensor, labels: Optional[torch.Tensor] = None, temperature: float = 0.07, base_temperature: float = 0.07,
@@ -77,42 +52,33 @@ def supcon_loss(features: torch.Tensor, labels: Optional[torch.Tensor] = None, t
         raise ValueError('features have no elements per view')
     if not (temperature > 0 and base_temperature > 0):
         raise ValueError(f'temperature {temperature} and base_temperature {base_temperature} must be > 0')
-    ops = _provider(ops, 'supcon_loss', features, labels)
+    ops = hip_ops.provider(ops, 'motionbert_amd.oneshot.supcon_loss', features, labels)
     lab = labels.detach().to(device=features.device, dtype=torch.int32).contiguous()
-    return _SupConFn.apply(ops, feat, lab, float(temperature), float(base_temperature), bool(normalize))
+    t, bt, norm = float(temperature), float(base_temperature), bool(normalize)
+    return _FusedLossFn.apply(lambda x, loss, dx: ops.supcon_loss(x, lab, t, bt, norm, loss, dx), 1, 0, feat)[0]
 
 
-class OneShotStep:
+class OneShotStep(TwoGroupStep):
     """One optimizer step of train_action_1shot.py:186-198: embeddings of batch [N,M,T,17,3], reshaped to [N, -1, hidden]
     (N * n_views samples arrive as N rows of one view), SupCon loss at `temperature`, backward, and the two AdamW groups of
-    :156-161 -- backbone at `lr_backbone`, head at `lr_head` -- as two flat one-launch optimizers; `decay()` is the per-epoch
-    StepLR(gamma=lr_decay).  The head's `fc1` output goes into the loss un-normalised: `mbx_supcon_loss` normalises the rows itself
+    `train.TwoGroupStep` (:156-161).  The head's `fc1` output goes into the loss un-normalised: `mbx_supcon_loss` normalises the rows itself
     and hands back the cotangent of `fc1`'s output, so F.normalize and its backward never run as torch kernels.
     Returns `loss.detach()` (device tensor, no host synchronisation).  Single-process only."""
 
     def __init__(self, model, temperature: float = 0.1, lr_backbone: float = 1e-4, lr_head: float = 1e-3, weight_decay: float = 0.01, ops=None):
-        from .train import FlatAdamW
         if not hasattr(model.head, 'fc1') or hasattr(model.head, 'fc2'):
             raise ValueError("OneShotStep needs ActionNet(version='embed')")
-        self.model, self.temperature, self.ops = model, float(temperature), ops
-        self.opt_backbone = FlatAdamW(model.backbone, lr=lr_backbone, weight_decay=weight_decay)
-        self.opt_head = FlatAdamW([('head.' + n, p) for n, p in model.head.named_parameters() if p.requires_grad], lr=lr_head,
-                                  weight_decay=weight_decay)
+        self.temperature, self.ops = float(temperature), ops
+        super().__init__(model, lr_backbone, lr_head, weight_decay)
 
     def __call__(self, batch_input: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
         head = self.model.head
         z = head.fc1(head.pooled(self.model.backbone, batch_input))           # [N, hidden], before F.normalize
-        self.opt_backbone.zero_grad(set_to_none=True)
-        self.opt_head.zero_grad(set_to_none=True)
+        self.zero_grad()
         loss = supcon_loss(z.reshape(len(batch_input), -1, z.shape[-1]), labels, temperature=self.temperature, normalize=True, ops=self.ops)
         loss.backward()
-        self.opt_backbone.step()
-        self.opt_head.step()
+        self.step()
         return loss.detach()
-
-    def decay(self, gamma: float):
-        self.opt_backbone.lr = self.opt_backbone.lr * gamma
-        self.opt_head.lr = self.opt_head.lr * gamma
 
 
 def _embed(model, batch):
@@ -132,17 +98,7 @@ class OneShotEvaluator:
     is the only host synchronisation.  `ops`: kernel provider (default: libmbx.so, tensors on the ROCm device)."""
 
     def __init__(self, ops=None, device=None):
-        if ops is None:
-            if not torch.cuda.is_available():
-                raise RuntimeError('motionbert_amd.oneshot.OneShotEvaluator runs on the ROCm device; there is no CPU path')
-            from . import hip_ops
-            ops = hip_ops.get()
-            device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-            if device.type != 'cuda':
-                raise RuntimeError('motionbert_amd.oneshot.OneShotEvaluator runs on the ROCm device; there is no CPU path')
-        else:
-            device = torch.device('cpu' if device is None else device)      # an injected provider decides where its tensors live
-        self.ops, self.device = ops, device
+        self.ops, self.device = hip_ops.evaluator_provider(ops, device, 'motionbert_amd.oneshot.OneShotEvaluator')
         self.anchors = self.anchor_labels = None
         self.reset()
 
@@ -198,10 +154,7 @@ def validate(anchor_loader, test_loader, model, ops=None, device=None):
     """Drop-in for the reference's `validate(anchor_loader, test_loader, model)` (train_action_1shot.py:58-69): the 1-NN accuracy of
     the test split against the exemplars, as a 0-dim tensor like the reference's `sum(pred == labels) / len(pred)`."""
     if ops is None and device is None:
-        params = list(model.parameters()) if hasattr(model, 'parameters') else []
-        if not params or not params[0].is_cuda:
-            raise RuntimeError('motionbert_amd.oneshot.validate runs on the ROCm device (move the model first); there is no CPU path')
-        device = params[0].device
+        device = hip_ops.model_device(model, 'motionbert_amd.oneshot.validate')
     ev = OneShotEvaluator(ops=ops, device=device)
     ev.set_anchors(model, anchor_loader)
     for batch, labels in test_loader:

@@ -20,18 +20,11 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from . import hip_ops
+
 SMPL_PARENTS = (-1, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16, 17, 18, 19, 20, 21)      # the public SMPL kinematic tree
 NUM_JOINTS, NUM_BETAS, POSE_FEATS, PACK_COLS, MAX_K = 24, 10, 207, 224, 32
-
-
-def _provider(ops, what: str, *tensors):
-    if ops is not None:
-        return ops
-    for t in tensors:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError(f'motionbert_amd.smpl.{what} runs on the ROCm device (move the module and the tensors first); there is no CPU path')
-    from . import hip_ops
-    return hip_ops.get()
+_MOVE = 'the module and the tensors'      # what a host tensor's error asks to move: the layer's buffers are checked with the arguments
 
 
 def _dense64(a):
@@ -262,7 +255,7 @@ class SMPLLayer(nn.Module):
 
     def prepare(self, F, K=0):
         """allocate the workspaces of a call shape and the packed table now (before a graph capture that has had no warm-up)"""
-        ops = _provider(self.ops, 'SMPLLayer', self.v_template)
+        ops = hip_ops.provider(self.ops, 'motionbert_amd.smpl.SMPLLayer', self.v_template, move=_MOVE)
         self.model_tensors(packed=ops)
         for kind, k in (('fwd', K), ('bwd', K), ('fwd', 0), ('bwd', 0)):
             self.workspace(ops, kind, F, k, self.v_template.device)
@@ -287,7 +280,7 @@ class SMPLLayer(nn.Module):
         else:
             rotmat = torch.cat([global_orient.reshape(F, 1, 3, 3), body_pose.reshape(F, 23, 3, 3)], dim=1)
         self._check(betas, rotmat)
-        ops = _provider(self.ops, 'SMPLLayer', betas, rotmat, self.v_template)
+        ops = hip_ops.provider(self.ops, 'motionbert_amd.smpl.SMPLLayer', betas, rotmat, self.v_template, move=_MOVE)
         verts, joints = _SMPLFn.apply(self, ops, 'layer', None, 1.0, betas, rotmat)
         return SMPLOutput(verts.to(betas.dtype), joints.to(betas.dtype))
 
@@ -300,7 +293,8 @@ class SMPLLayer(nn.Module):
         if Q.dim() != 2 or Q.shape[1] != self.num_vertices or not 1 <= Q.shape[0] <= MAX_K:
             raise ValueError(f'Q [1 <= K <= {MAX_K}, {self.num_vertices}] expected, got {tuple(Q.shape)}')
         self._check(betas, rotmat)
-        ops = _provider(ops if ops is not None else self.ops, 'SMPLLayer.forward_kp', betas, rotmat, self.v_template)
+        ops = hip_ops.provider(ops if ops is not None else self.ops, 'motionbert_amd.smpl.SMPLLayer.forward_kp', betas, rotmat, self.v_template,
+                               move=_MOVE)
         if Q.device != betas.device or Q.dtype != torch.float32 or not Q.is_contiguous():
             Q = Q.to(device=betas.device, dtype=torch.float32).contiguous()
         return _SMPLFn.apply(self, ops, 'kp', Q.detach(), float(scale), betas, rotmat)

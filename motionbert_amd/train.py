@@ -8,7 +8,12 @@ backbone itself runs in tens of milliseconds those pieces show, so they are part
                              kernel pass (`mbx_pose_loss`); the four loss values stay on the device.
   pose_loss_full(pred, gt, ...)  all seven losses of train.py:177-199 -- the three above plus loss_limb_var, loss_limb_gt, loss_angle and
                              loss_angle_velocity -- their weighted total and its gradient (`mbx_pose_loss_full`); the eight values the
-                             reference logs stay on the device.  `PretrainStepFull` / `GraphedTrainStepFull` are the steps built on it.
+                             reference logs stay on the device.  `PretrainStepFull` / `GraphedTrainStepFull` are the steps built on it:
+                             `PretrainStep` / `GraphedTrainStep` with the loss call and the width of the log overridden.
+  _FusedLossFn               the one autograd function under these losses, `loss_2d_weighted` and `oneshot.supcon_loss`: values and
+                             gradient from one launch, backward scales the stored gradient.
+  TwoGroupStep               backbone at one learning rate, head at another, as two `FlatAdamW`: the base of `ActionStep`,
+                             `oneshot.OneShotStep` and `mesh.MeshStep`.
   FlatAdamW                  the model's parameters re-laid into ONE flat fp32 buffer in backward-completion order -- the
                              same order in which the backbone's backward writes its single flat gradient buffer -- so that
                              `step()` is one launch of `mbx_adamw_step` over 42.5 M elements (and, under data parallelism,
@@ -16,6 +21,8 @@ backbone itself runs in tens of milliseconds those pieces show, so they are part
                              live on the device.
   GraphedTrainStep           forward + loss + backward + update captured once into a hipGraph and replayed per batch: no
                              Python / ctypes launch cost (~850 launches per step), which is what bounds small batches.
+
+Without an injected kernel provider (`ops=`), tensors that are not on a ROCm device raise (`hip_ops.provider`).
 """
 from __future__ import annotations
 
@@ -23,27 +30,32 @@ from typing import Optional
 
 import torch
 
+from . import hip_ops
 from .engine import grad_bucket
 from .model import named_parameter_tensors
 
 
-class _PoseLossFn(torch.autograd.Function):
+class _FusedLossFn(torch.autograd.Function):
+    """Loss values and gradient from ONE kernel call.  `launch(x, values, dx)` gets x contiguous fp32, fills `values` [n] and, where x needs
+    a gradient, `dx` = d values[total] / d x (else `dx` is None); backward only scales the stored gradient.  Returns `(values[total],
+    values)`, `values` not differentiable; with n > 1 the total is a copy, so that the log can be handed out beside it."""
+
     @staticmethod
-    def forward(ctx, ops, pred, gt, lambda_scale, lambda_velocity):
-        pred_c, gt_c = pred.contiguous().float(), gt.contiguous().float()
-        losses = torch.empty(4, dtype=torch.float32, device=pred.device)
-        dpred = torch.empty_like(pred_c) if ctx.needs_input_grad[1] else None
-        ops.pose_loss(pred_c, gt_c, lambda_scale, lambda_velocity, losses, dpred)
-        ctx.dpred = dpred
-        ctx.mark_non_differentiable(losses)
-        return losses[3].clone(), losses
+    def forward(ctx, launch, n, total, x):
+        x_c = x.contiguous().float()
+        values = torch.empty(n, dtype=torch.float32, device=x.device)
+        dx = torch.empty_like(x_c) if ctx.needs_input_grad[3] else None
+        launch(x_c, values, dx)
+        ctx.dx = dx
+        ctx.mark_non_differentiable(values)
+        return (values[total].clone() if n > 1 else values[total]), values
 
     @staticmethod
     @torch.autograd.function.once_differentiable
-    def backward(ctx, dtotal, _dlosses):
-        d = ctx.dpred
-        ctx.dpred = None
-        return None, (d * dtotal if d is not None else None), None, None, None
+    def backward(ctx, dtotal, _dvalues):
+        d = ctx.dx
+        ctx.dx = None
+        return None, None, None, (d * dtotal if d is not None else None)
 
 
 def pose_loss(pred: torch.Tensor, gt: torch.Tensor, lambda_scale: float = 0.5, lambda_velocity: float = 20.0, ops=None):
@@ -51,29 +63,9 @@ def pose_loss(pred: torch.Tensor, gt: torch.Tensor, lambda_scale: float = 0.5, l
     pred, gt [B,T,J,3]: `loss_mpjpe + lambda_scale * n_mpjpe + lambda_velocity * loss_velocity`
     (lib/model/loss.py:56-62,81-91,133-142 combined as train.py:176-189; defaults = configs/pose3d/MB_train_h36m.yaml:36-43).
     `total` is differentiable with respect to `pred`; its gradient was computed in the same kernel pass."""
-    if ops is None:
-        from . import hip_ops
-        ops = hip_ops.get()
-    return _PoseLossFn.apply(ops, pred, gt, float(lambda_scale), float(lambda_velocity))
-
-
-class _PoseLossFullFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, ops, pred, gt, lambdas6):
-        pred_c, gt_c = pred.contiguous().float(), gt.contiguous().float()
-        losses = torch.empty(8, dtype=torch.float32, device=pred.device)
-        dpred = torch.empty_like(pred_c) if ctx.needs_input_grad[1] else None
-        ops.pose_loss_full(pred_c, gt_c, lambdas6, losses, dpred)
-        ctx.dpred = dpred
-        ctx.mark_non_differentiable(losses)
-        return losses[7].clone(), losses
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dtotal, _dlosses):
-        d = ctx.dpred
-        ctx.dpred = None
-        return None, (d * dtotal if d is not None else None), None, None
+    ops = hip_ops.provider(ops, 'motionbert_amd.train.pose_loss', pred, gt)
+    gt_c, ls, lv = gt.detach().contiguous().float(), float(lambda_scale), float(lambda_velocity)
+    return _FusedLossFn.apply(lambda x, losses, dx: ops.pose_loss(x, gt_c, ls, lv, losses, dx), 4, 3, pred)
 
 
 def pose_loss_full(pred: torch.Tensor, gt: torch.Tensor, lambda_scale: float = 0.5, lambda_velocity: float = 20.0, lambda_lv: float = 0.,
@@ -84,39 +76,19 @@ def pose_loss_full(pred: torch.Tensor, gt: torch.Tensor, lambda_scale: float = 0
     (lib/model/loss.py:98-203 combined as train.py:185-191).  `total` is differentiable with respect to `pred`.  With the four new
     lambdas at 0 the total and the gradient are `pose_loss`'s bit for bit and the four extra values are still computed: the
     reference's log without a single `.item()`."""
-    if ops is None:
-        from . import hip_ops
-        ops = hip_ops.get()
+    ops = hip_ops.provider(ops, 'motionbert_amd.train.pose_loss_full', pred, gt)
+    gt_c = gt.detach().contiguous().float()
     lambdas6 = tuple(float(v) for v in (lambda_scale, lambda_velocity, lambda_lv, lambda_lg, lambda_a, lambda_av))
-    return _PoseLossFullFn.apply(ops, pred, gt, lambdas6)
-
-
-class _Loss2DFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, ops, pred, target, conf):
-        pred_c = pred.contiguous().float()
-        loss = torch.empty(1, dtype=torch.float32, device=pred.device)
-        dpred = torch.empty_like(pred_c) if ctx.needs_input_grad[1] else None
-        ops.loss_2d_weighted(pred_c, target, conf, loss, dpred)
-        ctx.dpred = dpred
-        return loss[0]
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dloss):
-        d = ctx.dpred
-        ctx.dpred = None
-        return None, (d * dloss if d is not None else None), None, None
+    return _FusedLossFn.apply(lambda x, losses, dx: ops.pose_loss_full(x, gt_c, lambdas6, losses, dx), 8, 7, pred)
 
 
 def loss_2d_weighted(pred: torch.Tensor, target: torch.Tensor, conf: torch.Tensor, ops=None) -> torch.Tensor:
     """`mean(|| (pred[..., :2] - target[..., :2]) * conf ||)` (lib/model/loss.py:72-77; the 2D branch of pre-training,
     train.py:200-203) with its gradient in the same kernel pass.  `target` [B,T,J,>=2] and `conf` [B,T,J,1] may be views of
     the 2D batch itself (`batch_gt`, `batch_input[..., 2:]`): no deep copy of the confidence (train.py:164)."""
-    if ops is None:
-        from . import hip_ops
-        ops = hip_ops.get()
-    return _Loss2DFn.apply(ops, pred, target.detach(), conf.detach())
+    ops = hip_ops.provider(ops, 'motionbert_amd.train.loss_2d_weighted', pred, target, conf)
+    target, conf = target.detach(), conf.detach()
+    return _FusedLossFn.apply(lambda x, loss, dx: ops.loss_2d_weighted(x, target, conf, loss, dx), 1, 0, pred)[0]
 
 
 class PretrainStep:
@@ -147,6 +119,12 @@ class PretrainStep:
         self.rootrel, self.mask, self.noise, self.no_conf = rootrel, mask, noise, no_conf
         self.ls, self.lv = float(lambda_scale), float(lambda_velocity)
 
+    log_width = 4
+
+    def loss_3d(self, pred, batch_gt):
+        """`(total, losses [log_width])` of a 3D batch: what `PretrainStepFull` overrides"""
+        return pose_loss(pred, batch_gt, self.ls, self.lv)
+
     def __call__(self, batch_input: torch.Tensor, batch_gt: torch.Tensor, has_3d: bool, has_gt: bool = True, seed=None) -> torch.Tensor:
         with torch.no_grad():
             conf = None
@@ -164,11 +142,11 @@ class PretrainStep:
         pred = self.net(batch_input)
         self.opt.zero_grad(set_to_none=True)
         if has_3d:
-            total, losses = pose_loss(pred, batch_gt, self.ls, self.lv)
+            total, losses = self.loss_3d(pred, batch_gt)
         else:
             total = loss_2d_weighted(pred, batch_gt, conf)
             z = total.detach() * 0
-            losses = torch.stack([z, z, z, total.detach()])
+            losses = torch.stack([z] * (self.log_width - 1) + [total.detach()])
         total.backward()
         self.opt.step()
         return losses
@@ -178,40 +156,17 @@ class PretrainStepFull(PretrainStep):
     """`PretrainStep` with all seven 3D losses of train.py:177-199: the same constructor, and nonzero `lambda_lv`, `lambda_lg`,
     `lambda_a`, `lambda_av` are accepted.  3D batches return the eight values of the reference's log,
     `losses` = [mpjpe, n_mpjpe, velocity, lv, lg, angle, angle_velocity, total] (`pose_loss_full`); 2D batches [0] * 7 + [2d_proj].
-    With the four lambdas at 0 the parameters move exactly as under `PretrainStep`."""
+    With the four lambdas at 0 the parameters move exactly as under `PretrainStep`.  Only `loss_3d` and `log_width` differ."""
     def __init__(self, net, optimizer, aug=None, rootrel: bool = True, mask: bool = True, noise: bool = True, no_conf: bool = False,
                  lambda_scale: float = 0.5, lambda_velocity: float = 20.0, lambda_lv=0.0, lambda_lg=0.0, lambda_a=0.0, lambda_av=0.0):
         super().__init__(net, optimizer, aug=aug, rootrel=rootrel, mask=mask, noise=noise, no_conf=no_conf, lambda_scale=lambda_scale,
                          lambda_velocity=lambda_velocity)
         self.lambdas4 = tuple(float(v) for v in (lambda_lv, lambda_lg, lambda_a, lambda_av))
 
-    def __call__(self, batch_input: torch.Tensor, batch_gt: torch.Tensor, has_3d: bool, has_gt: bool = True, seed=None) -> torch.Tensor:
-        # PretrainStep.__call__ with the eight-value loss in the 3D branch (PretrainStep itself stays as it is: its four-value
-        # `losses` is what its callers index)
-        with torch.no_grad():
-            conf = None
-            if self.no_conf:
-                batch_input = batch_input[..., :2]
-            if not has_3d:
-                conf = batch_input[..., 2:]
-            if self.rootrel:
-                batch_gt = batch_gt - batch_gt[:, :, 0:1, :]
-            else:
-                batch_gt = batch_gt.clone()
-                batch_gt[..., 2] = batch_gt[..., 2] - batch_gt[:, 0:1, 0:1, 2]
-            if self.mask or self.noise:
-                batch_input = self.aug.augment2D(batch_input, noise=(self.noise and has_gt), mask=self.mask, seed=seed)
-        pred = self.net(batch_input)
-        self.opt.zero_grad(set_to_none=True)
-        if has_3d:
-            total, losses = pose_loss_full(pred, batch_gt, self.ls, self.lv, *self.lambdas4)
-        else:
-            total = loss_2d_weighted(pred, batch_gt, conf)
-            z = total.detach() * 0
-            losses = torch.stack([z] * 7 + [total.detach()])
-        total.backward()
-        self.opt.step()
-        return losses
+    log_width = 8
+
+    def loss_3d(self, pred, batch_gt):
+        return pose_loss_full(pred, batch_gt, self.ls, self.lv, *self.lambdas4)
 
 
 def pretrain_epoch_plan(n_posetrack: int, n_instav: int, n_3d: int, epoch: int, train_2d: bool = True, curriculum: int = 30):
@@ -226,10 +181,34 @@ def pretrain_epoch_plan(n_posetrack: int, n_instav: int, n_3d: int, epoch: int, 
     return plan
 
 
-class ActionStep:
+class TwoGroupStep:
+    """The two AdamW groups of the fine-tuning trainers (train_action.py:143-149, train_action_1shot.py:156-161, train_mesh.py:316-321) --
+    `model.backbone` at `lr_backbone`, `model.head` at `lr_head` -- as two flat one-launch optimizers, `opt_backbone` and `opt_head`;
+    `decay()` is the per-epoch StepLR(gamma=lr_decay).  A step derives from it and keeps its own forward, loss and return value,
+    between `zero_grad()` (after the forward) and `step()` (backbone first)."""
+
+    def __init__(self, model, lr_backbone: float, lr_head: float, weight_decay: float):
+        self.model = model
+        self.opt_backbone = FlatAdamW(model.backbone, lr=lr_backbone, weight_decay=weight_decay)
+        self.opt_head = FlatAdamW([('head.' + n, p) for n, p in model.head.named_parameters() if p.requires_grad], lr=lr_head,
+                                  weight_decay=weight_decay)
+
+    def zero_grad(self):
+        self.opt_backbone.zero_grad(set_to_none=True)
+        self.opt_head.zero_grad(set_to_none=True)
+
+    def step(self):
+        self.opt_backbone.step()
+        self.opt_head.step()
+
+    def decay(self, gamma: float):
+        self.opt_backbone.lr = self.opt_backbone.lr * gamma
+        self.opt_head.lr = self.opt_head.lr * gamma
+
+
+class ActionStep(TwoGroupStep):
     """One optimizer step of train_action.py:172-188: scores = ActionNet(batch [N,M,T,17,3]), cross-entropy, backward, and the
-    two AdamW groups of train_action.py:143-149 -- backbone at `lr_backbone`, head at `lr_head`
-    (MB_ft_NTU60_xsub.yaml:7-9) -- as two flat one-launch optimizers; `decay()` is the per-epoch StepLR(gamma=lr_decay).
+    two AdamW groups of `TwoGroupStep` (MB_ft_NTU60_xsub.yaml:7-9).
     `distributed=True` (after init_process_group): the backbone is wrapped as `DistributedDSTformer(backbone, extra=model.head)`
     and attached, so that `model(batch)` itself all-reduces the backbone's gradient buckets while backward runs and the head's
     gradients by post-accumulate hooks (they come first in backward); BatchNorm statistics stay per rank as under the
@@ -237,29 +216,21 @@ class ActionStep:
 
     def __init__(self, model, lr_backbone: float = 1e-4, lr_head: float = 1e-3, weight_decay: float = 0.01, distributed: bool = False,
                  process_group=None, ops=None):
-        self.model, self.ddp = model, None
+        self.ddp = None
         if distributed:
             from .ddp import DistributedDSTformer
             self.ddp = DistributedDSTformer(model.backbone, process_group=process_group, extra=model.head, ops=ops).attach()
-        self.opt_backbone = FlatAdamW(model.backbone, lr=lr_backbone, weight_decay=weight_decay)
-        self.opt_head = FlatAdamW([('head.' + n, p) for n, p in model.head.named_parameters() if p.requires_grad], lr=lr_head,
-                                  weight_decay=weight_decay)
+        super().__init__(model, lr_backbone, lr_head, weight_decay)
 
     def __call__(self, batch_input: torch.Tensor, labels: torch.Tensor):
         out = self.model(batch_input)
-        self.opt_backbone.zero_grad(set_to_none=True)
-        self.opt_head.zero_grad(set_to_none=True)
+        self.zero_grad()
         loss = torch.nn.functional.cross_entropy(out, labels)
         loss.backward()
         if self.ddp is not None:
             self.ddp.wait()                      # (the backbone's backward already waited; covers a frozen backbone)
-        self.opt_backbone.step()
-        self.opt_head.step()
+        self.step()
         return loss.detach(), out.detach()
-
-    def decay(self, gamma: float):
-        self.opt_backbone.lr = self.opt_backbone.lr * gamma
-        self.opt_head.lr = self.opt_head.lr * gamma
 
 
 def flat_layout(names, shapes, depth):
@@ -391,10 +362,7 @@ class FlatAdamW(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        ops = self._ops
-        if ops is None:
-            from . import hip_ops
-            ops = hip_ops.get()
+        ops = hip_ops.provider(self._ops, 'motionbert_amd.train.FlatAdamW.step', self.flat)
         grp = self.param_groups[0]
         if grp['lr'] != self._lr:              # someone (an LR scheduler) wrote param_groups directly
             self.lr = grp['lr']
@@ -499,9 +467,13 @@ class GraphedTrainStep:
         with torch.no_grad():
             optimizer.flat.copy_(keep[0]); optimizer.exp_avg.copy_(keep[1]); optimizer.exp_avg_sq.copy_(keep[2]); optimizer.state_t.copy_(keep[3])
 
+    def _loss(self, pred):
+        """`(total, losses)` of the captured batch: what `GraphedTrainStepFull` overrides"""
+        return pose_loss(pred, self.gt, self.ls, self.lv)
+
     def _one(self):
         self.opt.zero_grad(set_to_none=True)
-        total, losses = pose_loss(self.model(self.x), self.gt, self.ls, self.lv)
+        total, losses = self._loss(self.model(self.x))
         total.backward()
         self.opt.step()
         return losses
@@ -524,12 +496,8 @@ class GraphedTrainStepFull(GraphedTrainStep):
     def __init__(self, model, optimizer: FlatAdamW, x: torch.Tensor, gt: torch.Tensor, lambda_scale: float = 0.5,
                  lambda_velocity: float = 20.0, lambda_lv: float = 0., lambda_lg: float = 0., lambda_a: float = 0., lambda_av: float = 0.,
                  warmup: int = 2):
-        self.lambdas4 = tuple(float(v) for v in (lambda_lv, lambda_lg, lambda_a, lambda_av))      # (read by _one during the capture)
+        self.lambdas4 = tuple(float(v) for v in (lambda_lv, lambda_lg, lambda_a, lambda_av))      # (read by _loss during the capture)
         super().__init__(model, optimizer, x, gt, lambda_scale=lambda_scale, lambda_velocity=lambda_velocity, warmup=warmup)
 
-    def _one(self):
-        self.opt.zero_grad(set_to_none=True)
-        total, losses = pose_loss_full(self.model(self.x), self.gt, self.ls, self.lv, *self.lambdas4)
-        total.backward()
-        self.opt.step()
-        return losses
+    def _loss(self, pred):
+        return pose_loss_full(pred, self.gt, self.ls, self.lv, *self.lambdas4)

@@ -345,3 +345,28 @@ def test_action_step_two_lr_groups_match_torch_adamw():
         assert float((p - q).abs().max()) <= 2 * lr * 3, n
         if p.ndim >= 2 and 'ts_attn' not in n:
             assert float((p - q).norm() / q.norm()) < 1e-4, (n, float((p - q).norm() / q.norm()))
+
+
+def test_pretrain_steps_2d_branch_same_log_value_and_bit_equal_parameters():
+    """The 2D branch (`has_3d=False`; once with `has_gt=False`: no noise) of `PretrainStep` and of `PretrainStepFull` with the four extra
+    lambdas at 0, B = 2, T = 9, J = 17: the logs are [0] * 3 + [v] and [0] * 7 + [v] with the same v, and the parameters after the steps
+    are bit-equal between the two classes."""
+    from motionbert_amd.train import FlatAdamW, PretrainStep, PretrainStepFull
+    aug = _aug_from_fixture()
+    nets, steps = [], []
+    for cls in (PretrainStep, PretrainStepFull):
+        m = build_model(dict(LITE, depth=1), seed=4).to(DEV)
+        nets.append(m)
+        steps.append(cls(m, FlatAdamW(m, lr=5e-4, weight_decay=0.01), aug=aug, rootrel=True, mask=True, noise=True))
+    assert isinstance(steps[1], PretrainStep) and steps[1].lambdas4 == (0.0,) * 4
+    for k, has_gt in enumerate((True, False)):
+        x = make_input(2, 9, 17, 80 + k).to(DEV)
+        l4, l8 = (s(x, x, has_3d=False, has_gt=has_gt, seed=500 + k) for s in steps)
+        assert l4.shape == (4,) and l8.shape == (8,)
+        v = l4[3]
+        assert float(v) > 0 and torch.isfinite(v)
+        assert torch.equal(l4, torch.cat([torch.zeros(3, device=DEV), v[None]])), (k, l4)
+        assert torch.equal(l8, torch.cat([torch.zeros(7, device=DEV), v[None]])), (k, l8)
+    for (n, p), q in zip(nets[0].named_parameters(), nets[1].parameters()):
+        assert torch.equal(p, q), n
+    assert float(steps[0].opt.state_t[0]) == 2.0 and float(steps[1].opt.state_t[0]) == 2.0
