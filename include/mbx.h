@@ -507,6 +507,31 @@ int mbx_smpl_bwd(const float* v_template, const float* shapedirs, const float* p
                  const float* rotmat, float scale, const float* dverts, const float* dkp, const float* djoints, float* drotmat,
                  float* dbetas, int F, int V, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- action recognition around the backbone (csrc/action.hip; lib/data/dataset_action.py:76-112,173-182, lib/utils/utils_data.py:7-29, ------
+ *      train_action.py:55-61,172-188, lib/utils/learning.py:25-37) -- mbx_version() >= 130
+ * mbx_action_input: NTURGBD.__getitem__ for a batch x [N,M,T,J,3] (x, y, confidence; f32) -> y of the same shape, one launch, one
+ * workgroup per sample.  Nine draws per sample, params [N,9] = A0 A1 (degrees) S0 S1 Tx0 Tx1 Ty0 Ty1 ratio: params_in as they are, or
+ * (params_in NULL) min(fma(hi - lo, u(stream k, index n), lo), hi) of the range of draw k with the counter-based hash of mbx_augment2d; params_out
+ * (may be NULL) receives them.  With f_t = t / (T - 1) (0 for T = 1), a_t = (A0 + (A1 - A0) f_t) pi / 180, s_t, tx_t, ty_t likewise:
+ *     x' = cos(a_t) s_t x - sin(a_t) s_t y + tx_t,  y' = sin(a_t) s_t x + cos(a_t) s_t y + ty_t     for EVERY joint of every person
+ * (an all-zero second person lands on (tx_t, ty_t), as in the reference).  Over the joints with confidence != 0: fewer than 4 -> the sample
+ * is 0; scale = max(xmax - xmin, ymax - ymin) ratio, scale == 0 -> the sample is 0; xs = (xmin + xmax - scale) / 2, ys likewise;
+ * x'' = ((x' - xs) / scale - 0.5) 2, y'' likewise; all three channels clipped to [-1, 1].
+ * flags: bit 0 the move (off: x' = x), bit 1 the crop (off: x', y' and the confidence are written as they are).
+ * N, M, T, J >= 1, J <= 32; every range lo <= hi (checked).  y may be x. */
+int mbx_action_input(const float* x, float* y, int N, int M, int T, int J, const float* params_in, float* params_out, float angle_lo,
+                     float angle_hi, float scale_lo, float scale_hi, float trans_lo, float trans_hi, float crop_lo, float crop_hi,
+                     int flags, uint64_t seed, void* stream);
+/* mbx_xent_topk: CrossEntropyLoss() (mean) of logits [N,C] f32 with labels [N] i32, its gradient and the top-1 / top-5 hits in one launch.
+ * Row loss = log sum_j exp(z_j - max z) - (z_y - max z); rank = #{j : z_j > z_y} + #{j < y : z_j == z_y}, a top-k hit iff rank < k.
+ *   values [3] f32 = mean loss, top-1 hits, top-5 hits;  dlogits [N,C] (may be NULL) = (softmax - onehot) grad_scale / N;
+ *   acc [4] f64 (may be NULL) += sum of row losses, top-1 hits, top-5 hits, N.
+ * One workgroup, fixed summation order (row losses are added in fp64): two calls on the same input return the same bits.  A label outside
+ * [0, C) gives NaN in its row's loss (hence the mean) and gradient, counts no hit and is never used as an index.
+ * 1 <= N <= 65536, 1 <= C <= 4096 (checked). */
+int mbx_xent_topk(const float* logits, const int* labels, int N, int C, float grad_scale, float* values, float* dlogits, double* acc,
+                  void* stream);
+
 /* ---- measurement aid (bench.py `roofline.sustained_mfma_tflops`; not part of the model) --------------------------------------------
  * The bf16 MFMA rate the part sustains under its power cap with nothing but v_mfma_f32_32x32x16_bf16 in the loop (pseudo-random
  * operands; n_wg workgroups of 4 waves, `iters` x 16 MFMAs per wave).  ws: >= mbx_mfma_probe_ws(n_wg) bytes = a float sink

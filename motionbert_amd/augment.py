@@ -12,6 +12,7 @@ the flip-back + average is one pass over the output: no deep copies of the input
 from __future__ import annotations
 
 import pickle
+from contextlib import nullcontext as _nullcontext
 from typing import Optional
 
 import torch
@@ -67,6 +68,45 @@ class Augmenter2D:
                                     (d['a'], d['b'], d['m'], d['s']), self.mask_ratio, self.mask_T_ratio,
                                     (1 if noise else 0) | (2 if mask else 0), seed)
         return y if (noise or motion_2d.shape[-1] == 3) else y[..., :2]
+
+
+#: random_move's defaults (lib/data/dataset_action.py:76-80): rotation in degrees, scale, translation
+MOVE_RANGES = ((-10.0, 10.0), (0.9, 1.1), (-0.1, 0.1))
+
+
+def action_input(x: torch.Tensor, random_move: bool = True, scale_range=(1, 1), seed: Optional[int] = None, params: Optional[torch.Tensor] = None,
+                 return_params: bool = False, ops=None, angle_range=MOVE_RANGES[0], move_scale_range=MOVE_RANGES[1],
+                 transform_range=MOVE_RANGES[2]):
+    """`NTURGBD.__getitem__` (lib/data/dataset_action.py:173-182) for a batch x [N,M,T,J,3] (x, y, confidence) in ONE launch of
+    `mbx_action_input`: `random_move` (:76-112, every joint of every person rotated, scaled and shifted by a transform that is
+    interpolated over the clip) followed by `crop_scale(scale_range)` (lib/utils/utils_data.py:7-29: the box of the joints with
+    confidence != 0 to [-1, 1], everything clipped; `scale_range=None` skips it, as a config's `scale_range: None` does).  Returns a NEW tensor.
+
+    Each sample uses nine draws, [A0, A1, S0, S1, Tx0, Tx1, Ty0, Ty1, ratio]: the rows of `params` [N,9] if given, otherwise counter-based
+    random numbers from `seed` (default: 62 bits from torch's CPU generator).  `return_params=True`: `(y, params_used [N,9])`."""
+    from . import hip_ops
+    if x.dim() != 5 or x.shape[-1] != 3:
+        raise ValueError(f'expected [N,M,T,J,3] keypoints with confidence, got {tuple(x.shape)}')
+    ops = hip_ops.provider(ops, 'motionbert_amd.augment.action_input', x, params, move='the batch')
+    xc = x.contiguous().float()
+    N = xc.shape[0]
+    if params is not None:
+        if tuple(params.shape) != (N, 9):
+            raise ValueError(f'params must be [{N}, 9], got {tuple(params.shape)}')
+        params = params.detach().to(device=xc.device, dtype=torch.float32).contiguous()
+    elif seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    crop = scale_range is not None and scale_range is not False
+    ranges = (tuple(angle_range), tuple(move_scale_range), tuple(transform_range), tuple(scale_range) if crop else (1.0, 1.0))
+    for lo, hi in ranges:
+        if not lo <= hi:
+            raise ValueError(f'range ({lo}, {hi}) has lo > hi')
+    y = torch.empty_like(xc)
+    used = torch.empty(N, 9, dtype=torch.float32, device=xc.device) if return_params else None
+    if N:
+        with (torch.cuda.device(xc.device) if xc.is_cuda else _nullcontext()):
+            ops.action_input(xc, y, params, used, ranges, (1 if random_move else 0) | (2 if crop else 0), 0 if seed is None else int(seed))
+    return (y, used) if return_params else y
 
 
 def flip_tta(model, x: torch.Tensor) -> torch.Tensor:

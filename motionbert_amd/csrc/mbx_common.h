@@ -126,6 +126,10 @@ struct WaveMax {
     static __device__ __forceinline__ float op(float a, float b) { return fmaxf(a, b); }
     static __device__ __forceinline__ float identity(float v) { return v; }
 };
+struct WaveMin {
+    static __device__ __forceinline__ float op(float a, float b) { return fminf(a, b); }
+    static __device__ __forceinline__ float identity(float v) { return v; }
+};
 template <typename Op> __device__ __forceinline__ float wave_reduce(float v) {
     v = Op::op(v, dpp_mov<0xB1>(v, v));    // quad_perm [1,0,3,2]
     v = Op::op(v, dpp_mov<0x4E>(v, v));    // quad_perm [2,3,0,1]
@@ -151,6 +155,7 @@ __device__ __forceinline__ float wave_lower_half(float v) {
 }
 __device__ __forceinline__ float wave_sum(float v) { return wave_reduce<WaveAdd>(v); }
 __device__ __forceinline__ float wave_max(float v) { return wave_reduce<WaveMax>(v); }
+__device__ __forceinline__ float wave_min(float v) { return wave_reduce<WaveMin>(v); }
 
 // ---------------------------------------------------------------- counter-based dropout masks (restated in motionbert_amd/dropmask.py)
 // element index = 64 bit, passed as its two halves (the 4 elements a thread owns differ only in the low two bits)

@@ -95,6 +95,85 @@ def shard_indices(n: int, shuffle: bool, epoch: int, seed: int, rank: int, world
     return np.resize(order, per * world)[rank::world]
 
 
+def pinned_batches(arrays, chunks, batch_size: int, device, ring: int = 3):
+    """The asynchronous batch stream under `PackedMotion3D.batches` and `PackedAction.batches`: for every index array of `chunks` a tuple
+    with one DEVICE tensor per array of `arrays` (numpy arrays or memory maps with the same first dimension; any dtype), holding the
+    chunk's rows in ascending index order.  ONE background thread gathers the rows (`np.take`) into a ring of pinned slots, the copy to
+    the device runs on a side stream while the previous batch is in use, and the loader thread and the slots are released when the
+    generator is closed, exhausted or abandoned.  On a host `device` the tensors are clones of the slots."""
+    device = torch.device(device)
+    cuda = device.type == 'cuda'
+    ring = max(2, int(ring))
+    slots = [tuple(torch.empty((batch_size,) + tuple(a.shape[1:]), dtype=torch.from_numpy(np.empty(0, dtype=a.dtype)).dtype, pin_memory=cuda)
+                   for a in arrays) for _ in range(ring)]
+    free, ready = queue.Queue(), queue.Queue(maxsize=ring)
+    for s in range(ring):
+        free.put(s)
+
+    stop = threading.Event()
+
+    def producer():                                   # ONE host thread: row gather from the page cache into pinned memory
+        try:
+            for ch in chunks:
+                s = free.get()
+                if s is None or stop.is_set():        # the consumer went away (break / exception): see the finally below
+                    return
+                srt = np.sort(ch)                     # ascending file offsets; the batch is a set, order inside it is irrelevant
+                for a, slot in zip(arrays, slots[s]):
+                    np.take(a, srt, axis=0, out=slot.numpy()[:len(ch)])
+                ready.put((s, len(ch)))
+            ready.put(None)
+        except Exception as e:                        # surface loader errors in the consumer
+            ready.put(e)
+    th = threading.Thread(target=producer, daemon=True)
+    th.start()
+    copy_stream = torch.cuda.Stream(device) if cuda else None
+    pending = None                                    # (slot, device tensors, event) of the batch in flight
+    try:
+        while True:
+            item = ready.get()
+            if isinstance(item, Exception):
+                raise item
+            nxt = None
+            if item is not None:
+                s, nb = item
+                if cuda:
+                    with torch.cuda.stream(copy_stream):
+                        dev = tuple(t[:nb].to(device, non_blocking=True) for t in slots[s])
+                        ev = torch.cuda.Event()
+                        ev.record(copy_stream)
+                else:
+                    dev, ev = tuple(t[:nb].clone() for t in slots[s]), None
+                nxt = (s, dev, ev)
+            if pending is not None:
+                s0, dev0, ev0 = pending
+                if ev0 is not None:
+                    torch.cuda.current_stream(device).wait_event(ev0)      # the copy finished before compute touches it ...
+                    ev0.synchronize()                                       # ... and before the host refills the pinned slot
+                    for t in dev0:
+                        t.record_stream(torch.cuda.current_stream(device))
+                free.put(s0)
+                pending = nxt
+                yield dev0
+            else:
+                pending = nxt
+            if item is None:
+                break
+    finally:
+        # also reached when the consumer abandons the generator (break, exception in the training loop, GeneratorExit):
+        # release the loader thread -- it may sit in free.get() or in ready.put() on a full queue -- and the pinned slots
+        stop.set()
+        free.put(None)
+        while th.is_alive():
+            try:
+                ready.get(timeout=0.05)
+            except queue.Empty:
+                pass
+        th.join()
+        if pending is not None and pending[2] is not None:
+            pending[2].synchronize()                   # an H2D copy still reading a pinned slot must finish before it is freed
+
+
 class PackedMotion3D:
     """Memory-mapped packed clips + an asynchronous batch stream.
 
@@ -152,83 +231,161 @@ class PackedMotion3D:
             chunks.pop()
         if not chunks:
             return
-        cuda = self.device.type == 'cuda'
-        shape = (batch_size,) + tuple(self.meta['clip_shape'])
         need_inp = self.input is not None and not (self.synthetic or self.gt_2d)     # otherwise the input is derived from the label
-        slots = [tuple(torch.empty(shape, dtype=torch.float32, pin_memory=cuda) for _ in range(2 if need_inp else 1)) for _ in range(self.ring)]
-        free, ready = queue.Queue(), queue.Queue(maxsize=self.ring)
-        for s in range(self.ring):
-            free.put(s)
-
-        stop = threading.Event()
-
-        def producer():                                   # ONE host thread: row gather from the page cache into pinned memory
-            try:
-                for ch in chunks:
-                    s = free.get()
-                    if s is None or stop.is_set():        # the consumer went away (break / exception): see the finally below
-                        return
-                    srt = np.sort(ch)                     # ascending file offsets; the batch is a set, order inside it is irrelevant
-                    np.take(self.label, srt, axis=0, out=slots[s][0].numpy()[:len(ch)])
-                    if need_inp:
-                        np.take(self.input, srt, axis=0, out=slots[s][1].numpy()[:len(ch)])
-                    ready.put((s, len(ch)))
-                ready.put(None)
-            except Exception as e:                        # surface loader errors in the consumer
-                ready.put(e)
-        th = threading.Thread(target=producer, daemon=True)
-        th.start()
         gen = torch.Generator(device=self.device)
         gen.manual_seed((seed * 1000003 + epoch) * 8191 + rank)
-        copy_stream = torch.cuda.Stream(self.device) if cuda else None
-        pending = None                                    # (slot, lab_dev, inp_dev, event) of the batch in flight
+        stream = pinned_batches([self.label, self.input] if need_inp else [self.label], chunks, batch_size, self.device, self.ring)
         try:
-            while True:
-                item = ready.get()
-                if isinstance(item, Exception):
-                    raise item
-                nxt = None
-                if item is not None:
-                    s, nb = item
-                    if cuda:
-                        with torch.cuda.stream(copy_stream):
-                            lab = slots[s][0][:nb].to(self.device, non_blocking=True)
-                            inp = slots[s][1][:nb].to(self.device, non_blocking=True) if need_inp else None
-                            ev = torch.cuda.Event()
-                            ev.record(copy_stream)
-                    else:
-                        lab = slots[s][0][:nb].clone()
-                        inp = slots[s][1][:nb].clone() if need_inp else None
-                        ev = None
-                    nxt = (s, lab, inp, ev)
-                if pending is not None:
-                    s0, lab0, inp0, ev0 = pending
-                    if ev0 is not None:
-                        torch.cuda.current_stream(self.device).wait_event(ev0)      # the copy finished before compute touches it ...
-                        ev0.synchronize()                                             # ... and before the host refills the pinned slot
-                        lab0.record_stream(torch.cuda.current_stream(self.device))
-                        if inp0 is not None:
-                            inp0.record_stream(torch.cuda.current_stream(self.device))
-                    free.put(s0)
-                    pending = nxt
-                    yield self._device_stage(inp0, lab0, gen)
-                else:
-                    pending = nxt
-                if item is None:
-                    break
+            for got in stream:
+                yield self._device_stage(got[1] if need_inp else None, got[0], gen)
         finally:
-            # also reached when the consumer abandons the generator (break, exception in the training loop, GeneratorExit):
-            # release the loader thread -- it may sit in free.get() or in ready.put() on a full queue -- and the pinned slots
-            stop.set()
-            free.put(None)
-            while th.is_alive():
-                try:
-                    ready.get(timeout=0.05)
-                except queue.Empty:
-                    pass
-            th.join()
-            if pending is not None and pending[3] is not None:
-                pending[3].synchronize()                   # an H2D copy still reading a pinned slot must finish before it is freed
+            stream.close()                                # the consumer went away: release the loader thread and the pinned slots now
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# action recognition (lib/data/dataset_action.py): the NTU annotation file, packed once
+# ---------------------------------------------------------------------------------------------------------------
+#: coco2h36m (dataset_action.py:31-74): H36M joint <- one COCO joint, or the mean of two; joint 7 (belly) is the mean of H36M 0 and 8
+_COCO_SINGLE = {1: 12, 2: 14, 3: 16, 4: 11, 5: 13, 6: 15, 9: 0, 11: 5, 12: 7, 13: 9, 14: 6, 15: 8, 16: 10}
+_COCO_PAIR = {0: (11, 12), 8: (5, 6), 10: (1, 2)}
+
+
+def _ntu_camera(x, img_shape):
+    """make_cam (dataset_action.py:19-29): pixels -> [-1, 1] along the longer image side"""
+    h, w = img_shape
+    return x / (w if w >= h else h) * 2 - 1
+
+
+def _ntu_track(x):
+    """human_tracking (dataset_action.py:114-128): the two detections of a frame swap names whenever person 0 of the previous frame is
+    nearer to person 1 of this one (summed joint distances); x [M,T,V,C]"""
+    if x.shape[0] == 1:
+        return x
+    keep = np.sum(np.linalg.norm(x[0, 1:] - x[0, :-1], axis=-1), axis=-1)
+    swap = np.sum(np.linalg.norm(x[0, 1:] - x[1, :-1], axis=-1), axis=-1)
+    sel = (np.cumsum(keep > swap) % 2)[:, None, None]
+    out = np.zeros(x.shape)
+    out[:, 0] = x[:, 0]
+    out[0, 1:] = x[1, 1:] * sel + x[0, 1:] * (1 - sel)
+    out[1, 1:] = x[0, 1:] * sel + x[1, 1:] * (1 - sel)
+    return out
+
+
+def _ntu_to_h36m(x):
+    """coco2h36m (dataset_action.py:31-74) for x [M,T,17,C]"""
+    y = np.zeros(x.shape)
+    for j, c in _COCO_SINGLE.items():
+        y[:, :, j] = x[:, :, c]
+    for j, (a, b) in _COCO_PAIR.items():
+        y[:, :, j] = (x[:, :, a] + x[:, :, b]) * 0.5
+    y[:, :, 7] = (y[:, :, 0] + y[:, :, 8]) * 0.5
+    return y
+
+
+def _ntu_frames(ori_len: int, target_len: int, rng) -> np.ndarray:
+    """resample (utils_data.py:68-89, replay=False): `target_len` frame indices spread over the clip; with `rng` (a training split) each
+    one is jittered inside its interval -- or, for a clip shorter than the target, rounded down or up at random."""
+    if rng is None:
+        return np.linspace(0, ori_len, num=target_len, endpoint=False, dtype=int)
+    even = np.linspace(0, ori_len, num=target_len, endpoint=False)
+    if ori_len < target_len:
+        sel = rng.randint(2, size=even.shape)
+        ids = np.sort(sel * np.floor(even) + (1 - sel) * np.ceil(even))
+    else:
+        ids = rng.random_sample(even.shape) * (even[1] - even[0]) + even
+    return np.clip(ids, a_min=0, a_max=ori_len - 1).astype(np.uint32)
+
+
+def pack_action(pkl_path: str, data_split: str, n_frames: int, out_prefix: str, check_split: bool = True) -> dict:
+    """The one-off host work of `ActionDataset.__init__` (dataset_action.py:130-160) for the annotation pickle of NTU RGB+D
+    ({'split': {name: [frame_dir]}, 'annotations': [{'frame_dir', 'label', 'total_frames', 'img_shape', 'keypoint' [M,T0,17,2],
+    'keypoint_score' [M,T0,17]}]}): camera normalisation, tracking, COCO -> H36M joints, resampling to `n_frames`, and an all-zero second
+    person for single-person samples.  Writes `<prefix>.motion.npy` [N,2,n_frames,17,3] float32, `<prefix>.label.npy` [N] int64 and
+    `<prefix>.json`; returns the metadata.
+
+    A split whose name contains 'train' (or any, with check_split=False), and not 'oneshot', is resampled with random numbers: they
+    come from `np.random.RandomState(0)` in sample order, which is what the reference's `np.random.seed(0)` amounts to, so the array
+    equals the reference's `dataset.motions` bit for bit."""
+    with open(pkl_path, 'rb') as f:
+        dataset = pickle.load(f)
+    members = None
+    if check_split:
+        if data_split not in dataset['split']:
+            raise ValueError(f'{pkl_path} has no split {data_split!r} (it has {sorted(dataset["split"])})')
+        members = set(dataset['split'][data_split])
+    is_train = ('train' in data_split or not check_split) and 'oneshot' not in data_split
+    rng = np.random.RandomState(0) if is_train else None
+    motions, labels = [], []
+    for sample in dataset['annotations']:
+        if members is not None and sample['frame_dir'] not in members:
+            continue
+        ids = _ntu_frames(sample['total_frames'], n_frames, rng)
+        cam = _ntu_to_h36m(_ntu_track(_ntu_camera(sample['keypoint'], sample['img_shape'])))
+        motion = np.concatenate((cam[:, ids], sample['keypoint_score'][..., None][:, ids]), axis=-1)
+        if motion.shape[0] == 1:
+            motion = np.concatenate((motion, np.zeros(motion.shape)), axis=0)
+        if motion.shape[0] != 2:
+            raise ValueError(f'{sample["frame_dir"]}: {motion.shape[0]} persons (the reference stacks samples of exactly two)')
+        motions.append(motion.astype(np.float32))
+        labels.append(int(sample['label']))
+    if not motions:
+        raise ValueError(f'{pkl_path}: split {data_split!r} is empty')
+    np.save(out_prefix + '.motion.npy', np.stack(motions))
+    np.save(out_prefix + '.label.npy', np.asarray(labels, dtype=np.int64))
+    meta = dict(n=len(motions), clip_shape=[2, int(n_frames), 17, 3], split=data_split, train=bool(is_train))
+    with open(out_prefix + '.json', 'w') as f:
+        json.dump(meta, f)
+    return meta
+
+
+class PackedAction:
+    """The packed NTU clips of `pack_action` + the asynchronous batch stream of `pinned_batches` + `NTURGBD.__getitem__` on the device.
+
+        ds = PackedAction(prefix, device='cuda', train=True, random_move=True, scale_range=(1, 1))
+        for batch, labels in ds.batches(32, shuffle=True, epoch=e, rank=r, world=w):    # [B,2,T,17,3] f32, [B] int64, on the device
+            ...
+    Every batch has been through `augment.action_input` (`mbx_action_input`: random_move + crop_scale in one launch) with a seed derived
+    from (seed, epoch, rank, batch index): an epoch is reproducible, and no two batches of a run share their draws.  `random_move` and
+    `scale_range` are the reference's arguments (dataset_action.py:170-182; `scale_range=None` skips crop_scale); `train=False` is the
+    validation loader of train_action.py:133 (`random_move=False`).  `ops`: kernel provider for host tensors (tests)."""
+
+    def __init__(self, prefix: str, device='cuda', train: bool = True, random_move: bool = True, scale_range: Optional[Tuple[float, float]] = (1, 1),
+                 ring: int = 3, ops=None):
+        with open(prefix + '.json') as f:
+            self.meta = json.load(f)
+        self.motion = np.load(prefix + '.motion.npy', mmap_mode='r')
+        self.label = np.load(prefix + '.label.npy')
+        if len(self.motion) != len(self.label):
+            raise ValueError(f'{prefix}: {len(self.motion)} clips but {len(self.label)} labels')
+        self.device = torch.device(device)
+        self.train, self.random_move, self.scale_range = bool(train), bool(random_move) and bool(train), scale_range
+        self.ring, self.ops = max(2, int(ring)), ops
+
+    def __len__(self):
+        return len(self.label)
+
+    @staticmethod
+    def batch_seed(seed: int, epoch: int, rank: int, batch: int) -> int:
+        return (((seed * 1000003 + epoch) * 8191 + rank) * 65537 + batch) % (1 << 63)
+
+    def batches(self, batch_size: int, shuffle: bool = True, epoch: int = 0, seed: int = 0, rank: int = 0, world: int = 1,
+                drop_last: bool = False) -> Iterator[Tuple[torch.Tensor, torch.Tensor]]:
+        from .augment import action_input
+        idx = shard_indices(len(self), shuffle, epoch, seed, rank, world)
+        chunks = [idx[i:i + batch_size] for i in range(0, len(idx), batch_size)]
+        if drop_last and chunks and len(chunks[-1]) < batch_size:
+            chunks.pop()
+        if not chunks:
+            return
+        stream = pinned_batches([self.motion, self.label], chunks, batch_size, self.device, self.ring)
+        try:
+            for k, (motion, labels) in enumerate(stream):
+                if self.random_move or self.scale_range:
+                    motion = action_input(motion, random_move=self.random_move, scale_range=self.scale_range,
+                                          seed=self.batch_seed(seed, epoch, rank, k), ops=self.ops)
+                yield motion, labels
+        finally:
+            stream.close()
 
 
 def m_per_class_batches(labels, m: int, batch_size: int, length: Optional[int] = None, seed: int = 0):

@@ -112,6 +112,8 @@ SIGNATURES = {
     'mbx_smpl_bwd_ws': (_sz, [_i, _i, _i]),
     'mbx_smpl_fwd': (_i, [_vp] * 5 + [C.POINTER(C.c_int)] + [_vp, _vp, _i, _vp, _vp, _f, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
     'mbx_smpl_bwd': (_i, [_vp] * 6 + [C.POINTER(C.c_int)] + [_vp, _vp, _i, _vp, _vp, _f] + [_vp] * 5 + [_i, _i, _vp, _sz, _vp]),
+    'mbx_action_input': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp] + [_f] * 8 + [_i, C.c_uint64, _vp]),
+    'mbx_xent_topk': (_i, [_vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp]),
     'mbx_rows_n_pack_bytes': (_sz, [_i, _i]),
     'mbx_rows_lnbwd_t': (_i, [_vp] * 6 + [_i, _i, _i, _vp]),
     'mbx_rows_n_pack_many': (_i, [_i64p, _i, _i, _i, _vp]),
@@ -693,6 +695,32 @@ class HipOps:
             raise RuntimeError('libmbx: nn_cosine: test labels without a hit counter')
         self._ck(self.lib.mbx_nn_cosine(_p(anchors), _p(anchor_labels), M, _p(test), _p(test_labels), N, D, _p(pred_label), _p(best_sim),
                                         _p(hits), self._stream()))
+
+    # ------------------------------------------------------------------ action recognition (train_action.py, lib/data/dataset_action.py)
+    def action_input(self, x, y, params_in, params_out, ranges, flags, seed):
+        """x, y [N,M,T,J,3] f32; params_in / params_out [N,9] f32 or None; ranges = ((angle lo, hi), (scale ..), (translation ..), (crop ..));
+        flags bit 0 move, bit 1 crop; all contiguous, on the device of x."""
+        if x.dim() != 5 or x.shape[-1] != 3:
+            raise RuntimeError(f'libmbx: action_input needs x [N,M,T,J,3], got {tuple(x.shape)}')
+        N, M, T, J, _ = x.shape
+        self._dense('action_input', torch.float32, x.numel(), x.device, x=x, y=y)
+        self._dense('action_input', torch.float32, N * 9, x.device, params_in=params_in, params_out=params_out)
+        (a0, a1), (s0, s1), (t0, t1), (c0, c1) = ranges
+        self._ck(self.lib.mbx_action_input(_p(x), _p(y), N, M, T, J, _p(params_in), _p(params_out), float(a0), float(a1), float(s0), float(s1),
+                                           float(t0), float(t1), float(c0), float(c1), int(flags), int(seed), self._stream()))
+
+    def xent_topk(self, logits, labels, values, dlogits, acc, grad_scale=1.0):
+        """logits [N,C] f32, labels [N] i32, values [3] f32, dlogits like logits or None, acc [4] f64 (accumulated) or None; all contiguous, on
+        the device of logits."""
+        if logits.dim() != 2:
+            raise RuntimeError(f'libmbx: xent_topk needs logits [N,C], got {tuple(logits.shape)}')
+        N, Cc = logits.shape
+        dev = logits.device
+        self._dense('xent_topk', torch.float32, N * Cc, dev, logits=logits, dlogits=dlogits)
+        self._dense('xent_topk', torch.float32, 3, dev, values=values)
+        self._dense('xent_topk', torch.int32, N, dev, labels=labels)
+        self._dense('xent_topk', torch.float64, 4, dev, acc=acc)
+        self._ck(self.lib.mbx_xent_topk(_p(logits), _p(labels), N, Cc, float(grad_scale), _p(values), _p(dlogits), _p(acc), self._stream()))
 
     # ------------------------------------------------------------------ mesh recovery (train_mesh.py, lib/model/model_mesh.py, loss_mesh.py)
     def rot6d_theta_fwd(self, x6, rotmat, aa):

@@ -10,7 +10,7 @@ backbone itself runs in tens of milliseconds those pieces show, so they are part
                              loss_angle_velocity -- their weighted total and its gradient (`mbx_pose_loss_full`); the eight values the
                              reference logs stay on the device.  `PretrainStepFull` / `GraphedTrainStepFull` are the steps built on it:
                              `PretrainStep` / `GraphedTrainStep` with the loss call and the width of the log overridden.
-  _FusedLossFn               the one autograd function under these losses, `loss_2d_weighted` and `oneshot.supcon_loss`: values and
+  _FusedLossFn               the one autograd function under these losses, `loss_2d_weighted`, `oneshot.supcon_loss` and `action.cross_entropy_topk`: values and
                              gradient from one launch, backward scales the stored gradient.
   TwoGroupStep               backbone at one learning rate, head at another, as two `FlatAdamW`: the base of `ActionStep`,
                              `oneshot.OneShotStep` and `mesh.MeshStep`.
@@ -212,11 +212,16 @@ class ActionStep(TwoGroupStep):
     `distributed=True` (after init_process_group): the backbone is wrapped as `DistributedDSTformer(backbone, extra=model.head)`
     and attached, so that `model(batch)` itself all-reduces the backbone's gradient buckets while backward runs and the head's
     gradients by post-accumulate hooks (they come first in backward); BatchNorm statistics stay per rank as under the
-    reference's nn.DataParallel."""
+    reference's nn.DataParallel.
+    `fused_loss=True`: loss, gradient and the top-1 / top-5 hits of train_action.py:180-184 come from one launch
+    (`action.cross_entropy_topk`) and are added to a device-side fp64 meter [sum of row losses, top-1 hits, top-5 hits, rows]; `meters()` is
+    the one host synchronisation and returns `(loss_avg, top-1 %, top-5 %)` -- the reference's three `.item()` per step become one
+    per logging interval -- and `reset_meters()` clears it.  The step returns the same pair either way."""
 
     def __init__(self, model, lr_backbone: float = 1e-4, lr_head: float = 1e-3, weight_decay: float = 0.01, distributed: bool = False,
-                 process_group=None, ops=None):
+                 process_group=None, ops=None, fused_loss: bool = False):
         self.ddp = None
+        self.fused_loss, self.ops, self.meter = bool(fused_loss), ops, None
         if distributed:
             from .ddp import DistributedDSTformer
             self.ddp = DistributedDSTformer(model.backbone, process_group=process_group, extra=model.head, ops=ops).attach()
@@ -225,12 +230,31 @@ class ActionStep(TwoGroupStep):
     def __call__(self, batch_input: torch.Tensor, labels: torch.Tensor):
         out = self.model(batch_input)
         self.zero_grad()
-        loss = torch.nn.functional.cross_entropy(out, labels)
+        if self.fused_loss:
+            from .action import cross_entropy_topk
+            if self.meter is None or self.meter.device != out.device:
+                self.meter = torch.zeros(4, dtype=torch.float64, device=out.device)
+            loss, _ = cross_entropy_topk(out, labels, acc=self.meter, ops=self.ops)
+        else:
+            loss = torch.nn.functional.cross_entropy(out, labels)
         loss.backward()
         if self.ddp is not None:
             self.ddp.wait()                      # (the backbone's backward already waited; covers a frozen backbone)
         self.step()
         return loss.detach(), out.detach()
+
+    def meters(self):
+        """`(loss_avg, top-1 %, top-5 %)` over the rows since the last `reset_meters()`, weighted by rows: the one host synchronisation."""
+        if not self.fused_loss:
+            raise RuntimeError('meters() needs ActionStep(fused_loss=True)')
+        total, h1, h5, rows = (0.0, 0.0, 0.0, 0.0) if self.meter is None else self.meter.cpu().tolist()
+        if rows == 0:
+            raise RuntimeError('meters() before any step')
+        return total / rows, 100.0 * h1 / rows, 100.0 * h5 / rows
+
+    def reset_meters(self):
+        if self.meter is not None:
+            self.meter.zero_()
 
 
 def flat_layout(names, shapes, depth):
