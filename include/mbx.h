@@ -532,6 +532,31 @@ int mbx_action_input(const float* x, float* y, int N, int M, int T, int J, const
 int mbx_xent_topk(const float* logits, const int* labels, int N, int C, float grad_scale, float* values, float* dlogits, double* acc,
                   void* stream);
 
+/* ---- mesh targets (csrc/smpl.hip; MotionSMPL.__getitem__, lib/data/dataset_mesh.py:63-97, for a batch of clips) -- mbx_version() >= 140 ----
+ * Inputs for N clips of T frames (F = N T <= 2^20), f32: pose [N,T,72] axis-angle, shape [N,T,10], motion_2d [N,T,17,3] (may be NULL without
+ * x2d); the model arrays, parents, Q [K,V] (1 <= K <= 32, row 0 = the root) as mbx_smpl_fwd takes them; scale (the data set: 1000).
+ * The flag of clip n is flips[n] != 0 (u8 [N]), or with flips NULL  u(seed, stream 0, index n) < flip_prob  of the counter-based hash of
+ * mbx_augment2d (flip_prob 0: never, 1: always).  Outputs, each may be NULL (not all five):
+ *   x2d [N,T,17,3]    motion_2d with the confidence clipped to [0,1]; a flipped clip is flip_data (utils_data.py:54-66): x negated, left and
+ *                     right joints swapped.  Must not alias motion_2d.
+ *   theta [N,T,82]    the pose, after flip_thetas (utils_mesh.py:458-484) in a flipped clip: components 1 and 2 of every joint negated, the
+ *                     nine left / right pairs swapped; then the ten shape values.  Copies and negations: bit-exact, signed zeros included.
+ *   kp_3d [N,T,K,3]   scale Q x - root,  verts [N,T,V,3]  scale x - root,  root = scale (Q x)[0] of the frame: scaled first, then subtracted
+ *                     (dataset_mesh.py:85-90).  x = the forward of mbx_smpl_fwd on betas = shape and R = Rodrigues of the (flipped) pose
+ *                     in smplx's form: angle = |r + 1e-8|, R = I + sin K + (1 - cos) K^2 (precise sinf / cosf; r = 0 gives I exactly).
+ *   flips_used [N]    u8, the flags applied.
+ * Launches: prepare (flips, Rodrigues into the workspace) -> the chain and vertex kernels of mbx_smpl_fwd (verts written once, keypoint
+ * partials per vertex tile; without kp_3d only the root's) -> centring (every workgroup adds the root's tile partials in tile order, subtracts
+ * the root from its share of verts in place; the first vertex chunk's workgroups finish and centre kp_3d).  verts equals the verts of
+ * mbx_smpl_fwd minus its kp[:, 0] bit for bit.  fp32, fixed summation order, no float atomics.  Without kp_3d and verts the model arrays, Q
+ * and ws are not read.  ws: >= mbx_mesh_gt_ws(F, V, K) bytes, 16-byte aligned; ws_bytes is checked.  F = 0 is a no-op.
+ * No [F,24,9] tensor is returned: the rotation matrices stay in the workspace, whose layout is not part of this interface. */
+size_t mbx_mesh_gt_ws(int F, int V, int K);
+int mbx_mesh_gt(const float* pose, const float* shape, const float* motion_2d, const unsigned char* flips, uint64_t seed, float flip_prob,
+                const float* v_template, const float* shapedirs, const float* posedirs, const float* Jt, const float* Jd, const int* parents,
+                const float* lbs_weights, const float* Q, int K, float scale, float* x2d, float* theta, float* kp_3d, float* verts,
+                unsigned char* flips_used, int N, int T, int V, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- measurement aid (bench.py `roofline.sustained_mfma_tflops`; not part of the model) --------------------------------------------
  * The bf16 MFMA rate the part sustains under its power cap with nothing but v_mfma_f32_32x32x16_bf16 in the loop (pseudo-random
  * operands; n_wg workgroups of 4 waves, `iters` x 16 MFMAs per wave).  ws: >= mbx_mfma_probe_ws(n_wg) bytes = a float sink

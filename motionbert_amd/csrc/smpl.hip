@@ -3,6 +3,10 @@
 //   mbx_smpl_fwd      : chain kernel (one thread per frame: joints, the 24 transforms A_j [F,24,12], pf [F,207]) -> vertex kernel (64
 //                       vertices x 32 frames per workgroup; lane = vertex, wave = 8 frames; pose blend, skinning, the tile's share of
 //                       Q x) -> keypoint finalize (tile partials added in tile order).
+//   mbx_mesh_gt       : the mesh targets of MotionSMPL.__getitem__ (lib/data/dataset_mesh.py:63-97) for a batch of clips: prepare kernel (clip
+//                       flip of the 2D input and of theta, Rodrigues into the workspace) -> the chain and vertex kernels of mbx_smpl_fwd ->
+//                       centring kernel (root = scale (Q x)[0] from the tile partials in tile order, subtracted from verts in place and from
+//                       the finished keypoints).
 //   mbx_smpl_bwd      : chain kernel again (nothing but betas and rotmat is saved) -> vertex backward (64 vertices x 16 frames per step;
 //                       phase 1, lane = vertex: vp, T, g, dvp recomputed into LDS; phase 2, lane = output column: d pf / d beta and d A
 //                       accumulated in registers over the workgroup's vertex tiles) -> split sum -> chain backward (one thread per frame).
@@ -10,6 +14,7 @@
 // fp32 FMAs on the vector unit (the fp32 MFMA of gfx950 runs at the same rate), fixed summation order, no floating-point atomics: two
 // calls on the same inputs give the same bits.  Frame-uniform operands (pf, A, betas, dkp) are read through wave-uniform addresses.
 #include "mbx_common.h"
+#include "aug_rng.h"
 
 #define SM_J 24
 #define SM_PF 207          // 23 * 9
@@ -229,6 +234,116 @@ __global__ __launch_bounds__(256) void smpl_kp_finish_kernel(const float* __rest
     float s = 0.0f;
     for (int t = 0; t < nvt; ++t) s += kpart[(size_t)t * n + i];
     kp[i] = scale * s;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// mesh targets (mbx_mesh_gt).  Prepare: 64 threads per frame, thread = joint (24: flip_thetas + Rodrigues), 2D joint (17: flip_data + the
+// confidence clip), shape coefficient (10) or the clip's flag (1).  The flag belongs to the CLIP n = f / T.
+// ---------------------------------------------------------------------------------------------------------------
+#define MG_CF 8            // centring: frames per workgroup
+#define MG_CV 2048         // centring: vertices per workgroup
+
+__device__ __forceinline__ int mg_theta_src(int j) {      // utils_mesh.py:475: (1,2) (4,5) (7,8) (10,11) (13,14) (16,17) (18,19) (20,21) (22,23)
+    if (j == 0) return 0;
+    if (j < 18) return j % 3 == 1 ? j + 1 : (j % 3 == 2 ? j - 1 : j);
+    return (j & 1) ? j - 1 : j + 1;
+}
+__device__ __forceinline__ int mg_joint_src(int j) {      // utils_data.py:61-65: left 4 5 6 11 12 13 <-> right 1 2 3 14 15 16
+    if ((j >= 1 && j <= 3) || (j >= 11 && j <= 13)) return j + 3;
+    if ((j >= 4 && j <= 6) || (j >= 14 && j <= 16)) return j - 3;
+    return j;
+}
+
+__global__ __launch_bounds__(256) void mesh_gt_prepare_kernel(const float* __restrict__ pose, const float* __restrict__ shape,
+                                                              const float* __restrict__ m2d, const unsigned char* __restrict__ flips,
+                                                              uint32_t slo, uint32_t shi, float flip_prob, float* __restrict__ x2d,
+                                                              float* __restrict__ theta, float* __restrict__ rot,
+                                                              unsigned char* __restrict__ flips_used, int F, int T) {
+    const int f = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int t = threadIdx.x & 63;
+    if (f >= F) return;
+    const int n = f / T;
+    const bool fl = flips ? flips[n] != 0 : aug_uniform(slo, shi, 0u, (uint32_t)n) < flip_prob;
+    if (t < SM_J) {
+        const float* p = pose + (size_t)f * 72 + (fl ? mg_theta_src(t) : t) * 3;
+        float r0 = p[0], r1 = p[1], r2 = p[2];
+        if (fl) { r1 = -r1; r2 = -r2; }
+        if (theta) {
+            float* o = theta + (size_t)f * 82 + t * 3;
+            o[0] = r0; o[1] = r1; o[2] = r2;
+        }
+        if (rot) {
+            // smplx batch_rodrigues: angle = |r + 1e-8|, d = r / angle, R = I + sin K + (1 - cos) K^2; r = 0 gives K = 0 and R = I exactly
+            const float a0 = r0 + 1e-8f, a1 = r1 + 1e-8f, a2 = r2 + 1e-8f;
+            const float angle = sqrtf(a0 * a0 + a1 * a1 + a2 * a2);
+            const float x = r0 / angle, y = r1 / angle, z = r2 / angle;
+            const float s = sinf(angle), c = 1.0f - cosf(angle);
+            float* R = rot + (size_t)f * 216 + t * 9;
+            R[0] = 1.0f - c * (y * y + z * z); R[1] = c * (x * y) - s * z;         R[2] = s * y + c * (x * z);
+            R[3] = s * z + c * (x * y);        R[4] = 1.0f - c * (x * x + z * z);  R[5] = c * (y * z) - s * x;
+            R[6] = c * (x * z) - s * y;        R[7] = s * x + c * (y * z);         R[8] = 1.0f - c * (x * x + y * y);
+        }
+    } else if (t < SM_J + 17) {
+        if (x2d) {
+            const int j = t - SM_J;
+            const float* p = m2d + ((size_t)f * 17 + (fl ? mg_joint_src(j) : j)) * 3;
+            const float cf = p[2];
+            float* o = x2d + ((size_t)f * 17 + j) * 3;
+            o[0] = fl ? -p[0] : p[0];
+            o[1] = p[1];
+            o[2] = cf < 0.0f ? 0.0f : (cf > 1.0f ? 1.0f : cf);      // np.clip(c, 0, 1): NaN stays NaN
+        }
+    } else if (t < SM_J + 27) {
+        if (theta) theta[(size_t)f * 82 + 72 + (t - SM_J - 17)] = shape[(size_t)f * 10 + (t - SM_J - 17)];
+    } else if (t == SM_J + 27) {
+        if (flips_used && f == n * T) flips_used[n] = fl ? 1 : 0;
+    }
+}
+
+// Centring: workgroup = MG_CF frames x MG_CV vertices.  Every workgroup forms the root of its frames from the tile partials of keypoint 0
+// in tile order (the sum and the product of smpl_kp_finish_kernel), so all workgroups of a frame hold the same bits; verts -= root in
+// place.  The workgroups of the first vertex chunk also finish the keypoints and subtract the root from them.
+__global__ __launch_bounds__(256) void mesh_gt_centre_kernel(const float* __restrict__ kpart, int nvt, int nout, float scale, float* verts,
+                                                             float* __restrict__ kp, int F, int V) {
+    // no contraction here: scale * s has to round before the root comes off it, as it does where smpl_kp_finish_kernel stores it (a fused
+    // multiply-subtract would leave the product's rounding error in keypoint 0 instead of an exact zero)
+#pragma clang fp contract(off)
+    __shared__ float root[MG_CF][3];
+    const int tid = threadIdx.x;
+    const int f0 = blockIdx.x * MG_CF;          // frame blocks on x: F / 8 of them, up to 2^17; vertex chunks on y: at most 512
+    if (tid < MG_CF * 3) {
+        const int i = tid / 3, c = tid - 3 * i;
+        const int f = min(f0 + i, F - 1);
+        float s = 0.0f;
+        for (int t = 0; t < nvt; ++t) s += kpart[((size_t)t * F + f) * nout + c];
+        root[i][c] = scale * s;
+    }
+    __syncthreads();
+    if (kp && blockIdx.y == 0) {
+        for (int idx = tid; idx < MG_CF * nout; idx += 256) {
+            const int i = idx / nout, o = idx - i * nout;
+            const int f = f0 + i;
+            if (f < F) {
+                float s = 0.0f;
+                for (int t = 0; t < nvt; ++t) s += kpart[((size_t)t * F + f) * nout + o];
+                kp[(size_t)f * nout + o] = scale * s - root[i][o % 3];
+            }
+        }
+    }
+    if (verts) {
+        const int e0 = blockIdx.y * (3 * MG_CV);
+        const int e1 = min(e0 + 3 * MG_CV, 3 * V);
+        for (int i = 0; i < MG_CF; ++i) {
+            if (f0 + i >= F) break;
+            float* row = verts + (size_t)(f0 + i) * 3 * V;
+            const float r0 = root[i][0], r1 = root[i][1], r2 = root[i][2];
+#pragma unroll 4
+            for (int e = e0 + tid; e < e1; e += 256) {
+                const int c = e % 3;
+                row[e] -= c == 0 ? r0 : (c == 1 ? r1 : r2);
+            }
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -528,6 +643,64 @@ extern "C" int mbx_smpl_fwd(const float* v_template, const float* shapedirs, con
         hipLaunchKernelGGL(smpl_kp_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)kpart, nvt, scale, kp, n);
         MBX_LAUNCH_CHECK("smpl_fwd (keypoints)");
     }
+    return 0;
+}
+
+// float offsets: the forward's layout with K keypoints (mbx_smpl_fwd_ws less its 256 spare bytes), then the rotation matrices [F,216]
+static inline size_t mg_rot_offset(int F, int V, int K) { return sm_common_floats(F) + (size_t)sm_tiles(V) * F * 3 * K; }
+
+extern "C" size_t mbx_mesh_gt_ws(int F, int V, int K) {
+    if (!sm_dims_ok(F, V, K) || F < 1 || K < 1) return 0;
+    return (mg_rot_offset(F, V, K) + (size_t)F * 216) * sizeof(float) + 256;
+}
+
+extern "C" int mbx_mesh_gt(const float* pose, const float* shape, const float* motion_2d, const unsigned char* flips, uint64_t seed,
+                           float flip_prob, const float* v_template, const float* shapedirs, const float* posedirs, const float* Jt,
+                           const float* Jd, const int* parents, const float* lbs_weights, const float* Q, int K, float scale, float* x2d,
+                           float* theta, float* kp_3d, float* verts, unsigned char* flips_used, int N, int T, int V, void* ws,
+                           size_t ws_bytes, void* stream) {
+    MBX_CHECK_ARG(N >= 0 && T >= 1 && (long long)N * T <= (1 << 20), "mesh_gt: bad sizes N=%d T=%d (T >= 1, N T <= 2^20)", N, T);
+    const int F = N * T;
+    MBX_CHECK_ARG(sm_dims_ok(F, V, K) && K >= 1, "mesh_gt: bad sizes F=%d V=%d K=%d (V >= 1, 1 <= K <= 32)", F, V, K);
+    SmplTree tree;
+    if (sm_tree(parents, tree, "mesh_gt")) return 1;
+    if (F == 0) return 0;
+    MBX_CHECK_ARG(x2d || theta || kp_3d || verts || flips_used, "mesh_gt: no output");
+    MBX_CHECK_ARG(flips || (flip_prob >= 0.0f && flip_prob <= 1.0f), "mesh_gt: flip_prob must lie in [0, 1]");
+    const bool body = kp_3d || verts;
+    MBX_CHECK_ARG(pose && shape, "mesh_gt: null pointer (pose, shape)");
+    MBX_CHECK_ARG(!x2d || motion_2d, "mesh_gt: x2d needs motion_2d");
+    MBX_CHECK_ARG(!x2d || x2d != motion_2d, "mesh_gt: x2d must not alias motion_2d (the flip permutes joints)");
+    MBX_CHECK_ARG(!body || (v_template && shapedirs && posedirs && Jt && Jd && lbs_weights && Q && ws),
+                  "mesh_gt: null pointer (kp_3d and verts need the model arrays, Q and a workspace)");
+    MBX_CHECK_ARG(!body || ws_bytes >= mbx_mesh_gt_ws(F, V, K), "mesh_gt: workspace of %zu bytes, %zu needed", ws_bytes, mbx_mesh_gt_ws(F, V, K));
+    MBX_CHECK_ARG((((uintptr_t)pose | (uintptr_t)shape | (uintptr_t)motion_2d | (uintptr_t)v_template | (uintptr_t)shapedirs | (uintptr_t)posedirs |
+                    (uintptr_t)Jt | (uintptr_t)Jd | (uintptr_t)lbs_weights | (uintptr_t)Q | (uintptr_t)x2d | (uintptr_t)theta | (uintptr_t)kp_3d |
+                    (uintptr_t)verts) & 3) == 0 && (!body || ((uintptr_t)ws & 15) == 0),
+                  "mesh_gt: pointers must be 4-byte aligned, the workspace 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    // the vertex kernel forms the partials of the Kv keypoints the caller reads: all K for kp_3d, the root alone for verts
+    const int Kv = kp_3d ? K : 1;
+    float* Aws = (float*)ws;
+    float* PFws = body ? Aws + (size_t)F * SM_A : nullptr;
+    float* G = body ? PFws + (size_t)F * SM_PFS : nullptr;
+    float* kpart = body ? G + (size_t)F * SM_A : nullptr;
+    float* rot = body ? Aws + mg_rot_offset(F, V, K) : nullptr;
+    hipLaunchKernelGGL(mesh_gt_prepare_kernel, dim3((F + 3) / 4), dim3(256), 0, s, pose, shape, motion_2d, flips, (uint32_t)seed,
+                       (uint32_t)(seed >> 32), flip_prob, x2d, theta, rot, flips_used, F, T);
+    MBX_LAUNCH_CHECK("mesh_gt (prepare)");
+    if (!body) return 0;
+    hipLaunchKernelGGL(smpl_chain_fwd_kernel, dim3((F + 63) / 64), dim3(64), 0, s, shape, (const float*)rot, Jt, Jd, tree, scale, Aws, PFws, G,
+                       (float*)nullptr, F);
+    MBX_LAUNCH_CHECK("mesh_gt (chain)");
+    const int nvt = sm_tiles(V);
+    hipLaunchKernelGGL(smpl_verts_fwd_kernel, dim3(nvt, (F + 4 * SM_FW - 1) / (4 * SM_FW)), dim3(256), 0, s, v_template, shapedirs, posedirs,
+                       lbs_weights, Q, shape, (const float*)Aws, (const float*)PFws, scale, verts, kpart, F, V, Kv);
+    MBX_LAUNCH_CHECK("mesh_gt (vertices)");
+    const int chunks = verts ? (V + MG_CV - 1) / MG_CV : 1;
+    hipLaunchKernelGGL(mesh_gt_centre_kernel, dim3((F + MG_CF - 1) / MG_CF, chunks), dim3(256), 0, s, (const float*)kpart, nvt, 3 * Kv, scale,
+                       verts, kp_3d, F, V);
+    MBX_LAUNCH_CHECK("mesh_gt (centring)");
     return 0;
 }
 

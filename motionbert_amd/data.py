@@ -12,6 +12,9 @@ collates on the host.  At 8 x 1,000 clips/s that is ~0.8 GB/s of pickle parsing.
   on the device        everything `MotionDataset3D.__getitem__` did per clip on the host: random flip of input and label
                        (`flip_data`, utils_data.py:54-66), the synthetic / gt_2d input (`x, y` of the label + confidence 1,
                        dataset_motion_3d.py:49-53), `crop_scale_3d` (utils_data.py:31-52) -- batched torch ops.
+  pack_action / PackedAction, pack_mesh / PackedMesh   the same scheme for the NTU annotation file (lib/data/dataset_action.py) and for the
+                       mesh detection files (lib/data/dataset_mesh.py); their `__getitem__` stages are HIP kernels (`mbx_action_input`,
+                       `mbx_mesh_gt`: the SMPL ground truth is computed on the device, nothing of vertex size crosses the host link).
   sharding             `rank` / `world`: every rank walks the same per-epoch permutation and takes a strided, equally sized
                        share (what DistributedSampler does), so the N ranks of the data-parallel run never exchange data.
 """
@@ -384,6 +387,145 @@ class PackedAction:
                     motion = action_input(motion, random_move=self.random_move, scale_range=self.scale_range,
                                           seed=self.batch_seed(seed, epoch, rank, k), ops=self.ops)
                 yield motion, labels
+        finally:
+            stream.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# mesh recovery (lib/data/dataset_mesh.py): the detection pickles of H36M / 3DPW / COCO, packed once
+# ---------------------------------------------------------------------------------------------------------------
+#: DataReaderH36M.read_2d (datareader_h36m.py:29-44): camera name -> (res_w, res_h)
+_H36M_RES = {'54138969': (1000, 1002), '60457274': (1000, 1002), '55011271': (1000, 1000), '58860488': (1000, 1000)}
+_MESH_RES = {'coco': (640, 640), 'pw3d': (1920, 1920)}      # dataset_mesh.py:28,30
+
+
+def _split_clips(vid_list, n_frames: int, data_stride: int, rng) -> list:
+    """split_clips (utils_data.py:91-112): windows of `n_frames` every `data_stride` frames inside one source; a source that is over
+    before it filled a window is resampled to `n_frames` (`resample` with its random rounding, here from `rng`), the last source excepted"""
+    result, saved, st, i = [], set(), 0, 0
+    while i < len(vid_list):
+        i += 1
+        if i - st == n_frames:
+            result.append(np.arange(st, i))
+            saved.add(vid_list[i - 1])
+            st += data_stride
+        if i == len(vid_list):
+            break
+        if vid_list[i] != vid_list[i - 1]:
+            if vid_list[i - 1] not in saved:
+                result.append(_ntu_frames(i - st, n_frames, rng).astype(np.int64) + st)
+                saved.add(vid_list[i - 1])
+            st = i
+    return result
+
+
+def _mesh_read_2d(part: dict, dataset: str, has_confidence: bool) -> np.ndarray:
+    """read_2d of DataReaderH36M (datareader_h36m.py:25-58) / DataReaderMesh (datareader_mesh.py:19-40) for one split: [frames,17,3] with
+    the reference's roundings (the division and the factor 2 in float32, the offset subtracted in float64)"""
+    xy = np.asarray(part['joint_2d'])[:, :, :2].astype(np.float32)
+    if dataset == 'h36m':
+        names = list(part['camera_name'])
+        bad = [i for i, c in enumerate(names) if c not in _H36M_RES]
+        if bad:
+            raise ValueError(f'{bad[0]} data item has an invalid camera name')
+        if len(names) != len(xy):
+            raise ValueError(f'{len(names)} camera names for {len(xy)} frames')
+        res = np.asarray([_H36M_RES[c] for c in names], dtype=np.float64).reshape(-1, 2)
+        off = np.stack([np.ones(len(names)), res[:, 1] / res[:, 0]], axis=1)[:, None, :]
+        xy = ((xy / 1000 * 2).astype(np.float64) - off).astype(np.float32)          # res_w is 1000 for every camera
+    else:
+        res_w, res_h = _MESH_RES[dataset]
+        xy = xy / res_w * 2 - np.asarray([1, res_h / res_w])
+    if has_confidence:
+        conf = np.asarray(part['confidence']).astype(np.float32)
+        if conf.ndim == 2:
+            conf = conf[:, :, None]
+    else:
+        conf = np.ones(xy.shape)[:, :, 0:1]
+    return np.concatenate((xy, conf), axis=2)
+
+
+def pack_mesh(pkl_path: str, dataset: str, data_split: str, clip_len: int, data_stride: int, out_prefix: str, sample_stride: int = 1) -> dict:
+    """The one-off host work of `SMPLDataset.__init__` (dataset_mesh.py:19-49) for the detection pickle of `dataset` in {'h36m', 'pw3d',
+    'coco'} ({'train' / 'test': {'joint_2d' [frames,17,>=2], 'confidence', 'source', 'smpl_pose' [frames,72], 'smpl_shape' [frames,10]} and,
+    for h36m, 'camera_name'}): `read_2d` of the data set's reader with its resolution, `split_clips` with the `n_frames` and strides of
+    dataset_mesh.py:25-30 (coco: single frames; the test split: stride = clip_len), and the SMPL parameters of every clip.  Writes
+    `<prefix>.motion2d.npy` [N,T,17,3], `<prefix>.pose.npy` [N,T,72], `<prefix>.shape.npy` [N,T,10] (float32) and `<prefix>.json`; returns
+    the metadata.  The arrays equal the reference's `motion_2d` / `motion_smpl_3d` bit for bit (the clip of the confidence and the flip
+    belong to `__getitem__`: `mesh.mesh_targets`): the random rounding of a short source's resampling comes from
+    `np.random.RandomState(0)`, drawn for the train split first, which is what the reference's `np.random.seed(0)` amounts to.
+
+    `sample_stride` other than 1 raises: the reference's camera loop indexes the unstrided list, and no config uses it."""
+    if dataset not in ('h36m', 'pw3d', 'coco'):
+        raise ValueError('Mesh dataset undefined.')                 # dataset_mesh.py:32
+    if data_split not in ('train', 'test'):
+        raise ValueError(f"data_split must be 'train' or 'test', got {data_split!r}")
+    if sample_stride != 1:
+        raise ValueError(f'sample_stride = {sample_stride}: only 1 is supported (the reference reads camera names unstrided)')
+    with open(pkl_path, 'rb') as f:
+        dt = pickle.load(f)
+    n_frames = 1 if dataset == 'coco' else int(clip_len)
+    strides = {'train': 1 if dataset == 'coco' else int(data_stride), 'test': 1 if dataset == 'coco' else int(clip_len)}
+    rng = np.random.RandomState(0)
+    ids = {split: _split_clips(dt[split]['source'], n_frames, strides[split], rng) for split in ('train', 'test')}[data_split]
+    if not ids:
+        raise ValueError(f'{pkl_path}: split {data_split!r} has no clip of {n_frames} frames')
+    ids = np.stack(ids)
+    part = dt[data_split]
+    motion = _mesh_read_2d(part, dataset, dataset != 'h36m' or 'confidence' in dt['train'])[ids].astype(np.float32)
+    pose = np.asarray(part['smpl_pose'])[ids].astype(np.float32)
+    shape = np.asarray(part['smpl_shape'])[ids].astype(np.float32)
+    if pose.shape != ids.shape + (72,) or shape.shape != ids.shape + (10,):
+        raise ValueError(f'{pkl_path}: smpl_pose [frames,72] and smpl_shape [frames,10] expected, clips are {pose.shape} / {shape.shape}')
+    np.save(out_prefix + '.motion2d.npy', motion)
+    np.save(out_prefix + '.pose.npy', pose)
+    np.save(out_prefix + '.shape.npy', shape)
+    meta = dict(n=int(len(ids)), clip_len=int(n_frames), dataset=dataset, split=data_split, data_stride=int(strides[data_split]))
+    with open(out_prefix + '.json', 'w') as f:
+        json.dump(meta, f)
+    return meta
+
+
+class PackedMesh:
+    """The packed clips of `pack_mesh` + the asynchronous batch stream of `pinned_batches` + `MotionSMPL.__getitem__` on the device.
+
+        ds = PackedMesh(prefix, smpl, device='cuda', train=True, flip=True)          # smpl: an SMPLLayer on the device
+        for batch_input, batch_gt in ds.batches(128, shuffle=True, epoch=e, rank=r, world=w):
+            ...          # [B,T,17,3] and {'theta' [B,T,82], 'kp_3d' [B,T,17,3], 'verts' [B,T,V,3]} on the device: MeshStep / MeshEvaluator take them
+    About 1 MB per batch crosses the host link (2D input, pose, shape); every batch goes through `mesh.mesh_targets` (`mbx_mesh_gt`: clip
+    flip, SMPL, H36M joints, root subtraction) with a seed derived from (seed, epoch, rank, batch index) as `PackedAction` derives it.
+    `train=False` (the test split) never flips.  `ops`: kernel provider for host tensors (tests)."""
+
+    def __init__(self, prefix: str, smpl, device='cuda', train: bool = True, flip: bool = True, ring: int = 3, ops=None):
+        with open(prefix + '.json') as f:
+            self.meta = json.load(f)
+        self.motion_2d = np.load(prefix + '.motion2d.npy', mmap_mode='r')
+        self.pose = np.load(prefix + '.pose.npy', mmap_mode='r')
+        self.shape = np.load(prefix + '.shape.npy', mmap_mode='r')
+        if not len(self.motion_2d) == len(self.pose) == len(self.shape):
+            raise ValueError(f'{prefix}: {len(self.motion_2d)} / {len(self.pose)} / {len(self.shape)} clips in the three arrays')
+        self.smpl = smpl
+        self.device = torch.device(device)
+        self.train, self.flip = bool(train), bool(flip) and bool(train)
+        self.ring, self.ops = max(2, int(ring)), ops
+
+    def __len__(self):
+        return len(self.pose)
+
+    def batches(self, batch_size: int, shuffle: bool = True, epoch: int = 0, seed: int = 0, rank: int = 0, world: int = 1,
+                drop_last: bool = False) -> Iterator[Tuple[torch.Tensor, dict]]:
+        from .mesh import mesh_targets
+        idx = shard_indices(len(self), shuffle, epoch, seed, rank, world)
+        chunks = [idx[i:i + batch_size] for i in range(0, len(idx), batch_size)]
+        if drop_last and chunks and len(chunks[-1]) < batch_size:
+            chunks.pop()
+        if not chunks:
+            return
+        stream = pinned_batches([self.motion_2d, self.pose, self.shape], chunks, batch_size, self.device, self.ring)
+        try:
+            for k, (motion_2d, pose, shape) in enumerate(stream):
+                yield mesh_targets(self.smpl, pose, shape, motion_2d, flip=self.flip, seed=PackedAction.batch_seed(seed, epoch, rank, k),
+                                   ops=self.ops)
         finally:
             stream.close()
 

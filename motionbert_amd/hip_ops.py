@@ -112,6 +112,8 @@ SIGNATURES = {
     'mbx_smpl_bwd_ws': (_sz, [_i, _i, _i]),
     'mbx_smpl_fwd': (_i, [_vp] * 5 + [C.POINTER(C.c_int)] + [_vp, _vp, _i, _vp, _vp, _f, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
     'mbx_smpl_bwd': (_i, [_vp] * 6 + [C.POINTER(C.c_int)] + [_vp, _vp, _i, _vp, _vp, _f] + [_vp] * 5 + [_i, _i, _vp, _sz, _vp]),
+    'mbx_mesh_gt_ws': (_sz, [_i, _i, _i]),
+    'mbx_mesh_gt': (_i, [_vp, _vp, _vp, _vp, C.c_uint64, _f] + [_vp] * 5 + [C.POINTER(C.c_int)] + [_vp, _vp, _i, _f] + [_vp] * 5 + [_i, _i, _i, _vp, _sz, _vp]),
     'mbx_action_input': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp] + [_f] * 8 + [_i, C.c_uint64, _vp]),
     'mbx_xent_topk': (_i, [_vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp]),
     'mbx_rows_n_pack_bytes': (_sz, [_i, _i]),
@@ -885,6 +887,42 @@ class HipOps:
                                        _p(model['Jt']), _p(model['Jd']), parents, _p(model['lbs_weights']), _p(Q), K, _p(betas), _p(rotmat),
                                        float(scale), _p(dverts), _p(dkp), _p(djoints), _p(drotmat), _p(dbetas), F, V, _p(ws), ws.numel(),
                                        self._stream()))
+
+    # ------------------------------------------------------------------ mesh targets (csrc/smpl.hip; motionbert_amd/mesh.py: mesh_targets)
+    def mesh_gt_ws(self, F, V, K, device):
+        return self._ws(('meshgt', F, V, K), self.lib.mbx_mesh_gt_ws, F, V, K, device=device)
+
+    def mesh_gt(self, model, Q, pose, shape, motion_2d, flips, seed, flip_prob, scale, x2d, theta, kp_3d, verts, flips_used, ws=None):
+        """model, Q [K,V] as smpl_fwd takes them; pose [N,T,72], shape [N,T,10] f32, motion_2d [N,T,17,3] f32 or None; flips [N] u8 or None
+        (then the flag of clip n is drawn from (seed, n) against flip_prob); outputs x2d [N,T,17,3] / theta [N,T,82] / kp_3d [N,T,K,3] /
+        verts [N,T,V,3] f32 and flips_used [N] u8, each may be None; ws: a uint8 workspace of mesh_gt_ws(N T, V, K) (allocated when None)."""
+        V, dev, parents = self._smpl_model('mesh_gt', model, False)
+        if pose.dim() != 3 or pose.shape[2] != 72 or pose.shape[1] < 1 or tuple(shape.shape) != tuple(pose.shape[:2]) + (10,):
+            raise RuntimeError(f'libmbx: mesh_gt needs pose [N,T >= 1,72] and shape [N,T,10], got {tuple(pose.shape)} / {tuple(shape.shape)}')
+        N, T = pose.shape[:2]
+        F = N * T
+        if x2d is None and theta is None and kp_3d is None and verts is None and flips_used is None:
+            raise RuntimeError('libmbx: mesh_gt: no output')
+        if Q is None or Q.dim() != 2 or Q.shape[1] != V or not 1 <= Q.shape[0] <= 32:
+            raise RuntimeError(f'libmbx: mesh_gt needs Q [1 <= K <= 32, {V}], got {None if Q is None else tuple(Q.shape)}')
+        K = Q.shape[0]
+        if x2d is not None and motion_2d is None:
+            raise RuntimeError('libmbx: mesh_gt: x2d needs motion_2d')
+        self._dense('mesh_gt', torch.float32, K * V, dev, Q=Q)
+        self._dense('mesh_gt', torch.float32, F * 72, dev, pose=pose)
+        self._dense('mesh_gt', torch.float32, F * 10, dev, shape=shape)
+        self._dense('mesh_gt', torch.float32, F * 51, dev, motion_2d=motion_2d, x2d=x2d)
+        self._dense('mesh_gt', torch.float32, F * 82, dev, theta=theta)
+        self._dense('mesh_gt', torch.float32, F * K * 3, dev, kp_3d=kp_3d)
+        self._dense('mesh_gt', torch.float32, F * V * 3, dev, verts=verts)
+        self._dense('mesh_gt', torch.uint8, N, dev, flips=flips, flips_used=flips_used)
+        if ws is None:
+            ws = self.mesh_gt_ws(F, V, K, dev)
+        self._dense('mesh_gt', torch.uint8, None, dev, ws=ws)
+        self._ck(self.lib.mbx_mesh_gt(_p(pose), _p(shape), _p(motion_2d), _p(flips), int(seed), float(flip_prob), _p(model['v_template']),
+                                      _p(model['shapedirs']), _p(model['posedirs']), _p(model['Jt']), _p(model['Jd']), parents,
+                                      _p(model['lbs_weights']), _p(Q), K, float(scale), _p(x2d), _p(theta), _p(kp_3d), _p(verts),
+                                      _p(flips_used), N, T, V, _p(ws), ws.numel(), self._stream()))
 
     # ------------------------------------------------------------------ dropout / drop-path (SURVEY 8 a15)
     def dropout(self, x, y, p, seed):

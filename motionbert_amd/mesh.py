@@ -14,6 +14,9 @@ skinning, built from the user's SMPL arrays) or any module with the reference's 
                                     `evaluate_mesh`'s dict and is the only host synchronisation: no vertex ever goes to the host.
     compute_error / compute_error_frames   the reference's signatures (utils_mesh.py:357-393) on the same kernel.
     flip_thetas_batch(thetas)       utils_mesh.py:486-513 on a tensor, bit for bit.
+    mesh_targets(smpl, pose, shape) the ground-truth stage of `MotionSMPL.__getitem__` (lib/data/dataset_mesh.py:63-97) for a batch of clips on the
+                                    device, one `mbx_mesh_gt`: the clip flip of the 2D input and of theta, SMPL from axis-angle, the H36M joints,
+                                    both root subtractions.  `motionbert_amd.data.PackedMesh` feeds it from packed arrays.
     flip_average(model, smpl, x)    the flip evaluation of train_mesh.py:83-108: the mean of the model's output and the flipped-back output of
                                     the flipped input, for `MeshEvaluator.update`.
 
@@ -27,7 +30,7 @@ import torch
 import torch.nn as nn
 
 from . import hip_ops
-from .smpl import SMPLLayer, rodrigues
+from .smpl import _MOVE, SMPLLayer, rodrigues
 from .train import TwoGroupStep
 
 LOSS_KEYS = ('loss_3d_pos', 'loss_3d_scale', 'loss_3d_velocity', 'loss_lv', 'loss_lg', 'loss_a', 'loss_av', 'loss_shape', 'loss_pose', 'loss_norm')
@@ -435,6 +438,82 @@ def flip_average(model, smpl, batch_input: torch.Tensor, output=None):
         back = {'theta': torch.cat([pose.reshape(N, T, -1), shape.reshape(N, T, -1)], dim=-1), 'verts': verts.reshape(N, T, -1, 3),
                 'kp_3d': kp.reshape(N, T, -1, 3)}
         return [{k: (output[0][k] + back[k].to(output[0][k].dtype)) * 0.5 for k in flipped}]
+
+
+# ---------------------------------------------------------------------------------------------------------------- targets
+TARGET_KEYS = ('theta', 'kp_3d', 'verts')
+
+
+def mesh_targets(smpl, pose, shape, motion_2d=None, flip=None, seed=None, flip_prob=0.5, want=TARGET_KEYS, return_flips=False, ops=None):
+    """`(motion_2d_out or None, {'theta': [N,T,82], 'kp_3d': [N,T,17,3], 'verts': [N,T,V,3]})`: what `MotionSMPL.__getitem__` returns for
+    every clip of a batch, from pose [N,T,72] (axis-angle), shape [N,T,10] and the 2D input motion_2d [N,T,17,3] (optional), in one
+    `mbx_mesh_gt` on the device.  `smpl`: an `SMPLLayer` with `J_regressor_h36m`.  Millimetres (`* 1000`), root = the regressed joint 0.
+
+    `flip`: None / False no clip is flipped (the test split); True every clip is flipped with probability `flip_prob`, drawn on the device
+    from `seed` (default: 62 bits from torch's CPU generator) and the clip's index; a [N] bool / uint8 tensor flips the clips it marks.  A
+    flipped clip has `flip_data` applied to its 2D input and `flip_thetas` to its pose before SMPL.  `want`: the keys to compute (a subset of
+    'theta', 'kp_3d', 'verts'; with `motion_2d` or `return_flips` it may be empty).  `return_flips=True` appends the flags used ([N] uint8).
+    No autograd, no host synchronisation; fp32."""
+    if not isinstance(smpl, SMPLLayer):
+        raise TypeError('mesh_targets needs an SMPLLayer')
+    Q = smpl.J_regressor_h36m
+    if Q is None:
+        raise ValueError('mesh_targets needs the model\'s J_regressor_h36m (the layer has none)')
+    want = tuple(want)
+    if any(k not in TARGET_KEYS for k in want) or len(set(want)) != len(want):
+        raise ValueError(f'want must be a subset of {TARGET_KEYS}, got {want}')
+    if not want and motion_2d is None and not return_flips:
+        raise ValueError('mesh_targets: nothing to compute (empty want, no motion_2d, return_flips off)')
+    if pose.dim() != 3 or pose.shape[2] != 72 or pose.shape[1] < 1:
+        raise ValueError(f'pose [N,T,72] expected, got {tuple(pose.shape)}')
+    N, T = pose.shape[:2]
+    if tuple(shape.shape) != (N, T, 10):
+        raise ValueError(f'shape [{N},{T},10] expected, got {tuple(shape.shape)}')
+    if motion_2d is not None and tuple(motion_2d.shape) != (N, T, 17, 3):
+        raise ValueError(f'motion_2d [{N},{T},17,3] expected, got {tuple(motion_2d.shape)}')
+    flags = None
+    if torch.is_tensor(flip):
+        if tuple(flip.shape) != (N,) or flip.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f'flip [{N}] bool or uint8 expected, got {tuple(flip.shape)} {flip.dtype}')
+        flags = flip
+    elif flip is not None and not isinstance(flip, bool):
+        raise ValueError(f'flip must be None, a bool or a [N] tensor, got {flip!r}')
+    if not 0.0 <= float(flip_prob) <= 1.0:
+        raise ValueError(f'flip_prob must lie in [0, 1], got {flip_prob}')
+    ops = hip_ops.provider(ops, 'motionbert_amd.mesh.mesh_targets', pose, shape, motion_2d, flags, smpl.v_template, move=_MOVE)
+    dev = pose.device
+    if any(t is not None and t.device != dev for t in (shape, motion_2d, flags, smpl.v_template)):
+        raise ValueError(f'mesh_targets: the layer and every tensor must be on one device (pose is on {dev})')
+    prob = 0.0
+    if flip is True:
+        prob = float(flip_prob)
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    with torch.no_grad():
+        pose, shape = pose.detach().float().contiguous(), shape.detach().float().contiguous()
+        m2d = None if motion_2d is None else motion_2d.detach().float().contiguous()
+        if flags is not None:
+            flags = flags.detach().to(torch.uint8).contiguous()
+        if Q.dtype != torch.float32 or not Q.is_contiguous():
+            Q = Q.float().contiguous()
+        K, V = Q.shape[0], smpl.num_vertices
+        if not N:
+            out = {'theta': pose.new_empty(0, T, 82), 'kp_3d': pose.new_empty(0, T, K, 3), 'verts': pose.new_empty(0, T, V, 3)}
+            res = (None if m2d is None else torch.empty_like(m2d), {k: out[k] for k in want})
+            return res + (torch.empty(0, dtype=torch.uint8, device=dev),) if return_flips else res
+        x2d = None if m2d is None else torch.empty_like(m2d)
+        out = {}
+        if 'theta' in want:
+            out['theta'] = torch.empty(N, T, 82, dtype=torch.float32, device=dev)
+        if 'kp_3d' in want:
+            out['kp_3d'] = torch.empty(N, T, K, 3, dtype=torch.float32, device=dev)
+        if 'verts' in want:
+            out['verts'] = torch.empty(N, T, V, 3, dtype=torch.float32, device=dev)
+        used = torch.empty(N, dtype=torch.uint8, device=dev) if return_flips else None
+        ops.mesh_gt(smpl.model_tensors(), Q, pose, shape, m2d, flags, 0 if seed is None else int(seed), prob, 1000.0, x2d, out.get('theta'),
+                    out.get('kp_3d'), out.get('verts'), used, ws=smpl.workspace(ops, 'gt', N * T, K, dev))
+    res = (x2d, {k: out[k] for k in want})
+    return res + (used,) if return_flips else res
 
 
 # ---------------------------------------------------------------------------------------------------------------- step

@@ -244,13 +244,14 @@ class SMPLLayer(nn.Module):
         return d
 
     def workspace(self, ops, kind, F, K, device):
-        """one workspace per (direction, F, K, device), kept: a captured graph replays with the addresses of its capture"""
+        """one workspace per (kind, F, K, device), kept: a captured graph replays with the addresses of its capture.  kind: 'fwd', 'bwd', or
+        'gt' (the targets of mesh.mesh_targets)"""
         key = (kind, F, K, str(device))
         ws = self._ws.get(key)
         if ws is None:
             if len(self._ws) >= 16:
                 self._ws.clear()
-            ws = self._ws[key] = (ops.smpl_fwd_ws if kind == 'fwd' else ops.smpl_bwd_ws)(F, self.num_vertices, K, device)
+            ws = self._ws[key] = getattr(ops, {'fwd': 'smpl_fwd_ws', 'bwd': 'smpl_bwd_ws', 'gt': 'mesh_gt_ws'}[kind])(F, self.num_vertices, K, device)
         return ws
 
     def prepare(self, F, K=0):
