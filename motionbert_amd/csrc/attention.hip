@@ -37,6 +37,7 @@
 // instruction would touch 32 rows x 16 bytes).  They are staged through LDS tiles that are dead by then and copied out with
 // eight lanes per 128-byte row segment.
 #include "attention_common.h"
+#include "mbx_diag.h"
 
 // threads per workgroup: long sequences (K/V or Q/dO shared in LDS) use 8 waves -- one 32-row block each for T <= 256 --
 // so that the two workgroups a CU holds (72 KiB of LDS each) give every SIMD four waves to hide latency behind
@@ -579,15 +580,14 @@ struct Raw4b {     // four bf16 in a uint2 -> fp32
         v[2] = __uint_as_float(r.y << 16); v[3] = __uint_as_float(r.y & 0xffff0000u);
     }
 };
-#ifndef MBX_ATTN_DBG
-#define MBX_ATTN_DBG 0      // ablation bits of diagnostic builds (timing only): 1 no compute loops, 2 no copy-out stores, 4 no tile / statistics loads, 8 no exp2 (p = 1)
-#endif
-// Diagnostic builds only (-DMBX_ATTN_TRACE, tools/attn_trace.py): 8 int64 per workgroup (thread 0) -- s_memrealtime (100 MHz) at entry,
-// loads of the fill issued, tiles + statistics in LDS (first barrier passed), compute done (second barrier), gradients staged (third
-// barrier), copy-out stores issued, stores acknowledged; the hardware id.  The buffer address comes from MBX_TRACE_BUF.
+// Diagnostic builds only (-DMBX_ATTN_TRACE, tools/attn_trace.py): ATTN_TRACE_SLOTS int64 per problem (thread 0) -- s_memrealtime (100 MHz) at
+// entry, loads of the fill issued, tiles + statistics in LDS (first barrier passed), compute done (second barrier), gradients staged (third
+// barrier), copy-out stores issued, stores acknowledged; the hardware id.  Behind the records of all problems, ATTN_TRACE_WAVES int64 per
+// problem: every wave's stamp at the end of its compute loops.
 #ifdef MBX_ATTN_TRACE
 __device__ long long* g_attn_trace;
-#define AT_TS(slot_) do { if (threadIdx.x == 0) ats[slot_] = (long long)wall_clock64(); __builtin_amdgcn_sched_barrier(0); } while (0)
+static constexpr int ATTN_TRACE_SLOTS = 9, ATTN_TRACE_WAVES = 16;
+#define AT_TS(slot_) MBX_STAMP_IF(threadIdx.x == 0, ats[slot_])
 #else
 #define AT_TS(slot_) do { } while (0)
 #endif
@@ -601,7 +601,7 @@ __global__ __launch_bounds__(1024, 1) void attn_bwd_fused_kernel(const bf16_t* _
     constexpr int RSTR = rm_stride<T>(HD), CH = HD / 8;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 #ifdef MBX_ATTN_TRACE
-    long long ats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    long long ats[ATTN_TRACE_SLOTS - 1] = {};
 #endif
     AT_TS(0);
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), g = lane >> 5;
@@ -752,7 +752,7 @@ __global__ __launch_bounds__(1024, 1) void attn_bwd_fused_kernel(const bf16_t* _
     }
     AT_TS(3);
 #ifdef MBX_ATTN_TRACE
-    if (g_attn_trace != nullptr && (threadIdx.x & 63) == 0) g_attn_trace[(size_t)gridDim.x * 9 + (size_t)blockIdx.x * 16 + (threadIdx.x >> 6)] = (long long)wall_clock64();
+    if (g_attn_trace != nullptr && (threadIdx.x & 63) == 0) g_attn_trace[(size_t)gridDim.x * ATTN_TRACE_SLOTS + (size_t)blockIdx.x * ATTN_TRACE_WAVES + (threadIdx.x >> 6)] = (long long)wall_clock64();
 #endif
     __syncthreads();                       // every wave is done reading the tiles: they become the output staging area
     AT_TS(4);
@@ -812,10 +812,10 @@ __global__ __launch_bounds__(1024, 1) void attn_bwd_fused_kernel(const bf16_t* _
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     AT_TS(7);
     if (g_attn_trace != nullptr && threadIdx.x == 0) {
-        long long* const tr = g_attn_trace + (size_t)blockIdx.x * 9;
+        long long* const tr = g_attn_trace + (size_t)blockIdx.x * ATTN_TRACE_SLOTS;
 #pragma unroll
-        for (int k = 0; k < 8; ++k) tr[k] = ats[k];
-        tr[8] = (long long)__builtin_amdgcn_s_getreg(63492) | ((long long)__builtin_amdgcn_s_getreg(63508) << 32);
+        for (int k = 0; k < ATTN_TRACE_SLOTS - 1; ++k) tr[k] = ats[k];
+        tr[ATTN_TRACE_SLOTS - 1] = mbx_hw_id();
     }
 #endif
 }
@@ -909,9 +909,8 @@ static int launch_bwd(const void* qkv, const void* o, const void* d_o, const flo
     return 0;
 }
 
-#ifdef MBX_ATTN_TRACE
-#define MBX_ATTN_TRACE_SET(s_) do { static long long* const tb = [] { const char* e = getenv("MBX_TRACE_BUF"); return e ? (long long*)strtoull(e, nullptr, 0) : (long long*)nullptr; }(); \
-                                    (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_attn_trace), &tb, sizeof(tb), 0, hipMemcpyHostToDevice, (s_)); } while (0)
+#ifdef MBX_ATTN_TRACE   // (1024 threads = ATTN_TRACE_WAVES waves per problem)
+#define MBX_ATTN_TRACE_SET(s_) mbx_diag_arm(HIP_SYMBOL(g_attn_trace), (size_t)nprob * (ATTN_TRACE_SLOTS + ATTN_TRACE_WAVES) * sizeof(long long), (s_))
 #else
 #define MBX_ATTN_TRACE_SET(s_) do { } while (0)
 #endif

@@ -31,8 +31,8 @@
 // The product build has no switches: constants below that read like knobs are closed A/B experiments (numbers in DESIGN.md and
 // profiles/r0*_*.txt); ablation switches (`dbg`) and cycle stamps exist in -DMBX_DIAG builds only (tools/build_variants.py diag).
 #include "mbx_common.h"
+#include "mbx_diag.h"
 #include "gelu_fast.h"
-#include <stdlib.h>
 #include <tuple>
 #include <type_traits>
 
@@ -115,6 +115,10 @@ struct NtLnTail {
 // that no compute wave stalls on the vector-memory path in front of its MFMAs.  Correct, and 5-24 % slower on every shape
 // (lnb_qkv 0.777 -> 0.822 ms, proj 0.341 -> 0.424 ms): one wave issues the 24 instructions more slowly than eight waves issue
 // three each -- DMA-only loop 0.436 -> 0.490 ms -- and at 96 VGPRs the residual epilogue spills.  profiles/r03_ntp_ablation.txt)
+#ifdef MBX_DIAG         // the stamps of this kernel: slot 0, four per k-tile, two for the epilogue -- of one workgroup
+static constexpr int NTP_TRACE_WG = 4000;
+static constexpr int ntp_trace_slots(int nk) { return 3 + 4 * nk; }
+#endif
 template <int EPI>
 __global__ __launch_bounds__(512, 4) void gemm_nt_pipe_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ W,
                                                               const float* __restrict__ bias, bf16_t* __restrict__ out_t,
@@ -181,12 +185,12 @@ __global__ __launch_bounds__(512, 4) void gemm_nt_pipe_kernel(const bf16_t* __re
     }
     const int i = lane & 31, g = lane >> 5;
     int stage = 0;
-    // diagnostics: cycle stamps of one wave of one workgroup (MBX_TRACE_BUF), 4 per k-tile + 2 for the epilogue
-    const bool tr_on = trace != nullptr && blockIdx.x == 4000 && tid == 0;
+    // diagnostics (tools/nt_trace.py): cycle stamps of one wave of workgroup NTP_TRACE_WG, 1 + 4 per k-tile + 2 for the epilogue
 #ifdef MBX_TRACE
-#define TSTAMP(slot_) do { if (tr_on) trace[slot_] = (long long)__builtin_readcyclecounter(); } while (0)
+    const bool tr_on = trace != nullptr && blockIdx.x == NTP_TRACE_WG && tid == 0;
+#define TSTAMP(slot_) do { if (tr_on) trace[slot_] = mbx_cycles(); } while (0)
 #else
-#define TSTAMP(slot_) do { (void)tr_on; } while (0)
+#define TSTAMP(slot_) do { (void)trace; } while (0)
 #endif
     TSTAMP(0);
     for (int kt = 0; kt < nk; ++kt) {
@@ -661,6 +665,11 @@ __device__ __forceinline__ void nt256_epilogue(f32x16_t (&acc)[2][4], char* smem
 // of the remainder), acc = A_hi W_hi^T + A_hi W_lo^T + A_lo W_hi^T on the same accumulators -- three passes over k as ONE
 // stream of 3 K/32 k-tiles through the ring (the A_lo W_lo^T term, 2^-16 relative, is dropped); products of bf16 are exact
 // in the fp32 MFMA accumulation, so the result is fp32-class (~1e-6) at a third of the bf16 rate.  T-typed tensors are fp32.
+#ifdef MBX_DIAG         // the stamps of this kernel, of one workgroup: the second wave group's record starts PP_TRACE_GROUP int64 behind the first's;
+                        // in a record slot 0 and four per k-tile, and at PP_TRACE_EDGE entry / epilogue issued / epilogue acknowledged
+static constexpr int PP_TRACE_WG = 3000, PP_TRACE_GROUP = 2048, PP_TRACE_EDGE = 1000;
+static constexpr int pp_trace_slots(int nk) { return PP_TRACE_GROUP + (4 * nk + 1 > PP_TRACE_EDGE + 3 ? 4 * nk + 1 : PP_TRACE_EDGE + 3); }
+#endif
 template <int EPI, bool X3 = false>
 __global__ __launch_bounds__(512, 2) void gemm_nt_pp256_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ W,
                                                                const bf16_t* __restrict__ A_lo, const bf16_t* __restrict__ W_lo,
@@ -683,7 +692,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp256_kernel(const bf16_t* __r
     const int wm = wave >> 2, wn = wave & 3;   // wave tile: rows [128 wm, +128), cols [64 wn, +64)
     const bool trailing = wave >= 4;            // wave-uniform (readfirstlane above)
 #ifdef MBX_DIAG
-    if (trace != nullptr && blockIdx.x == 3000 && (tid == 0 || tid == 256)) trace[(tid == 256 ? 2048 : 0) + 1000] = (long long)__builtin_readcyclecounter();
+    if (trace != nullptr && blockIdx.x == PP_TRACE_WG && (tid == 0 || tid == 256)) trace[(tid == 256 ? PP_TRACE_GROUP : 0) + PP_TRACE_EDGE] = mbx_cycles();
 #endif
 
     const int lr = lane >> 2, lp = lane & 3;
@@ -737,10 +746,10 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp256_kernel(const bf16_t* __r
     const int i = lane & 31, g = lane >> 5;
     int stage = 0;
 #ifdef MBX_DIAG
-    // cycle stamps of the first wave of each group of ONE workgroup (tools/pp_trace.py): 4 per k-tile
-    const bool tr_on = trace != nullptr && blockIdx.x == 3000 && (tid == 0 || tid == 256);
-    long long* const tr = trace + (tid == 256 ? 2048 : 0);
-#define PSTAMP(slot_) do { if (tr_on) tr[slot_] = (long long)__builtin_readcyclecounter(); } while (0)
+    // cycle stamps of the first wave of each group of workgroup PP_TRACE_WG (tools/pp_trace.py): 1 + 4 per k-tile
+    const bool tr_on = trace != nullptr && blockIdx.x == PP_TRACE_WG && (tid == 0 || tid == 256);
+    long long* const tr = trace + (tid == 256 ? PP_TRACE_GROUP : 0);
+#define PSTAMP(slot_) do { if (tr_on) tr[slot_] = mbx_cycles(); } while (0)
 #else
 #define PSTAMP(slot_) do { } while (0)
 #endif
@@ -812,11 +821,11 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp256_kernel(const bf16_t* __r
 
     nt256_epilogue<EPI, TO>(acc, smem, bias, out_t, out2_t, out_f, resid, aux, M, N, m0, n0, wave, lane, st_bias, st_rsum, st_part, pl_hi, pl_lo);
 #ifdef MBX_DIAG
-    if (trace != nullptr && blockIdx.x == 3000 && (tid == 0 || tid == 256)) {
-        long long* const tr2 = trace + (tid == 256 ? 2048 : 0);
-        tr2[1001] = (long long)__builtin_readcyclecounter();
+    if (trace != nullptr && blockIdx.x == PP_TRACE_WG && (tid == 0 || tid == 256)) {
+        long long* const tr2 = trace + (tid == 256 ? PP_TRACE_GROUP : 0);
+        tr2[PP_TRACE_EDGE + 1] = mbx_cycles();
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        tr2[1002] = (long long)__builtin_readcyclecounter();
+        tr2[PP_TRACE_EDGE + 2] = mbx_cycles();
     }
 #endif
 }
@@ -827,21 +836,20 @@ static int set_lds_attr(K kernel, size_t bytes, const char* who) {
 }
 
 // The kernels' trailing diagnostic arguments (gemm_nt_pipe_kernel: dbg, trace; gemm_nt_pp256_kernel: trace), made HERE and nowhere else:
-// none in the product build, the MBX_DBG switches and the MBX_TRACE_BUF stamp buffer in a -DMBX_DIAG build (`live` = false: the entries
-// that were never wired to the environment pass 0 / NULL).  launch_diag appends them to the kernel's arguments.
+// none in the product build, the MBX_DBG switches and the armed stamp buffer (mbx_diag.h) in a -DMBX_DIAG build (`live` = false: the
+// entries that were never wired pass 0 / NULL).  launch_diag appends them to the kernel's arguments.  nk = the k-tiles the kernel stamps:
+// the buffer is handed over only if it holds every slot those can touch.
 #ifdef MBX_DIAG
-static long long* diag_trace_buf() {
-    static long long* const buf = [] { const char* e = getenv("MBX_TRACE_BUF"); return e ? (long long*)strtoull(e, nullptr, 0) : (long long*)nullptr; }();
-    return buf;
-}
-static std::tuple<int, long long*> ntp_diag(bool live) {
+static std::tuple<int, long long*> ntp_diag(bool live, int nk) {
     static const int dbg = mbx_env_int("MBX_DBG", 0);
-    return {live ? dbg : 0, live ? diag_trace_buf() : nullptr};
+    return {live ? dbg : 0, live ? mbx_diag_trace((size_t)ntp_trace_slots(nk) * sizeof(long long)) : nullptr};
 }
-static std::tuple<long long*> pp256_diag(bool live) { return {live ? diag_trace_buf() : nullptr}; }
+static std::tuple<long long*> pp256_diag(bool live, int nk) {
+    return {live ? mbx_diag_trace((size_t)pp_trace_slots(nk) * sizeof(long long)) : nullptr};
+}
 #else
-static std::tuple<> ntp_diag(bool) { return {}; }
-static std::tuple<> pp256_diag(bool) { return {}; }
+static std::tuple<> ntp_diag(bool, int) { return {}; }
+static std::tuple<> pp256_diag(bool, int) { return {}; }
 #endif
 template <class Kern, class Diag, class... Args>
 static void launch_diag(Kern kernel, dim3 grid, size_t shm, hipStream_t s, const Diag& diag, Args... args) {
@@ -857,7 +865,7 @@ static int launch_pp256(const char* who, const void* a, const void* w, const voi
     const int ntn = (N + Q_BN - 1) / Q_BN, ntm = (M + Q_BM - 1) / Q_BM;
     const size_t shm = Q_NSTAGE * Q_STAGE;
     if (set_lds_attr(gemm_nt_pp256_kernel<EPI, X3>, shm, who)) return 1;
-    launch_diag(gemm_nt_pp256_kernel<EPI, X3>, dim3((unsigned)ntn * ntm), shm, s, pp256_diag(!X3), (const bf16_t*)a, (const bf16_t*)w,
+    launch_diag(gemm_nt_pp256_kernel<EPI, X3>, dim3((unsigned)ntn * ntm), shm, s, pp256_diag(!X3, K / Q_BK), (const bf16_t*)a, (const bf16_t*)w,
                 (const bf16_t*)a_lo, (const bf16_t*)w_lo, bias, (TO*)out_t, (TO*)out2_t, out_f, resid, (const TO*)aux, M, N, K, ntn, st_bias,
                 st_rsum, st_part, (bf16_t*)pl_hi, (bf16_t*)pl_lo);
     MBX_LAUNCH_CHECK(who);
@@ -887,7 +895,7 @@ int mbx_launch_gemm_nt_x3(const void* a_hi, const void* a_lo, const void* w_hi, 
 
 // the 256 x 128 kernel: the generic epilogues and the two LayerNorm-backward ones (rowc, extra, ln).  env_wired = false is
 // mbx_gemm_nt_lnbwd_t, which never read the environment: in EVERY build it ignores MBX_NTP_LDS_PAD (no LDS padding, product build
-// included), and in a -DMBX_DIAG build it passes dbg = 0 / trace = NULL instead of MBX_DBG / MBX_TRACE_BUF.  Kept as it was.
+// included), and in a -DMBX_DIAG build it passes dbg = 0 / trace = NULL instead of MBX_DBG / the armed buffer.  Kept as it was.
 template <int EPI>
 static int launch_ntp(const char* who, const void* a, const void* w, const float* bias, void* out_t, void* out2_t, float* out_f,
                       const float* resid, const void* aux, int M, int N, int K, hipStream_t s, const float* rowc = nullptr,
@@ -895,7 +903,7 @@ static int launch_ntp(const char* who, const void* a, const void* w, const float
     const int ntn = (N + P_BN - 1) / P_BN, ntm = (M + P_BM - 1) / P_BM;
     const size_t shm = P_NSTAGE * P_STAGE + (env_wired ? (size_t)mbx_env_int("MBX_NTP_LDS_PAD", 0) * 1024 : 0);   // diagnostics: padding -> one workgroup per CU
     if (set_lds_attr(gemm_nt_pipe_kernel<EPI>, shm, who)) return 1;
-    launch_diag(gemm_nt_pipe_kernel<EPI>, dim3((unsigned)ntn * ntm), shm, s, ntp_diag(env_wired), (const bf16_t*)a, (const bf16_t*)w, bias,
+    launch_diag(gemm_nt_pipe_kernel<EPI>, dim3((unsigned)ntn * ntm), shm, s, ntp_diag(env_wired, K / P_BK), (const bf16_t*)a, (const bf16_t*)w, bias,
                 (bf16_t*)out_t, (bf16_t*)out2_t, out_f, resid, (const bf16_t*)aux, M, N, K, ntn, reinterpret_cast<const float4*>(rowc), extra, ln);
     MBX_LAUNCH_CHECK(who);
     return 0;
@@ -1171,8 +1179,9 @@ static constexpr int U_TILE = U_BMS * 512, U_STAGE = 2 * U_TILE;   // 16 KiB per
 
 // X3 (precision 'bf16x3'): dW = dY_hi^T A_hi + dY_hi^T A_lo + dY_lo^T A_hi, the three passes laid end to end as ONE token
 // stream of 3 * ceil(M / 32) chunks (pass p: tokens of (dY_hi, A_hi), (dY_hi, A_lo), (dY_lo, A_hi)); db sums passes 0 and 2.
-#ifdef MBX_TN_TRACE
+#ifdef MBX_TN_TRACE     // diagnostic builds (tools/tn_trace.py): TN_TRACE_SLOTS int64 for each of the two wave groups of every workgroup
 __device__ long long* g_tn_trace;
+static constexpr int TN_TRACE_SLOTS = 5;
 #endif
 template <bool X3>
 __global__ __launch_bounds__(512, 2) void gemm_tn_pipe256_kernel(const bf16_t* __restrict__ dY, const bf16_t* __restrict__ A,
@@ -1312,9 +1321,9 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_pipe256_kernel(const bf16_t* _
     } while (0)
 #define U_BARRIER() do { __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_sched_barrier(0); } while (0)
     int stage = 0;
-#ifdef MBX_TN_TRACE     // diagnostic builds (tools/tn_trace.py): cycles of wave 0 / wave 4 of every workgroup in the four parts of a chunk, summed
-    long long tt[4] = {0, 0, 0, 0}, t0 = (long long)__builtin_readcyclecounter();
-#define TN_TS(k_) do { const long long t1_ = (long long)__builtin_readcyclecounter(); tt[k_] += t1_ - t0; t0 = t1_; __builtin_amdgcn_sched_barrier(0); } while (0)
+#ifdef MBX_TN_TRACE     // cycles of wave 0 / wave 4 of every workgroup in the four parts of a chunk, summed; the number of chunks
+    long long tt[TN_TRACE_SLOTS - 1] = {}, t0 = mbx_cycles();
+#define TN_TS(k_) do { const long long t1_ = mbx_cycles(); tt[k_] += t1_ - t0; t0 = t1_; __builtin_amdgcn_sched_barrier(0); } while (0)
 #else
 #define TN_TS(k_) do { } while (0)
 #endif
@@ -1344,8 +1353,8 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_pipe256_kernel(const bf16_t* _
     }
 #ifdef MBX_TN_TRACE
     if (g_tn_trace != nullptr && (tid == 0 || tid == 256)) {
-        long long* const tr = g_tn_trace + ((size_t)blockIdx.x * 2 + (tid == 256)) * 5;
-        tr[0] = tt[0]; tr[1] = tt[1]; tr[2] = tt[2]; tr[3] = tt[3]; tr[4] = nc;
+        long long* const tr = g_tn_trace + ((size_t)blockIdx.x * 2 + (tid == 256)) * TN_TRACE_SLOTS;
+        tr[0] = tt[0]; tr[1] = tt[1]; tr[2] = tt[2]; tr[3] = tt[3]; tr[TN_TRACE_SLOTS - 1] = nc;
     }
 #endif
 #undef TN_TS
@@ -1435,13 +1444,11 @@ static int launch_tn256(const TnPlan& p, const void* dy, const void* a, const vo
     const char* who = X3 ? "gemm_tn_x3" : "gemm_tn_pipe256";
     const size_t shm = 4 * U_STAGE;
     if (set_lds_attr(gemm_tn_pipe256_kernel<X3>, shm, who)) return 1;
-#ifdef MBX_TN_TRACE
-    if (!X3) {
-        static long long* const tb = [] { const char* e = getenv("MBX_TRACE_BUF"); return e ? (long long*)strtoull(e, nullptr, 0) : (long long*)nullptr; }();
-        (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_tn_trace), &tb, sizeof(tb), 0, hipMemcpyHostToDevice, s);
-    }
+    const int grid = 8 * ((p.splits + 7) / 8) * p.tiles;
+#ifdef MBX_TN_TRACE     // (X3 too: its grid differs from the bf16 launch that may have armed the symbol before it)
+    mbx_diag_arm(HIP_SYMBOL(g_tn_trace), (size_t)grid * 2 * TN_TRACE_SLOTS * sizeof(long long), s);
 #endif
-    hipLaunchKernelGGL(gemm_tn_pipe256_kernel<X3>, dim3(8 * ((p.splits + 7) / 8) * p.tiles), dim3(512), shm, s, (const bf16_t*)dy, (const bf16_t*)a,
+    hipLaunchKernelGGL(gemm_tn_pipe256_kernel<X3>, dim3(grid), dim3(512), shm, s, (const bf16_t*)dy, (const bf16_t*)a,
                        (const bf16_t*)dy_lo, (const bf16_t*)a_lo, p.part_w(ws, dw), p.part_b(ws, db), M, N, K, p.ntk, p.tiles, p.splits, p.cps);
     MBX_LAUNCH_CHECK(who);
     return tn_finalize(p, ws, dw, db, N, K, s);

@@ -18,10 +18,8 @@
 //     complete a 128-byte line.
 #include "mbx_common.h"
 #include "lds_stream.h"
+#include "mbx_diag.h"
 
-#ifndef MBX_ROWS_DBG
-#define MBX_ROWS_DBG 0      // ablation bits of diagnostic builds (timing only): 1 no epilogue, 2 no LDS-DMA, 4 no fragment reads, 16 no MFMAs
-#endif
 static constexpr int R_BM = 128;               // token rows per workgroup
 static constexpr int R_SL = 8;                 // MFMA slots (= weight fragments) per ring stage
 static constexpr int R_STAGE = R_SL * 1024;
@@ -70,12 +68,13 @@ __host__ __device__ constexpr int rows_vm_window(int p, bool own, bool prev) {
     return n;
 }
 
-// Diagnostic builds only (-DMBX_ROWS_TRACE, tools/rows_trace.py): 8 int64 per workgroup -- s_memrealtime (100 MHz) at entry, after the
+// Diagnostic builds only (-DMBX_ROWS_TRACE, tools/rows_trace.py): ROWS_TRACE_SLOTS int64 per workgroup -- s_memrealtime (100 MHz) at entry, after the
 // prologue (operand in registers, first stages landed), after chunk 0, at half of the chunks, after the loop, after the last epilogue
 // with its stores acknowledged; the hardware id; the shader cycles of the whole workgroup.
 #ifdef MBX_ROWS_TRACE
 __device__ long long* g_rows_trace;
-#define RS_STAMP(slot_) do { tsr[slot_] = (long long)wall_clock64(); __builtin_amdgcn_sched_barrier(0); } while (0)      // (kept in scalar registers until the end)
+static constexpr int ROWS_TRACE_SLOTS = 8;
+#define RS_STAMP(slot_) MBX_STAMP(tsr[slot_])      // (kept in scalar registers until the end)
 #else
 #define RS_STAMP(slot_) do { } while (0)
 #endif
@@ -92,7 +91,7 @@ __global__ __launch_bounds__(256, 2) void rows_nk_kernel(const void* __restrict_
     const int i = lane & 31, g = lane >> 5;
 #ifdef MBX_ROWS_TRACE
     long long tsr[6] = {0, 0, 0, 0, 0, 0};
-    const long long cyc0 = (long long)__builtin_readcyclecounter();
+    const long long cyc0 = mbx_cycles();
 #endif
     RS_STAMP(0);
     // Work units: the first `nfull` workgroups (whole rounds of the chip: 2 per CU) take one 128-row tile each and all of N; the row
@@ -310,11 +309,11 @@ __global__ __launch_bounds__(256, 2) void rows_nk_kernel(const void* __restrict_
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     RS_STAMP(5);
     if (g_rows_trace != nullptr && threadIdx.x == 0) {
-        long long* const tr = g_rows_trace + (size_t)blockIdx.x * 8;
+        long long* const tr = g_rows_trace + (size_t)blockIdx.x * ROWS_TRACE_SLOTS;
 #pragma unroll
         for (int k = 0; k < 6; ++k) tr[k] = tsr[k];
-        tr[6] = (long long)__builtin_amdgcn_s_getreg(63492) | ((long long)__builtin_amdgcn_s_getreg(63508) << 32);
-        tr[7] = (long long)__builtin_readcyclecounter() - cyc0;
+        tr[6] = mbx_hw_id();
+        tr[ROWS_TRACE_SLOTS - 1] = mbx_cycles() - cyc0;
     }
 #endif
 }
@@ -343,13 +342,11 @@ static int launch_rows_nk(const void* a, const void* packed, const float* bias, 
     for (int pp = 8; pp > 1; --pp)
         if (nch % pp == 0 && (tiles - nfull) * pp <= slots) { parts = pp; break; }
     if (parts == 1) nfull = tiles;
+    const int grid = nfull + (tiles - nfull) * parts;
 #ifdef MBX_ROWS_TRACE
-    {
-        static long long* const tb = [] { const char* e = getenv("MBX_TRACE_BUF"); return e ? (long long*)strtoull(e, nullptr, 0) : (long long*)nullptr; }();
-        (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_rows_trace), &tb, sizeof(tb), 0, hipMemcpyHostToDevice, s);
-    }
+    mbx_diag_arm(HIP_SYMBOL(g_rows_trace), (size_t)grid * ROWS_TRACE_SLOTS * sizeof(long long), s);
 #endif
-    hipLaunchKernelGGL((rows_nk_kernel<K, EPI, FROMX>), dim3(nfull + (tiles - nfull) * parts), dim3(256), shm, s, a, (const char*)packed, bias,
+    hipLaunchKernelGGL((rows_nk_kernel<K, EPI, FROMX>), dim3(grid), dim3(256), shm, s, a, (const char*)packed, bias,
                        rsum, mean, rstd, (bf16_t*)out, eps, M, N, nfull, parts);
     MBX_LAUNCH_CHECK("rows_gemm_nk");
     return 0;

@@ -35,16 +35,15 @@
 // ran 4 us slower than the others (profiles/r06_rn_trace.txt).
 #include "mbx_common.h"
 #include "lds_stream.h"
+#include "mbx_diag.h"
 
-#ifndef MBX_RN_DBG
-#define MBX_RN_DBG 0        // ablation bits of diagnostic builds (timing only, results wrong): 1 no epilogue, 2 no loop (prologue + epilogue only)
-#endif
-// Diagnostic builds only (-DMBX_RN_TRACE, tools/rn_trace.py): 12 int64 per workgroup of the LayerNorm-backward kernel (wave 0, lane 0) --
+// Diagnostic builds only (-DMBX_RN_TRACE, tools/rn_trace.py): RN_TRACE_SLOTS int64 per workgroup of the LayerNorm-backward kernel (wave 0, lane 0) --
 // s_memrealtime (100 MHz) at entry, first stage landed, end of the loop, after the drain + barrier, after xhat -> LDS, after pass 1,
-// after each quarter of pass 2 (stores issued), stores acknowledged.  The buffer address comes from the environment variable MBX_TRACE_BUF.
+// after each quarter of pass 2 (stores issued), stores acknowledged; the hardware id.
 #ifdef MBX_RN_TRACE
 __device__ long long* g_rn_trace;
-#define RN_TS(slot_) do { tsr[slot_] = (long long)wall_clock64(); __builtin_amdgcn_sched_barrier(0); } while (0)      // (kept in scalar registers until the end)
+static constexpr int RN_TRACE_SLOTS = 12;
+#define RN_TS(slot_) MBX_STAMP(tsr[slot_])      // (kept in scalar registers until the end)
 #else
 #define RN_TS(slot_) do { } while (0)
 #endif
@@ -202,7 +201,7 @@ __global__ __launch_bounds__(256, 1) void rows_n_lnbwd_kernel(const bf16_t* __re
     constexpr int RN_N = RnGeo<NT>::N, NQ = RnGeo<NT>::NQ;
     extern __shared__ __attribute__((aligned(16))) char ring[];
 #ifdef MBX_RN_TRACE
-    long long tsr[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    long long tsr[RN_TRACE_SLOTS - 1] = {};
 #endif
     RN_TS(0);
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -370,10 +369,10 @@ __global__ __launch_bounds__(256, 1) void rows_n_lnbwd_kernel(const bf16_t* __re
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     RN_TS(10);
     if (g_rn_trace != nullptr && threadIdx.x == 0) {
-        long long* const tr = g_rn_trace + (size_t)blockIdx.x * 12;
+        long long* const tr = g_rn_trace + (size_t)blockIdx.x * RN_TRACE_SLOTS;
 #pragma unroll
-        for (int k = 0; k < 11; ++k) tr[k] = tsr[k];
-        tr[11] = (long long)__builtin_amdgcn_s_getreg(63492) | ((long long)__builtin_amdgcn_s_getreg(63508) << 32);
+        for (int k = 0; k < RN_TRACE_SLOTS - 1; ++k) tr[k] = tsr[k];
+        tr[RN_TRACE_SLOTS - 1] = mbx_hw_id();
     }
 #endif
 }
@@ -572,17 +571,15 @@ extern "C" int mbx_rows_lnbwd_t(const void* dy, const void* packed, const void* 
     MBX_CHECK_ARG(dx_t != dres_t && dx_t != xhat && dx_t != dy, "rows_lnbwd_t: dx_t aliases an input (rows past M re-read row M - 1 after it was stored)");
     const void* kern = N == 512 ? reinterpret_cast<const void*>(rows_n_lnbwd_kernel<16>) : reinterpret_cast<const void*>(rows_n_lnbwd_kernel<8>);
     if (mbx_set_dyn_lds(kern, RN_RING + 4 * 8192, "rows_lnbwd_t")) return 1;
+    const int grid = (M + RN_BM - 1) / RN_BM;
 #ifdef MBX_RN_TRACE
-    {
-        static long long* const tb = [] { const char* e = getenv("MBX_TRACE_BUF"); return e ? (long long*)strtoull(e, nullptr, 0) : (long long*)nullptr; }();
-        (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_rn_trace), &tb, sizeof(tb), 0, hipMemcpyHostToDevice, (hipStream_t)stream);
-    }
+    mbx_diag_arm(HIP_SYMBOL(g_rn_trace), (size_t)grid * RN_TRACE_SLOTS * sizeof(long long), (hipStream_t)stream);
 #endif
     if (N == 512)
-        hipLaunchKernelGGL(rows_n_lnbwd_kernel<16>, dim3((M + RN_BM - 1) / RN_BM), dim3(256), RN_RING + 4 * 8192, (hipStream_t)stream, (const bf16_t*)dy,
+        hipLaunchKernelGGL(rows_n_lnbwd_kernel<16>, dim3(grid), dim3(256), RN_RING + 4 * 8192, (hipStream_t)stream, (const bf16_t*)dy,
                            (const char*)packed, (const bf16_t*)xhat, rstd, (const bf16_t*)dres_t, (bf16_t*)dx_t, M, K);
     else
-        hipLaunchKernelGGL(rows_n_lnbwd_kernel<8>, dim3((M + RN_BM - 1) / RN_BM), dim3(256), RN_RING + 4 * 8192, (hipStream_t)stream, (const bf16_t*)dy,
+        hipLaunchKernelGGL(rows_n_lnbwd_kernel<8>, dim3(grid), dim3(256), RN_RING + 4 * 8192, (hipStream_t)stream, (const bf16_t*)dy,
                            (const char*)packed, (const bf16_t*)xhat, rstd, (const bf16_t*)dres_t, (bf16_t*)dx_t, M, K);
     MBX_LAUNCH_CHECK("rows_lnbwd_t");
     return 0;

@@ -35,9 +35,11 @@ int mbx_set_dyn_lds(const void* kernel, size_t bytes, const char* who);
 int mbx_cu_count();
 
 // ---------------------------------------------------------------- diagnostics switches
-// The product library reads NO environment variables: every kernel choice is fixed at build time.  A/B variants and
-// ablation switches exist only in -DMBX_DIAG builds (tools/build_variants.py -> tools/variants/libmbx_*.so, loaded by the
-// measurement scripts through MBX_LIB), where mbx_env_int() consults the environment.
+// The product library reads NO environment variables: every kernel choice is fixed at build time.  Only a -DMBX_DIAG build
+// (tools/build_variants.py -> tools/variants/libmbx_*.so, loaded by the measurement scripts through MBX_LIB) consults the
+// environment, through mbx_env_int() and for two variables: MBX_DBG (ablation bits of the gemm_pipe.hip kernels) and
+// MBX_NTP_LDS_PAD (KiB of LDS padding of the 256 x 128 kernel).  The trace builds (-DMBX_TRACE, -DMBX_*_TRACE) read none either:
+// their stamp buffer arrives through mbx_diag_set_trace (mbx_diag.h), their ablation bits (-DMBX_*_DBG) are compile-time.
 #ifdef MBX_DIAG
 #include <stdlib.h>
 static inline int mbx_env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }

@@ -41,13 +41,8 @@
 #include "gelu_fast.h"
 
 #include "lds_stream.h"
+#include "mbx_diag.h"       // MBX_MLP_DBG ablation bits (tools/build_variants.py name -DMBX_MLP_DBG=bits), MBX_MLP_TRACE stamps
 
-// Ablation switches of diagnostic builds (tools/build_variants.py name -DMBX_MLP_DBG=bits; results are wrong, timing only):
-// 1 no GELU micro-steps beside fc2, 2 no LDS-DMA in the loop, 4 no fragment reads, 8 no epilogue, 16 no MFMAs, 32 no barriers,
-// 64 no stages at all (prologue + epilogue only), 128 GELU micro-steps spread over all four stages of a chunk (dummy source)
-#ifndef MBX_MLP_DBG
-#define MBX_MLP_DBG 0
-#endif
 // The tile's one-touch activation traffic is non-temporal: the stores of y in the epilogue and the LDS-DMA loads of o and the residual
 // rows in the prologue.  (The weight stream, 2.5 MiB that all 32 CUs of an XCD re-read every tile, competes with ~20 MiB of
 // activations per tile period for the 4 MiB L2.)  Measured in three sessions (profiles/r05_mlp_variants.txt): -1.6 / -2.7 / -2.2 %
@@ -114,15 +109,16 @@ __device__ __forceinline__ float2 ge_bias_ld(const char* p) {
 // (the accumulator layout holds columns 8 q + 4 g + e of a token, an operand fragment 8 consecutive ones: one v_permlane32_swap
 // per register pair) and takes the LayerNorm statistics of y1 from the same values.  y1 never exists in HBM (- 8 bytes per element),
 // one launch less per Block half.
-// Diagnostic builds only (tools/build_variants.py name -DMBX_MLP_TRACE; tools/mlp_trace.py): 24 int64 per workgroup (wave 0):
+// Diagnostic builds only (tools/build_variants.py name -DMBX_MLP_TRACE; tools/mlp_trace.py): MLP_TRACE_SLOTS int64 per workgroup (wave 0):
 // s_memrealtime ticks (100 MHz) in slots 0..14 (phases) and 16..20 (the four stages of chunk 8), the hardware id in slot 15, the
-// shader-cycle counter at entry / exit in slots 22 / 23.  The buffer address comes from the environment variable MBX_TRACE_BUF.
+// shader-cycle counter at entry / exit in slots 22 / 23.
 #ifdef MBX_MLP_TRACE
 __device__ long long* g_mlp_trace;
-#define MF_TS(slot_) do { if (tr_on) tr[slot_] = (long long)wall_clock64(); __builtin_amdgcn_sched_barrier(0); } while (0)
+static constexpr int MLP_TRACE_SLOTS = 24;
+#define MF_TS(slot_) MBX_STAMP_IF(tr_on, tr[slot_])
 // (the stage stamps inside the chunk loop stay in scalar registers and are written out at the end: nothing for the loop to carry in VGPRs)
 #if MBX_MLP_TRACE + 0 >= 2      // (a second trace build: these five stamps cost the register allocator 20 bytes of scratch in the PROJ form)
-#define MF_TSC(slot_) do { if (c == 8) tsc[(slot_) - 16] = (long long)wall_clock64(); __builtin_amdgcn_sched_barrier(0); } while (0)
+#define MF_TSC(slot_) MBX_STAMP_IF(c == 8, tsc[(slot_) - 16])
 #else
 #define MF_TSC(slot_) do { } while (0)
 #endif
@@ -165,10 +161,10 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_kernel(const bf16_t* __restr
     float* const bps = reinterpret_cast<float*>(smem + F_RING + (size_t)(2 * hidden + C) * 4 + (C == 512 ? 4 * 4096 : 0));   // PROJ: bp [C] behind everything else
 #ifdef MBX_MLP_TRACE
     const bool tr_on = g_mlp_trace != nullptr && tid == 0;
-    long long* const tr = g_mlp_trace + (size_t)blockIdx.x * 24;
-    if (tr_on) { tr[15] = (long long)__builtin_amdgcn_s_getreg(63492) | ((long long)__builtin_amdgcn_s_getreg(63508) << 32); tr[22] = (long long)__builtin_readcyclecounter(); }
-#endif
+    long long* const tr = g_mlp_trace + (size_t)blockIdx.x * MLP_TRACE_SLOTS;
+    if (tr_on) { tr[15] = mbx_hw_id(); tr[MLP_TRACE_SLOTS - 2] = mbx_cycles(); }
     long long tsc[5] = {0, 0, 0, 0, 0};
+#endif
     MF_TS(0);
 
     // (Measured and dropped, round 4: a start stagger of the first workgroup of every CU by k/8 of a tile period, to run the memory
@@ -604,7 +600,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fused_kernel(const bf16_t* __restr
     MF_TS(13);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     MF_TS(14);
-    if (tr_on) { tr[23] = (long long)__builtin_readcyclecounter(); tr[16] = tsc[0]; tr[17] = tsc[1]; tr[18] = tsc[2]; tr[19] = tsc[3]; tr[20] = tsc[4]; }
+    if (tr_on) { tr[MLP_TRACE_SLOTS - 1] = mbx_cycles(); tr[16] = tsc[0]; tr[17] = tsc[1]; tr[18] = tsc[2]; tr[19] = tsc[3]; tr[20] = tsc[4]; }
 #endif
     if (want_stats) {
         constexpr float nh = (float)(C / 2);                          // values per lane
@@ -639,13 +635,11 @@ static int launch_mlp_fused(const void* a, const void* packed, const float* b1, 
                             const float* bp = nullptr) {
     const size_t shm = F_RING + (size_t)(2 * hidden + C) * sizeof(float) + (C == 512 ? 4 * 4096 : 0) + (PROJ ? C * sizeof(float) : 0);
     if (mbx_set_dyn_lds(reinterpret_cast<const void*>(mlp_fused_kernel<C, PROJ>), shm, "mlp_fused_fwd")) return 1;
+    const int grid = (M + F_BM - 1) / F_BM;
 #ifdef MBX_MLP_TRACE
-    {
-        static long long* const tb = [] { const char* e = getenv("MBX_TRACE_BUF"); return e ? (long long*)strtoull(e, nullptr, 0) : (long long*)nullptr; }();
-        (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_mlp_trace), &tb, sizeof(tb), 0, hipMemcpyHostToDevice, s);
-    }
+    mbx_diag_arm(HIP_SYMBOL(g_mlp_trace), (size_t)grid * MLP_TRACE_SLOTS * sizeof(long long), s);
 #endif
-    hipLaunchKernelGGL((mlp_fused_kernel<C, PROJ>), dim3((M + F_BM - 1) / F_BM), dim3(256), shm, s, (const bf16_t*)a, (const char*)packed, b1, b2,
+    hipLaunchKernelGGL((mlp_fused_kernel<C, PROJ>), dim3(grid), dim3(256), shm, s, (const bf16_t*)a, (const char*)packed, b1, b2,
                        rsum, raw_in, resid, y, (bf16_t*)yb, eps, mean, rstd, M, hidden, bp);
     MBX_LAUNCH_CHECK("mlp_fused_fwd");
     return 0;

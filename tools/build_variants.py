@@ -1,10 +1,15 @@
 """Build diagnostic / A-B variants of the kernel library next to the product one.
 
-    python tools/build_variants.py diag                      # -DMBX_DIAG: env switches (MBX_DBG, MBX_TRACE_BUF, ...) are live
+    python tools/build_variants.py diag                      # -DMBX_DIAG: the MBX_DBG / MBX_NTP_LDS_PAD environment switches are live
     python tools/build_variants.py name -DFOO=1 -DBAR=2      # any extra compile flags
 
-Output: tools/variants/libmbx_<name>.so (git-ignored, travels to the GPU box with gpurun).  The measurement scripts pick a
-variant with MBX_LIB=tools/variants/libmbx_<name>.so; the product library (motionbert_amd/libmbx.so) has no switches."""
+The diagnostic flags (csrc/mbx_diag.h): -DMBX_DIAG (with -DMBX_TRACE: the cycle stamps of nt_trace.py), -DMBX_TN_TRACE, -DMBX_ROWS_TRACE,
+-DMBX_RN_TRACE, -DMBX_MLP_TRACE (=2: five more stamps), -DMBX_ATTN_TRACE, and the ablation bits -DMBX_{ROWS,RN,MLP,ATTN}_DBG=bits.  A build
+with any of the first seven exports mbx_diag_set_trace(buf, bytes): tools/trace_common.py arms it with a sized stamp buffer, and a traced
+launch stamps only if the buffer holds what its grid writes.  No build reads a buffer address from the environment.
+
+Output: tools/variants/libmbx_<name>.so (git-ignored).  The measurement scripts pick a variant with
+MBX_LIB=tools/variants/libmbx_<name>.so; the product library (motionbert_amd/libmbx.so) has no switches."""
 import os
 import subprocess
 import sys

@@ -2,23 +2,21 @@
 per workgroup (s_memrealtime, 10 ns ticks), all workgroups of one launch (-DMBX_MLP_TRACE=2: also the four stages of one chunk).
     python tools/build_variants.py mlptrace -DMBX_MLP_TRACE
     MBX_LIB=tools/variants/libmbx_mlptrace.so python tools/mlp_trace.py [clips] [proj=1]"""
-import os
 import sys
 
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import trace_common as tc            # (first: it puts the repository root on sys.path)
+from motionbert_amd import hip_ops
 
 clips = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 proj = (sys.argv[2] if len(sys.argv) > 2 else '1') == '1'
 C, hidden, M, dev, BF = 512, 1024, clips * 243 * 17, 'cuda', torch.bfloat16
 tiles = (M + 127) // 128
-buf = torch.zeros(24 * tiles + 64, dtype=torch.int64, device=dev)
-os.environ['MBX_TRACE_BUF'] = hex(buf.data_ptr())
-from motionbert_amd import hip_ops   # noqa: E402
-
 ops = hip_ops.get()
+SLOTS = 24                           # MLP_TRACE_SLOTS (mlp_fused.hip)
+buf = tc.arm(ops, SLOTS * tiles)
 g = torch.Generator(device=dev).manual_seed(0)
 x = torch.randn(M, C, device=dev, generator=g)
 a = x.to(BF)
@@ -34,24 +32,17 @@ if proj:
 else:
     pk = ops.mlp_pack_weights(w1, w2)
     fn = lambda: ops.mlp_fused_fwd(None, 1, pk, b1, b2, rsum, x, y, None, 1e-6, None, None)
-for _ in range(3):
-    fn()
-torch.cuda.synchronize()
-e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-e0.record()
-fn()
-e1.record()
-torch.cuda.synchronize()
-t = buf.cpu().numpy()
-raw = t[:24 * tiles].reshape(tiles, 24)
+ms = tc.timed_launch(fn, buf)
+tc.check_need(ops, buf, SLOTS * tiles)
+raw = tc.records(buf, tiles, SLOTS)
+assert len(raw) == tiles, f'{len(raw)} of {tiles} workgroups wrote their record'
 st = raw[:, :16].astype(np.float64)
 cyc0, cyc1 = raw[:, 22].astype(np.float64), raw[:, 23].astype(np.float64)
 if not proj:
     st[:, 7] = st[:, 6]
 for k in (1, 2, 3):      # the pipelined prologue (round 5) is one phase: stamps 1..3 are not written
     st[:, k] = np.where(st[:, k] == 0, st[:, k - 1], st[:, k])
-t0 = st[:, 0].min()
-us = (st[:, :15] - t0) / 100.0          # 100 MHz ticks -> us since the first workgroup's entry
+us = tc.to_us(st[:, :15])               # 100 MHz ticks -> us since the first workgroup's entry
 names = ['o -> X fragments (DMA + wait + reads)', 'barrier', 'residual half 0 -> acc2', 'residual half 1 -> acc2', 'fp32 -> operand / barrier',
          'first weight stages landed', 'proj stages', 'y1 -> operand + statistics', 'A(0) + gelu(0)', 'chunk loop', 'B(n-1)',
          'drain + barrier', 'epilogue (image + stores issued)', 'stores acknowledged']
@@ -59,8 +50,9 @@ dur = np.diff(us, axis=1)
 total = us[:, 14] - us[:, 0]
 order = np.argsort(us[:, 0])
 rounds = [('first 256 workgroups', order[:256]), ('workgroups 2048..4095', order[2048:4096]), ('last 1024 workgroups', order[-1024:]), ('all', order)]
-print(f'# mlp_fused_kernel<512, {"true" if proj else "false"}> at {clips} clips: {tiles} tiles, launch {e0.elapsed_time(e1):.3f} ms (trace build), '
-      f'{e0.elapsed_time(e1) * 1e3 / (tiles / 256):.1f} us per tile round')
+rounds = [r for r in rounds if len(r[1])]      # (a launch of fewer than 2049 workgroups has no middle)
+print(f'# mlp_fused_kernel<512, {"true" if proj else "false"}> at {clips} clips: {tiles} tiles, launch {ms:.3f} ms (trace build), '
+      f'{ms * 1e3 / (tiles / 256):.1f} us per tile round')
 print(f'# effective shader clock inside a tile: {np.median((cyc1 - cyc0) / (total * 1e-6)) / 1e9:.3f} GHz (median over workgroups)')
 print(f'{"phase (median us per tile)":46s}' + ''.join(f'{n:>24s}' for n, _ in rounds))
 for k, nm in enumerate(names):

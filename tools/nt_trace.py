@@ -1,9 +1,10 @@
-"""Diagnostics: per-k-tile cycle stamps of one wave of gemm_nt_pipe (MBX_TRACE_BUF)."""
-import os, sys
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+"""Diagnostics (MBX_DIAG + MBX_TRACE build): per-k-tile cycle stamps of one wave of one workgroup (number 4000) of gemm_nt_pipe, the 256 x 128
+kernel.  It runs the resid and lnbwd epilogues, and store only for N < 256 (wider ones run gemm_nt_pp256: tools/pp_trace.py).
+    python tools/build_variants.py diagtrace -DMBX_DIAG -DMBX_TRACE
+    MBX_LIB=tools/variants/libmbx_diagtrace.so python tools/nt_trace.py [N K [store|resid|lnbwd]]"""
+import sys
 import torch
-buf = torch.zeros(4096, dtype=torch.int64, device='cuda')
-os.environ['MBX_TRACE_BUF'] = hex(buf.data_ptr())
+import trace_common as tc      # (puts the repository root on sys.path)
 from motionbert_amd import hip_ops
 from motionbert_amd.engine import EPI_STORE, EPI_RESID
 ops = hip_ops.get()
@@ -13,16 +14,15 @@ a = torch.randn(M, K, device='cuda').bfloat16(); w = torch.randn(N, K, device='c
 out = torch.empty(M, N, device='cuda', dtype=torch.bfloat16)
 outf, resid = torch.empty(M, N, device='cuda'), torch.randn(M, N, device='cuda')
 rowc = torch.rand(M, 4, device='cuda')
-for it in range(3):
-    if mode == 'resid':
-        ops.gemm_nt(a, w, None, EPI_RESID, out_f=outf, resid=resid)
-    elif mode == 'lnbwd':
-        ops.gemm_nt_lnbwd(a, w, out, rowc, resid, None, outf, torch.empty_like(out))
-    else:
-        ops.gemm_nt(a, w, None, EPI_STORE, out_t=out)
-torch.cuda.synchronize()
-t = buf.cpu().tolist()
 nk = K // 32
+buf = tc.arm(ops, 3 + 4 * nk)      # ntp_trace_slots (gemm_pipe.hip): entry, four per k-tile, epilogue issued / acknowledged
+dx_t = torch.empty_like(out)
+fn = {'resid': lambda: ops.gemm_nt(a, w, None, EPI_RESID, out_f=outf, resid=resid),
+      'lnbwd': lambda: ops.gemm_nt_lnbwd(a, w, out, rowc, resid, None, outf, dx_t),
+      'store': lambda: ops.gemm_nt(a, w, None, EPI_STORE, out_t=out)}[mode]
+tc.timed_launch(fn, buf, warm=2)
+tc.check_need(ops, buf, 3 + 4 * nk)
+t = buf.cpu().tolist()
 t0 = t[0]
 print(f'N={N} K={K} {mode}'); print('k-tile: wait(vmcnt)  barrier  issue  compute   [cycles]')
 for kt in range(nk):
