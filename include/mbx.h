@@ -557,6 +557,36 @@ int mbx_mesh_gt(const float* pose, const float* shape, const float* motion_2d, c
                 const float* lbs_weights, const float* Q, int K, float scale, float* x2d, float* theta, float* kp_3d, float* verts,
                 unsigned char* flips_used, int N, int T, int V, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- in-the-wild inference around the backbone (csrc/wild.hip; infer_wild.py:56-97, lib/data/dataset_wild.py:15-86, ------------------------
+ *      lib/utils/utils_data.py:7-29) -- mbx_version() >= 150
+ * mbx_wild_input: halpe2h36m + the normalisation of read_input for F frames of S tracks.  kp [F,26,3] f64 (x, y, confidence of the Halpe-26
+ * joints, the tracks one after another) -> y [F,17,channels] f32, channels 3 or 2 (2: without the confidence, args.no_conf).  H36M joint j
+ * takes Halpe joint {19,12,14,16,11,13,15,*,18,0,17,5,7,9,6,8,10}[j]; joint 7 = (Halpe 18 + Halpe 19) * 0.5 in all three channels.
+ * flags bit 0, pixel mode:  xy = (xy - (half_w, half_h)) / pix_scale    (half_w = w / 2, half_h = h / 2, pix_scale = min(w, h) / 2)
+ * flags bit 1, crop mode (after the pixel mode where both are set), per track, over the joints whose mapped confidence is != 0: fewer than
+ *   4 -> the track is 0 in all three channels; scale = max(xmax - xmin, ymax - ymin) * ratio, scale == 0 -> the track is 0;
+ *   xs = (xmin + xmax - scale) / 2, ys likewise; xy = ((xy - (xs, ys)) / scale - 0.5) * 2; all three channels clipped to [-1, 1].
+ * Every operation is float64 in this order, without contraction, rounded to f32 at the store: the reference's bits.
+ * chunk_tab [n_chunks,3] i32 = (track, first frame, frames) with 1 <= frames <= MBX_WILD_CHUNK, a chunk never spans tracks, every frame in
+ * exactly one chunk; seq_chunk_ptr [S+1] i32: the chunks of track s are seq_chunk_ptr[s] .. seq_chunk_ptr[s+1] - 1 (a track may have
+ * none).  Both live on the device; a row that points outside [0,F) or [0,S) is skipped.  box [S,4] f64 (may be NULL) = (xs, ys, scale,
+ * valid joints) per track, (0, 0, 0, valid joints) for a track that is zeroed; with box given it is computed in pixel-only mode too.
+ * Three launches (chunk partials -> per-track fold in chunk order -> transform), no atomics.  ws: >= mbx_wild_input_ws(F, S) bytes, 8-byte
+ * aligned; ws_bytes is checked.  F = 0 is a no-op. */
+#define MBX_WILD_CHUNK 64
+size_t mbx_wild_input_ws(int F, int S);
+int mbx_wild_input(const double* kp, const int* chunk_tab, int n_chunks, const int* seq_chunk_ptr, int S, int F, double half_w,
+                   double half_h, double pix_scale, double ratio, int flags, int channels, float* y, double* box, void* ws,
+                   size_t ws_bytes, void* stream);
+/* mbx_wild_output: infer_wild.py:81-96 for n clips of T frames, one launch.  pred [n,T,17,3] f32 (NOT modified), x [n,T,17,x_channels] f32
+ * the network input (read with flags bit 1 only), dst_frames [n] i32 on the device: clip i is written to rows dst_frames[i] ..
+ * dst_frames[i] + T - 1 of out [F,17,3] f32 (the caller guarantees that they exist; a negative entry skips the clip).
+ * flags bit 0 rootrel: joint 0 of every frame = 0; otherwise only [clip, frame 0, joint 0, z] = 0 (the reference's quirk);
+ * bit 1 gt_2d: then xy = x[..., :2]; bit 2 pixel mode: then p = p * pix_scale in f32 (pix_scale = float32(min(w, h) / 2)) and
+ * xy = f32(f64(p) + (half_w, half_h)) -- numpy's arithmetic for a float32 array times a scalar, plus a float64 array. */
+int mbx_wild_output(const float* pred, const float* x, int x_channels, const int* dst_frames, int n, int T, int flags, float pix_scale,
+                    double half_w, double half_h, float* out, void* stream);
+
 /* ---- measurement aid (bench.py `roofline.sustained_mfma_tflops`; not part of the model) --------------------------------------------
  * The bf16 MFMA rate the part sustains under its power cap with nothing but v_mfma_f32_32x32x16_bf16 in the loop (pseudo-random
  * operands; n_wg workgroups of 4 waves, `iters` x 16 MFMAs per wave).  ws: >= mbx_mfma_probe_ws(n_wg) bytes = a float sink

@@ -116,6 +116,9 @@ SIGNATURES = {
     'mbx_mesh_gt': (_i, [_vp, _vp, _vp, _vp, C.c_uint64, _f] + [_vp] * 5 + [C.POINTER(C.c_int)] + [_vp, _vp, _i, _f] + [_vp] * 5 + [_i, _i, _i, _vp, _sz, _vp]),
     'mbx_action_input': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp] + [_f] * 8 + [_i, C.c_uint64, _vp]),
     'mbx_xent_topk': (_i, [_vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp]),
+    'mbx_wild_input_ws': (_sz, [_i, _i]),
+    'mbx_wild_input': (_i, [_vp, _vp, _i, _vp, _i, _i] + [C.c_double] * 4 + [_i, _i, _vp, _vp, _vp, _sz, _vp]),
+    'mbx_wild_output': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _f, C.c_double, C.c_double, _vp, _vp]),
     'mbx_rows_n_pack_bytes': (_sz, [_i, _i]),
     'mbx_rows_lnbwd_t': (_i, [_vp] * 6 + [_i, _i, _i, _vp]),
     'mbx_rows_n_pack_many': (_i, [_i64p, _i, _i, _i, _vp]),
@@ -723,6 +726,50 @@ class HipOps:
         self._dense('xent_topk', torch.int32, N, dev, labels=labels)
         self._dense('xent_topk', torch.float64, 4, dev, acc=acc)
         self._ck(self.lib.mbx_xent_topk(_p(logits), _p(labels), N, Cc, float(grad_scale), _p(values), _p(dlogits), _p(acc), self._stream()))
+
+    # ------------------------------------------------------------------ in-the-wild inference (infer_wild.py, lib/data/dataset_wild.py)
+    def wild_input(self, kp, chunk_tab, seq_chunk_ptr, half_w, half_h, pix_scale, ratio, flags, y, box):
+        """kp [F,26,3] f64; chunk_tab [n_chunks,3] / seq_chunk_ptr [S+1] i32 (motionbert_amd.wild.chunk_table); flags bit 0 pixel mode,
+        bit 1 crop mode; y [F,17,2|3] f32; box [S,4] f64 or None; all contiguous, on the device of kp."""
+        if kp.dim() != 3 or tuple(kp.shape[1:]) != (26, 3):
+            raise RuntimeError(f'libmbx: wild_input needs kp [F,26,3], got {tuple(kp.shape)}')
+        F, dev = kp.shape[0], kp.device
+        if y.dim() != 3 or y.shape[0] != F or y.shape[1] != 17 or y.shape[2] not in (2, 3):
+            raise RuntimeError(f'libmbx: wild_input needs y [{F},17,2|3], got {tuple(y.shape)}')
+        if chunk_tab.dim() != 2 or chunk_tab.shape[1] != 3 or seq_chunk_ptr.dim() != 1 or seq_chunk_ptr.numel() < 2:
+            raise RuntimeError(f'libmbx: wild_input needs chunk_tab [n_chunks,3] and seq_chunk_ptr [S+1], got {tuple(chunk_tab.shape)} / {tuple(seq_chunk_ptr.shape)}')
+        S, n_chunks = seq_chunk_ptr.numel() - 1, chunk_tab.shape[0]
+        self._dense('wild_input', torch.float64, F * 78, dev, kp=kp)
+        self._dense('wild_input', torch.float32, F * 17 * y.shape[2], dev, y=y)
+        self._dense('wild_input', torch.int32, None, dev, chunk_tab=chunk_tab, seq_chunk_ptr=seq_chunk_ptr)
+        self._dense('wild_input', torch.float64, S * 4, dev, box=box)
+        ws = self._ws(('wildin', F, S), self.lib.mbx_wild_input_ws, F, S, device=dev)
+        self._ck(self.lib.mbx_wild_input(_p(kp), _p(chunk_tab), n_chunks, _p(seq_chunk_ptr), S, F, float(half_w), float(half_h), float(pix_scale),
+                                         float(ratio), int(flags), y.shape[2], _p(y), _p(box), _p(ws), ws.numel(), self._stream()))
+
+    def wild_output(self, pred, x, dst_frames, dst_max, flags, pix_scale, half_w, half_h, out):
+        """pred [n,T,17,3] f32 (not modified); x [n,T,17,2|3] f32 or None (read with flags bit 1, gt_2d); dst_frames [n] i32 on the device
+        with `dst_max` its largest entry (host int: the rows dst_max .. dst_max + T - 1 of out must exist, checked here); flags bit 0
+        rootrel, bit 1 gt_2d, bit 2 pixel mode; out [F,17,3] f32."""
+        if pred.dim() != 4 or tuple(pred.shape[2:]) != (17, 3) or pred.shape[1] < 1:
+            raise RuntimeError(f'libmbx: wild_output needs pred [n,T >= 1,17,3], got {tuple(pred.shape)}')
+        n, T = pred.shape[:2]
+        dev = pred.device
+        if out.dim() != 3 or tuple(out.shape[1:]) != (17, 3):
+            raise RuntimeError(f'libmbx: wild_output needs out [F,17,3], got {tuple(out.shape)}')
+        if n and not 0 <= int(dst_max) <= out.shape[0] - T:
+            raise RuntimeError(f'libmbx: wild_output: a clip of {T} frames at row {int(dst_max)} does not fit out [{out.shape[0]},17,3]')
+        xc = 0
+        if x is not None:
+            if x.dim() != 4 or tuple(x.shape[:3]) != (n, T, 17) or x.shape[3] not in (2, 3):
+                raise RuntimeError(f'libmbx: wild_output needs x [{n},{T},17,2|3], got {tuple(x.shape)}')
+            xc = x.shape[3]
+        elif int(flags) & 2:
+            raise RuntimeError('libmbx: wild_output: gt_2d needs the network input x')
+        self._dense('wild_output', torch.float32, None, dev, pred=pred, x=x, out=out)
+        self._dense('wild_output', torch.int32, n, dev, dst_frames=dst_frames)
+        self._ck(self.lib.mbx_wild_output(_p(pred), _p(x), xc, _p(dst_frames), n, T, int(flags), float(pix_scale), float(half_w), float(half_h),
+                                          _p(out), self._stream()))
 
     # ------------------------------------------------------------------ mesh recovery (train_mesh.py, lib/model/model_mesh.py, loss_mesh.py)
     def rot6d_theta_fwd(self, x6, rotmat, aa):

@@ -1,0 +1,287 @@
+"""In-the-wild inference on the device: AlphaPose detections in, 3D poses out (reference `infer_wild.py:56-97` +
+`lib/data/dataset_wild.py`, without the video reader and the renderer).
+
+    kp = read_alphapose('alphapose-results.json', focus=1)           # [F,26,3] float64, host
+    poses = infer(model, kp)                                          # [F,17,3] float32, numpy
+    tracks = read_alphapose('alphapose-results.json', by_track=True)  # idx -> [F_idx,26,3]
+    poses = infer(model, tracks, vid_size=(1920, 1080), pixel=True)   # idx -> [F_idx,17,3], every tracked person in one pass
+
+The reference runs one clip per forward at batch 1, two forwards per clip for the flip, two deep copies in `flip_data`, a `.cpu()` per
+clip, a numpy input stage on the host and one person per run (`--focus`).  Here the detections are uploaded once, `mbx_wild_input`
+(halpe2h36m + pixel / crop normalisation, float64 arithmetic in the reference's order: its bits) writes the network input of every
+track, the clips of all tracks are pooled into batches (`clip_plan`: full clips together, tails grouped by equal length), every batch is
+one `flip_tta` forward, `mbx_wild_output` writes each batch straight into its rows of ONE stitched result, and one device-to-host copy
+ends the run.
+
+    read_alphapose   the JSON part of `read_input` (dataset_wild.py:67-76); host only
+    wild_input       halpe2h36m + normalisation (:77-86) on the device
+    clip_plan        the clips of `WildDetDataset` (:94-102) pooled over tracks; host only
+    wild_output      infer_wild.py:81-96 for one batch of clips
+    infer            the loop of infer_wild.py:56-97
+
+There is no CPU path: without an injected kernel provider (`ops=`) the tensors live on the ROCm device and libmbx.so does the work."""
+from __future__ import annotations
+
+import json
+import math
+from collections import OrderedDict
+from contextlib import nullcontext as _nullcontext
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import hip_ops
+
+#: frames per chunk of the box reduction (MBX_WILD_CHUNK in include/mbx.h); a chunk never spans tracks
+CHUNK_FRAMES = 64
+PIXEL, CROP = 1, 2                       # flags of mbx_wild_input
+ROOTREL, GT_2D, OUT_PIXEL = 1, 2, 4      # flags of mbx_wild_output
+
+
+# ---------------------------------------------------------------------------------------------------------------- host: the JSON
+def read_alphapose(json_path, focus=None, by_track: bool = False):
+    """The detections of an AlphaPose result file (Halpe-26): items in file order, `keypoints` reshaped to [-1,3], float64
+    (dataset_wild.py:67-76).  `focus`: only the items with that `idx`, as the reference filters.  Returns [F,26,3]; with
+    `by_track=True` an ordered dict idx -> [F_idx,26,3], the keys in order of first appearance, file order inside a track.
+    ValueError on a joint count other than 26, on non-finite values and on an empty selection."""
+    with open(json_path, 'r') as f:
+        results = json.load(f)
+    tracks: Dict[object, List[np.ndarray]] = OrderedDict()
+    for n, item in enumerate(results):
+        if focus is not None and item['idx'] != focus:
+            continue
+        kpts = np.array(item['keypoints'], dtype=np.float64).reshape([-1, 3])
+        if kpts.shape[0] != 26:
+            raise ValueError(f'{json_path}: item {n} has {kpts.shape[0]} joints; Halpe-26 detections expected')
+        if not np.isfinite(kpts).all():
+            raise ValueError(f'{json_path}: item {n} has non-finite keypoints')
+        tracks.setdefault(item['idx'] if by_track else None, []).append(kpts)
+    if not tracks:
+        raise ValueError(f'{json_path}: no detections' + ('' if focus is None else f' with idx == {focus!r}'))
+    if by_track:
+        return OrderedDict((k, np.stack(v)) for k, v in tracks.items())
+    return np.stack(tracks[None])
+
+
+# ---------------------------------------------------------------------------------------------------------------- host: plans
+def _check_lens(seq_lens, F=None) -> List[int]:
+    lens = [int(v) for v in seq_lens]
+    if not lens or any(v < 0 for v in lens):
+        raise ValueError(f'seq_lens must be a non-empty list of track lengths >= 0, got {list(seq_lens)}')
+    if F is not None and sum(lens) != F:
+        raise ValueError(f'seq_lens {lens} sum to {sum(lens)}, not to the {F} frames given')
+    return lens
+
+
+def chunk_table(seq_lens) -> Tuple[np.ndarray, np.ndarray]:
+    """(chunk_tab [n_chunks,3] int32 = (track, first frame, frames), seq_chunk_ptr [S+1] int32) for mbx_wild_input: every track cut into
+    chunks of at most CHUNK_FRAMES frames; a chunk never spans tracks."""
+    lens = _check_lens(seq_lens)
+    rows, ptr, start = [], [0], 0
+    for s, n in enumerate(lens):
+        for f0 in range(0, n, CHUNK_FRAMES):
+            rows.append((s, start + f0, min(CHUNK_FRAMES, n - f0)))
+        ptr.append(len(rows))
+        start += n
+    return np.asarray(rows, dtype=np.int32).reshape(-1, 3), np.asarray(ptr, dtype=np.int32)
+
+
+def clip_plan(seq_lens, clip_len: int) -> List[Tuple[int, List[int]]]:
+    """The reference's clips (`WildDetDataset.__len__ / __getitem__`: ceil(F / clip_len) per track, the last one shorter) pooled over the
+    tracks of `seq_lens`: a list of groups `(T, [frame offsets])`.  The full clips of all tracks come first, as one group in frame order; then
+    the tails, grouped by equal length in order of first appearance.  A clip's offset is its first row in the frame-major arrays of all
+    tracks one after another: where it is read from the network input and where its poses go in the result."""
+    lens = _check_lens(seq_lens)
+    clip_len = int(clip_len)
+    if clip_len < 1:
+        raise ValueError(f'clip_len must be >= 1, got {clip_len}')
+    full: List[int] = []
+    tails: Dict[int, List[int]] = OrderedDict()
+    start = 0
+    for n in lens:
+        for i in range(math.ceil(n / clip_len)):
+            st, end = i * clip_len, min((i + 1) * clip_len, n)
+            if end - st == clip_len:
+                full.append(start + st)
+            else:
+                tails.setdefault(end - st, []).append(start + st)
+        start += n
+    return ([(clip_len, full)] if full else []) + list(tails.items())
+
+
+# ---------------------------------------------------------------------------------------------------------------- device stages
+def _provider(ops, where: str, t):
+    """(ops, device): an injected provider keeps the tensors where they are (the host for arrays); otherwise libmbx.so on the ROCm device"""
+    if ops is not None:
+        return ops, (t.device if isinstance(t, torch.Tensor) else torch.device('cpu'))
+    if isinstance(t, torch.Tensor) and t.is_cuda:
+        return hip_ops.get(), t.device
+    if not torch.cuda.is_available():
+        raise RuntimeError(f'{where} runs on the ROCm device; there is no CPU path')
+    return hip_ops.get(), torch.device('cuda', torch.cuda.current_device())
+
+
+def _on(dev):
+    return torch.cuda.device(dev) if dev.type == 'cuda' else _nullcontext()
+
+
+def _pixel_consts(vid_size):
+    w, h = vid_size
+    if not (w > 0 and h > 0):
+        raise ValueError(f'vid_size must be (w, h) > 0, got {vid_size!r}')
+    return float(np.float64(w) / 2.0), float(np.float64(h) / 2.0), float(min(w, h) / 2.0)      # dataset_wild.py:79-81
+
+
+def wild_input(kp, vid_size=None, scale_range=None, seq_lens=None, channels: int = 3, return_box: bool = False, ops=None):
+    """`halpe2h36m` + the normalisation of `read_input` (dataset_wild.py:77-86) on the device, bit for bit.  kp [F,26,3] float64 (tensor or
+    array; uploaded once) -> [F,17,channels] float32 on the device.  `seq_lens`: track lengths summing to F (default: one track); every
+    track gets its own crop box.
+
+    Pixel mode, `vid_size=(w, h)`: (xy - (w, h) / 2) / (min(w, h) / 2).  Crop mode, `scale_range=[r, r]`: `crop_scale` over the whole track
+    -- the box over the joints whose mapped confidence is != 0; fewer than 4 of them, or scale == 0, gives an all-zero track (all three
+    channels); every channel clipped to [-1, 1]; joints without confidence are still transformed.  With both, pixel mode runs first, as in
+    the reference; with neither, ValueError (the reference dies with UnboundLocalError).  A range with lo != hi draws a random ratio per
+    call: that belongs to training and is refused.  `channels=2` drops the confidence (args.no_conf), written directly.  Rows are
+    clip-contiguous: clip i of a track is the view `y[start + i * clip_len : start + (i + 1) * clip_len]`.
+    `return_box=True`: `(y, box)` with box [S,4] float64 = (xs, ys, scale, valid joints) per track, (0, 0, 0, valid joints) for a zeroed
+    one: crop-mode xy map back through  (v / 2 + 0.5) * scale + (xs, ys)."""
+    if not vid_size and not scale_range:
+        raise ValueError('wild_input needs vid_size (pixel mode), scale_range (crop mode) or both')
+    if channels not in (2, 3):
+        raise ValueError(f'channels must be 2 or 3, got {channels}')
+    flags, half_w, half_h, pix_scale, ratio = 0, 0.0, 0.0, 1.0, 1.0
+    if vid_size:
+        flags |= PIXEL
+        half_w, half_h, pix_scale = _pixel_consts(vid_size)
+    if scale_range:
+        lo, hi = scale_range
+        if lo != hi:
+            raise ValueError(f'scale_range {list(scale_range)} draws a random crop ratio: that is a training augmentation; inference passes [r, r] '
+                             f'(the reference: [1, 1])')
+        flags |= CROP
+        ratio = float(lo)
+    ops, dev = _provider(ops, 'motionbert_amd.wild.wild_input', kp)
+    if not isinstance(kp, torch.Tensor):
+        kp = torch.from_numpy(np.ascontiguousarray(kp, dtype=np.float64))
+    if kp.dim() != 3 or tuple(kp.shape[1:]) != (26, 3):
+        raise ValueError(f'expected Halpe-26 detections [F,26,3], got {tuple(kp.shape)}')
+    F = kp.shape[0]
+    lens = _check_lens([F] if seq_lens is None else seq_lens, F)
+    kp = kp.to(device=dev, dtype=torch.float64).contiguous()
+    y = torch.empty(F, 17, channels, dtype=torch.float32, device=dev)
+    box = torch.zeros(len(lens), 4, dtype=torch.float64, device=dev) if return_box else None
+    if F:
+        tab, ptr = chunk_table(lens)
+        both = torch.from_numpy(np.concatenate([tab.reshape(-1), ptr])).to(dev)               # one upload
+        with _on(dev):
+            ops.wild_input(kp, both[:tab.size].view(-1, 3), both[tab.size:], half_w, half_h, pix_scale, ratio, flags, y, box)
+    return (y, box) if return_box else y
+
+
+def _out_flags(rootrel, gt_2d, vid_size):
+    flags, half_w, half_h, pix_scale = (ROOTREL if rootrel else 0) | (GT_2D if gt_2d else 0), 0.0, 0.0, 1.0
+    if vid_size:
+        flags |= OUT_PIXEL
+        half_w, half_h, pix_scale = _pixel_consts(vid_size)        # infer_wild.py:95-96: min(vid_size) / 2.0 and np.array(vid_size) / 2.0
+    return flags, half_w, half_h, pix_scale
+
+
+def wild_output(pred: torch.Tensor, dst: torch.Tensor, dst_frames: Sequence[int], x: Optional[torch.Tensor] = None, rootrel: bool = False,
+                gt_2d: bool = False, vid_size=None, ops=None):
+    """The output stage of infer_wild.py:81-96 for a batch: pred [n,T,17,3] float32 (not modified; the reference writes in place) goes to
+    rows dst_frames[i] .. dst_frames[i] + T - 1 of dst [F,17,3] float32 (`dst_frames`: host integers).  `rootrel`: joint 0 of every frame
+    is 0; otherwise only [clip, frame 0, joint 0, z] is (a quirk of the reference, kept).  `gt_2d`: xy from the network input x
+    [n,T,17,2|3].  `vid_size=(w, h)`: pixel coordinates in numpy's arithmetic there -- the float32 product p * float32(min(w, h) / 2),
+    and for xy that product widened to float64, (w, h) / 2 added, the sum rounded to float32.  Returns dst."""
+    if pred.dim() != 4 or tuple(pred.shape[2:]) != (17, 3):
+        raise ValueError(f'expected pred [n,T,17,3], got {tuple(pred.shape)}')
+    n, T = pred.shape[:2]
+    frames = [int(v) for v in dst_frames]
+    if len(frames) != n:
+        raise ValueError(f'{n} clips but {len(frames)} destination offsets')
+    if dst.dim() != 3 or tuple(dst.shape[1:]) != (17, 3) or dst.dtype != torch.float32 or not dst.is_contiguous():
+        raise ValueError(f'expected a contiguous float32 dst [F,17,3], got {tuple(dst.shape)} {dst.dtype}')
+    if any(not 0 <= v <= dst.shape[0] - T for v in frames):
+        raise ValueError(f'a clip of {T} frames at one of the offsets {frames} does not fit dst [{dst.shape[0]},17,3]')
+    if gt_2d and x is None:
+        raise ValueError('gt_2d takes xy from the network input: pass x')
+    ops = hip_ops.provider(ops, 'motionbert_amd.wild.wild_output', pred, dst, x, move='pred, dst and x')
+    flags, half_w, half_h, pix_scale = _out_flags(rootrel, gt_2d, vid_size)
+    if n:
+        table = torch.tensor(frames, dtype=torch.int32).to(pred.device)
+        with _on(pred.device):
+            ops.wild_output(pred.contiguous().float(), None if x is None else x.contiguous().float(), table, max(frames), flags, pix_scale, half_w,
+                            half_h, dst)
+    return dst
+
+
+def infer(model, kp_or_tracks, *, clip_len: int = 243, vid_size=None, pixel: bool = False, flip: bool = True, rootrel: bool = False,
+          gt_2d: bool = False, no_conf: bool = False, max_batch: int = 64, ops=None):
+    """The loop of infer_wild.py:56-97.  `kp_or_tracks`: [F,26,3] detections of one person (array or tensor) -> numpy [F,17,3] float32, or
+    a dict idx -> [F_idx,26,3] (`read_alphapose(by_track=True)`) -> a dict idx -> [F_idx,17,3], every person in the same pass.
+
+    Input stage as infer_wild.py:56-61: `pixel=True` means `vid_size` without a crop, otherwise `scale_range=[1, 1]`.  The full clips of
+    all tracks go in batches of at most `max_batch`, each group of equal-length tail clips in batches of its own.  The network call is
+    `flip_tta(model, x)` (`flip`) or `model(x)`, under no_grad and eval(); `rootrel`, `gt_2d`, `no_conf` are the config switches of the
+    same names.  Every batch goes through `mbx_wild_output` into its rows of one [F,17,3] device tensor; one device-to-host copy ends the
+    run.  A DataParallel-wrapped or a bare model is accepted; `clip_len > model.maxlen` raises."""
+    net = model.module if hasattr(model, 'module') else model
+    clip_len, max_batch = int(clip_len), int(max_batch)
+    if clip_len < 1 or max_batch < 1:
+        raise ValueError(f'clip_len and max_batch must be >= 1, got {clip_len} and {max_batch}')
+    maxlen = getattr(net, 'maxlen', None)
+    if maxlen is not None and clip_len > maxlen:
+        raise ValueError(f'clip_len {clip_len} is longer than the model takes (maxlen = {maxlen})')
+    if pixel and not vid_size:
+        raise ValueError('pixel=True needs vid_size=(w, h)')
+    as_dict = isinstance(kp_or_tracks, dict)
+    if as_dict:
+        if not kp_or_tracks:
+            raise ValueError('no tracks')
+        keys = list(kp_or_tracks)
+        parts = [kp_or_tracks[k] for k in keys]
+        for k, p in zip(keys, parts):
+            if len(p.shape) != 3 or tuple(p.shape[1:]) != (26, 3):
+                raise ValueError(f'track {k!r}: expected Halpe-26 detections [F,26,3], got {tuple(p.shape)}')
+        lens = [int(p.shape[0]) for p in parts]
+        if all(isinstance(p, torch.Tensor) for p in parts):
+            kp = torch.cat([p.to(torch.float64) for p in parts])
+        else:
+            kp = np.concatenate([np.asarray(p.cpu() if isinstance(p, torch.Tensor) else p, dtype=np.float64) for p in parts])
+    else:
+        kp, lens = kp_or_tracks, None
+    if ops is None and not isinstance(kp, torch.Tensor):
+        dev = hip_ops.model_device(net, 'motionbert_amd.wild.infer')
+        kp = torch.from_numpy(np.ascontiguousarray(kp, dtype=np.float64)).to(dev)             # the one upload
+    y = wild_input(kp, vid_size=vid_size if pixel else None, scale_range=None if pixel else [1, 1], seq_lens=lens,
+                   channels=2 if no_conf else 3, ops=ops)
+    F, dev = y.shape[0], y.device
+    lens = [F] if lens is None else lens
+    out = torch.empty(F, 17, 3, dtype=torch.float32, device=dev)
+    plan = clip_plan(lens, clip_len)
+    prov = hip_ops.provider(ops, 'motionbert_amd.wild.infer', y)
+    flags, half_w, half_h, pix_scale = _out_flags(rootrel, gt_2d, vid_size if pixel else None)
+    offsets = [o for _, offs in plan for o in offs]
+    table = torch.tensor(offsets, dtype=torch.int32).to(dev) if offsets else None              # every batch's destinations, one upload
+    if hasattr(model, 'eval'):
+        model.eval()
+    from .augment import flip_tta
+    at = 0
+    with torch.no_grad(), _on(dev):
+        for T, offs in plan:
+            for b0 in range(0, len(offs), max_batch):
+                part = offs[b0:b0 + max_batch]
+                n = len(part)
+                if all(part[i + 1] - part[i] == T for i in range(n - 1)):
+                    x = y[part[0]:part[0] + n * T].view(n, T, 17, y.shape[2])                  # consecutive clips: a view
+                else:
+                    x = torch.stack([y[o:o + T] for o in part])
+                pred = flip_tta(net, x) if flip else model(x)                                  # infer_wild.py:73-80
+                prov.wild_output(pred.contiguous().float(), x if gt_2d else None, table[at:at + n], max(part), flags, pix_scale, half_w, half_h, out)
+                at += n
+    res = out.cpu().numpy()                                                                    # the one device-to-host copy
+    if not as_dict:
+        return res
+    ends = np.cumsum(lens)
+    return OrderedDict((k, res[e - n:e]) for k, e, n in zip(keys, ends, lens))
