@@ -587,6 +587,54 @@ int mbx_wild_input(const double* kp, const int* chunk_tab, int n_chunks, const i
 int mbx_wild_output(const float* pred, const float* x, int x_channels, const int* dst_frames, int n, int T, int flags, float pix_scale,
                     double half_w, double half_h, float* out, void* stream);
 
+/* ---- in-the-wild mesh recovery (csrc/smpl.hip, csrc/wild.hip; infer_wild_mesh.py:42-56,108-154) -- mbx_version() >= 160 ----------------------
+ * mbx_wild_mesh: infer_wild_mesh.py:115-141 for n clips of T frames (nT = n T) after the two network calls, written straight to each
+ * clip's rows of the stitched results.  Pass A: rotmat_a [nT,24,9], betas_a [nT,10], the head's output on x.  Pass B (theta_b [nT,82], the
+ * head's theta on flip_data(x); NULL: single-pass mode): pose = flip_thetas (utils_mesh.py:458-484) of theta_b[:, :72], R = Rodrigues in the
+ * form of mbx_mesh_gt (angle = |r + 1e-8|), shape = theta_b[:, 72:].  Model arrays, parents, Q [K,V], scale as mbx_smpl_fwd takes them.
+ * dst_frames [n] i32 ON THE DEVICE: clip i goes to rows dst_frames[i] .. dst_frames[i] + T - 1; dst_max: the largest entry, from the host's
+ * plan (dst_max + T > F is refused; a device entry outside [0, F - T] skips its clip).  Outputs, each may be NULL (not all three), with x and
+ * kp of a pass what mbx_smpl_fwd gives for its parameters:
+ *   verts [F,V,3]  (scale x_a + scale x_b) * 0.5        kp [F,K,3]  (kp_a + kp_b) * 0.5
+ *   theta [F,82]   (theta_a + [flipped pose_b | shape_b]) * 0.5      (needs theta_a [nT,82])
+ * every product and sum rounded in fp32 (no contraction), as (a + b) / 2.0 of fp32 tensors rounds.  Single-pass mode: the bits of pass A
+ * (verts and kp of mbx_smpl_fwd, theta_a copied).
+ * Launches: prepare (pass B's rotations and shape and a copy of pass A's into the workspace, the theta rows) -> the chain kernel of
+ * mbx_smpl_fwd over the 2 nT parameter sets -> vertex kernel (a wave evaluates both parameter sets of its frames with the per-pass operation
+ * order of mbx_smpl_fwd and stores the mean once: the vertices of the single passes never reach memory; keypoint partials per vertex tile
+ * and pass) -> keypoint finish (tile order).  fp32, fixed summation order, no float atomics.  ws: >= mbx_wild_mesh_ws(nT, V, K with kp else
+ * 0, pair) bytes, 16-byte aligned; ws_bytes is checked.  nT = 0 is a no-op.  Refused: what mbx_smpl_fwd refuses, nT (2 nT with pass B)
+ * > 2^20, a clip that does not fit F. */
+size_t mbx_wild_mesh_ws(int nT, int V, int K, int pair);
+int mbx_wild_mesh(const float* v_template, const float* shapedirs, const float* posedirs, const float* Jt, const float* Jd,
+                  const int* parents, const float* lbs_weights, const float* Q, int K, const float* rotmat_a, const float* betas_a,
+                  const float* theta_a, const float* theta_b, float scale, const int* dst_frames, int dst_max, int n, int T, int F,
+                  float* verts, float* kp, float* theta, int V, void* ws, size_t ws_bytes, void* stream);
+/* mbx_scale_fit: the minimiser of err(p) = mean_i |p0 x_i + (p1,p2,p3) - y_i| (infer_wild_mesh.py:42-43) for S tracks in one launch, where the
+ * reference runs 400 least_squares starts on the host.  ref [F,17,3] f64 (the reference motion), kp [F,17,3] f32 (the stitched keypoints),
+ * seq_ptr [S+1] i32 on the device: track s owns frames seq_ptr[s] .. seq_ptr[s+1] - 1.  x = ref - ref[:, :1] in f64; y = kp - kp[:, :1] in
+ * f32 (numpy on the float32 reg3d_all), widened; everything after that is f64 without contraction.
+ * The objective is convex (a mean of norms of a function affine in p).  Iteratively reweighted least squares: w_i = 1 / max(r_i, delta),
+ * delta = MBX_SCALE_FIT_DELTA max|y|; every iteration is the weighted similarity fit in closed form from ten sums over the points
+ * (W, W x [3], W y [3], W x.x, W x.y, sum r); first iteration w = 1; stop when |ds| <= MBX_SCALE_FIT_TOL max(|s|, 1e-300) and
+ * |dt|_inf <= MBX_SCALE_FIT_TOL max|y|, at most MBX_SCALE_FIT_CAP iterations.
+ * fit [S,6] f64 = scale, t [3], objective at (scale, t), iterations.  iterations < 0 is a status and the other five are NaN:
+ *   -1 the track has no frames (or seq_ptr is not monotone inside [0,F]): nothing is read;  -2 the reference motion has no extent
+ *   (sum w |x - xbar|^2 <= 1e-12 sum w |x|^2);  -3 the cap was reached.
+ * One workgroup per track, the whole solve in the kernel: no host synchronisation, no float atomics, fixed summation order; a track's
+ * result does not depend on the other tracks of the call (pooled and single-track calls give equal bits). */
+#define MBX_SCALE_FIT_DELTA 1e-12
+#define MBX_SCALE_FIT_TOL 1e-13
+#define MBX_SCALE_FIT_CAP 2000
+int mbx_scale_fit(const double* ref, const float* kp, const int* seq_ptr, int S, int F, double* fit, void* stream);
+/* mbx_wild_mesh_place: infer_wild_mesh.py:153-154 in place, per track:
+ *   verts[f,v] = f32( f64( f32(verts[f,v] - kp[f,0]) ) + ref[f,0] * fit[s,0] )
+ * numpy 2's arithmetic for that line (a float32 difference added to a float64 root_cam), rounded to float32 once.  verts [F,V,3] f32,
+ * kp [F,K,3] f32, ref [F,17,3] f64, seq_ptr [S+1] i32 and fit [S,6] f64 on the device.  One launch; a frame outside every track is left as
+ * it is; a track whose fit holds a status receives that fit's NaN. */
+int mbx_wild_mesh_place(float* verts, const float* kp, int K, const double* ref, const int* seq_ptr, int S, const double* fit, int F,
+                        int V, void* stream);
+
 /* ---- measurement aid (bench.py `roofline.sustained_mfma_tflops`; not part of the model) --------------------------------------------
  * The bf16 MFMA rate the part sustains under its power cap with nothing but v_mfma_f32_32x32x16_bf16 in the loop (pseudo-random
  * operands; n_wg workgroups of 4 waves, `iters` x 16 MFMAs per wave).  ws: >= mbx_mfma_probe_ws(n_wg) bytes = a float sink

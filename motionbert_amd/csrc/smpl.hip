@@ -7,6 +7,10 @@
 //                       flip of the 2D input and of theta, Rodrigues into the workspace) -> the chain and vertex kernels of mbx_smpl_fwd ->
 //                       centring kernel (root = scale (Q x)[0] from the tile partials in tile order, subtracted from verts in place and from
 //                       the finished keypoints).
+//   mbx_wild_mesh     : the paired SMPL stage of in-the-wild mesh recovery (infer_wild_mesh.py:115-141) for a batch of clips: prepare kernel
+//                       (flip_thetas + Rodrigues of the flipped pass, the theta mean) -> the chain kernel over both parameter sets -> a vertex
+//                       kernel whose waves evaluate both sets of their frames and store the mean once, to the clip's rows of the stitched
+//                       result -> keypoint finish.
 //   mbx_smpl_bwd      : chain kernel again (nothing but betas and rotmat is saved) -> vertex backward (64 vertices x 16 frames per step;
 //                       phase 1, lane = vertex: vp, T, g, dvp recomputed into LDS; phase 2, lane = output column: d pf / d beta and d A
 //                       accumulated in registers over the workgroup's vertex tiles) -> split sum -> chain backward (one thread per frame).
@@ -254,6 +258,17 @@ __device__ __forceinline__ int mg_joint_src(int j) {      // utils_data.py:61-65
     return j;
 }
 
+// smplx batch_rodrigues: angle = |r + 1e-8|, d = r / angle, R = I + sin K + (1 - cos) K^2; r = 0 gives K = 0 and R = I exactly
+__device__ __forceinline__ void mg_rodrigues(float r0, float r1, float r2, float* __restrict__ R) {
+    const float a0 = r0 + 1e-8f, a1 = r1 + 1e-8f, a2 = r2 + 1e-8f;
+    const float angle = sqrtf(a0 * a0 + a1 * a1 + a2 * a2);
+    const float x = r0 / angle, y = r1 / angle, z = r2 / angle;
+    const float s = sinf(angle), c = 1.0f - cosf(angle);
+    R[0] = 1.0f - c * (y * y + z * z); R[1] = c * (x * y) - s * z;         R[2] = s * y + c * (x * z);
+    R[3] = s * z + c * (x * y);        R[4] = 1.0f - c * (x * x + z * z);  R[5] = c * (y * z) - s * x;
+    R[6] = c * (x * z) - s * y;        R[7] = s * x + c * (y * z);         R[8] = 1.0f - c * (x * x + y * y);
+}
+
 __global__ __launch_bounds__(256) void mesh_gt_prepare_kernel(const float* __restrict__ pose, const float* __restrict__ shape,
                                                               const float* __restrict__ m2d, const unsigned char* __restrict__ flips,
                                                               uint32_t slo, uint32_t shi, float flip_prob, float* __restrict__ x2d,
@@ -272,17 +287,7 @@ __global__ __launch_bounds__(256) void mesh_gt_prepare_kernel(const float* __res
             float* o = theta + (size_t)f * 82 + t * 3;
             o[0] = r0; o[1] = r1; o[2] = r2;
         }
-        if (rot) {
-            // smplx batch_rodrigues: angle = |r + 1e-8|, d = r / angle, R = I + sin K + (1 - cos) K^2; r = 0 gives K = 0 and R = I exactly
-            const float a0 = r0 + 1e-8f, a1 = r1 + 1e-8f, a2 = r2 + 1e-8f;
-            const float angle = sqrtf(a0 * a0 + a1 * a1 + a2 * a2);
-            const float x = r0 / angle, y = r1 / angle, z = r2 / angle;
-            const float s = sinf(angle), c = 1.0f - cosf(angle);
-            float* R = rot + (size_t)f * 216 + t * 9;
-            R[0] = 1.0f - c * (y * y + z * z); R[1] = c * (x * y) - s * z;         R[2] = s * y + c * (x * z);
-            R[3] = s * z + c * (x * y);        R[4] = 1.0f - c * (x * x + z * z);  R[5] = c * (y * z) - s * x;
-            R[6] = c * (x * z) - s * y;        R[7] = s * x + c * (y * z);         R[8] = 1.0f - c * (x * x + y * y);
-        }
+        if (rot) mg_rodrigues(r0, r1, r2, rot + (size_t)f * 216 + t * 9);
     } else if (t < SM_J + 17) {
         if (x2d) {
             const int j = t - SM_J;
@@ -344,6 +349,168 @@ __global__ __launch_bounds__(256) void mesh_gt_centre_kernel(const float* __rest
             }
         }
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// in-the-wild mesh recovery (mbx_wild_mesh): the model's pass on x (A) and its flipped-back pass on flip_data(x) (B), their mean written
+// once to each clip's rows of the stitched results.  The chain kernel sees 2 nT parameter sets: [0,nT) pass A, [nT,2nT) pass B.
+// ---------------------------------------------------------------------------------------------------------------
+// the row of frame f (of clip f / T) in the stitched results, -1 where the clip's entry does not fit [0,F)
+__device__ __forceinline__ int wm_row(const int* __restrict__ dst_frames, int f, int T, int F) {
+    const int clip = f / T;
+    const int d = dst_frames[clip];
+    return (d >= 0 && d <= F - T) ? d + (f - clip * T) : -1;
+}
+// (scale a + scale b) * 0.5 with every product and sum rounded: what (a' + b') / 2.0 of the two passes' fp32 tensors gives
+__device__ __forceinline__ float wm_pair(float scale, float a, float b) {
+#pragma clang fp contract(off)
+    const float pa = scale * a;
+    const float pb = scale * b;
+    const float s = pa + pb;
+    return s * 0.5f;
+}
+
+// 64 threads per frame: thread = joint (24: flip_thetas + Rodrigues of pass B, the theta mean), shape coefficient (10); all 64 copy pass
+// A's rotations next to pass B's.  theta_b == NULL (single-pass mode, launched for theta alone): theta_a is copied to its rows.
+__global__ __launch_bounds__(256) void wild_mesh_prepare_kernel(const float* __restrict__ rotmat_a, const float* __restrict__ betas_a,
+                                                                const float* __restrict__ theta_a, const float* __restrict__ theta_b,
+                                                                const int* __restrict__ dst_frames, float* __restrict__ rot2,
+                                                                float* __restrict__ betas2, float* __restrict__ theta, int nT, int T, int F) {
+    const int f = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int t = threadIdx.x & 63;
+    if (f >= nT) return;
+    const int row = theta ? wm_row(dst_frames, f, T, F) : -1;
+    if (theta_b) {
+        for (int e = t; e < 216; e += 64) rot2[(size_t)f * 216 + e] = rotmat_a[(size_t)f * 216 + e];
+        if (t < 10) betas2[(size_t)f * 10 + t] = betas_a[(size_t)f * 10 + t];
+    }
+    if (t < SM_J) {
+        if (theta_b) {
+            const float* p = theta_b + (size_t)f * 82 + mg_theta_src(t) * 3;
+            const float r0 = p[0], r1 = -p[1], r2 = -p[2];
+            mg_rodrigues(r0, r1, r2, rot2 + (size_t)(nT + f) * 216 + t * 9);
+            if (row >= 0) {
+                const float* a = theta_a + (size_t)f * 82 + t * 3;
+                float* o = theta + (size_t)row * 82 + t * 3;
+                o[0] = (a[0] + r0) * 0.5f; o[1] = (a[1] + r1) * 0.5f; o[2] = (a[2] + r2) * 0.5f;
+            }
+        } else if (row >= 0) {
+            const float* a = theta_a + (size_t)f * 82 + t * 3;
+            float* o = theta + (size_t)row * 82 + t * 3;
+            o[0] = a[0]; o[1] = a[1]; o[2] = a[2];
+        }
+    } else if (t < SM_J + 10) {
+        const int k = t - SM_J;
+        if (theta_b) {
+            const float sb = theta_b[(size_t)f * 82 + 72 + k];
+            betas2[(size_t)(nT + f) * 10 + k] = sb;
+            if (row >= 0) theta[(size_t)row * 82 + 72 + k] = (theta_a[(size_t)f * 82 + 72 + k] + sb) * 0.5f;
+        } else if (row >= 0) {
+            theta[(size_t)row * 82 + 72 + k] = theta_a[(size_t)f * 82 + 72 + k];
+        }
+    }
+}
+
+// The vertex kernel of the paired stage: smpl_verts_fwd_kernel's tile (64 vertices, lane = vertex, SM_FW parameter sets per wave) and its
+// operation order per parameter set.  PAIR: a wave's SM_FW sets are SM_FW / 2 output frames of pass A and the same frames of pass B; the two
+// x meet in registers and one store writes their mean.  Not PAIR: SM_FW output frames, the bits of smpl_verts_fwd_kernel, stitched.
+// betas / Aws / PFws / kpart are indexed by parameter set (FC = nT or 2 nT of them).
+template <bool PAIR>
+__global__ __launch_bounds__(256) void wild_mesh_verts_kernel(const float* __restrict__ vt, const float* __restrict__ sd, const float* __restrict__ pd,
+                                                              const float* __restrict__ lbsw, const float* __restrict__ Q,
+                                                              const float* __restrict__ betas, const float* __restrict__ Aws,
+                                                              const float* __restrict__ PFws, float scale, const int* __restrict__ dst_frames,
+                                                              float* __restrict__ verts, float* __restrict__ kpart, int nT, int T, int F, int V,
+                                                              int K) {
+    constexpr int NP = PAIR ? 2 : 1;
+    constexpr int NO = SM_FW / NP;              // output frames per wave
+    __shared__ float qs[32 * 65];
+    __shared__ float xs[4][3][64];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int v0 = blockIdx.x * SM_VT;
+    const bool live = v0 + lane < V;
+    const int v = live ? v0 + lane : V - 1;
+    const int f0 = blockIdx.y * (4 * NO) + wave * NO;
+    const int FC = NP * nT;
+    if (kpart) {
+        for (int idx = tid; idx < K * 64; idx += 256) {
+            const int k = idx >> 6, l = idx & 63;
+            qs[k * 65 + l] = (v0 + l < V) ? Q[(size_t)k * V + v0 + l] : 0.0f;
+        }
+    }
+    float w[SM_J];
+    unsigned mask = 0;
+#pragma unroll
+    for (int j = 0; j < SM_J; ++j) {
+        w[j] = lbsw[(size_t)v * SM_J + j];
+        if (__ballot(w[j] != 0.0f) != 0ull) mask |= 1u << j;
+    }
+    int fi[SM_FW];                              // parameter set of slot i: pass (i / NO), output frame f0 + i % NO
+#pragma unroll
+    for (int i = 0; i < SM_FW; ++i) fi[i] = min(f0 + (i % NO), nT - 1) + (i / NO) * nT;
+    float vp[SM_FW][3];
+    smpl_vposed<SM_FW>(vt, sd, pd, betas, PFws, fi, v, V, vp);
+    __syncthreads();
+    const int nout = 3 * K;
+#pragma unroll
+    for (int io = 0; io < NO; ++io) {
+        const bool fl = f0 + io < nT;
+        float x[NP][3];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            const int i = p * NO + io;
+            float Tm[12];
+            smpl_blend(w, mask, Aws + (size_t)fi[i] * SM_A, Tm);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) x[p][c] = Tm[c * 4] * vp[i][0] + Tm[c * 4 + 1] * vp[i][1] + Tm[c * 4 + 2] * vp[i][2] + Tm[c * 4 + 3];
+        }
+        if (verts && fl) {
+            const int row = wm_row(dst_frames, fi[io], T, F);           // wave-uniform
+            if (row >= 0 && live) {
+                float* o = verts + ((size_t)row * V + v) * 3;
+                if (PAIR) {
+                    o[0] = wm_pair(scale, x[0][0], x[NP - 1][0]); o[1] = wm_pair(scale, x[0][1], x[NP - 1][1]);
+                    o[2] = wm_pair(scale, x[0][2], x[NP - 1][2]);
+                } else {
+                    o[0] = scale * x[0][0]; o[1] = scale * x[0][1]; o[2] = scale * x[0][2];
+                }
+            }
+        }
+        if (kpart) {
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                xs[wave][0][lane] = x[p][0]; xs[wave][1][lane] = x[p][1]; xs[wave][2][lane] = x[p][2];
+                __syncthreads();
+                for (int o = lane; o < nout; o += 64) {
+                    const int k = o / 3, c = o - 3 * k;
+                    float s = 0.0f;
+                    for (int l = 0; l < 64; ++l) s += qs[k * 65 + l] * xs[wave][c][l];
+                    if (fl) kpart[((size_t)blockIdx.x * FC + fi[p * NO + io]) * nout + o] = s;
+                }
+                __syncthreads();
+            }
+        }
+    }
+}
+
+// keypoints: the tile partials of each pass added in tile order and scaled as smpl_kp_finish_kernel does, then the mean, to the clip's rows
+template <bool PAIR>
+__global__ __launch_bounds__(256) void wild_mesh_kp_finish_kernel(const float* __restrict__ kpart, int nvt, float scale,
+                                                                  const int* __restrict__ dst_frames, float* __restrict__ kp, int nT, int T,
+                                                                  int F, int nout) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t n = (size_t)nT * nout;
+    if (i >= n) return;
+    const int f = (int)(i / nout), o = (int)(i - (size_t)f * nout);
+    const int row = wm_row(dst_frames, f, T, F);
+    if (row < 0) return;
+    const size_t nc = PAIR ? 2 * n : n;                 // one tile's partials
+    float sa = 0.0f, sb = 0.0f;
+    for (int t = 0; t < nvt; ++t) sa += kpart[(size_t)t * nc + i];
+    if (PAIR)
+        for (int t = 0; t < nvt; ++t) sb += kpart[(size_t)t * nc + n + i];
+    kp[(size_t)row * nout + o] = PAIR ? wm_pair(scale, sa, sb) : scale * sa;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -701,6 +868,83 @@ extern "C" int mbx_mesh_gt(const float* pose, const float* shape, const float* m
     hipLaunchKernelGGL(mesh_gt_centre_kernel, dim3((F + MG_CF - 1) / MG_CF, chunks), dim3(256), 0, s, (const float*)kpart, nvt, 3 * Kv, scale,
                        verts, kp_3d, F, V);
     MBX_LAUNCH_CHECK("mesh_gt (centring)");
+    return 0;
+}
+
+// float offsets for FC = nT or 2 nT parameter sets: the forward's layout with K keypoints over FC frames, then (pair) the rotation matrices
+// [FC,216] and the shapes [FC,10] of both passes
+extern "C" size_t mbx_wild_mesh_ws(int nT, int V, int K, int pair) {
+    if (nT < 1 || nT > (1 << 20) / (pair ? 2 : 1)) return 0;
+    const int FC = pair ? 2 * nT : nT;
+    if (!sm_dims_ok(FC, V, K)) return 0;
+    return (mg_rot_offset(FC, V, K) + (pair ? (size_t)FC * 226 : 0)) * sizeof(float) + 256;
+}
+
+extern "C" int mbx_wild_mesh(const float* v_template, const float* shapedirs, const float* posedirs, const float* Jt, const float* Jd,
+                             const int* parents, const float* lbs_weights, const float* Q, int K, const float* rotmat_a, const float* betas_a,
+                             const float* theta_a, const float* theta_b, float scale, const int* dst_frames, int dst_max, int n, int T, int F,
+                             float* verts, float* kp, float* theta, int V, void* ws, size_t ws_bytes, void* stream) {
+    const bool pair = theta_b != nullptr;
+    MBX_CHECK_ARG(n >= 0 && T >= 1 && (long long)n * T * (pair ? 2 : 1) <= (1 << 20),
+                  "wild_mesh: bad sizes n=%d T=%d (T >= 1, n T <= 2^20, 2 n T with pass B)", n, T);
+    const int nT = n * T, FC = pair ? 2 * nT : nT;
+    MBX_CHECK_ARG(sm_dims_ok(FC, V, K) && F >= 0, "wild_mesh: bad sizes n T=%d V=%d K=%d F=%d (V >= 1, K <= 32, F >= 0)", nT, V, K, F);
+    SmplTree tree;
+    if (sm_tree(parents, tree, "wild_mesh")) return 1;
+    if (nT == 0) return 0;
+    MBX_CHECK_ARG(dst_max >= 0 && (long long)dst_max + T <= F, "wild_mesh: a clip of %d frames at row %d does not fit the %d rows of the result",
+                  T, dst_max, F);
+    MBX_CHECK_ARG(verts || kp || theta, "wild_mesh: no output");
+    MBX_CHECK_ARG(dst_frames && rotmat_a && betas_a, "wild_mesh: null pointer (dst_frames, rotmat_a, betas_a)");
+    MBX_CHECK_ARG(!theta || theta_a, "wild_mesh: theta needs theta_a");
+    const bool body = verts || kp;
+    MBX_CHECK_ARG(!body || (v_template && shapedirs && posedirs && Jt && Jd && lbs_weights), "wild_mesh: null pointer (model arrays)");
+    MBX_CHECK_ARG(!kp || (Q && K >= 1), "wild_mesh: kp needs a regressor Q [K,V] with K >= 1");
+    MBX_CHECK_ARG(!(body || pair) || ws, "wild_mesh: null workspace");
+    const int Kv = kp ? K : 0;
+    MBX_CHECK_ARG(!(body || pair) || ws_bytes >= mbx_wild_mesh_ws(nT, V, Kv, pair), "wild_mesh: workspace of %zu bytes, %zu needed", ws_bytes,
+                  mbx_wild_mesh_ws(nT, V, Kv, pair));
+    MBX_CHECK_ARG((((uintptr_t)v_template | (uintptr_t)shapedirs | (uintptr_t)posedirs | (uintptr_t)Jt | (uintptr_t)Jd | (uintptr_t)lbs_weights |
+                    (uintptr_t)Q | (uintptr_t)rotmat_a | (uintptr_t)betas_a | (uintptr_t)theta_a | (uintptr_t)theta_b | (uintptr_t)dst_frames |
+                    (uintptr_t)verts | (uintptr_t)kp | (uintptr_t)theta) & 3) == 0 && ((uintptr_t)ws & 15) == 0,
+                  "wild_mesh: pointers must be 4-byte aligned, the workspace 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    float* Aws = (float*)ws;
+    float* PFws = Aws + (size_t)FC * SM_A;
+    float* G = PFws + (size_t)FC * SM_PFS;
+    float* kpart = G + (size_t)FC * SM_A;
+    float* rot2 = pair ? Aws + mg_rot_offset(FC, V, Kv) : nullptr;
+    float* betas2 = pair ? rot2 + (size_t)FC * 216 : nullptr;
+    if (pair || theta) {
+        hipLaunchKernelGGL(wild_mesh_prepare_kernel, dim3((nT + 3) / 4), dim3(256), 0, s, rotmat_a, betas_a, theta_a, theta_b, dst_frames, rot2,
+                           betas2, theta, nT, T, F);
+        MBX_LAUNCH_CHECK("wild_mesh (prepare)");
+    }
+    if (!body) return 0;
+    const float* betas = pair ? betas2 : betas_a;
+    const float* rot = pair ? rot2 : rotmat_a;
+    hipLaunchKernelGGL(smpl_chain_fwd_kernel, dim3((FC + 63) / 64), dim3(64), 0, s, betas, rot, Jt, Jd, tree, scale, Aws, PFws, G, (float*)nullptr,
+                       FC);
+    MBX_LAUNCH_CHECK("wild_mesh (chain)");
+    const int nvt = sm_tiles(V);
+    const int per_wg = 4 * (pair ? SM_FW / 2 : SM_FW);
+    const dim3 grid(nvt, (nT + per_wg - 1) / per_wg);
+    if (pair)
+        hipLaunchKernelGGL(wild_mesh_verts_kernel<true>, grid, dim3(256), 0, s, v_template, shapedirs, posedirs, lbs_weights, Q, betas,
+                           (const float*)Aws, (const float*)PFws, scale, dst_frames, verts, kp ? kpart : (float*)nullptr, nT, T, F, V, Kv);
+    else
+        hipLaunchKernelGGL(wild_mesh_verts_kernel<false>, grid, dim3(256), 0, s, v_template, shapedirs, posedirs, lbs_weights, Q, betas,
+                           (const float*)Aws, (const float*)PFws, scale, dst_frames, verts, kp ? kpart : (float*)nullptr, nT, T, F, V, Kv);
+    MBX_LAUNCH_CHECK("wild_mesh (vertices)");
+    if (kp) {
+        const size_t cnt = (size_t)nT * 3 * K;
+        const dim3 g((unsigned)((cnt + 255) / 256));
+        if (pair)
+            hipLaunchKernelGGL(wild_mesh_kp_finish_kernel<true>, g, dim3(256), 0, s, (const float*)kpart, nvt, scale, dst_frames, kp, nT, T, F, 3 * K);
+        else
+            hipLaunchKernelGGL(wild_mesh_kp_finish_kernel<false>, g, dim3(256), 0, s, (const float*)kpart, nvt, scale, dst_frames, kp, nT, T, F, 3 * K);
+        MBX_LAUNCH_CHECK("wild_mesh (keypoints)");
+    }
     return 0;
 }
 

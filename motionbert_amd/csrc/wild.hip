@@ -11,6 +11,8 @@
 //                     The mapped and pixel-normalised coordinates are never stored: launch 3 recomputes them with the same operations
 //                     (hence the same bits) that launch 1 took the box of.
 //   mbx_wild_output : infer_wild.py:81-96 for a batch of clips, written straight to each clip's rows of the stitched [F,17,3] result.
+//   mbx_scale_fit   : solve_scale of infer_wild_mesh.py:42-56 for S tracks, one workgroup per track, the whole IRLS solve in the kernel.
+//   mbx_wild_mesh_place : infer_wild_mesh.py:153-154 in place, in numpy 2's arithmetic.
 #include "mbx_common.h"
 #include <math.h>
 
@@ -287,5 +289,186 @@ extern "C" int mbx_wild_output(const float* pred, const float* x, int x_channels
     hipLaunchKernelGGL(wild_output_kernel, dim3(wi_clamp_grid((total + WI_THREADS - 1) / WI_THREADS, WI_GRID_CAP)), dim3(WI_THREADS), 0,
                        (hipStream_t)stream, pred, x, x_channels, dst_frames, total, T, flags, pix_scale, half_w, half_h, out);
     MBX_LAUNCH_CHECK("wild_output");
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// mbx_scale_fit: the camera-frame scale of infer_wild_mesh.py:42-56.  One workgroup per track runs the whole iteratively reweighted
+// least-squares solve: a pass over the track's points leaves ten sums (thread partials in point order, DPP inside a wave, the waves added in
+// wave order), every thread forms the same closed-form update from them and the same decision to stop.  Point p of a track is frame
+// p / 17, joint p % 17, whatever else the call holds: pooled and single-track calls add the same values in the same order.
+// ---------------------------------------------------------------------------------------------------------------
+#define SF_THREADS 1024
+#define SF_WAVES (SF_THREADS / MBX_WAVE)
+#define SF_Q 10
+
+// wave_sum of mbx_common.h for float64 (the masked rows of the two row_bcast steps receive 0).  Every lane of the wave must be active.
+__device__ __forceinline__ double wave_sum_d(double v) {
+    v = v + dpp_mov_d<0xB1>(v, v);
+    v = v + dpp_mov_d<0x4E>(v, v);
+    v = v + dpp_mov_d<0x141>(v, v);
+    v = v + dpp_mov_d<0x140>(v, v);
+    v = v + dpp_mov_d<0x142, 0xa>(0.0, v);
+    v = v + dpp_mov_d<0x143, 0xc>(0.0, v);
+    const uint64_t b = __builtin_bit_cast(uint64_t, v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, 63), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(b >> 32), 63);
+    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+
+// x = ref - ref[:, :1] in float64; y = kp - kp[:, :1] in float32 (numpy on the float32 reg3d_all), widened
+__device__ __forceinline__ void sf_point(const double* __restrict__ ref, const float* __restrict__ kp, int f0, int p, double (&x)[3], double (&y)[3]) {
+    const int f = f0 + p / WI_J, j = p % WI_J;
+    const double* rf = ref + (size_t)f * (WI_J * 3);
+    const float* kf = kp + (size_t)f * (WI_J * 3);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        x[c] = rf[j * 3 + c] - rf[c];
+        y[c] = (double)(kf[j * 3 + c] - kf[c]);
+    }
+}
+
+// the sums of q[0 .. nq) over the workgroup, the same bits in every thread
+template <int NQ> __device__ __forceinline__ void sf_fold(double (&q)[NQ], double (*red)[SF_Q], int lane, int wave) {
+#pragma unroll
+    for (int k = 0; k < NQ; ++k) q[k] = wave_sum_d(q[k]);
+    __syncthreads();                                                          // the previous fold's readers are through
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < NQ; ++k) red[wave][k] = q[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NQ; ++k) {
+        double s = red[0][k];
+        for (int w = 1; w < SF_WAVES; ++w) s += red[w][k];
+        q[k] = s;
+    }
+}
+
+__global__ __launch_bounds__(SF_THREADS) void scale_fit_kernel(const double* __restrict__ ref, const float* __restrict__ kp,
+                                                               const int* __restrict__ seq_ptr, int F, double* __restrict__ fit) {
+    __shared__ double red[SF_WAVES][SF_Q];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int trk = blockIdx.x;
+    const int f0 = seq_ptr[trk], f1 = seq_ptr[trk + 1];
+    double* out = fit + (size_t)trk * 6;
+    const double nan = __builtin_nan("");
+    if (f0 < 0 || f1 > F || f0 >= f1) {                                       // uniform over the workgroup
+        if (tid < 6) out[tid] = tid == 5 ? -1.0 : nan;
+        return;
+    }
+    const int N = (f1 - f0) * WI_J;
+    // max |y|: the magnitude delta and the stopping rule hang on
+    double ymax = 0.0;
+    for (int p = tid; p < N; p += SF_THREADS) {
+        double x[3], y[3];
+        sf_point(ref, kp, f0, p, x, y);
+        ymax = fmax(ymax, fmax(fabs(y[0]), fmax(fabs(y[1]), fabs(y[2]))));
+    }
+    ymax = wave_reduce_d<WaveMaxD>(ymax);
+    if (lane == 0) red[wave][0] = ymax;
+    __syncthreads();
+    ymax = red[0][0];
+    for (int w = 1; w < SF_WAVES; ++w) ymax = fmax(ymax, red[w][0]);
+    const double delta = MBX_SCALE_FIT_DELTA * ymax;
+    double s = 0.0, t0 = 0.0, t1 = 0.0, t2 = 0.0;
+    int status = -3, it = 0;
+    for (; it < MBX_SCALE_FIT_CAP; ++it) {
+        double q[SF_Q];
+#pragma unroll
+        for (int k = 0; k < SF_Q; ++k) q[k] = 0.0;
+        for (int p = tid; p < N; p += SF_THREADS) {
+            double x[3], y[3];
+            sf_point(ref, kp, f0, p, x, y);
+            const double e0 = s * x[0] + t0 - y[0], e1 = s * x[1] + t1 - y[1], e2 = s * x[2] + t2 - y[2];
+            const double r = sqrt(e0 * e0 + e1 * e1 + e2 * e2);
+            const double w = it == 0 ? 1.0 : 1.0 / fmax(r, delta);
+            q[0] += w;
+            q[1] += w * x[0]; q[2] += w * x[1]; q[3] += w * x[2];
+            q[4] += w * y[0]; q[5] += w * y[1]; q[6] += w * y[2];
+            q[7] += w * (x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+            q[8] += w * (x[0] * y[0] + x[1] * y[1] + x[2] * y[2]);
+            q[9] += r;
+        }
+        sf_fold<SF_Q>(q, red, lane, wave);
+        const double W = q[0];
+        const double den = q[7] - (q[1] * q[1] + q[2] * q[2] + q[3] * q[3]) / W;
+        if (!(den > 1e-12 * q[7])) { status = -2; break; }
+        const double sn = (q[8] - (q[1] * q[4] + q[2] * q[5] + q[3] * q[6]) / W) / den;
+        const double n0 = (q[4] - sn * q[1]) / W, n1 = (q[5] - sn * q[2]) / W, n2 = (q[6] - sn * q[3]) / W;
+        const double ds = fabs(sn - s), dt = fmax(fabs(n0 - t0), fmax(fabs(n1 - t1), fabs(n2 - t2)));
+        s = sn; t0 = n0; t1 = n1; t2 = n2;
+        if (it > 0 && ds <= MBX_SCALE_FIT_TOL * fmax(fabs(sn), 1e-300) && dt <= MBX_SCALE_FIT_TOL * ymax) { status = 0; ++it; break; }
+    }
+    if (status < 0) {
+        if (tid < 6) out[tid] = tid == 5 ? (double)status : nan;
+        return;
+    }
+    double o[1] = {0.0};
+    for (int p = tid; p < N; p += SF_THREADS) {
+        double x[3], y[3];
+        sf_point(ref, kp, f0, p, x, y);
+        const double e0 = s * x[0] + t0 - y[0], e1 = s * x[1] + t1 - y[1], e2 = s * x[2] + t2 - y[2];
+        o[0] += sqrt(e0 * e0 + e1 * e1 + e2 * e2);
+    }
+    sf_fold<1>(o, red, lane, wave);
+    if (tid == 0) {
+        out[0] = s; out[1] = t0; out[2] = t1; out[3] = t2; out[4] = o[0] / (double)N; out[5] = (double)it;
+    }
+}
+
+extern "C" int mbx_scale_fit(const double* ref, const float* kp, const int* seq_ptr, int S, int F, double* fit, void* stream) {
+    MBX_CHECK_ARG(S >= 0 && F >= 0 && (long long)F * WI_J <= (1ll << 30), "scale_fit: bad sizes S=%d F=%d (S, F >= 0, 17 F <= 2^30)", S, F);
+    if (S == 0) return 0;
+    MBX_CHECK_ARG(seq_ptr && fit && (F == 0 || (ref && kp)), "scale_fit: null pointer");
+    MBX_CHECK_ARG(((uintptr_t)ref & 7) == 0 && ((uintptr_t)fit & 7) == 0 && ((uintptr_t)kp & 3) == 0 && ((uintptr_t)seq_ptr & 3) == 0,
+                  "scale_fit: ref and fit must be 8-byte aligned, kp and seq_ptr 4-byte aligned");
+    MBX_CHECK_ARG(S <= (1 << 20), "scale_fit: %d tracks are too many (at most 2^20)", S);
+    hipLaunchKernelGGL(scale_fit_kernel, dim3(S), dim3(SF_THREADS), 0, (hipStream_t)stream, ref, kp, seq_ptr, F, fit);
+    MBX_LAUNCH_CHECK("scale_fit");
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// mbx_wild_mesh_place: infer_wild_mesh.py:153-154.  Workgroup = one frame x PL_CHUNK values; the frame's track is found by bisection in
+// seq_ptr (uniform over the workgroup).
+// ---------------------------------------------------------------------------------------------------------------
+#define PL_CHUNK 4096
+
+__global__ __launch_bounds__(WI_THREADS) void wild_mesh_place_kernel(float* verts, const float* __restrict__ kp, int K,
+                                                                      const double* __restrict__ ref, const int* __restrict__ seq_ptr, int S,
+                                                                      const double* __restrict__ fit, int F, int V) {
+    const int f = blockIdx.x;
+    int lo = 0, hi = S;                                                       // the last s with seq_ptr[s] <= f
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (seq_ptr[mid] <= f) lo = mid; else hi = mid;
+    }
+    if (!(seq_ptr[lo] <= f && f < seq_ptr[lo + 1])) return;
+    const double sc = fit[(size_t)lo * 6];
+    const float* k0 = kp + (size_t)f * K * 3;
+    const double* r0 = ref + (size_t)f * (WI_J * 3);
+    const float kx = k0[0], ky = k0[1], kz = k0[2];
+    const double cx = r0[0] * sc, cy = r0[1] * sc, cz = r0[2] * sc;           // root_cam = ref_pose[:, :1] * scale
+    float* row = verts + (size_t)f * 3 * V;
+    const int e0 = blockIdx.y * PL_CHUNK, e1 = min(e0 + PL_CHUNK, 3 * V);
+    for (int e = e0 + threadIdx.x; e < e1; e += WI_THREADS) {
+        const int c = e % 3;
+        const float d = row[e] - (c == 0 ? kx : (c == 1 ? ky : kz));
+        row[e] = (float)((double)d + (c == 0 ? cx : (c == 1 ? cy : cz)));
+    }
+}
+
+extern "C" int mbx_wild_mesh_place(float* verts, const float* kp, int K, const double* ref, const int* seq_ptr, int S, const double* fit, int F,
+                                   int V, void* stream) {
+    MBX_CHECK_ARG(F >= 0 && F <= (1 << 24) && V >= 1 && V <= (1 << 20) && K >= 1 && K <= 32 && S >= 0 && S <= (1 << 20),
+                  "wild_mesh_place: bad sizes F=%d V=%d K=%d S=%d (V >= 1, 1 <= K <= 32)", F, V, K, S);
+    if (F == 0 || S == 0) return 0;
+    MBX_CHECK_ARG(verts && kp && ref && seq_ptr && fit, "wild_mesh_place: null pointer");
+    MBX_CHECK_ARG(((uintptr_t)ref & 7) == 0 && ((uintptr_t)fit & 7) == 0 && (((uintptr_t)verts | (uintptr_t)kp | (uintptr_t)seq_ptr) & 3) == 0,
+                  "wild_mesh_place: ref and fit must be 8-byte aligned, verts, kp and seq_ptr 4-byte aligned");
+    const int chunks = (3 * V + PL_CHUNK - 1) / PL_CHUNK;
+    hipLaunchKernelGGL(wild_mesh_place_kernel, dim3(F, chunks), dim3(WI_THREADS), 0, (hipStream_t)stream, verts, kp, K, ref, seq_ptr, S, fit, F, V);
+    MBX_LAUNCH_CHECK("wild_mesh_place");
     return 0;
 }

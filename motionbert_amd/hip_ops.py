@@ -119,6 +119,10 @@ SIGNATURES = {
     'mbx_wild_input_ws': (_sz, [_i, _i]),
     'mbx_wild_input': (_i, [_vp, _vp, _i, _vp, _i, _i] + [C.c_double] * 4 + [_i, _i, _vp, _vp, _vp, _sz, _vp]),
     'mbx_wild_output': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _f, C.c_double, C.c_double, _vp, _vp]),
+    'mbx_wild_mesh_ws': (_sz, [_i, _i, _i, _i]),
+    'mbx_wild_mesh': (_i, [_vp] * 5 + [C.POINTER(C.c_int)] + [_vp, _vp, _i] + [_vp] * 4 + [_f, _vp] + [_i] * 4 + [_vp] * 3 + [_i, _vp, _sz, _vp]),
+    'mbx_scale_fit': (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    'mbx_wild_mesh_place': (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp]),
     'mbx_rows_n_pack_bytes': (_sz, [_i, _i]),
     'mbx_rows_lnbwd_t': (_i, [_vp] * 6 + [_i, _i, _i, _vp]),
     'mbx_rows_n_pack_many': (_i, [_i64p, _i, _i, _i, _vp]),
@@ -970,6 +974,83 @@ class HipOps:
                                       _p(model['shapedirs']), _p(model['posedirs']), _p(model['Jt']), _p(model['Jd']), parents,
                                       _p(model['lbs_weights']), _p(Q), K, float(scale), _p(x2d), _p(theta), _p(kp_3d), _p(verts),
                                       _p(flips_used), N, T, V, _p(ws), ws.numel(), self._stream()))
+
+    # ------------------------------------------------------------------ in-the-wild mesh recovery (infer_wild_mesh.py; csrc/smpl.hip, csrc/wild.hip)
+    def wild_mesh_ws(self, nT, V, K, pair, device):
+        return self._ws(('wildmesh', nT, V, K, bool(pair)), self.lib.mbx_wild_mesh_ws, nT, V, K, int(bool(pair)), device=device)
+
+    def wild_mesh(self, model, Q, rotmat_a, betas_a, theta_a, theta_b, scale, dst_frames, dst_max, T, verts, kp, theta, ws=None):
+        """model, Q [K,V] as smpl_fwd takes them; pass A: rotmat_a [nT,24,9] (or [nT,24,3,3]), betas_a [nT,10], theta_a [nT,82] or None;
+        pass B: theta_b [nT,82] or None (single-pass mode); dst_frames [n] i32 on the device with nT = n T, dst_max its largest entry (host);
+        outputs verts [F,V,3] / kp [F,K,3] / theta [F,82] f32, each may be None; ws: a uint8 workspace of wild_mesh_ws (allocated when
+        None)."""
+        V, dev, parents = self._smpl_model('wild_mesh', model, False)
+        nT = self._smpl_frames('wild_mesh', betas_a, rotmat_a)
+        T = int(T)
+        n = dst_frames.numel()
+        if T < 1 or n * T != nT:
+            raise RuntimeError(f'libmbx: wild_mesh: {n} clips of {T} frames, but parameters of {nT} frames')
+        if verts is None and kp is None and theta is None:
+            raise RuntimeError('libmbx: wild_mesh: no output')
+        F = (verts if verts is not None else kp if kp is not None else theta).shape[0]
+        K = 0
+        if Q is not None:
+            if Q.dim() != 2 or Q.shape[1] != V or not 1 <= Q.shape[0] <= 32:
+                raise RuntimeError(f'libmbx: wild_mesh needs Q [1 <= K <= 32, {V}], got {tuple(Q.shape)}')
+            K = Q.shape[0]
+        if kp is not None and Q is None:
+            raise RuntimeError('libmbx: wild_mesh: kp needs the regressor Q')
+        if theta is not None and theta_a is None:
+            raise RuntimeError('libmbx: wild_mesh: theta needs theta_a')
+        if n and not 0 <= int(dst_max) <= F - T:
+            raise RuntimeError(f'libmbx: wild_mesh: a clip of {T} frames at row {int(dst_max)} does not fit the {F} rows of the result')
+        self._dense('wild_mesh', torch.float32, K * V, dev, Q=Q)
+        self._dense('wild_mesh', torch.float32, nT * 10, dev, betas_a=betas_a)
+        self._dense('wild_mesh', torch.float32, nT * 216, dev, rotmat_a=rotmat_a)
+        self._dense('wild_mesh', torch.float32, nT * 82, dev, theta_a=theta_a, theta_b=theta_b)
+        self._dense('wild_mesh', torch.float32, F * V * 3, dev, verts=verts)
+        self._dense('wild_mesh', torch.float32, F * K * 3, dev, kp=kp)
+        self._dense('wild_mesh', torch.float32, F * 82, dev, theta=theta)
+        self._dense('wild_mesh', torch.int32, n, dev, dst_frames=dst_frames)
+        if not n:
+            return
+        pair = theta_b is not None
+        if ws is None:
+            ws = self.wild_mesh_ws(nT, V, K if kp is not None else 0, pair, dev)
+        self._dense('wild_mesh', torch.uint8, None, dev, ws=ws)
+        self._ck(self.lib.mbx_wild_mesh(_p(model['v_template']), _p(model['shapedirs']), _p(model['posedirs']), _p(model['Jt']), _p(model['Jd']),
+                                        parents, _p(model['lbs_weights']), _p(Q), K, _p(rotmat_a), _p(betas_a), _p(theta_a), _p(theta_b),
+                                        float(scale), _p(dst_frames), int(dst_max), n, T, F, _p(verts), _p(kp), _p(theta), V, _p(ws), ws.numel(),
+                                        self._stream()))
+
+    def scale_fit(self, ref, kp, seq_ptr, fit):
+        """ref [F,17,3] f64, kp [F,17,3] f32, seq_ptr [S+1] i32 -> fit [S,6] f64 = scale, t [3], objective, iterations (< 0: a status)"""
+        if ref.dim() != 3 or tuple(ref.shape[1:]) != (17, 3) or tuple(kp.shape) != tuple(ref.shape):
+            raise RuntimeError(f'libmbx: scale_fit needs ref and kp [F,17,3], got {tuple(ref.shape)} / {tuple(kp.shape)}')
+        F, S, dev = ref.shape[0], seq_ptr.numel() - 1, fit.device
+        if S < 0 or tuple(fit.shape) != (S, 6):
+            raise RuntimeError(f'libmbx: scale_fit needs seq_ptr [S+1] and fit [S,6], got {tuple(seq_ptr.shape)} / {tuple(fit.shape)}')
+        self._dense('scale_fit', torch.float64, F * 51, dev, ref=ref)
+        self._dense('scale_fit', torch.float32, F * 51, dev, kp=kp)
+        self._dense('scale_fit', torch.int32, S + 1, dev, seq_ptr=seq_ptr)
+        self._dense('scale_fit', torch.float64, S * 6, dev, fit=fit)
+        self._ck(self.lib.mbx_scale_fit(_p(ref), _p(kp), _p(seq_ptr), S, F, _p(fit), self._stream()))
+
+    def wild_mesh_place(self, verts, kp, ref, seq_ptr, fit):
+        """verts [F,V,3] f32 in place, kp [F,K,3] f32, ref [F,17,3] f64, seq_ptr [S+1] i32, fit [S,6] f64"""
+        if verts.dim() != 3 or verts.shape[2] != 3 or verts.shape[1] < 1 or kp.dim() != 3 or kp.shape[0] != verts.shape[0] or kp.shape[2] != 3 \
+                or not 1 <= kp.shape[1] <= 32 or tuple(ref.shape) != (verts.shape[0], 17, 3):
+            raise RuntimeError(f'libmbx: wild_mesh_place needs verts [F,V,3], kp [F,K,3] and ref [F,17,3], got {tuple(verts.shape)} / '
+                               f'{tuple(kp.shape)} / {tuple(ref.shape)}')
+        F, V, K, S, dev = verts.shape[0], verts.shape[1], kp.shape[1], seq_ptr.numel() - 1, verts.device
+        if S < 0 or tuple(fit.shape) != (S, 6):
+            raise RuntimeError(f'libmbx: wild_mesh_place needs seq_ptr [S+1] and fit [S,6], got {tuple(seq_ptr.shape)} / {tuple(fit.shape)}')
+        self._dense('wild_mesh_place', torch.float32, F * V * 3, dev, verts=verts)
+        self._dense('wild_mesh_place', torch.float32, F * K * 3, dev, kp=kp)
+        self._dense('wild_mesh_place', torch.float64, F * 51, dev, ref=ref)
+        self._dense('wild_mesh_place', torch.int32, S + 1, dev, seq_ptr=seq_ptr)
+        self._dense('wild_mesh_place', torch.float64, S * 6, dev, fit=fit)
+        self._ck(self.lib.mbx_wild_mesh_place(_p(verts), _p(kp), K, _p(ref), _p(seq_ptr), S, _p(fit), F, V, self._stream()))
 
     # ------------------------------------------------------------------ dropout / drop-path (SURVEY 8 a15)
     def dropout(self, x, y, p, seed):

@@ -20,7 +20,8 @@ skinning, built from the user's SMPL arrays) or any module with the reference's 
     flip_average(model, smpl, x)    the flip evaluation of train_mesh.py:83-108: the mean of the model's output and the flipped-back output of
                                     the flipped input, for `MeshEvaluator.update`.
 
-Not here: the 49-joint map of `utils_smpl.SMPL`, translation estimation, rendering, `infer_wild_mesh.py`, a DDP variant of the step.
+Not here: the 49-joint map of `utils_smpl.SMPL`, rendering, a DDP variant of the step.  `infer_wild_mesh.py` (with its scale fit and camera
+placement) is `motionbert_amd.wild.infer_mesh`.
 
 There is no CPU path: without an injected kernel provider (`ops=`), tensors that are not on a ROCm device raise.
 """
@@ -120,7 +121,9 @@ class SMPLRegressor(nn.Module):
             self.J_regressor = self.J_regressor.to(device=device, dtype=dtype)    # once, not per forward as the reference moves it: a host copy per step
         return self.J_regressor
 
-    def forward(self, feat, init_pose=None, init_shape=None):
+    def forward_params(self, feat):
+        """The head without SMPL: feat [N,T,J,C] -> `(rotmat [NT,24,3,3], shape [NT,10], theta [NT,82])`, the parameters `forward` hands to
+        the SMPL layer and its `theta` (24 axis-angle joints | shape).  `wild.infer_mesh` feeds them to one `mbx_wild_mesh` launch."""
         N, T, J, C = feat.shape
         NT = N * T
         feat = feat.reshape(N, T, -1)
@@ -132,16 +135,20 @@ class SMPLRegressor(nn.Module):
         pred_shape = pred_shape.expand(T, N, -1).permute(1, 0, 2).reshape(NT, -1)
         rotmat, aa = rot6d_to_rotmat_theta(pred_pose.float(), ops=self.ops)
         rotmat, aa = rotmat.to(pred_pose.dtype), aa.to(pred_pose.dtype)                         # (the kernels are fp32)
-        pred_rotmat = rotmat.view(NT, 24, 3, 3)
+        return rotmat.view(NT, 24, 3, 3), pred_shape, torch.cat([aa.reshape(NT, 72), pred_shape], dim=1)
+
+    def forward(self, feat, init_pose=None, init_shape=None):
+        NT = feat.shape[0] * feat.shape[1]
+        pred_rotmat, pred_shape, theta = self.forward_params(feat)
         if isinstance(self.smpl, SMPLLayer):
             # the project's own layer: vertices in millimetres and the 17 regressed joints from one fused launch (no [NT,V,3] product
             # with 1000 and no batched [17,V] matmul; their gradients come back through mbx_smpl_bwd)
             verts, kp = self.smpl.forward_kp(pred_shape, pred_rotmat, self._regressor(pred_shape.device, torch.float32), 1000.0, ops=self.ops)
-            return [{'theta': torch.cat([aa.reshape(NT, 72), pred_shape], dim=1), 'verts': verts.to(pred_pose.dtype), 'kp_3d': kp.to(pred_pose.dtype)}]
+            return [{'theta': theta, 'verts': verts.to(theta.dtype), 'kp_3d': kp.to(theta.dtype)}]
         pred_output = self.smpl(betas=pred_shape, body_pose=pred_rotmat[:, 1:], global_orient=pred_rotmat[:, 0].unsqueeze(1), pose2rot=False)
         pred_vertices = pred_output.vertices * 1000.0
         pred_joints = torch.matmul(self._regressor(pred_vertices.device, pred_vertices.dtype)[None].expand(NT, -1, -1), pred_vertices)
-        return [{'theta': torch.cat([aa.reshape(NT, 72), pred_shape], dim=1),       # (N*T, 72+10)
+        return [{'theta': theta,                                                    # (N*T, 72+10)
                  'verts': pred_vertices,                                            # (N*T, V, 3)
                  'kp_3d': pred_joints}]                                             # (N*T, 17, 3)
 

@@ -19,6 +19,16 @@ ends the run.
     wild_output      infer_wild.py:81-96 for one batch of clips
     infer            the loop of infer_wild.py:56-97
 
+Mesh recovery in the wild (reference `infer_wild_mesh.py:42-56,99-154`) shares the input stage, the plan and the batching:
+
+    meshes = infer_mesh(model, smpl, kp, ref_3d=X3D)                  # {'verts': [F,V,3] mm, 'kp_3d': [F,17,3], 'scale': float}
+
+    infer_mesh       the loop of infer_wild_mesh.py:108-146: per batch the backbone and the head's parameters for x and flip_data(x), and ONE
+                     `mbx_wild_mesh` launch that evaluates SMPL for both parameter sets and writes their mean into the stitched rows
+    solve_scale      infer_wild_mesh.py:42-56 as one `mbx_scale_fit` launch: the convex fit solved by iteratively reweighted least squares
+                     where the reference runs 400 starts of `scipy.optimize.least_squares` on the host
+    place            infer_wild_mesh.py:153-154 in place (`mbx_wild_mesh_place`)
+
 There is no CPU path: without an injected kernel provider (`ops=`) the tensors live on the ROCm device and libmbx.so does the work."""
 from __future__ import annotations
 
@@ -216,6 +226,40 @@ def wild_output(pred: torch.Tensor, dst: torch.Tensor, dst_frames: Sequence[int]
     return dst
 
 
+def _tracks(kp_or_tracks):
+    """(kp, lens or None, keys or None) of one person's detections or of a dict idx -> [F_idx,26,3]: the tracks one after another"""
+    if not isinstance(kp_or_tracks, dict):
+        return kp_or_tracks, None, None
+    if not kp_or_tracks:
+        raise ValueError('no tracks')
+    keys = list(kp_or_tracks)
+    parts = [kp_or_tracks[k] for k in keys]
+    for k, p in zip(keys, parts):
+        if len(p.shape) != 3 or tuple(p.shape[1:]) != (26, 3):
+            raise ValueError(f'track {k!r}: expected Halpe-26 detections [F,26,3], got {tuple(p.shape)}')
+    lens = [int(p.shape[0]) for p in parts]
+    if all(isinstance(p, torch.Tensor) for p in parts):
+        kp = torch.cat([p.to(torch.float64) for p in parts])
+    else:
+        kp = np.concatenate([np.asarray(p.cpu() if isinstance(p, torch.Tensor) else p, dtype=np.float64) for p in parts])
+    return kp, lens, keys
+
+
+def _batches(plan, max_batch):
+    """(T, offsets) of every network call: each group of the plan in parts of at most max_batch clips"""
+    for T, offs in plan:
+        for b0 in range(0, len(offs), max_batch):
+            yield T, offs[b0:b0 + max_batch]
+
+
+def _clips(y, part, T):
+    """[n,T,17,C]: the clips of y at the offsets `part` (consecutive clips: a view)"""
+    n = len(part)
+    if all(part[i + 1] - part[i] == T for i in range(n - 1)):
+        return y[part[0]:part[0] + n * T].view(n, T, 17, y.shape[2])
+    return torch.stack([y[o:o + T] for o in part])
+
+
 def infer(model, kp_or_tracks, *, clip_len: int = 243, vid_size=None, pixel: bool = False, flip: bool = True, rootrel: bool = False,
           gt_2d: bool = False, no_conf: bool = False, max_batch: int = 64, ops=None):
     """The loop of infer_wild.py:56-97.  `kp_or_tracks`: [F,26,3] detections of one person (array or tensor) -> numpy [F,17,3] float32, or
@@ -235,22 +279,8 @@ def infer(model, kp_or_tracks, *, clip_len: int = 243, vid_size=None, pixel: boo
         raise ValueError(f'clip_len {clip_len} is longer than the model takes (maxlen = {maxlen})')
     if pixel and not vid_size:
         raise ValueError('pixel=True needs vid_size=(w, h)')
-    as_dict = isinstance(kp_or_tracks, dict)
-    if as_dict:
-        if not kp_or_tracks:
-            raise ValueError('no tracks')
-        keys = list(kp_or_tracks)
-        parts = [kp_or_tracks[k] for k in keys]
-        for k, p in zip(keys, parts):
-            if len(p.shape) != 3 or tuple(p.shape[1:]) != (26, 3):
-                raise ValueError(f'track {k!r}: expected Halpe-26 detections [F,26,3], got {tuple(p.shape)}')
-        lens = [int(p.shape[0]) for p in parts]
-        if all(isinstance(p, torch.Tensor) for p in parts):
-            kp = torch.cat([p.to(torch.float64) for p in parts])
-        else:
-            kp = np.concatenate([np.asarray(p.cpu() if isinstance(p, torch.Tensor) else p, dtype=np.float64) for p in parts])
-    else:
-        kp, lens = kp_or_tracks, None
+    kp, lens, keys = _tracks(kp_or_tracks)
+    as_dict = keys is not None
     if ops is None and not isinstance(kp, torch.Tensor):
         dev = hip_ops.model_device(net, 'motionbert_amd.wild.infer')
         kp = torch.from_numpy(np.ascontiguousarray(kp, dtype=np.float64)).to(dev)             # the one upload
@@ -269,19 +299,203 @@ def infer(model, kp_or_tracks, *, clip_len: int = 243, vid_size=None, pixel: boo
     from .augment import flip_tta
     at = 0
     with torch.no_grad(), _on(dev):
-        for T, offs in plan:
-            for b0 in range(0, len(offs), max_batch):
-                part = offs[b0:b0 + max_batch]
-                n = len(part)
-                if all(part[i + 1] - part[i] == T for i in range(n - 1)):
-                    x = y[part[0]:part[0] + n * T].view(n, T, 17, y.shape[2])                  # consecutive clips: a view
-                else:
-                    x = torch.stack([y[o:o + T] for o in part])
-                pred = flip_tta(net, x) if flip else model(x)                                  # infer_wild.py:73-80
-                prov.wild_output(pred.contiguous().float(), x if gt_2d else None, table[at:at + n], max(part), flags, pix_scale, half_w, half_h, out)
-                at += n
+        for T, part in _batches(plan, max_batch):
+            n = len(part)
+            x = _clips(y, part, T)
+            pred = flip_tta(net, x) if flip else model(x)                                      # infer_wild.py:73-80
+            prov.wild_output(pred.contiguous().float(), x if gt_2d else None, table[at:at + n], max(part), flags, pix_scale, half_w, half_h, out)
+            at += n
     res = out.cpu().numpy()                                                                    # the one device-to-host copy
     if not as_dict:
         return res
     ends = np.cumsum(lens)
     return OrderedDict((k, res[e - n:e]) for k, e, n in zip(keys, ends, lens))
+
+
+# ---------------------------------------------------------------------------------------------------------------- mesh recovery
+_MOVE_MESH = 'the model and the SMPL layer'
+FIT_STATUS = {-1: 'has no frames', -2: 'has a reference motion without extent', -3: 'did not converge (mbx_scale_fit iteration cap)'}
+
+
+def _seq_ptr(lens, dev):
+    return torch.tensor(np.concatenate([[0], np.cumsum(lens)]), dtype=torch.int32).to(dev)
+
+
+def _as_ref(ref_3d, F, dev):
+    if not isinstance(ref_3d, torch.Tensor):
+        ref_3d = torch.from_numpy(np.ascontiguousarray(ref_3d, dtype=np.float64))
+    if ref_3d.dim() != 3 or tuple(ref_3d.shape) != (F, 17, 3):
+        raise ValueError(f'expected a reference motion [{F},17,3], got {tuple(ref_3d.shape)}')
+    return ref_3d.to(device=dev, dtype=torch.float64).contiguous()
+
+
+def _fit_rows(fit_host, keys):
+    """[(scale, t [3], objective, iterations)] of fit [S,6] on the host; ValueError naming the track on a status"""
+    rows = []
+    for s, row in enumerate(np.asarray(fit_host, dtype=np.float64).reshape(-1, 6)):
+        if not row[5] >= 1:
+            raise ValueError(f'solve_scale: track {keys[s] if keys is not None else s!r} {FIT_STATUS.get(int(row[5]) if row[5] == row[5] else 0, "gave no fit")}')
+        rows.append((float(row[0]), row[1:4].copy(), float(row[4]), int(row[5])))
+    return rows
+
+
+def _scale_fit(ref, kp, lens, prov):
+    fit = torch.empty(len(lens), 6, dtype=torch.float64, device=kp.device)
+    with _on(kp.device):
+        prov.scale_fit(ref, kp, _seq_ptr(lens, kp.device), fit)
+    return fit
+
+
+def solve_scale(ref_3d, kp_3d, seq_lens=None, ops=None):
+    """`solve_scale` of infer_wild_mesh.py:42-56 on the device: the scale and translation that minimise
+    mean_i |scale x_i + t - y_i| for x = ref_3d - ref_3d[:, :1] (float64) and y = kp_3d - kp_3d[:, :1] (float32, as numpy forms it),
+    by iteratively reweighted least squares in one `mbx_scale_fit` launch (the objective is convex: the reference's 400 starts look
+    for an optimum that is unique).  ref_3d [F,17,3] (array or tensor), kp_3d [F,17,3] float32.  Returns `(scale, t [3], objective,
+    iterations)`; with `seq_lens` (track lengths summing to F) a list of them, one fit per track.  ValueError naming the track when it
+    has no frames, its reference motion has no extent, or the iteration did not converge."""
+    if not isinstance(kp_3d, torch.Tensor):
+        kp_3d = torch.from_numpy(np.ascontiguousarray(kp_3d, dtype=np.float32))
+    if kp_3d.dim() != 3 or tuple(kp_3d.shape[1:]) != (17, 3):
+        raise ValueError(f'expected keypoints [F,17,3], got {tuple(kp_3d.shape)}')
+    prov, dev = _provider(ops, 'motionbert_amd.wild.solve_scale', kp_3d)
+    F = kp_3d.shape[0]
+    lens = _check_lens([F] if seq_lens is None else seq_lens, F)
+    kp = kp_3d.to(device=dev, dtype=torch.float32).contiguous()
+    rows = _fit_rows(_scale_fit(_as_ref(ref_3d, F, dev), kp, lens, prov).cpu().numpy(), None)
+    return rows[0] if seq_lens is None else rows
+
+
+def place(verts, kp_3d, ref_3d, fit, seq_lens=None, ops=None):
+    """infer_wild_mesh.py:153-154 in place: verts [F,V,3] float32 (a tensor, modified and returned) = verts - kp_3d[:, :1] + ref_3d[:, :1]
+    * scale, in numpy 2's arithmetic (the float32 difference added to the float64 root_cam), rounded to float32 once.  `fit`: what
+    `solve_scale` returned (one tuple, or with `seq_lens` the list of them), or the [S,6] float64 tensor of `mbx_scale_fit`."""
+    if not isinstance(verts, torch.Tensor) or verts.dim() != 3 or verts.shape[2] != 3 or verts.dtype != torch.float32 or not verts.is_contiguous():
+        raise ValueError('place needs verts as a contiguous float32 tensor [F,V,3] (it is modified in place)')
+    F = verts.shape[0]
+    if not isinstance(kp_3d, torch.Tensor):
+        kp_3d = torch.from_numpy(np.ascontiguousarray(kp_3d, dtype=np.float32))
+    if kp_3d.dim() != 3 or kp_3d.shape[0] != F or kp_3d.shape[2] != 3:
+        raise ValueError(f'expected keypoints [{F},K,3], got {tuple(kp_3d.shape)}')
+    prov = hip_ops.provider(ops, 'motionbert_amd.wild.place', verts, move='verts')
+    dev = verts.device
+    lens = _check_lens([F] if seq_lens is None else seq_lens, F)
+    if isinstance(fit, torch.Tensor):
+        table = fit.to(device=dev, dtype=torch.float64).contiguous()
+    else:
+        rows = fit if isinstance(fit, list) else [fit]
+        table = torch.zeros(len(rows), 6, dtype=torch.float64)
+        table[:, 0] = torch.tensor([float(r[0]) for r in rows], dtype=torch.float64)
+        table = table.to(dev)
+    if tuple(table.shape) != (len(lens), 6):
+        raise ValueError(f'{len(lens)} tracks but fits of shape {tuple(table.shape)}')
+    if F:
+        with _on(dev):
+            prov.wild_mesh_place(verts, kp_3d.to(device=dev, dtype=torch.float32).contiguous(), _as_ref(ref_3d, F, dev), _seq_ptr(lens, dev), table)
+    return verts
+
+
+MESH_KEYS = ('verts', 'kp_3d', 'theta')
+
+
+def infer_mesh(model, smpl, kp_or_tracks, *, clip_len: int = 243, vid_size=None, pixel: bool = False, flip: bool = True, ref_3d=None,
+               max_batch: int = 64, want=('verts', 'kp_3d'), to_host: bool = True, ops=None):
+    """The loop of infer_wild_mesh.py:99-154.  `model`: a `mesh.MeshRegressor` (bare or DataParallel-wrapped) whose head's `smpl` is an
+    `SMPLLayer`; `smpl`: that layer (with `J_regressor_h36m`).  `kp_or_tracks` as `infer` takes it: [F,26,3] detections of one person ->
+    a dict `verts` [F,V,3] (millimetres) / `kp_3d` [F,17,3] (/ `theta` [F,82] when `want` names it), or a dict idx -> detections -> a dict
+    idx -> such a dict, every person in the same pass.
+
+    Input stage, clip plan and batching are `infer`'s.  Per batch the backbone and `head.forward_params` run on x and (`flip`) on
+    `mesh.flip_input(x)`, and ONE `mbx_wild_mesh` launch evaluates SMPL for both parameter sets and writes the mean (lines 115-141) into
+    the batch's rows of the stitched results: the vertices of the single passes never exist in memory.  `ref_3d` ([F,17,3], or a dict
+    matching the tracks): the reference motion of `--ref_3d_motion_path`; then `solve_scale` (one `mbx_scale_fit` for all tracks) and the
+    placement of lines 148-154 (`mbx_wild_mesh_place`) follow on the device, and the result gains `scale`.  `to_host=False` returns device
+    tensors (the vertices of a long video are hundreds of MB).  Host reads: the results at the end, and the fits when `ref_3d` is given."""
+    from .mesh import flip_input
+    from .smpl import SMPLLayer
+    net = model.module if hasattr(model, 'module') else model
+    head = getattr(net, 'head', None)
+    if head is None or not hasattr(head, 'forward_params') or not hasattr(net, 'backbone'):
+        raise TypeError('infer_mesh needs a mesh.MeshRegressor (a backbone and a head with forward_params)')
+    if not isinstance(smpl, SMPLLayer) or not isinstance(head.smpl, SMPLLayer):
+        raise TypeError('infer_mesh needs an SMPLLayer, as `smpl` and in the head; mesh.flip_average is the route for other layers')
+    Q = smpl.J_regressor_h36m
+    if Q is None:
+        raise ValueError('infer_mesh needs the layer\'s J_regressor_h36m (it has none)')
+    want = tuple(want)
+    if not want or any(k not in MESH_KEYS for k in want) or len(set(want)) != len(want):
+        raise ValueError(f'want must be a non-empty subset of {MESH_KEYS}, got {want}')
+    clip_len, max_batch = int(clip_len), int(max_batch)
+    if clip_len < 1 or max_batch < 1:
+        raise ValueError(f'clip_len and max_batch must be >= 1, got {clip_len} and {max_batch}')
+    maxlen = getattr(net.backbone, 'maxlen', getattr(net, 'maxlen', None))
+    if maxlen is not None and clip_len > maxlen:
+        raise ValueError(f'clip_len {clip_len} is longer than the model takes (maxlen = {maxlen})')
+    if pixel and not vid_size:
+        raise ValueError('pixel=True needs vid_size=(w, h)')
+    kp, lens, keys = _tracks(kp_or_tracks)
+    if ref_3d is not None and (keys is not None) != isinstance(ref_3d, dict):
+        raise ValueError('ref_3d must be a dict matching the tracks where the detections are one, an array otherwise')
+    if isinstance(ref_3d, dict):
+        if list(ref_3d) != keys:
+            raise ValueError(f'ref_3d has the tracks {list(ref_3d)}, the detections {keys}')
+        for k, n in zip(keys, lens):
+            if tuple(ref_3d[k].shape) != (n, 17, 3):
+                raise ValueError(f'track {k!r}: expected a reference motion [{n},17,3], got {tuple(ref_3d[k].shape)}')
+        ref_3d = np.concatenate([np.asarray(ref_3d[k].cpu() if isinstance(ref_3d[k], torch.Tensor) else ref_3d[k], dtype=np.float64) for k in keys])
+    if ops is None and not isinstance(kp, torch.Tensor):
+        dev = hip_ops.model_device(net, 'motionbert_amd.wild.infer_mesh')
+        kp = torch.from_numpy(np.ascontiguousarray(kp, dtype=np.float64)).to(dev)             # the one upload
+    y = wild_input(kp, vid_size=vid_size if pixel else None, scale_range=None if pixel else [1, 1], seq_lens=lens, ops=ops)     # :99-104
+    F, dev = y.shape[0], y.device
+    lens = [F] if lens is None else lens
+    ref = None if ref_3d is None else _as_ref(ref_3d, F, dev)
+    prov = hip_ops.provider(ops, 'motionbert_amd.wild.infer_mesh', y, smpl.v_template, move=_MOVE_MESH)
+    if Q.device != dev or Q.dtype != torch.float32 or not Q.is_contiguous():
+        Q = Q.to(device=dev, dtype=torch.float32).contiguous()
+    K, V = Q.shape[0], smpl.num_vertices
+    verts = torch.empty(F, V, 3, dtype=torch.float32, device=dev) if 'verts' in want else None
+    kp3d = torch.empty(F, K, 3, dtype=torch.float32, device=dev) if ('kp_3d' in want or ref is not None) else None
+    theta = torch.empty(F, 82, dtype=torch.float32, device=dev) if 'theta' in want else None
+    plan = clip_plan(lens, clip_len)
+    offsets = [o for _, offs in plan for o in offs]
+    table = torch.tensor(offsets, dtype=torch.int32).to(dev) if offsets else None              # every batch's destinations, one upload
+    if hasattr(model, 'eval'):
+        model.eval()
+    tensors = smpl.model_tensors()
+
+    def params(x):
+        n, T = x.shape[:2]
+        rot, shape, th = head.forward_params(net.backbone.get_representation(x).reshape([n, T, 17, -1]))
+        return rot.float().contiguous(), shape.float().contiguous(), th.float().contiguous()
+
+    at = 0
+    with torch.no_grad(), _on(dev):
+        for T, part in _batches(plan, max_batch):
+            n = len(part)
+            x = _clips(y, part, T)
+            rot_a, shape_a, theta_a = params(x)                                                # :115
+            theta_b = params(flip_input(x))[2] if flip else None                               # :116-117
+            prov.wild_mesh(tensors, Q, rot_a, shape_a, theta_a if theta is not None else None, theta_b, 1000.0, table[at:at + n], max(part), T,
+                           verts, kp3d, theta)                                                 # :118-141, stitched
+            at += n
+    out = {'verts': verts, 'kp_3d': kp3d if 'kp_3d' in want else None, 'theta': theta}
+    fits = None
+    if ref is not None:                                                                        # :148-154
+        fit = _scale_fit(ref, kp3d, lens, prov)
+        if verts is not None and F:
+            with _on(dev):
+                prov.wild_mesh_place(verts, kp3d, ref, _seq_ptr(lens, dev), fit)
+        fits = _fit_rows(fit.cpu().numpy(), keys)
+    out = {k: (v.cpu().numpy() if to_host else v) for k, v in out.items() if v is not None}
+    if keys is None:
+        if fits is not None:
+            out['scale'] = fits[0][0]
+        return out
+    res, end = OrderedDict(), 0
+    for i, (k, n) in enumerate(zip(keys, lens)):
+        res[k] = {name: v[end:end + n] for name, v in out.items()}
+        if fits is not None:
+            res[k]['scale'] = fits[i][0]
+        end += n
+    return res
+
