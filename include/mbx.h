@@ -635,7 +635,34 @@ int mbx_scale_fit(const double* ref, const float* kp, const int* seq_ptr, int S,
 int mbx_wild_mesh_place(float* verts, const float* kp, int K, const double* ref, const int* seq_ptr, int S, const double* fit, int F,
                         int V, void* stream);
 
-/* ---- measurement aid (bench.py `roofline.sustained_mfma_tflops`; not part of the model) --------------------------------------------
+/* ---- the 2D half of pre-training (csrc/motion2d.hip; lib/data/dataset_motion_2d.py:116-147, train.py:162-172, --------------------------------
+ *      lib/utils/utils_data.py:7-29,54-66) -- mbx_version() >= 170
+ * mbx_motion2d_input: InstaVDataset2D.__getitem__ and the no_grad block of train_epoch for a 2D batch x [N,T,J,3] (x, y, confidence; f32),
+ * one launch, one workgroup per sample.  Two draws per sample, params [N,2] = (ratio, u_flip): params_in as they are, or (params_in NULL)
+ * ratio = min(fma(hi - lo, u(stream 16, index n), lo), hi) and u_flip = u(stream 17, index n) with the counter-based hash of mbx_augment2d
+ * (streams 0-14 are the augmentation's: one seed serves both); params_out (may be NULL, may be params_in) receives them.
+ * flags: bit 0 crop -- over the joints with confidence != 0: fewer than 4 -> the sample is 0; scale = max(xmax - xmin, ymax - ymin) ratio,
+ *          scale == 0 -> the sample is 0; xs = (xmin + xmax - scale) / 2, ys likewise; x'' = ((x - xs) / scale - 0.5) 2, y'' likewise; all three
+ *          channels clipped to [-1, 1] (the operations, and the bits, of mbx_action_input's crop);
+ *        bit 1 zeroing -- a joint whose confidence is 0 becomes (0, 0, 0);
+ *        bit 2 flip -- if u_flip < flip_prob the clip is flip_data: x negated, joint j reads joint perm[j] of the 17-joint left / right table
+ *          (J = 17 is required with this bit);
+ *        bit 3 noise, bit 4 mask -- the arguments and bits of mbx_augment2d's flags 1 and 2;  bit 5 rootrel.
+ * Outputs, each may be NULL (not all four):
+ *   data [N,T,J,3]  the data set's item;   conf [N,T,J] = data[..., 2]
+ *   gt [N,T,J,3]    rootrel: data - data[:, :, 0:1] in all three channels; otherwise data with channel 2 minus data[n,0,0,2]
+ *   x_aug [N,T,J,3] what mbx_augment2d writes for data with the same seed and arguments, bit for bit
+ * A sample of at most MBX_MOTION2D_RESIDENT joints (T J) is read once and kept in LDS; a larger one is read twice (the second time from L2).
+ * Refused: null x, no output, N, T, J < 1, J > 32, lo > hi, flip_prob outside [0, 1], unknown flag bits, the flip with J != 17, noise without
+ * its arrays, N T J >= 2^32, an output that overlaps x (the flip reads other joints of the frame). */
+#define MBX_MOTION2D_RESIDENT 1536
+int mbx_motion2d_input(const float* x, float* data, float* gt, float* conf, float* x_aug, int N, int T, int J, const float* params_in,
+                       float* params_out, float ratio_lo, float ratio_hi, float flip_prob, const float* noise_mean,
+                       const float* noise_std, const float* noise_weight, float uniform_range, float jitter_std, float d2c_a,
+                       float d2c_b, float d2c_m, float d2c_s, float mask_ratio, float mask_T_ratio, int flags, uint64_t seed,
+                       void* stream);
+
+/* ---- measurement aid (bench.py`roofline.sustained_mfma_tflops`; not part of the model) --------------------------------------------
  * The bf16 MFMA rate the part sustains under its power cap with nothing but v_mfma_f32_32x32x16_bf16 in the loop (pseudo-random
  * operands; n_wg workgroups of 4 waves, `iters` x 16 MFMAs per wave).  ws: >= mbx_mfma_probe_ws(n_wg) bytes = a float sink
  * [n_wg * 256] followed by int64 [n_wg][2] = {shader cycles, 100 MHz real-time ticks} of every workgroup's loop (effective clock).

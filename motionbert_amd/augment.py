@@ -6,6 +6,9 @@ and both masks as ONE kernel on the batch already resident in HBM; the reference
 copies them to the device and runs ~25 element-wise kernels.  Random numbers are counter-based (a 64-bit seed per call from
 torch's CPU generator), so a call is reproducible from its seed.
 
+`action_input` and `motion2d_input` are the per-clip `__getitem__` stages of the NTU and of the 2D pre-training data sets, one launch each;
+`motion2d_input` can also write what `train_epoch`'s `no_grad` block derives from a 2D batch (target, confidence, augmented input).
+
 `flip_tta(model, x)` is the evaluation pattern of train.py:67-72 / infer_wild.py:75-80 -- model(x), model(flip(x)), flip
 back, average -- as ONE forward over 2B samples in which the flipped half is an index remap inside the embedding kernel and
 the flip-back + average is one pass over the output: no deep copies of the input (`flip_data` deep-copies) or the output."""
@@ -107,6 +110,65 @@ def action_input(x: torch.Tensor, random_move: bool = True, scale_range=(1, 1), 
         with (torch.cuda.device(xc.device) if xc.is_cuda else _nullcontext()):
             ops.action_input(xc, y, params, used, ranges, (1 if random_move else 0) | (2 if crop else 0), 0 if seed is None else int(seed))
     return (y, used) if return_params else y
+
+
+#: flag bits of `mbx_motion2d_input` (include/mbx.h)
+M2D_CROP, M2D_ZERO, M2D_FLIP, M2D_NOISE, M2D_MASK, M2D_ROOTREL = 1, 2, 4, 8, 16, 32
+_M2D_OUTPUTS = ('data', 'gt', 'conf', 'x_aug')
+
+
+def motion2d_input(x: torch.Tensor, *, scale_range=(0.25, 1), zero_unseen: bool = True, flip_prob: float = 0.5, aug: Optional[Augmenter2D] = None,
+                   noise: bool = False, mask: bool = False, rootrel: bool = True, want=('data',), seed: Optional[int] = None,
+                   params: Optional[torch.Tensor] = None, return_params: bool = False, ops=None):
+    """`InstaVDataset2D.__getitem__` (lib/data/dataset_motion_2d.py:139-147) and the `no_grad` block of `train_epoch` for a 2D batch
+    (train.py:162-172) for x [N,T,J,3] (x, y, confidence) in ONE launch of `mbx_motion2d_input`: `crop_scale(scale_range)` (`None` skips it),
+    zeroing of the joints with confidence 0, `flip_data` of the clips whose draw is below `flip_prob`; then, from that item `data`, the
+    target `gt` (`rootrel`: `data - data[:, :, 0:1]`, else the confidence channel minus `data[n,0,0,2]`), `conf` = `data[..., 2:]` and
+    `x_aug` = `aug.augment2D(data, noise=noise, mask=mask)` with the same `seed` (bit for bit).  Returns a dict of the NEW tensors named in
+    `want` ('data', 'gt', 'conf' [N,T,J,1], 'x_aug').
+
+    Each sample uses two draws, (ratio, u_flip): the rows of `params` [N,2] if given, otherwise counter-based random numbers from `seed`
+    (default: 62 bits from torch's CPU generator) on streams the augmentation does not use.  `return_params=True`: `(dict, params_used [N,2])`."""
+    from . import hip_ops
+    if x.dim() != 4 or x.shape[-1] != 3:
+        raise ValueError(f'expected [N,T,J,3] keypoints with confidence, got {tuple(x.shape)}')
+    want = tuple(want)
+    if not want or any(w not in _M2D_OUTPUTS for w in want) or len(set(want)) != len(want):
+        raise ValueError(f'want must name some of {_M2D_OUTPUTS} once each, got {want}')
+    if (noise or mask) and aug is None:
+        raise ValueError('noise / mask need an Augmenter2D (aug=)')
+    if not 0.0 <= float(flip_prob) <= 1.0:
+        raise ValueError(f'flip_prob = {flip_prob} is not in [0, 1]')
+    if flip_prob > 0 and x.shape[2] != 17:
+        raise ValueError(f'the flip uses the 17-joint left/right table of lib/utils/utils_data.py:60-61, J = {x.shape[2]} (pass flip_prob=0)')
+    crop = scale_range is not None and scale_range is not False
+    lo, hi = (float(scale_range[0]), float(scale_range[1])) if crop else (1.0, 1.0)
+    if not lo <= hi:
+        raise ValueError(f'range ({lo}, {hi}) has lo > hi')
+    ops = hip_ops.provider(ops, 'motionbert_amd.augment.motion2d_input', x, params, move='the batch')
+    xc = x.contiguous().float()
+    N, T, J, _ = xc.shape
+    if params is not None:
+        if tuple(params.shape) != (N, 2):
+            raise ValueError(f'params must be [{N}, 2], got {tuple(params.shape)}')
+        params = params.detach().to(device=xc.device, dtype=torch.float32).contiguous()
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    out = {w: torch.empty((N, T, J, 1 if w == 'conf' else 3), dtype=torch.float32, device=xc.device) for w in want}
+    used = torch.empty(N, 2, dtype=torch.float32, device=xc.device) if return_params else None
+    flags = ((M2D_CROP if crop else 0) | (M2D_ZERO if zero_unseen else 0) | (M2D_FLIP if flip_prob > 0 else 0) | (M2D_NOISE if noise else 0) |
+             (M2D_MASK if mask else 0) | (M2D_ROOTREL if rootrel else 0))
+    if N:
+        d = (aug.d2c_params if aug is not None else None) or dict(a=0.0, b=0.0, m=0.0, s=0.0)
+        ur = float(aug.noise['uniform_range']) if (aug is not None and aug.noise is not None and 'uniform_range' in aug.noise) else 0.06
+        with (torch.cuda.device(xc.device) if xc.is_cuda else _nullcontext()):
+            ops.motion2d_input(xc, out.get('data'), out.get('gt'), out.get('conf'), out.get('x_aug'), params, used, (lo, hi), float(flip_prob),
+                               aug._noise_on(xc.device) if noise else None, ur, aug.noise_std if aug is not None else 0.002,
+                               (d['a'], d['b'], d['m'], d['s']), aug.mask_ratio if aug is not None else 0.0,
+                               aug.mask_T_ratio if aug is not None else 0.0, flags, int(seed))
+        if aug is not None and 'x_aug' in want:
+            aug.last_seed = int(seed)
+    return (out, used) if return_params else out
 
 
 def flip_tta(model, x: torch.Tensor) -> torch.Tensor:

@@ -10,56 +10,20 @@
 // Random numbers are counter-based: u(stream, index) = hash(seed, stream, index) -- a value depends only on WHICH number it is,
 // so the torch restatement in oracle/augment_oracle.py reproduces every draw.
 #include "mbx_common.h"
-#include "aug_rng.h"
+#include "aug2d_point.h"
 
-// standard normal: Box-Muller on two uniforms of the streams (stream, stream + 1)
-__device__ __forceinline__ float aug_normal(uint32_t slo, uint32_t shi, uint32_t stream, uint32_t idx) {
-    const float u1 = aug_uniform(slo, shi, stream, idx), u2 = aug_uniform(slo, shi, stream + 1, idx);
-    return sqrtf(-2.0f * logf(u1 + (1.0f / 33554432.0f))) * cosf(6.28318530717958647692f * u2);
-}
-// streams: 0 sel, 1-2 gaussian x, 3-4 gaussian y, 5 uniform x, 6 uniform y, 7-8 jitter x, 9-10 jitter y, 11-12 confidence shift,
-//          13 joint mask, 14 frame mask
-#define AUG_K 27
+// the per-point body (and the stream table of the random numbers) is aug2d_point.h: mbx_motion2d_input calls the same function
 __global__ __launch_bounds__(256) void augment2d_kernel(const float* __restrict__ x, float* __restrict__ y, int B, int T, int J, int Cin,
                                                         const float* __restrict__ nmean, const float* __restrict__ nstd,
                                                         const float* __restrict__ nweight, float urange, float jitter_std, float a,
                                                         float b, float m, float s, float mask_ratio, float mask_T_ratio, int flags,
                                                         uint32_t slo, uint32_t shi) {
+    const Aug2dArgs A = {nmean, nstd, nweight, urange, jitter_std, a, b, m, s, mask_ratio, mask_T_ratio, flags};
     const size_t total = (size_t)B * T * J;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
         const int j = (int)(i % J), t = (int)((i / J) % T), bb = (int)(i / ((size_t)J * T));
         float px = x[i * Cin], py = x[i * Cin + 1], conf = Cin > 2 ? x[i * Cin + 2] : 1.0f;
-        if (flags & 1) {          // add_noise (augmentation.py:29-66)
-            // key-frame position of frame t: align_corners = True
-            const float pos = T > 1 ? (float)t * (float)(AUG_K - 1) / (float)(T - 1) : 0.f;
-            int k0 = (int)floorf(pos);
-            if (k0 > AUG_K - 2) k0 = AUG_K - 2;
-            const float wgt = pos - (float)k0;
-            float d[2] = {0.f, 0.f};
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                const uint32_t ki = (uint32_t)((bb * AUG_K + k0 + kk) * J + j);
-                const bool gauss = aug_uniform(slo, shi, 0, ki) < nweight[j];
-                const float gx = aug_normal(slo, shi, 1, ki) * nstd[j * 2] + nmean[j * 2];
-                const float gy = aug_normal(slo, shi, 3, ki) * nstd[j * 2 + 1] + nmean[j * 2 + 1];
-                const float ux = (aug_uniform(slo, shi, 5, ki) - 0.5f) * urange, uy = (aug_uniform(slo, shi, 6, ki) - 0.5f) * urange;
-                const float wk = kk == 0 ? 1.0f - wgt : wgt;
-                d[0] += wk * (gauss ? gx : ux);
-                d[1] += wk * (gauss ? gy : uy);
-            }
-            const uint32_t ti = (uint32_t)(t * J + j);                 // jitter: shared by the whole batch (augmentation.py:47)
-            d[0] += aug_normal(slo, shi, 7, ti) * jitter_std;
-            d[1] += aug_normal(slo, shi, 9, ti) * jitter_std;
-            px += d[0];
-            py += d[1];
-            const float dis = sqrtf(d[0] * d[0] + d[1] * d[1]);
-            conf = a / (dis + a) + b * dis + aug_normal(slo, shi, 11, (uint32_t)i) * s + m;   // dis2conf (augmentation.py:22-27)
-            conf = fminf(fmaxf(conf, 0.f), 1.f);
-        }
-        if (flags & 2) {          // add_mask (augmentation.py:67-74): x * (rand > mask_ratio) * (rand_T > mask_T_ratio)
-            const bool keep = aug_uniform(slo, shi, 13, (uint32_t)i) > mask_ratio && aug_uniform(slo, shi, 14, (uint32_t)t) > mask_T_ratio;
-            if (!keep) { px = 0.f; py = 0.f; conf = 0.f; }
-        }
+        aug2d_point(A, slo, shi, T, J, bb, t, j, px, py, conf);
         y[i * 3] = px; y[i * 3 + 1] = py; y[i * 3 + 2] = conf;
     }
 }

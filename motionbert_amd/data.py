@@ -15,6 +15,8 @@ collates on the host.  At 8 x 1,000 clips/s that is ~0.8 GB/s of pickle parsing.
   pack_action / PackedAction, pack_mesh / PackedMesh   the same scheme for the NTU annotation file (lib/data/dataset_action.py) and for the
                        mesh detection files (lib/data/dataset_mesh.py); their `__getitem__` stages are HIP kernels (`mbx_action_input`,
                        `mbx_mesh_gt`: the SMPL ground truth is computed on the device, nothing of vertex size crosses the host link).
+  pack_posetrack / pack_instav / PackedMotion2D   the same scheme for the two 2D sets of pre-training (lib/data/dataset_motion_2d.py); their
+                       `__getitem__` stage and the 2D front end of the training step are one launch of `mbx_motion2d_input`.
   sharding             `rank` / `world`: every rank walks the same per-epoch permutation and takes a strided, equally sized
                        share (what DistributedSampler does), so the N ranks of the data-parallel run never exchange data.
 """
@@ -526,6 +528,171 @@ class PackedMesh:
             for k, (motion_2d, pose, shape) in enumerate(stream):
                 yield mesh_targets(self.smpl, pose, shape, motion_2d, flip=self.flip, seed=PackedAction.batch_seed(seed, epoch, rank, k),
                                    ops=self.ops)
+        finally:
+            stream.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the 2D half of pre-training (lib/data/dataset_motion_2d.py): PoseTrack and InstaVariety, packed once
+# ---------------------------------------------------------------------------------------------------------------
+#: posetrack2h36m (dataset_motion_2d.py:14-74): H36M joint <- one PoseTrack joint; the root is the mean of the hips, the belly the mean of
+#: root and neck, and their confidences the minimum of the two
+_POSETRACK_SINGLE = {1: 12, 2: 14, 3: 16, 4: 11, 5: 13, 6: 15, 8: 1, 9: 0, 10: 2, 11: 5, 12: 7, 13: 9, 14: 6, 15: 8, 16: 10}
+
+
+def _posetrack_to_h36m(x):
+    """posetrack2h36m (dataset_motion_2d.py:54-74) for x [T,17,C]"""
+    y = np.zeros(x.shape)
+    for j, c in _POSETRACK_SINGLE.items():
+        y[:, j] = x[:, c]
+    y[:, 0] = (x[:, 11] + x[:, 12]) * 0.5
+    y[:, 7] = (y[:, 0] + y[:, 8]) * 0.5
+    y[:, 0, 2] = np.minimum(x[:, 11, 2], x[:, 12, 2])
+    y[:, 7, 2] = np.minimum(y[:, 0, 2], y[:, 8, 2])
+    return y
+
+
+def _crop_scale_host(motion, scale_range, rng):
+    """crop_scale (utils_data.py:7-29) for one clip in numpy's own arithmetic, the ratio from `rng` -- drawn, as there, only once four valid
+    joints were found"""
+    valid = motion[motion[..., 2] != 0][:, :2]
+    if len(valid) < 4:
+        return np.zeros(motion.shape)
+    xmin, xmax, ymin, ymax = min(valid[:, 0]), max(valid[:, 0]), min(valid[:, 1]), max(valid[:, 1])
+    ratio = rng.uniform(low=scale_range[0], high=scale_range[1], size=1)[0]
+    scale = max(xmax - xmin, ymax - ymin) * ratio
+    if scale == 0:
+        return np.zeros(motion.shape)
+    result = motion.copy()
+    result[..., :2] = (motion[..., :2] - [(xmin + xmax - scale) / 2, (ymin + ymax - scale) / 2]) / scale
+    result[..., :2] = (result[..., :2] - 0.5) * 2
+    return np.clip(result, -1, 1)
+
+
+def pack_posetrack(annot_dir: str, out_prefix: str, scale_range=(0.25, 1), seed: int = 0) -> dict:
+    """The whole of `PoseTrackDataset2D.__init__` (dataset_motion_2d.py:78-110) for the annotation files of `annot_dir` (the reference
+    reads `data/motion2d/posetrack18_annotations/train/`): the tracks of every file in `sorted(os.listdir)` order, the first 30 frames of a
+    track of at least 30, the `<= 306` filter on the summed confidence, `crop_scale(scale_range)`, `posetrack2h36m`, zeroing of the joints
+    with confidence 0, and the filter that keeps the tracks whose root is visible in all 30 frames.  Writes `<prefix>.motion2d.npy`
+    [N,30,17,3] float32 (what `torch.FloatTensor` makes of the reference's array) and `<prefix>.json`; returns the metadata.
+
+    The crop ratios come from `np.random.RandomState(seed)` in motion order, which is what the reference's `np.random.seed(seed)` amounts
+    to: the array equals the reference's `motions_2d` bit for bit.  The crop is drawn ONCE, here, as in the reference (its `__getitem__`
+    only flips): `PackedMotion2D(kind='posetrack')`."""
+    files = sorted(os.listdir(annot_dir))
+    if not files:
+        raise ValueError(f'no annotation files under {annot_dir}')
+    rng = np.random.RandomState(seed)
+    tracks = []
+    for name in files:
+        with open(os.path.join(annot_dir, name), 'r') as f:
+            annots = json.load(f)['annotations']
+        by_track = {}                                  # insertion order = first appearance, as the reference's defaultdict keeps it
+        for a in annots:
+            by_track.setdefault(a['track_id'], []).append(np.array(a['keypoints']).reshape(-1, 3))
+        tracks += list(by_track.values())
+    kept = []
+    for track in tracks:
+        if len(track) < 30:
+            continue
+        motion = np.array(track[:30])
+        if np.sum(motion[:, :, 2]) <= 306:            # valid joint num threshold
+            continue
+        motion = _posetrack_to_h36m(_crop_scale_host(motion, scale_range, rng))
+        motion[motion[:, :, 2] == 0] = 0
+        if np.sum(motion[:, 0, 2]) < 30:
+            continue                                   # root all visible (needed for framewise rootrel)
+        kept.append(motion)
+    if not kept:
+        raise ValueError(f'{annot_dir}: no track passed the filters')
+    np.save(out_prefix + '.motion2d.npy', np.array(kept).astype(np.float32))
+    meta = dict(n=len(kept), clip_shape=[30, 17, 3], kind='posetrack', scale_range=[float(scale_range[0]), float(scale_range[1])], seed=int(seed))
+    with open(out_prefix + '.json', 'w') as f:
+        json.dump(meta, f)
+    return meta
+
+
+def pack_instav(motion_npy: str, id_npy: str, out_prefix: str, n_frames: int = 81, data_stride: int = 27, valid_threshold: float = 0.0,
+                seed: int = 0) -> dict:
+    """The whole of `InstaVDataset2D.__init__` (dataset_motion_2d.py:124-133) for `motion_all.npy` [frames,17,3] and `id_all.npy` [frames]:
+    `split_clips(id_all, n_frames, data_stride)` with the random rounding of a short video's resampling from `np.random.RandomState(seed)`
+    (the reference's `np.random.seed(seed)`), then the clips whose first root confidence is above `valid_threshold`.  Writes the clips
+    materialised, `<prefix>.motion2d.npy` [N,n_frames,17,3] float32, and `<prefix>.json`; returns the metadata.  The per-clip stage of
+    `__getitem__` (crop, zeroing, flip) is `mbx_motion2d_input`: `PackedMotion2D(kind='instav')`."""
+    motion_all, id_all = np.load(motion_npy, mmap_mode='r'), np.load(id_npy)
+    if len(motion_all) != len(id_all):
+        raise ValueError(f'{len(motion_all)} frames but {len(id_all)} video ids')
+    ids = _split_clips(id_all, int(n_frames), int(data_stride), np.random.RandomState(seed))
+    if not ids:
+        raise ValueError(f'{motion_npy}: no clip of {n_frames} frames')
+    ids = np.stack(ids).astype(np.int64)
+    ids = ids[np.asarray(motion_all[ids[:, 0], 0, 2]) > valid_threshold]
+    if not len(ids):
+        raise ValueError(f'{motion_npy}: no clip passed the valid_threshold filter')
+    out = np.lib.format.open_memmap(out_prefix + '.motion2d.npy', mode='w+', dtype=np.float32, shape=(len(ids), int(n_frames)) + tuple(motion_all.shape[1:]))
+    for i, row in enumerate(ids):
+        out[i] = motion_all[row]
+    out.flush()
+    meta = dict(n=int(len(ids)), clip_shape=[int(n_frames)] + list(motion_all.shape[1:]), kind='instav', data_stride=int(data_stride), seed=int(seed))
+    with open(out_prefix + '.json', 'w') as f:
+        json.dump(meta, f)
+    return meta
+
+
+class PackedMotion2D:
+    """The packed clips of `pack_posetrack` / `pack_instav` + the asynchronous batch stream of `pinned_batches` + the data sets'
+    `__getitem__` on the device, and optionally the 2D front end of the pre-training step in the same launch.
+
+        ds = PackedMotion2D(prefix, device='cuda', kind='instav', flip=True, scale_range=(0.25, 1))
+        for motion_2d, target in ds.batches(64, epoch=e, rank=r, world=w):        # [B,T,17,3] twice (the same tensor): the reference's loader
+            ...
+        for x_aug, gt, conf in ds.batches(64, epoch=e, front=step, has_gt=False): # what PretrainStep.step_prepared takes
+            ...
+    kind='instav': crop_scale(scale_range) with a ratio per clip and batch, zeroing of unseen joints, random flip (dataset_motion_2d.py:
+    139-147).  kind='posetrack': the flip only (:116-121; its crop happened once, at pack time).  Every batch is ONE launch of
+    `mbx_motion2d_input` with a seed derived from (seed, epoch, rank, batch index) as `PackedAction` derives it.  With `front=step` (a
+    `PretrainStep`) the same launch also writes the target, the confidence and the augmented input of train.py:162-172 with the step's
+    `rootrel`, `mask` and `noise` (noise only if `has_gt`); a step with `no_conf` is refused (the reference cannot form `conf` there either).
+    `ops`: kernel provider for host tensors (tests)."""
+
+    def __init__(self, prefix: str, device='cuda', kind: str = 'instav', flip: bool = True, scale_range: Optional[Tuple[float, float]] = (0.25, 1),
+                 ring: int = 3, ops=None):
+        if kind not in ('instav', 'posetrack'):
+            raise ValueError(f"kind must be 'instav' or 'posetrack', got {kind!r}")
+        with open(prefix + '.json') as f:
+            self.meta = json.load(f)
+        self.motion_2d = np.load(prefix + '.motion2d.npy', mmap_mode='r')
+        self.device = torch.device(device)
+        self.kind, self.flip = kind, bool(flip)
+        self.scale_range = tuple(scale_range) if (kind == 'instav' and scale_range) else None
+        self.ring, self.ops = max(2, int(ring)), ops
+
+    def __len__(self):
+        return len(self.motion_2d)
+
+    def batches(self, batch_size: int, shuffle: bool = True, epoch: int = 0, seed: int = 0, rank: int = 0, world: int = 1,
+                drop_last: bool = False, front=None, has_gt: bool = True):
+        from .augment import motion2d_input
+        if front is not None and front.no_conf:
+            raise ValueError('PackedMotion2D: a step with no_conf has no 2D front end (conf = batch_input[..., 2:] would be empty)')
+        idx = shard_indices(len(self), shuffle, epoch, seed, rank, world)
+        chunks = [idx[i:i + batch_size] for i in range(0, len(idx), batch_size)]
+        if drop_last and chunks and len(chunks[-1]) < batch_size:
+            chunks.pop()
+        if not chunks:
+            return
+        stage = dict(scale_range=self.scale_range, zero_unseen=self.kind == 'instav', flip_prob=0.5 if self.flip else 0.0, ops=self.ops)
+        stream = pinned_batches([self.motion_2d], chunks, batch_size, self.device, self.ring)
+        try:
+            for k, (motion,) in enumerate(stream):
+                s = PackedAction.batch_seed(seed, epoch, rank, k)
+                if front is None:
+                    data = motion2d_input(motion, want=('data',), seed=s, **stage)['data']
+                    yield data, data
+                else:
+                    out = motion2d_input(motion, want=('x_aug', 'gt', 'conf'), seed=s, aug=front.aug, noise=bool(front.noise and has_gt),
+                                         mask=bool(front.mask), rootrel=bool(front.rootrel), **stage)
+                    yield out['x_aug'], out['gt'], out['conf']
         finally:
             stream.close()
 

@@ -115,6 +115,7 @@ SIGNATURES = {
     'mbx_mesh_gt_ws': (_sz, [_i, _i, _i]),
     'mbx_mesh_gt': (_i, [_vp, _vp, _vp, _vp, C.c_uint64, _f] + [_vp] * 5 + [C.POINTER(C.c_int)] + [_vp, _vp, _i, _f] + [_vp] * 5 + [_i, _i, _i, _vp, _sz, _vp]),
     'mbx_action_input': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp] + [_f] * 8 + [_i, C.c_uint64, _vp]),
+    'mbx_motion2d_input': (_i, [_vp] * 5 + [_i, _i, _i, _vp, _vp] + [_f] * 3 + [_vp] * 3 + [_f] * 8 + [_i, C.c_uint64, _vp]),
     'mbx_xent_topk': (_i, [_vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp]),
     'mbx_wild_input_ws': (_sz, [_i, _i]),
     'mbx_wild_input': (_i, [_vp, _vp, _i, _vp, _i, _i] + [C.c_double] * 4 + [_i, _i, _vp, _vp, _vp, _sz, _vp]),
@@ -717,6 +718,25 @@ class HipOps:
         (a0, a1), (s0, s1), (t0, t1), (c0, c1) = ranges
         self._ck(self.lib.mbx_action_input(_p(x), _p(y), N, M, T, J, _p(params_in), _p(params_out), float(a0), float(a1), float(s0), float(s1),
                                            float(t0), float(t1), float(c0), float(c1), int(flags), int(seed), self._stream()))
+
+    def motion2d_input(self, x, data, gt, conf, x_aug, params_in, params_out, ratio_range, flip_prob, noise, uniform_range, jitter_std, d2c,
+                       mask_ratio, mask_T_ratio, flags, seed):
+        """x [N,T,J,3] f32; data / gt / x_aug like x, conf [N,T,J,1], each or None; params_in / params_out [N,2] f32 or None; noise = (mean,
+        std, weight) or None; flags bit 0 crop, 1 zero unseen, 2 flip, 3 noise, 4 mask, 5 rootrel; all contiguous, on the device of x."""
+        if x.dim() != 4 or x.shape[-1] != 3:
+            raise RuntimeError(f'libmbx: motion2d_input needs x [N,T,J,3], got {tuple(x.shape)}')
+        N, T, J, _ = x.shape
+        self._dense('motion2d_input', torch.float32, x.numel(), x.device, x=x, data=data, gt=gt, x_aug=x_aug)
+        self._dense('motion2d_input', torch.float32, N * T * J, x.device, conf=conf)
+        self._dense('motion2d_input', torch.float32, N * 2, x.device, params_in=params_in, params_out=params_out)
+        mean, std, weight = noise if noise is not None else (None, None, None)
+        self._dense('motion2d_input', torch.float32, 2 * J, x.device, noise_mean=mean, noise_std=std)      # the kernel reads entry j of each
+        self._dense('motion2d_input', torch.float32, J, x.device, noise_weight=weight)
+        a, b, m, s = d2c
+        self._ck(self.lib.mbx_motion2d_input(_p(x), _p(data), _p(gt), _p(conf), _p(x_aug), N, T, J, _p(params_in), _p(params_out),
+                                             float(ratio_range[0]), float(ratio_range[1]), float(flip_prob), _p(mean), _p(std), _p(weight),
+                                             float(uniform_range), float(jitter_std), float(a), float(b), float(m), float(s),
+                                             float(mask_ratio), float(mask_T_ratio), int(flags), int(seed), self._stream()))
 
     def xent_topk(self, logits, labels, values, dlogits, acc, grad_scale=1.0):
         """logits [N,C] f32, labels [N] i32, values [3] f32, dlogits like logits or None, acc [4] f64 (accumulated) or None; all contiguous, on

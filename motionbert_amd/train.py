@@ -139,6 +139,14 @@ class PretrainStep:
                 batch_gt[..., 2] = batch_gt[..., 2] - batch_gt[:, 0:1, 0:1, 2]
             if self.mask or self.noise:
                 batch_input = self.aug.augment2D(batch_input, noise=(self.noise and has_gt), mask=self.mask, seed=seed)
+        return self.step_prepared(batch_input, batch_gt, conf, has_3d)
+
+    def step_prepared(self, batch_input: torch.Tensor, batch_gt: torch.Tensor, conf: Optional[torch.Tensor] = None, has_3d: bool = False) -> torch.Tensor:
+        """The step after its `no_grad` block: forward on the (augmented) `batch_input`, the loss against the prepared target `batch_gt` --
+        for a 2D batch weighted by `conf`, the confidence before augmentation --, backward, update.  `__call__` ends here; a front end that
+        prepared the three tensors itself (`PackedMotion2D.batches(front=step)`: one launch of `mbx_motion2d_input`) starts here."""
+        if not has_3d and conf is None:
+            raise ValueError('a 2D batch needs conf (the confidence before augmentation)')
         pred = self.net(batch_input)
         self.opt.zero_grad(set_to_none=True)
         if has_3d:
@@ -179,6 +187,51 @@ def pretrain_epoch_plan(n_posetrack: int, n_instav: int, n_3d: int, epoch: int, 
         plan += [('posetrack', False, True, int(n_posetrack)), ('instav', False, False, int(n_instav))]
     plan.append(('3d', True, True, int(n_3d)))
     return plan
+
+
+def run_pretrain_epoch(step, posetrack, instav, motion3d, batch_size: int, epoch: int, seed: int = 0, rank: int = 0, world: int = 1,
+                       train_2d: bool = True, curriculum: int = 30):
+    """One pre-training epoch (train.py:325-330) over the three packed sets: `posetrack` and `instav` are `data.PackedMotion2D` (either may be
+    None with `train_2d=False` or before the curriculum epoch), `motion3d` a `data.PackedMotion3D`, `step` a `PretrainStep`.  Walks
+    `pretrain_epoch_plan` with the per-rank batch counts of equal shards: every 2D batch comes from the one-launch front end
+    (`batches(front=step)`) and goes to `step.step_prepared`, every 3D batch to `step(...)`.  The logged losses are summed on the device;
+    ONE host synchronisation at the end returns `{loader: {'batches': n, 'losses': [mean of each logged value]}}` in plan order."""
+    sets = {'posetrack': posetrack, 'instav': instav, '3d': motion3d}
+
+    def per_rank(ds):                                   # batches of one rank: equal shards (shard_indices), the last batch kept
+        share = 0 if ds is None else -(-len(ds) // world)
+        return -(-share // batch_size)
+    plan = pretrain_epoch_plan(per_rank(posetrack), per_rank(instav), per_rank(motion3d), epoch, train_2d=train_2d, curriculum=curriculum)
+    sums = []
+    for name, has_3d, has_gt, n_batches in plan:
+        ds = sets[name]
+        if ds is None:
+            if n_batches:
+                raise ValueError(f'the plan has {n_batches} batches of {name!r} but no data set was given')
+            continue
+        acc, count = None, 0
+        kw = dict(shuffle=True, epoch=epoch, seed=seed, rank=rank, world=world)
+        if has_3d:
+            for batch_input, batch_gt in ds.batches(batch_size, **kw):
+                losses = step(batch_input, batch_gt, has_3d=True, has_gt=has_gt)
+                acc, count = (losses.detach().clone() if acc is None else acc + losses.detach()), count + 1
+        else:
+            for x_aug, gt, conf in ds.batches(batch_size, front=step, has_gt=has_gt, **kw):
+                losses = step.step_prepared(x_aug, gt, conf, has_3d=False)
+                acc, count = (losses.detach().clone() if acc is None else acc + losses.detach()), count + 1
+        if count != n_batches:
+            raise RuntimeError(f'{name}: {count} batches, the plan says {n_batches}')
+        sums.append((name, acc, count))
+    live = [a for _, a, c in sums if c]
+    host = torch.stack(live).cpu().tolist() if live else []              # the one synchronisation
+    out, k = {}, 0
+    for name, acc, count in sums:
+        if count:
+            out[name] = dict(batches=count, losses=[v / count for v in host[k]])
+            k += 1
+        else:
+            out[name] = dict(batches=0, losses=[])
+    return out
 
 
 class TwoGroupStep:
