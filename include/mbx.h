@@ -662,6 +662,30 @@ int mbx_motion2d_input(const float* x, float* data, float* gt, float* conf, floa
                        float d2c_b, float d2c_m, float d2c_s, float mask_ratio, float mask_T_ratio, int flags, uint64_t seed,
                        void* stream);
 
+/* ---- AMASS: the regressed joints of SMPL-H + DMPL without the vertices (csrc/amass.hip; tools/preprocess_amass.py:29-60, ----------------------
+ *      tools/convert_amass.py:26-31) -- mbx_version() >= 180
+ * mbx_amass_joints: kp [F,K,3] f32 = Q . vertices of human_body_prior's BodyModel(num_betas=16, num_dmpls=8) (52 joints, linear blend
+ * skinning as smplx.lbs.lbs evaluates it, then + trans), for poses [F,156] (52 axis-angle vectors: root, 21 body, 30 hand; smplx's
+ * Rodrigues form, angle = |r + 1e-8|), betas [16] (betas_per_frame = 0: one per sequence) or [F,16], dmpls [F,8] or NULL (zeros), trans
+ * [F,3] or NULL (zeros).  The vertices never exist: the model arrives folded (motionbert_amd/amass.py, in float64, once per body model):
+ *   c = [betas, dmpls];  feat = [1, c, R_1 - I, .., R_51 - I]  (484 values);  J = Jt + Jd c  (Jt [52,3], Jd [52,3,24])
+ *   A_k = [G_k | Gt_k - G_k J_k] from the kinematic chain over parents [52] (a host array; forward-ordered, parents[0] = -1)
+ *   kp_j = sum over the pairs p = (j,k), in pair order, of  G_k (P[p] . feat) + (Gt_k - G_k J_k) s[p],   then + qs[j] trans
+ * with pairs [Np,2] i32 (sorted by j, then k; j < K, k < 52), P [Np,3,484], s [Np], qs [K] on the device:
+ *   P[(j,k)] = sum_v Q[j,v] w[v,k] [T_v | S_v | posedirs_v],  s[(j,k)] = sum_v Q[j,v] w[v,k],  qs[j] = sum_v Q[j,v].
+ * flags: bit 0 camera -- the step of convert_amass.py in the same launch: (x, y, z) -> (x, -z, y), then x float32(0.298); equal in value
+ *          to those two operations applied to the unflagged output;
+ *        bit 1 -- the product P . feat on the vector unit (fmaf chains in k order) instead of the exact-fp32 MFMA: the measured
+ *          alternative (tools/amass_bench.py), not the default.
+ * One launch, no workspace; a workgroup owns MBX_AMASS_TILE frames.  fp32, no atomics, fixed summation order; a frame's result does not
+ * depend on the other frames of the launch (a launch over [0,F) equals the launches over its single frames bit for bit).  F = 0 is a
+ * no-op.  Refused: F < 0, K < 1, K > 32, Np < 0, Np > 17 * 52, unknown flag bits, null model arrays, parents that are no forward-ordered
+ * tree, a P that is not 16-byte aligned. */
+#define MBX_AMASS_TILE 16
+int mbx_amass_joints(const float* poses, const float* betas, int betas_per_frame, const float* dmpls, const float* trans, const float* Jt,
+                     const float* Jd, const int* parents, const int* pairs, const float* P, const float* s, const float* qs, int Np, int K,
+                     int flags, float* kp, int F, void* stream);
+
 /* ---- measurement aid (bench.py`roofline.sustained_mfma_tflops`; not part of the model) --------------------------------------------
  * The bf16 MFMA rate the part sustains under its power cap with nothing but v_mfma_f32_32x32x16_bf16 in the loop (pseudo-random
  * operands; n_wg workgroups of 4 waves, `iters` x 16 MFMAs per wave).  ws: >= mbx_mfma_probe_ws(n_wg) bytes = a float sink

@@ -116,6 +116,7 @@ SIGNATURES = {
     'mbx_mesh_gt': (_i, [_vp, _vp, _vp, _vp, C.c_uint64, _f] + [_vp] * 5 + [C.POINTER(C.c_int)] + [_vp, _vp, _i, _f] + [_vp] * 5 + [_i, _i, _i, _vp, _sz, _vp]),
     'mbx_action_input': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp] + [_f] * 8 + [_i, C.c_uint64, _vp]),
     'mbx_motion2d_input': (_i, [_vp] * 5 + [_i, _i, _i, _vp, _vp] + [_f] * 3 + [_vp] * 3 + [_f] * 8 + [_i, C.c_uint64, _vp]),
+    'mbx_amass_joints': (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, C.POINTER(C.c_int)] + [_vp] * 4 + [_i, _i, _i, _vp, _i, _vp]),
     'mbx_xent_topk': (_i, [_vp, _vp, _i, _i, _f, _vp, _vp, _vp, _vp]),
     'mbx_wild_input_ws': (_sz, [_i, _i]),
     'mbx_wild_input': (_i, [_vp, _vp, _i, _vp, _i, _i] + [C.c_double] * 4 + [_i, _i, _vp, _vp, _vp, _sz, _vp]),
@@ -737,6 +738,38 @@ class HipOps:
                                              float(ratio_range[0]), float(ratio_range[1]), float(flip_prob), _p(mean), _p(std), _p(weight),
                                              float(uniform_range), float(jitter_std), float(a), float(b), float(m), float(s),
                                              float(mask_ratio), float(mask_T_ratio), int(flags), int(seed), self._stream()))
+
+    # ------------------------------------------------------------------ AMASS joints (csrc/amass.hip; motionbert_amd/amass.py)
+    def amass_joints(self, model, poses, betas, dmpls, trans, kp, camera=False, fma=False):
+        """model: the folded SMPL-H dict of amass.SMPLHModel.tensors(): Jt [52,3], Jd [52,3,24], pairs [Np,2] i32, P [Np,3,484], s [Np],
+        qs [K] f32 on the device of poses, parents (52 host ints); poses [F,156], betas [16] or [F,16], dmpls [F,8] or None, trans [F,3] or
+        None, kp [F,K,3] f32; camera: the step of convert_amass.py in the launch; fma: the vector-unit product (measurement only)."""
+        if poses.dim() != 2 or poses.shape[1] != 156:
+            raise RuntimeError(f'libmbx: amass_joints needs poses [F,156], got {tuple(poses.shape)}')
+        F, dev = poses.shape[0], poses.device
+        pairs, P, qs = model['pairs'], model['P'], model['qs']
+        Np, K = pairs.shape[0], qs.numel()
+        if not 1 <= K <= 32 or Np > 17 * 52 or pairs.dim() != 2 or pairs.shape[1] != 2:
+            raise RuntimeError(f'libmbx: amass_joints needs 1 <= K <= 32 joints and pairs [Np <= 884, 2], got K = {K}, pairs {tuple(pairs.shape)}')
+        if betas.shape not in ((16,), (F, 16)):
+            raise RuntimeError(f'libmbx: amass_joints needs betas [16] or [{F},16], got {tuple(betas.shape)}')
+        self._dense('amass_joints', torch.float32, F * 156, dev, poses=poses)
+        self._dense('amass_joints', torch.float32, None, dev, betas=betas)
+        self._dense('amass_joints', torch.float32, F * 8, dev, dmpls=dmpls)
+        self._dense('amass_joints', torch.float32, F * 3, dev, trans=trans)
+        self._dense('amass_joints', torch.float32, F * K * 3, dev, kp=kp)
+        self._dense('amass_joints', torch.float32, 156, dev, Jt=model['Jt'])
+        self._dense('amass_joints', torch.float32, 156 * 24, dev, Jd=model['Jd'])
+        self._dense('amass_joints', torch.int32, Np * 2, dev, pairs=pairs)
+        self._dense('amass_joints', torch.float32, Np * 3 * 484, dev, P=P)
+        self._dense('amass_joints', torch.float32, Np, dev, s=model['s'])
+        self._dense('amass_joints', torch.float32, K, dev, qs=qs)
+        parents = [int(p) for p in model['parents']]
+        if len(parents) != 52:
+            raise RuntimeError(f'libmbx: amass_joints needs 52 parents, got {len(parents)}')
+        self._ck(self.lib.mbx_amass_joints(_p(poses), _p(betas), int(betas.dim() == 2), _p(dmpls), _p(trans), _p(model['Jt']), _p(model['Jd']),
+                                           (C.c_int * 52)(*parents), _p(pairs), _p(P), _p(model['s']), _p(qs), Np, K,
+                                           int(bool(camera)) | (2 if fma else 0), _p(kp), F, self._stream()))
 
     def xent_topk(self, logits, labels, values, dlogits, acc, grad_scale=1.0):
         """logits [N,C] f32, labels [N] i32, values [3] f32, dlogits like logits or None, acc [4] f64 (accumulated) or None; all contiguous, on
