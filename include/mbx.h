@@ -686,6 +686,34 @@ int mbx_amass_joints(const float* poses, const float* betas, int betas_per_frame
                      const float* Jd, const int* parents, const int* pairs, const float* P, const float* s, const float* qs, int Np, int K,
                      int flags, float* kp, int F, void* stream);
 
+/* ---- ragged batches: clips of different lengths in one inference forward (csrc/attention.hip, csrc/elementwise.hip, csrc/wild.hip) ----------
+ *      -- mbx_version() >= 190
+ * A ragged batch is F frames of J joints, the clips one after another (the layout mbx_wild_input writes), and two device tables:
+ *   clip_tab [n_clips,2] i32 = (first frame, frames) of every clip;   frame_t [F] i32 = the index of every frame inside its clip.
+ * Every row-wise kernel and the spatial attention (mbx_attn_fwd with B = 1, T = F) take such a batch as it is; the three entries below are
+ * the kernels that know where a clip starts.  Inference only: there is no backward, no dropout.
+ * mbx_attn_fwd_ragged: temporal attention.  Problem (clip b, joint j, head h) reads tokens first_b J + j + s J, s < frames_b, of qkv [F J,3C] T
+ * and writes those rows of o [F J,C] T and lse [F J,H] f32: per problem the fragment walk and the arithmetic of
+ * mbx_attn_fwd(B = 1, T = frames_b, temporal) on the clip's rows, hence its bits.  The tiles are sized for max_len (>= every frames_b):
+ * max_len > 32 runs one workgroup per problem, otherwise one problem per wave, four per workgroup, each with its own length.
+ * max_len <= 256 (refused beyond: the streamed kernels take one length per call).  A table row with first < 0, frames < 1, frames > max_len or
+ * first + frames > F is skipped: nothing of that clip is written.  hd 32 or 64, bf16 or f32; n_clips = 0 is a no-op. */
+int mbx_attn_fwd_ragged(const void* qkv, void* o, float* lse, const int* clip_tab, int n_clips, int F, int max_len, int J, int H, int hd,
+                        float scale, int dtype, void* stream);
+/* mbx_embed_fwd / mbx_embed_fwd_tta for a ragged batch x [F,J,Din]: the temporal row of frame f is temp[frame_t[f]] (temp [n_temp,C]);
+ * same operations in the same order, hence the bits of the per-clip calls.  The TTA form writes h [2F J,C]: rows F J .. 2 F J - 1 are the
+ * flipped view and use the same frame_t.  A frame whose frame_t lies outside [0, n_temp) is skipped. */
+int mbx_embed_fwd_ragged(const float* x, const float* w, const float* b, const float* pos, const float* temp, const int* frame_t, float* h,
+                         int F, int J, int Din, int C, int n_temp, void* stream);
+int mbx_embed_fwd_tta_ragged(const float* x, const int* perm, const float* w, const float* b, const float* pos, const float* temp,
+                             const int* frame_t, float* h, int F, int J, int Din, int C, int n_temp, void* stream);
+/* mbx_wild_output for one ragged batch: pred [Fb,17,3] f32 (NOT modified) holds whole clips one after another and goes to rows dst0 ..
+ * dst0 + Fb - 1 of out [F,17,3] f32 (refused when they do not exist); x [Fb,17,x_channels] is the batch's network input and frame_t [Fb] the
+ * batch's part of the table above.  Flags and arithmetic are mbx_wild_output's; without rootrel, z of joint 0 is zeroed at every frame with
+ * frame_t == 0 -- the reference's quirk at frame 0 of every clip. */
+int mbx_wild_output_ragged(const float* pred, const float* x, int x_channels, const int* frame_t, int Fb, int dst0, int F, int flags,
+                           float pix_scale, double half_w, double half_h, float* out, void* stream);
+
 /* ---- measurement aid (bench.py`roofline.sustained_mfma_tflops`; not part of the model) --------------------------------------------
  * The bf16 MFMA rate the part sustains under its power cap with nothing but v_mfma_f32_32x32x16_bf16 in the loop (pseudo-random
  * operands; n_wg workgroups of 4 waves, `iters` x 16 MFMAs per wave).  ws: >= mbx_mfma_probe_ws(n_wg) bytes = a float sink

@@ -171,9 +171,13 @@ def motion2d_input(x: torch.Tensor, *, scale_range=(0.25, 1), zero_unseen: bool 
     return (out, used) if return_params else out
 
 
-def flip_tta(model, x: torch.Tensor) -> torch.Tensor:
-    """(model(x) + flip_back(model(flip(x)))) / 2 under no_grad, 17-joint H36M layout (train.py:67-72)."""
+def flip_tta(model, x: torch.Tensor, clip_lens=None, tables=None) -> torch.Tensor:
+    """(model(x) + flip_back(model(flip(x)))) / 2 under no_grad, 17-joint H36M layout (train.py:67-72).
+    With `clip_lens` it is the ragged form: x [F,17,dim_in] holds clips of those lengths one after another
+    (`DSTformer.forward_ragged`, which also explains `tables`), and the result is [F,17,dim_out]."""
     if model.num_joints != 17:
         raise ValueError('flip_tta uses the 17-joint left/right table of lib/utils/utils_data.py:60-61')
     with torch.no_grad():
+        if clip_lens is not None:
+            return model.forward_ragged(x, clip_lens, return_rep='flip_tta', tables=tables)
         return model.forward(x, return_rep='flip_tta')

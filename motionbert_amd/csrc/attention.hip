@@ -26,6 +26,7 @@
 // with wave-private LDS, four problems per 256-thread workgroup; longer ones share the tiles across the
 // eight waves of a workgroup, one 32-row query (key) block per wave.  Kernel map:
 //   attn_fwd_kernel<T, HD, SHARED>        forward, both forms
+//   attn_fwd_ragged_kernel<T, HD, SHARED> forward, temporal, clips of different lengths from a table (the same per-problem body)
 //   attn_bwd_small_kernel<T, HD>          backward, L <= 32: dQ, dK, dV from tiles staged once per wave
 //   attn_bwd_fused_kernel<HD>             backward, bf16, 32 < L <= 256: ONE workgroup of 16 waves per problem, Q / K / V / dO
 //                                         staged once, dQ role (8 waves) and dK/dV role (8 waves) concurrently
@@ -52,9 +53,12 @@ template <bool SHARED> struct AttnBlockKV { static constexpr int THREADS = SHARE
 // forward: flash-style walk over 32-key fragments with a running row max / row sum (the whole row
 // is at most 8 fragments, but keeping only one fragment of scores live keeps the wave at ~100 VGPRs)
 // ================================================================================================
-template <typename T, int HD, bool SHARED, bool DROP = false>
-__global__ __launch_bounds__(AttnBlock<SHARED>::THREADS, (sizeof(T) == 2 && !DROP) ? 4 : 1) void attn_fwd_kernel(const T* __restrict__ qkv, T* __restrict__ o, float* __restrict__ lse,
-                                                       int Tn, int J, int H, float scale, int mode, int nprob, int KP, MbxDrop dr) {
+// The body of both forward kernels.  `decode(prob)` names this wave's (SHARED: this workgroup's) problem: attn_fwd_kernel takes it from
+// the dense [B,T,J] layout, attn_fwd_ragged_kernel from a table of clips -- one body, hence one instruction sequence per problem.
+// pvalid false: the wave walks a problem that exists (every address is good, every barrier is met) and stores nothing.
+template <typename T, int HD, bool SHARED, bool DROP, typename Decode>
+__device__ __forceinline__ void attn_fwd_body(const T* __restrict__ qkv, T* __restrict__ o, float* __restrict__ lse, int H, float scale,
+                                              int nprob, int KP, const MbxDrop& dr, Decode decode) {
     constexpr bool IS_BF = sizeof(T) == 2;
     constexpr int KSTR = rm_stride<T>(HD);
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -64,9 +68,9 @@ __global__ __launch_bounds__(AttnBlock<SHARED>::THREADS, (sizeof(T) == 2 && !DRO
     const int KBYTES = KP * KSTR;
     const int VBYTES = KP * VSTR;
     int prob = SHARED ? (int)blockIdx.x : (int)blockIdx.x * 4 + wave;
-    const bool pvalid = prob < nprob;
+    bool pvalid = prob < nprob;
     prob = min(prob, nprob - 1);
-    const Prob P = decode_prob(prob, mode, Tn, J, H);
+    const Prob P = decode(prob, pvalid);
     const int gtid = SHARED ? tid : lane, gsize = SHARED ? AttnBlock<SHARED>::THREADS : 64;
     char* kt = smem + (SHARED ? 0 : wave * (KBYTES + VBYTES));
     char* vt = kt + KBYTES;
@@ -155,6 +159,38 @@ constexpr int MBX_ATTN_Q_EARLY = 1;
             *reinterpret_cast<uint4*>(ob + (size_t)r * ostride + ch * (16 / (int)sizeof(T))) = a;
         }
     }
+}
+
+template <typename T, int HD, bool SHARED, bool DROP = false>
+__global__ __launch_bounds__(AttnBlock<SHARED>::THREADS, (sizeof(T) == 2 && !DROP) ? 4 : 1) void attn_fwd_kernel(const T* __restrict__ qkv, T* __restrict__ o, float* __restrict__ lse,
+                                                       int Tn, int J, int H, float scale, int mode, int nprob, int KP, MbxDrop dr) {
+    attn_fwd_body<T, HD, SHARED, DROP>(qkv, o, lse, H, scale, nprob, KP, dr, [=](int prob, bool&) { return decode_prob(prob, mode, Tn, J, H); });
+}
+
+// Ragged temporal attention (inference): the rows of qkv are F frames of J joints, clip b owns frames clip_tab[b] = (first, frames) and
+// problem (b, j, h) is tok0 = first J + j, tstep = J, L = frames -- its own length, so a workgroup of the wave-private form may hold
+// four different ones.  KP (the tile rows, a multiple of 32) covers the longest clip of the call.  A table row that points outside
+// [0, F) or has frames outside [1, max_len] is skipped: its waves walk problem (frame 0, L = 1) and store nothing.
+template <typename T, int HD, bool SHARED>
+__global__ __launch_bounds__(AttnBlock<SHARED>::THREADS, sizeof(T) == 2 ? 4 : 1) void attn_fwd_ragged_kernel(const T* __restrict__ qkv, T* __restrict__ o,
+                                                       float* __restrict__ lse, const int* __restrict__ clip_tab, int F, int max_len, int J, int H,
+                                                       float scale, int nprob, int KP) {
+    MbxDrop dr;
+    dr.seed_lo = dr.seed_hi = dr.thresh = 0u;
+    dr.scale = 1.0f;
+    attn_fwd_body<T, HD, SHARED, false>(qkv, o, lse, H, scale, nprob, KP, dr, [=](int prob, bool& pvalid) {
+        Prob P;
+        P.h = prob % H;
+        const int rest = prob / H, j = rest % J, b = rest / J;
+        const int first = clip_tab[2 * b], frames = clip_tab[2 * b + 1];
+        const bool ok = first >= 0 && frames >= 1 && frames <= max_len && first <= F - frames;
+        pvalid = pvalid && ok;
+        P.tok0 = (size_t)(ok ? first : 0) * J + j;
+        P.tstep = J;
+        P.L = ok ? frames : 1;
+        P.dbase = 0;
+        return P;
+    });
 }
 
 // ================================================================================================
@@ -874,6 +910,41 @@ static int attn_fwd_impl(const void* qkv, void* o, float* lse, int B, int T, int
     return hd == 64 ? MBX_FWD(float, 64) : MBX_FWD(float, 32);
 #undef MBX_FWD
 #undef MBX_FWD2
+}
+template <typename T, int HD, bool SHARED>
+static int launch_fwd_ragged(const void* qkv, void* o, float* lse, const int* clip_tab, int F, int max_len, int J, int H, float scale,
+                             int nprob, int KP, hipStream_t s) {
+    const size_t per = (size_t)2 * KP * rm_stride<T>(HD);
+    const size_t shm = SHARED ? per : 4 * per;
+    auto kern = attn_fwd_ragged_kernel<T, HD, SHARED>;
+    if (set_lds(kern, shm, "attn_fwd_ragged")) return 1;
+    const int grid = SHARED ? nprob : (nprob + 3) / 4;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(AttnBlock<SHARED>::THREADS), shm, s, (const T*)qkv, (T*)o, lse, clip_tab, F, max_len, J, H, scale,
+                       nprob, KP);
+    MBX_LAUNCH_CHECK("attn_fwd_ragged");
+    return 0;
+}
+// temporal attention of a ragged batch (mbx.h): per clip the problems, the fragment walk and the arithmetic of mbx_attn_fwd(B = 1, T = frames)
+extern "C" int mbx_attn_fwd_ragged(const void* qkv, void* o, float* lse, const int* clip_tab, int n_clips, int F, int max_len, int J, int H,
+                                   int hd, float scale, int dtype, void* stream) {
+    MBX_CHECK_ARG(n_clips >= 0, "attn_fwd_ragged: bad clip count %d", n_clips);
+    if (n_clips == 0) return 0;
+    MBX_CHECK_ARG(qkv && o && lse && clip_tab, "attn_fwd_ragged: null pointer");
+    MBX_CHECK_ARG(scale > 0.f, "attn_fwd_ragged: scale must be positive (the running max is taken over the raw scores), got %g", (double)scale);
+    MBX_CHECK_ARG(F >= 1 && max_len >= 1, "attn_fwd_ragged: bad sizes F=%d max_len=%d (both >= 1)", F, max_len);
+    MBX_CHECK_ARG(max_len <= 256, "attn_fwd_ragged: clips of up to %d frames; the ragged form keeps a clip's K and V in LDS and takes at most 256 "
+                  "(longer clips: mbx_attn_fwd per clip, the streamed kernels)", max_len);
+    if (check_attn_args("attn_fwd_ragged", 1, F, J, H, hd, MBX_ATTN_TEMPORAL, dtype)) return 1;
+    MBX_CHECK_ARG((long long)n_clips * J * H < (1ll << 31) - 4, "attn_fwd_ragged: %d clips x %d joints x %d heads exceed 2^31 problems", n_clips, J, H);
+    const int nprob = n_clips * J * H;
+    const int KP = ((max_len + 31) / 32) * 32;
+    hipStream_t s = (hipStream_t)stream;
+#define MBX_FWDR(TT, HDV)                                                                                            \
+    (KP > 32 ? launch_fwd_ragged<TT, HDV, true>(qkv, o, lse, clip_tab, F, max_len, J, H, scale, nprob, KP, s)        \
+             : launch_fwd_ragged<TT, HDV, false>(qkv, o, lse, clip_tab, F, max_len, J, H, scale, nprob, KP, s))
+    if (dtype == MBX_BF16) return hd == 64 ? MBX_FWDR(bf16_t, 64) : MBX_FWDR(bf16_t, 32);
+    return hd == 64 ? MBX_FWDR(float, 64) : MBX_FWDR(float, 32);
+#undef MBX_FWDR
 }
 extern "C" int mbx_attn_fwd(const void* qkv, void* o, float* lse, int B, int T, int J, int H, int hd, float scale, int mode,
                             int dtype, void* stream) {

@@ -56,7 +56,7 @@ int mbx_cu_count() {
     g_cus[dev].store(c, std::memory_order_relaxed);
     return c;
 }
-extern "C" int mbx_version(void) { return 180; }
+extern "C" int mbx_version(void) { return 190; }
 
 static inline int clamp_grid(size_t want, int cap) { return (int)(want < (size_t)cap ? (want ? want : 1) : (size_t)cap); }
 
@@ -355,6 +355,69 @@ extern "C" int mbx_embed_fwd(const float* x, const float* w, const float* b, con
     }
     MBX_LAUNCH_CHECK("embed_fwd");
     return 0;
+}
+
+// Ragged batch (inference; clips of different lengths one after another, F frames in all): the temporal row of frame f is
+// temp[frame_t[f]], the index of the frame INSIDE its clip.  One thread per channel quad; the same fma chain over k and the same
+// association ((xW + b) + pos) + temp as the kernels above, hence their bits.  TTA: 2F rows, rows F .. 2F-1 are the flipped view
+// (mbx_embed_fwd_tta's remap: joint j reads joint perm[j], channel 0 negated) and use the same frame_t.  A frame whose frame_t lies
+// outside [0, n_temp) is skipped (the table is device memory: the host cannot check it here).
+template <bool TTA>
+__global__ __launch_bounds__(256) void embed_fwd_ragged_kernel(const float* __restrict__ x, const int* __restrict__ perm,
+                                                               const float* __restrict__ w, const float* __restrict__ b,
+                                                               const float* __restrict__ pos, const float* __restrict__ temp,
+                                                               const int* __restrict__ frame_t, float* __restrict__ h, int F, int J,
+                                                               int Din, int C, int n_temp) {
+    const int c4n = C >> 2;
+    const size_t rows = (size_t)(TTA ? 2 : 1) * F * J, total = rows * c4n;
+    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+        const size_t mo = idx / c4n;
+        const int c = (int)(idx % c4n) * 4;
+        const int j = (int)(mo % J);
+        size_t f = mo / J;
+        const bool flip = TTA && f >= (size_t)F;
+        if (flip) f -= F;
+        const int t = frame_t[f];
+        if (t < 0 || t >= n_temp) continue;
+        const size_t ms = f * J + (flip ? perm[j] : j);
+        const float4 bb = *reinterpret_cast<const float4*>(b + c);
+        const float4 pp = *reinterpret_cast<const float4*>(pos + (size_t)j * C + c);
+        const float4 tt = *reinterpret_cast<const float4*>(temp + (size_t)t * C + c);
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+        for (int k = 0; k < Din; ++k) {
+            float xv = x[ms * Din + k];
+            if (flip && k == 0) xv = -xv;
+            a0 = fmaf(xv, w[(size_t)(c + 0) * Din + k], a0);
+            a1 = fmaf(xv, w[(size_t)(c + 1) * Din + k], a1);
+            a2 = fmaf(xv, w[(size_t)(c + 2) * Din + k], a2);
+            a3 = fmaf(xv, w[(size_t)(c + 3) * Din + k], a3);
+        }
+        *reinterpret_cast<float4*>(h + mo * C + c) =
+            make_float4(((a0 + bb.x) + pp.x) + tt.x, ((a1 + bb.y) + pp.y) + tt.y, ((a2 + bb.z) + pp.z) + tt.z, ((a3 + bb.w) + pp.w) + tt.w);
+    }
+}
+static int embed_fwd_ragged_impl(const char* who, const float* x, const int* perm, const float* w, const float* b, const float* pos,
+                                 const float* temp, const int* frame_t, float* h, int F, int J, int Din, int C, int n_temp, bool tta,
+                                 void* stream) {
+    MBX_CHECK_ARG(x && w && b && pos && temp && frame_t && h && (!tta || perm), "%s: null pointer", who);
+    MBX_CHECK_ARG(F > 0 && J > 0 && Din > 0 && C > 0 && C % 4 == 0 && n_temp > 0, "%s: bad shape (C %% 4 != 0?)", who);
+    const int grid = clamp_grid(((size_t)(tta ? 2 : 1) * F * J * (C / 4) + 255) / 256, 256 * 16);
+    if (tta)
+        hipLaunchKernelGGL(embed_fwd_ragged_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, perm, w, b, pos, temp, frame_t, h, F, J,
+                           Din, C, n_temp);
+    else
+        hipLaunchKernelGGL(embed_fwd_ragged_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, perm, w, b, pos, temp, frame_t, h, F, J,
+                           Din, C, n_temp);
+    MBX_LAUNCH_CHECK(who);
+    return 0;
+}
+extern "C" int mbx_embed_fwd_ragged(const float* x, const float* w, const float* b, const float* pos, const float* temp, const int* frame_t,
+                                    float* h, int F, int J, int Din, int C, int n_temp, void* stream) {
+    return embed_fwd_ragged_impl("embed_fwd_ragged", x, nullptr, w, b, pos, temp, frame_t, h, F, J, Din, C, n_temp, false, stream);
+}
+extern "C" int mbx_embed_fwd_tta_ragged(const float* x, const int* perm, const float* w, const float* b, const float* pos, const float* temp,
+                                        const int* frame_t, float* h, int F, int J, int Din, int C, int n_temp, void* stream) {
+    return embed_fwd_ragged_impl("embed_fwd_tta_ragged", x, perm, w, b, pos, temp, frame_t, h, F, J, Din, C, n_temp, true, stream);
 }
 
 // ------------------------------------------------------------------------------------------------

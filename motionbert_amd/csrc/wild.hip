@@ -11,6 +11,7 @@
 //                     The mapped and pixel-normalised coordinates are never stored: launch 3 recomputes them with the same operations
 //                     (hence the same bits) that launch 1 took the box of.
 //   mbx_wild_output : infer_wild.py:81-96 for a batch of clips, written straight to each clip's rows of the stitched [F,17,3] result.
+//   mbx_wild_output_ragged : the same for one packed batch of clips of different lengths (rows dst0 .. dst0 + Fb - 1).
 //   mbx_scale_fit   : solve_scale of infer_wild_mesh.py:42-56 for S tracks, one workgroup per track, the whole IRLS solve in the kernel.
 //   mbx_wild_mesh_place : infer_wild_mesh.py:153-154 in place, in numpy 2's arithmetic.
 #include "mbx_common.h"
@@ -289,6 +290,55 @@ extern "C" int mbx_wild_output(const float* pred, const float* x, int x_channels
     hipLaunchKernelGGL(wild_output_kernel, dim3(wi_clamp_grid((total + WI_THREADS - 1) / WI_THREADS, WI_GRID_CAP)), dim3(WI_THREADS), 0,
                        (hipStream_t)stream, pred, x, x_channels, dst_frames, total, T, flags, pix_scale, half_w, half_h, out);
     MBX_LAUNCH_CHECK("wild_output");
+    return 0;
+}
+
+// The output stage of one RAGGED batch: pred [Fb,17,3] holds whole clips of different lengths one after another and goes to rows
+// dst0 .. dst0 + Fb - 1 of out; frame_t [Fb] = the index of each frame inside its clip.  The reference zeroes z of joint 0 of frame 0 of
+// every clip (infer_wild.py:84): here that is every frame with frame_t == 0.  Everything else is wild_output_kernel's arithmetic.
+__global__ __launch_bounds__(WI_THREADS) void wild_output_ragged_kernel(const float* __restrict__ pred, const float* __restrict__ x, int xc,
+                                                                         const int* __restrict__ frame_t, size_t total, int flags,
+                                                                         float pix_scale, double half_w, double half_h, float* __restrict__ out) {
+    const bool rootrel = flags & 1, gt2d = flags & 2, pixel = flags & 4;
+    for (size_t idx = (size_t)blockIdx.x * WI_THREADS + threadIdx.x; idx < total; idx += (size_t)gridDim.x * WI_THREADS) {
+        const int f = (int)(idx / WI_J), j = (int)(idx % WI_J);
+        const float* p = pred + idx * 3;
+        float px = p[0], py = p[1], pz = p[2];
+        if (rootrel) {
+            if (j == 0) px = py = pz = 0.f;
+        } else if (j == 0 && frame_t[f] == 0) {
+            pz = 0.f;
+        }
+        if (gt2d) {
+            const float* xi = x + idx * xc;
+            px = xi[0]; py = xi[1];
+        }
+        if (pixel) {
+            px = px * pix_scale; py = py * pix_scale; pz = pz * pix_scale;
+            px = (float)((double)px + half_w);
+            py = (float)((double)py + half_h);
+        }
+        float* o = out + idx * 3;
+        o[0] = px; o[1] = py; o[2] = pz;
+    }
+}
+
+extern "C" int mbx_wild_output_ragged(const float* pred, const float* x, int x_channels, const int* frame_t, int Fb, int dst0, int F, int flags,
+                                      float pix_scale, double half_w, double half_h, float* out, void* stream) {
+    MBX_CHECK_ARG(Fb >= 0 && F >= 0 && dst0 >= 0 && (long long)dst0 + Fb <= (long long)F,
+                  "wild_output_ragged: a batch of %d frames at row %d does not fit out [%d,17,3]", Fb, dst0, F);
+    if (Fb == 0) return 0;
+    MBX_CHECK_ARG(pred && frame_t && out, "wild_output_ragged: null pointer");
+    MBX_CHECK_ARG((flags & ~7) == 0, "wild_output_ragged: unknown flags %d (bit 0 rootrel, bit 1 gt_2d, bit 2 pixel mode)", flags);
+    if (flags & 2) MBX_CHECK_ARG(x && (x_channels == 2 || x_channels == 3), "wild_output_ragged: gt_2d needs the network input x with 2 or 3 channels (got %d)", x_channels);
+    if (flags & 4)
+        MBX_CHECK_ARG(isfinite(pix_scale) && isfinite(half_w) && isfinite(half_h), "wild_output_ragged: bad pixel mode pix_scale=%g half_w=%g half_h=%g",
+                      (double)pix_scale, half_w, half_h);
+    MBX_CHECK_ARG(Fb <= (1 << 26), "wild_output_ragged: a batch of %d frames is too large", Fb);
+    const size_t total = (size_t)Fb * WI_J;
+    hipLaunchKernelGGL(wild_output_ragged_kernel, dim3(wi_clamp_grid((total + WI_THREADS - 1) / WI_THREADS, WI_GRID_CAP)), dim3(WI_THREADS), 0,
+                       (hipStream_t)stream, pred, x, x_channels, frame_t, total, flags, pix_scale, half_w, half_h, out + (size_t)dst0 * (WI_J * 3));
+    MBX_LAUNCH_CHECK("wild_output_ragged");
     return 0;
 }
 

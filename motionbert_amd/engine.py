@@ -381,15 +381,36 @@ class Engine:
             self.Wn, self.Wt = ops.prep_weights(P, linear_names(cfg), self.T, need_grad, x3=self.x3)
 
     # ------------------------------------------------------------------ forward
-    def forward(self, x: torch.Tensor, return_rep, need_grad: bool, tta_perm=None):
+    def forward(self, x: torch.Tensor, return_rep, need_grad: bool, tta_perm=None, ragged=None):
         """`return_rep`: False (pose output), True (representation, DSTformer.py:360) or a tuple ('pool', persons, p, seed):
         the ActionNet pooling of model_action.py:15-24 fused onto the representation (mean over persons and frames of the
-        dropped-out representation -> [B / persons, J, R])."""
+        dropped-out representation -> [B / persons, J, R]).
+        `ragged` = (clip_tab, frame_t, n_clips, max_len), inference only: x [1,F,J,Din] holds clips of different lengths one after
+        another; clip_tab [n_clips,2] int32 = (first frame, frames) and frame_t [F] int32 = the index of every frame inside its clip, both
+        on the device.  Only the embedding and the temporal attention know where a clip starts; every other kernel runs on the F J rows
+        as on a batch of one clip of F frames."""
         cfg, ops, P = self.cfg, self.ops, self.P
         pool = return_rep if isinstance(return_rep, tuple) else None
         return_rep = bool(return_rep)
         self.dev = x.device
         B, T, J, Din = x.shape
+        self.ragged = None
+        if ragged is not None:
+            if need_grad or self.drop_seed is not None or pool is not None:
+                raise RuntimeError('a ragged batch is an inference path: no gradient, no dropout and no pooled representation')
+            clip_tab, frame_t, n_clips, max_len = ragged
+            if B != 1 or frame_t.numel() != T or clip_tab.numel() != 2 * n_clips or not 1 <= n_clips <= T:
+                raise RuntimeError(f'a ragged batch is x [1,F,J,C] with frame_t [F] and clip_tab [n_clips,2]: got x {tuple(x.shape)}, frame_t '
+                                   f'{tuple(frame_t.shape)}, clip_tab {tuple(clip_tab.shape)} for {n_clips} clips')
+            if not 1 <= max_len <= min(cfg.maxlen, 256):
+                raise RuntimeError(f'a ragged batch takes clips of 1 .. {min(cfg.maxlen, 256)} frames, got max_len = {max_len}')
+            if 2 * T * max(cfg.H, J) >= 1 << 31:      # the problem counts of the spatial attention (2 F H) and the token index are 32-bit
+                raise RuntimeError(f'a ragged batch of {T} frames is too large')
+            if tta_perm is not None:      # the doubled batch: the same clips again, F frames further on
+                clip_tab = clip_tab.reshape(n_clips, 2).repeat(2, 1)
+                clip_tab[n_clips:, 0] += T
+                n_clips = 2 * n_clips
+            self.ragged = (clip_tab.contiguous(), n_clips, int(max_len))
         if tta_perm is not None:      # flip test-time augmentation: the batch doubles, the second half is the flipped view
             B = 2 * B
         M, C = B * T * J, cfg.C
@@ -397,7 +418,11 @@ class Engine:
         self.rawln = not need_grad and self.fold and self.drop_seed is None and self.rawln_allowed and self._can('can_fuse_mlp')
         self.prepare_weights(need_grad)
         h = self._f(M, C)
-        if tta_perm is not None:
+        if ragged is not None and tta_perm is not None:
+            ops.embed_fwd_tta_ragged(x, tta_perm, P['joints_embed.weight'], P['joints_embed.bias'], P['pos_embed'], P['temp_embed'], frame_t, h, T, J)
+        elif ragged is not None:
+            ops.embed_fwd_ragged(x, P['joints_embed.weight'], P['joints_embed.bias'], P['pos_embed'], P['temp_embed'], frame_t, h, T, J)
+        elif tta_perm is not None:
             ops.embed_fwd_tta(x, tta_perm, P['joints_embed.weight'], P['joints_embed.bias'], P['pos_embed'], P['temp_embed'], h, B // 2, T, J)
         else:
             ops.embed_fwd(x, P['joints_embed.weight'], P['joints_embed.bias'], P['pos_embed'], P['temp_embed'], h, B, T, J)
@@ -524,7 +549,11 @@ class Engine:
             ops.gemm_nt(xn, self.Wn[lin], self.Bf[lin] if self.fold else P.get(lin + '.bias'), EPI_STORE, out_t=qkv)
         dm = self._drops(pre, sub)
         o, lse = self._t(M, C), self._f(M, cfg.H)
-        ops.attn_fwd(qkv, o, lse, self.B, self.Tlen, cfg.J, cfg.H, cfg.scale, mode, drop=dm.attn if dm else None)
+        if self.ragged is not None and mode == MODE_TEMPORAL:      # every clip its own length; the B Tlen frames are one packed batch
+            clip_tab, n_clips, max_len = self.ragged
+            ops.attn_fwd_ragged(qkv, o, lse, clip_tab, n_clips, self.B * self.Tlen, max_len, cfg.J, cfg.H, cfg.scale)
+        else:
+            ops.attn_fwd(qkv, o, lse, self.B, self.Tlen, cfg.J, cfg.H, cfg.scale, mode, drop=dm.attn if dm else None)
         if defer_proj:      # no-grad: proj + residual run inside the MLP kernel that follows
             return x, None, None, dict(o=o, proj=f'{pre}.{attn}.proj')
         o_op = self._mm(o)      # (bf16x3: the operand planes are kept for the weight gradient too -- o itself stays fp32 for the attention backward)

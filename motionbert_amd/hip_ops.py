@@ -121,6 +121,10 @@ SIGNATURES = {
     'mbx_wild_input_ws': (_sz, [_i, _i]),
     'mbx_wild_input': (_i, [_vp, _vp, _i, _vp, _i, _i] + [C.c_double] * 4 + [_i, _i, _vp, _vp, _vp, _sz, _vp]),
     'mbx_wild_output': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _f, C.c_double, C.c_double, _vp, _vp]),
+    'mbx_wild_output_ragged': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _f, C.c_double, C.c_double, _vp, _vp]),
+    'mbx_attn_fwd_ragged': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),
+    'mbx_embed_fwd_ragged': (_i, [_vp] * 7 + [_i] * 5 + [_vp]),
+    'mbx_embed_fwd_tta_ragged': (_i, [_vp] * 8 + [_i] * 5 + [_vp]),
     'mbx_wild_mesh_ws': (_sz, [_i, _i, _i, _i]),
     'mbx_wild_mesh': (_i, [_vp] * 5 + [C.POINTER(C.c_int)] + [_vp, _vp, _i] + [_vp] * 4 + [_f, _vp] + [_i] * 4 + [_vp] * 3 + [_i, _vp, _sz, _vp]),
     'mbx_scale_fit': (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
@@ -576,6 +580,21 @@ class HipOps:
         self._ck(self.lib.mbx_attn_fwd(_p(qkv), _p(o), _p(lse), B, T, J, H, hd, float(scale), int(mode), _DT[qkv.dtype],
                                        self._stream()))
 
+    def attn_fwd_ragged(self, qkv, o, lse, clip_tab, n_clips, F, max_len, J, H, scale):
+        """temporal attention of a ragged batch: qkv [F J,3C], o [F J,C], lse [F J,H]; clip_tab [>= n_clips,2] i32 on the device =
+        (first frame, frames), every clip of at most max_len <= 256 frames."""
+        if qkv.shape[0] != F * J or o.shape[0] != F * J or lse.numel() != F * J * H or qkv.shape[-1] != 3 * o.shape[-1]:
+            raise RuntimeError(f'libmbx: attn_fwd_ragged needs qkv [{F * J},3C], o [{F * J},C] and lse [{F * J},{H}], got {tuple(qkv.shape)}, '
+                               f'{tuple(o.shape)}, {tuple(lse.shape)}')
+        if not all(t.is_contiguous() and t.device == qkv.device for t in (qkv, o, lse, clip_tab)) or o.dtype != qkv.dtype:
+            raise RuntimeError('libmbx: attn_fwd_ragged needs contiguous tensors of one dtype on one device')
+        self._dense('attn_fwd_ragged', torch.float32, F * J * H, qkv.device, lse=lse)
+        self._dense('attn_fwd_ragged', torch.int32, None, qkv.device, clip_tab=clip_tab)
+        if clip_tab.numel() < 2 * n_clips:
+            raise RuntimeError(f'libmbx: attn_fwd_ragged: a table of {clip_tab.numel() // 2} rows for {n_clips} clips')
+        self._ck(self.lib.mbx_attn_fwd_ragged(_p(qkv), _p(o), _p(lse), _p(clip_tab), int(n_clips), int(F), int(max_len), J, H, o.shape[-1] // H,
+                                              float(scale), _DT[qkv.dtype], self._stream()))
+
     def attn_bwd(self, qkv, o, do, lse, dqkv, B, T, J, H, scale, mode, drop=None):
         hd = o.shape[-1] // H
         if isinstance(dqkv, tuple):      # bf16x3 (fp32 kernels): dq / dk / dv as operand planes
@@ -648,6 +667,29 @@ class HipOps:
     def embed_fwd_tta(self, x, perm, w, b, pos, temp, h, B, T, J):
         self._ck(self.lib.mbx_embed_fwd_tta(_p(x), _p(perm), _p(w), _p(b), _p(pos), _p(temp), _p(h), B, T, J, x.shape[-1], h.shape[-1],
                                             self._stream()))
+
+    def embed_fwd_ragged(self, x, w, b, pos, temp, frame_t, h, F, J):
+        """embed_fwd for a ragged batch x [F,J,Din]: frame f takes the temporal row temp[frame_t[f]] (frame_t [F] i32 on the device)"""
+        self._embed_ragged('embed_fwd_ragged', x, None, w, b, pos, temp, frame_t, h, F, J)
+
+    def embed_fwd_tta_ragged(self, x, perm, w, b, pos, temp, frame_t, h, F, J):
+        """embed_fwd_tta for a ragged batch: h [2 F J,C], rows F J .. are the flipped view with the same frame_t"""
+        self._embed_ragged('embed_fwd_tta_ragged', x, perm, w, b, pos, temp, frame_t, h, F, J)
+
+    def _embed_ragged(self, what, x, perm, w, b, pos, temp, frame_t, h, F, J):
+        rows, C, dev = (1 if perm is None else 2) * F * J, h.shape[-1], x.device
+        n_temp = temp.numel() // C
+        self._dense(what, torch.float32, None, dev, w=w, b=b, pos=pos, temp=temp)
+        self._dense(what, torch.float32, F * J * x.shape[-1], dev, x=x)
+        self._dense(what, torch.float32, rows * C, dev, h=h)
+        self._dense(what, torch.int32, F, dev, frame_t=frame_t)
+        if perm is None:
+            self._ck(self.lib.mbx_embed_fwd_ragged(_p(x), _p(w), _p(b), _p(pos), _p(temp), _p(frame_t), _p(h), F, J, x.shape[-1], C, n_temp,
+                                                   self._stream()))
+        else:
+            self._dense(what, torch.int32, J, dev, perm=perm)
+            self._ck(self.lib.mbx_embed_fwd_tta_ragged(_p(x), _p(perm), _p(w), _p(b), _p(pos), _p(temp), _p(frame_t), _p(h), F, J, x.shape[-1], C,
+                                                       n_temp, self._stream()))
 
     def flip_average(self, out2, perm, out):
         B, T, J, D = out.shape
@@ -827,6 +869,29 @@ class HipOps:
         self._dense('wild_output', torch.int32, n, dev, dst_frames=dst_frames)
         self._ck(self.lib.mbx_wild_output(_p(pred), _p(x), xc, _p(dst_frames), n, T, int(flags), float(pix_scale), float(half_w), float(half_h),
                                           _p(out), self._stream()))
+
+    def wild_output_ragged(self, pred, x, frame_t, dst0, flags, pix_scale, half_w, half_h, out):
+        """wild_output for one ragged batch: pred [Fb,17,3] f32 (not modified) goes to rows dst0 .. dst0 + Fb - 1 of out [F,17,3]; x
+        [Fb,17,2|3] f32 or None (gt_2d); frame_t [Fb] i32 on the device = the index of each frame inside its clip (z of joint 0 is
+        zeroed where it is 0, unless rootrel)."""
+        if pred.dim() != 3 or tuple(pred.shape[1:]) != (17, 3):
+            raise RuntimeError(f'libmbx: wild_output_ragged needs pred [Fb,17,3], got {tuple(pred.shape)}')
+        Fb, dev = pred.shape[0], pred.device
+        if out.dim() != 3 or tuple(out.shape[1:]) != (17, 3):
+            raise RuntimeError(f'libmbx: wild_output_ragged needs out [F,17,3], got {tuple(out.shape)}')
+        if not 0 <= int(dst0) <= out.shape[0] - Fb:
+            raise RuntimeError(f'libmbx: wild_output_ragged: a batch of {Fb} frames at row {int(dst0)} does not fit out [{out.shape[0]},17,3]')
+        xc = 0
+        if x is not None:
+            if x.dim() != 3 or tuple(x.shape[:2]) != (Fb, 17) or x.shape[2] not in (2, 3):
+                raise RuntimeError(f'libmbx: wild_output_ragged needs x [{Fb},17,2|3], got {tuple(x.shape)}')
+            xc = x.shape[2]
+        elif int(flags) & 2:
+            raise RuntimeError('libmbx: wild_output_ragged: gt_2d needs the network input x')
+        self._dense('wild_output_ragged', torch.float32, None, dev, pred=pred, x=x, out=out)
+        self._dense('wild_output_ragged', torch.int32, Fb, dev, frame_t=frame_t)
+        self._ck(self.lib.mbx_wild_output_ragged(_p(pred), _p(x), xc, _p(frame_t), Fb, int(dst0), out.shape[0], int(flags), float(pix_scale),
+                                                 float(half_w), float(half_h), _p(out), self._stream()))
 
     # ------------------------------------------------------------------ mesh recovery (train_mesh.py, lib/model/model_mesh.py, loss_mesh.py)
     def rot6d_theta_fwd(self, x6, rotmat, aa):

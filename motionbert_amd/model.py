@@ -26,10 +26,14 @@ import os
 from collections import OrderedDict
 from typing import Dict
 
+import numpy as np
 import torch
 import torch.nn as nn
 
 from .engine import Engine, ModelCfg, grad_bucket
+
+#: the longest clip of a ragged batch: temporal attention keeps a clip's K and V resident in LDS (csrc/attention.hip)
+RAGGED_MAX = 256
 
 #: precision -> dtype of the T-typed tensors.  'bf16x3' computes every Linear as three bf16 MFMA passes over hi / lo operand
 #: planes (fp32-class accuracy at a third of the bf16 rate); all its tensors are fp32 like 'fp32'.
@@ -127,10 +131,12 @@ class _DSTformerFn(torch.autograd.Function):
         eng.fold = eng.fold and fold
         eng.gelu_d = eng.gelu_d and gelu_d
         with _device_of(x):
-            tta = None
+            tta = ragged = None
+            if isinstance(return_rep, tuple) and return_rep[0] == 'ragged':      # ('ragged', tables, what to return)
+                ragged, return_rep = return_rep[1], return_rep[2]
             if isinstance(return_rep, tuple) and return_rep[0] == 'tta':
                 tta, return_rep = return_rep[1], False
-            out, saved = eng.forward(x, return_rep, need_grad, tta_perm=tta)
+            out, saved = eng.forward(x, return_rep, need_grad, tta_perm=tta, ragged=ragged)
         if need_grad:
             ctx.eng, ctx.saved_acts, ctx.names, ctx.grad_sync = eng, saved, names, grad_sync
             ctx.pshapes = [p.shape for p in params]
@@ -219,9 +225,35 @@ def named_parameter_tensors(model):
     return names, tuple(params)
 
 
-def run(ops, model, x, return_rep=False, grad_sync=None):
+def ragged_tables(clip_lens, maxlen: int = RAGGED_MAX):
+    """Host tables of a ragged batch whose clips have `clip_lens` frames, one after another: (clip_tab [n,2] int32 = (first frame,
+    frames), frame_t [F] int32 = the index of every frame inside its clip, max_len).  ValueError unless every length is an integer in
+    [1, min(maxlen, 256)]."""
+    try:
+        lens = [int(v) for v in clip_lens]
+        exact = all(v == w for v, w in zip(lens, clip_lens))
+    except (TypeError, ValueError):
+        raise ValueError(f'clip_lens must be a sequence of integers, got {clip_lens!r}') from None
+    cap = min(int(maxlen), RAGGED_MAX)
+    if not lens or not exact or any(not 1 <= v <= cap for v in lens):
+        raise ValueError(f'clip_lens must be a non-empty sequence of integers in [1, {cap}] (min(maxlen, {RAGGED_MAX})), got {list(clip_lens)}')
+    a = np.asarray(lens, dtype=np.int64)
+    first = np.cumsum(a) - a
+    if int(a.sum()) >= 1 << 26:
+        raise ValueError(f'a ragged batch of {int(a.sum())} frames is too large')
+    clip_tab = np.stack([first, a], 1).astype(np.int32)
+    frame_t = (np.arange(int(a.sum())) - np.repeat(first, a)).astype(np.int32)
+    return clip_tab, frame_t, int(a.max())
+
+
+def run(ops, model, x, return_rep=False, grad_sync=None, ragged=None):
     """Run the fused path of `model` on `x` with an explicit kernel provider.  `grad_sync` (optional) is
-    told about finished gradient buckets during backward (see motionbert_amd.ddp)."""
+    told about finished gradient buckets during backward (see motionbert_amd.ddp).  `ragged`: the tables of
+    `Engine.forward(..., ragged=)` for x [1,F,J,dim_in], under no_grad and eval()."""
+    if ragged is not None:
+        if torch.is_grad_enabled() or (model.training and any(r > 0 for r in model.drop_rates)):
+            raise RuntimeError('a ragged batch is an inference path: call it under torch.no_grad(), in eval() where the model has dropout')
+        return_rep = ('ragged', tuple(ragged), return_rep)
     cfg = make_cfg(model)
     names, params = named_parameter_tensors(model)
     for n, p in zip(names, params):
@@ -372,6 +404,40 @@ class DSTformer(nn.Module):
 
     def get_representation(self, x):
         return self.forward(x, return_rep=True)
+
+    def forward_ragged(self, x, clip_lens, return_rep=False, tables=None):
+        """Clips of DIFFERENT lengths in one forward, without padding: x [F, J, dim_in] holds the clips one after another and
+        `clip_lens` (host integers, each in [1, min(maxlen, 256)], summing to F) says how long each is.  Returns [F, J, dim_out]
+        (or [F, J, dim_rep] with `return_rep`): per clip what `self(x[a:b][None])[0]` returns, up to the batch-composition noise of
+        the GEMMs.  Inference only: call it under torch.no_grad(), in eval().  Temporal attention and the temporal embedding follow
+        the clips; everything else runs on the F J rows as they are.
+        `tables`: `(clip_tab, frame_t)` of `ragged_tables(clip_lens)` already on x's device (int32) -- a caller with many batches uploads
+        them once (motionbert_amd.wild.infer); by default they are built and uploaded here."""
+        if x.dim() != 3 or x.shape[1] != self.num_joints or x.shape[2] != self.dim_in:
+            raise ValueError(f'expected a ragged batch [F, {self.num_joints}, {self.dim_in}], got {tuple(x.shape)}')
+        clip_tab, frame_t, max_len = ragged_tables(clip_lens, self.maxlen)
+        if frame_t.size != x.shape[0]:
+            raise ValueError(f'clip_lens {list(clip_lens)} sum to {frame_t.size}, not to the {x.shape[0]} frames given')
+        self._check(x[None, :1])
+        if torch.is_grad_enabled() or (self.training and any(r > 0 for r in self.drop_rates)):
+            raise RuntimeError('forward_ragged is an inference path: call it under torch.no_grad(), in eval() where the model has dropout')
+        from . import hip_ops
+        x = x.contiguous().float()[None]
+        if tables is None:
+            both = torch.from_numpy(np.concatenate([clip_tab.reshape(-1), frame_t])).to(x.device)      # one upload
+            tables = both[:clip_tab.size].view(-1, 2), both[clip_tab.size:]
+        tab_d, ft_d = tables
+        if tab_d.numel() != clip_tab.size or ft_d.numel() != frame_t.size or tab_d.dtype != torch.int32 or ft_d.dtype != torch.int32 or \
+                tab_d.device != x.device or ft_d.device != x.device:
+            raise ValueError('tables must be (clip_tab [n,2], frame_t [F]) of ragged_tables(clip_lens) as int32 tensors on x\'s device')
+        ragged = (tab_d, ft_d, clip_tab.shape[0], max_len)
+        if return_rep == 'flip_tta':   # motionbert_amd.augment.flip_tta(model, x, clip_lens)
+            if not isinstance(self.head, nn.Linear):
+                raise RuntimeError('flip test-time augmentation is an evaluation path on the pose head')
+            from .augment import FLIP_PERM
+            perm = torch.tensor(FLIP_PERM, dtype=torch.int32, device=x.device)
+            return run(hip_ops.get(), self, x, ('tta', perm), None, ragged=ragged)[0]
+        return run(hip_ops.get(), self, x, bool(return_rep) or not isinstance(self.head, nn.Linear), None, ragged=ragged)[0]
 
     def get_pooled_representation(self, x, persons: int = 1, dropout: float = 0.0):
         """`[B, T, J, dim_in] -> [B / persons, J, dim_rep]`: the representation averaged over the T frames and over `persons`

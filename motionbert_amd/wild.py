@@ -16,6 +16,7 @@ ends the run.
     read_alphapose   the JSON part of `read_input` (dataset_wild.py:67-76); host only
     wild_input       halpe2h36m + normalisation (:77-86) on the device
     clip_plan        the clips of `WildDetDataset` (:94-102) pooled over tracks; host only
+    ragged_plan      the same clips in frame order, cut into batches of whole clips of any length (`infer(batching='ragged')`); host only
     wild_output      infer_wild.py:81-96 for one batch of clips
     infer            the loop of infer_wild.py:56-97
 
@@ -118,6 +119,30 @@ def clip_plan(seq_lens, clip_len: int) -> List[Tuple[int, List[int]]]:
                 tails.setdefault(end - st, []).append(start + st)
         start += n
     return ([(clip_len, full)] if full else []) + list(tails.items())
+
+
+def ragged_plan(seq_lens, clip_len: int, max_frames: int) -> List[Tuple[int, List[int]]]:
+    """The same clips as `clip_plan` (ceil(F / clip_len) per track, the last one shorter), kept in frame order and cut into ragged
+    batches: a list of `(first row, [clip lengths])`.  A batch holds whole consecutive clips, as many as fit into `max_frames` frames
+    (>= clip_len), so it is the view `y[first row : first row + sum(clip lengths)]` of the frame-major arrays of all tracks one after
+    another; a clip never spans tracks, and every frame lies in exactly one clip of one batch."""
+    lens = _check_lens(seq_lens)
+    clip_len, max_frames = int(clip_len), int(max_frames)
+    if clip_len < 1 or max_frames < clip_len:
+        raise ValueError(f'clip_len must be >= 1 and max_frames >= clip_len, got {clip_len} and {max_frames}')
+    plan: List[Tuple[int, List[int]]] = []
+    row0, cur, start = 0, [], 0
+    for n in lens:
+        for st in range(0, n, clip_len):
+            c = min(clip_len, n - st)
+            if cur and sum(cur) + c > max_frames:
+                plan.append((row0, cur))
+                row0, cur = start + st, []
+            cur.append(c)
+        start += n
+    if cur:
+        plan.append((row0, cur))
+    return plan
 
 
 # ---------------------------------------------------------------------------------------------------------------- device stages
@@ -261,7 +286,7 @@ def _clips(y, part, T):
 
 
 def infer(model, kp_or_tracks, *, clip_len: int = 243, vid_size=None, pixel: bool = False, flip: bool = True, rootrel: bool = False,
-          gt_2d: bool = False, no_conf: bool = False, max_batch: int = 64, ops=None):
+          gt_2d: bool = False, no_conf: bool = False, max_batch: int = 64, batching: str = 'equal', ops=None):
     """The loop of infer_wild.py:56-97.  `kp_or_tracks`: [F,26,3] detections of one person (array or tensor) -> numpy [F,17,3] float32, or
     a dict idx -> [F_idx,26,3] (`read_alphapose(by_track=True)`) -> a dict idx -> [F_idx,17,3], every person in the same pass.
 
@@ -269,11 +294,22 @@ def infer(model, kp_or_tracks, *, clip_len: int = 243, vid_size=None, pixel: boo
     all tracks go in batches of at most `max_batch`, each group of equal-length tail clips in batches of its own.  The network call is
     `flip_tta(model, x)` (`flip`) or `model(x)`, under no_grad and eval(); `rootrel`, `gt_2d`, `no_conf` are the config switches of the
     same names.  Every batch goes through `mbx_wild_output` into its rows of one [F,17,3] device tensor; one device-to-host copy ends the
-    run.  A DataParallel-wrapped or a bare model is accepted; `clip_len > model.maxlen` raises."""
+    run.  A DataParallel-wrapped or a bare model is accepted; `clip_len > model.maxlen` raises.
+
+    `batching='ragged'`: clips of DIFFERENT lengths share a network call (`ragged_plan`: whole consecutive clips in frame order, at most
+    `max_batch * clip_len` frames per batch).  Every batch is a view of the input stage's output, one `forward_ragged` (through `flip_tta`
+    with `flip`) and one `mbx_wild_output_ragged`; the clip tables of the whole run are uploaded once.  A scene of many short tracks then
+    takes ceil(frames / (max_batch clip_len)) network calls instead of one per distinct tail length.  `clip_len <= 256`."""
     net = model.module if hasattr(model, 'module') else model
     clip_len, max_batch = int(clip_len), int(max_batch)
     if clip_len < 1 or max_batch < 1:
         raise ValueError(f'clip_len and max_batch must be >= 1, got {clip_len} and {max_batch}')
+    if batching not in ('equal', 'ragged'):
+        raise ValueError(f"batching must be 'equal' or 'ragged', got {batching!r}")
+    if batching == 'ragged' and clip_len > 256:
+        raise ValueError(f"batching='ragged' takes clips of at most 256 frames, got clip_len = {clip_len}")
+    if batching == 'ragged' and not hasattr(net, 'forward_ragged'):
+        raise TypeError("batching='ragged' needs a model with forward_ragged")
     maxlen = getattr(net, 'maxlen', None)
     if maxlen is not None and clip_len > maxlen:
         raise ValueError(f'clip_len {clip_len} is longer than the model takes (maxlen = {maxlen})')
@@ -289,14 +325,16 @@ def infer(model, kp_or_tracks, *, clip_len: int = 243, vid_size=None, pixel: boo
     F, dev = y.shape[0], y.device
     lens = [F] if lens is None else lens
     out = torch.empty(F, 17, 3, dtype=torch.float32, device=dev)
-    plan = clip_plan(lens, clip_len)
     prov = hip_ops.provider(ops, 'motionbert_amd.wild.infer', y)
     flags, half_w, half_h, pix_scale = _out_flags(rootrel, gt_2d, vid_size if pixel else None)
+    plan = clip_plan(lens, clip_len) if batching == 'equal' else []
     offsets = [o for _, offs in plan for o in offs]
     table = torch.tensor(offsets, dtype=torch.int32).to(dev) if offsets else None              # every batch's destinations, one upload
     if hasattr(model, 'eval'):
         model.eval()
     from .augment import flip_tta
+    if batching == 'ragged':
+        _infer_ragged(net, y, out, ragged_plan(lens, clip_len, max_batch * clip_len), flip, gt_2d, prov, flags, pix_scale, half_w, half_h)
     at = 0
     with torch.no_grad(), _on(dev):
         for T, part in _batches(plan, max_batch):
@@ -310,6 +348,29 @@ def infer(model, kp_or_tracks, *, clip_len: int = 243, vid_size=None, pixel: boo
         return res
     ends = np.cumsum(lens)
     return OrderedDict((k, res[e - n:e]) for k, e, n in zip(keys, ends, lens))
+
+
+def _infer_ragged(net, y, out, plan, flip, gt_2d, prov, flags, pix_scale, half_w, half_h):
+    """the batches of `ragged_plan` through the network and `wild_output_ragged`; the tables of all batches go up in one copy"""
+    from .augment import flip_tta
+    from .model import ragged_tables
+    if not plan:
+        return
+    dev = y.device
+    tabs = [ragged_tables(cl)[0] for _, cl in plan]               # firsts count from the batch's own first row
+    frame_t = np.concatenate([ragged_tables(cl)[1] for _, cl in plan])
+    n_tab = sum(t.size for t in tabs)
+    both = torch.from_numpy(np.concatenate([t.reshape(-1) for t in tabs] + [frame_t])).to(dev)      # one upload
+    at = 0
+    with torch.no_grad(), _on(dev):
+        for (row0, cl), tab in zip(plan, tabs):
+            Fb = int(tab[:, 1].sum())
+            x = y[row0:row0 + Fb]                                 # a view: whole consecutive clips
+            ft = both[n_tab + row0:n_tab + row0 + Fb]
+            tables = (both[at:at + tab.size].view(-1, 2), ft)
+            at += tab.size
+            pred = flip_tta(net, x, clip_lens=cl, tables=tables) if flip else net.forward_ragged(x, cl, tables=tables)
+            prov.wild_output_ragged(pred.contiguous().float(), x if gt_2d else None, ft, row0, flags, pix_scale, half_w, half_h, out)
 
 
 # ---------------------------------------------------------------------------------------------------------------- mesh recovery
