@@ -714,6 +714,39 @@ int mbx_embed_fwd_tta_ragged(const float* x, const int* perm, const float* w, co
 int mbx_wild_output_ragged(const float* pred, const float* x, int x_channels, const int* frame_t, int Fb, int dst0, int F, int flags,
                            float pix_scale, double half_w, double half_h, float* out, void* stream);
 
+/* ---- mesh video frames (csrc/render.hip; the view of lib/utils/vismo.py:297-334, motion2video_mesh) -- mbx_version() >= 200 ------------------
+ * A z-buffered, flat-shaded render in fixed point: orthographic along +z (smaller z is nearer), image x right with mesh x, image y down with
+ * mesh y, inside the bounding cube of the whole motion of a track.  S = size ss samples per side (size <= MBX_RENDER_MAX_SIZE, ss 1 or 2).
+ * mbx_render_project: verts [F,V,3] f32, cube [n_tracks,4] f32 = (cx, cy, cz, inv) with inv = 1 / (2 R), seq_ptr [n_tracks+1] i32 (track s owns
+ * frames seq_ptr[s] .. seq_ptr[s+1] - 1), all on the device -> out [F,V,3] i32.  In fp32, every operation rounded on its own:
+ *   xq = floor(((x - cx) inv + 0.5f) (S MBX_RENDER_SUB))    yq likewise from y    zq = floor(((z - cz) inv + 0.5f) MBX_RENDER_ZQ)
+ * A product that is not finite or not below 2^30 in magnitude, and every vertex of a frame outside all tracks, gives 2^30 (outside the guard
+ * below).  One launch.  F = 0 is a no-op.
+ * mbx_render_raster: vq [F,V,3] i32 (the projection), verts [F,V,3] f32 (for the normals), faces [Nf,3] i32 -> rgb [F,size,size,3] u8 and,
+ * where given, face_id [F,S,S] i32 (-1 where empty) and depth [F,S,S] i32 (0x7fffffff where empty); every element is written.
+ *   dropped   a face with an index outside [0,V), an |xq| or |yq| > 2^17, a zq outside [0, MBX_RENDER_ZQ], or doubled area A2 = 0
+ *   coverage  sample (i,j) sits at (SUB j + SUB / 2, SUB i + SUB / 2).  The face is oriented so that A2 = E01(p2) > 0 whatever its winding, with
+ *             Eab(s) = (bx - ax)(sy - ay) - (by - ay)(sx - ax) in int64, and w0 = E12(s), w1 = E20(s), w2 = E01(s), w0 + w1 + w2 = A2.
+ *             Covered: every w_i > 0, or w_i = 0 on an edge a -> b with by - ay > 0 or (by = ay and bx - ax > 0); the neighbour's reversed
+ *             edge answers the opposite, so a sample on a shared edge belongs to exactly one face
+ *   depth     d = floor((w0 z0 + w1 z1 + w2 z2) / A2), int64 (A2 < 2^38, numerator < 2^58)
+ *   winner    the minimum of (d << 32) | face over the covering faces: nearer wins, then the lower face index; independent of any order
+ *   shading   flat, from the fp32 vertices taken in ascending index order a < b < c: n = cross(vb - va, vc - va), I = 0.35 + 0.65 |n_z| / |n|
+ *             (|n|^2 zero or not finite: |n_z| / |n| = 0), channel = floor((alpha colour) I + 255 (1 - alpha) + 0.5) clipped to [0, 255], fp32
+ *             without contraction; background 255
+ *   ss = 2    pixel = (a + b + c + d + 2) >> 2 of its four samples' channels, in the same launch
+ * Three launches (frame boxes, face boxes and colours, tiles), no global atomics, every output element written once.  ws: >=
+ * mbx_render_raster_ws(F, Nf) bytes, 8-byte aligned; ws_bytes is checked.  F = 0 is a no-op.  Refused: Nf < 1 or >= 2^28, F > 65535, size or ss
+ * out of range, a colour outside [0, 255], alpha outside [0, 1]. */
+#define MBX_RENDER_SUB 16
+#define MBX_RENDER_ZQ (1 << 20)
+#define MBX_RENDER_MAX_SIZE 2048
+int mbx_render_project(const float* verts, const float* cube, const int* seq_ptr, int n_tracks, int F, int V, int size, int ss, int* out,
+                       void* stream);
+size_t mbx_render_raster_ws(int F, int Nf);
+int mbx_render_raster(const int* vq, const float* verts, const int* faces, int F, int V, int Nf, int size, int ss, float red, float green,
+                      float blue, float alpha, unsigned char* rgb, int* face_id, int* depth, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- measurement aid (bench.py`roofline.sustained_mfma_tflops`; not part of the model) --------------------------------------------
  * The bf16 MFMA rate the part sustains under its power cap with nothing but v_mfma_f32_32x32x16_bf16 in the loop (pseudo-random
  * operands; n_wg workgroups of 4 waves, `iters` x 16 MFMAs per wave).  ws: >= mbx_mfma_probe_ws(n_wg) bytes = a float sink

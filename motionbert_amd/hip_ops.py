@@ -129,6 +129,9 @@ SIGNATURES = {
     'mbx_wild_mesh': (_i, [_vp] * 5 + [C.POINTER(C.c_int)] + [_vp, _vp, _i] + [_vp] * 4 + [_f, _vp] + [_i] * 4 + [_vp] * 3 + [_i, _vp, _sz, _vp]),
     'mbx_scale_fit': (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     'mbx_wild_mesh_place': (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _i, _vp]),
+    'mbx_render_project': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    'mbx_render_raster_ws': (_sz, [_i, _i]),
+    'mbx_render_raster': (_i, [_vp, _vp, _vp] + [_i] * 5 + [_f] * 4 + [_vp, _vp, _vp, _vp, _sz, _vp]),
     'mbx_rows_n_pack_bytes': (_sz, [_i, _i]),
     'mbx_rows_lnbwd_t': (_i, [_vp] * 6 + [_i, _i, _i, _vp]),
     'mbx_rows_n_pack_many': (_i, [_i64p, _i, _i, _i, _vp]),
@@ -1169,6 +1172,33 @@ class HipOps:
         self._dense('wild_mesh_place', torch.int32, S + 1, dev, seq_ptr=seq_ptr)
         self._dense('wild_mesh_place', torch.float64, S * 6, dev, fit=fit)
         self._ck(self.lib.mbx_wild_mesh_place(_p(verts), _p(kp), K, _p(ref), _p(seq_ptr), S, _p(fit), F, V, self._stream()))
+
+    # ------------------------------------------------------------------ mesh video frames (motionbert_amd/render.py)
+    def render_project(self, verts, cube, seq_ptr, size, ss, out):
+        """verts [F,V,3] f32, cube [n_tracks,4] f32, seq_ptr [n_tracks+1] i32 -> out [F,V,3] i32 (mbx_render_project)"""
+        if verts.dim() != 3 or verts.shape[2] != 3 or cube.dim() != 2 or cube.shape[1] != 4 or cube.shape[0] < 1:
+            raise RuntimeError(f'libmbx: render_project needs verts [F,V,3] and cube [n_tracks,4], got {tuple(verts.shape)} / {tuple(cube.shape)}')
+        F, V, n_tracks, dev = verts.shape[0], verts.shape[1], cube.shape[0], verts.device
+        self._dense('render_project', torch.float32, F * V * 3, dev, verts=verts)
+        self._dense('render_project', torch.float32, n_tracks * 4, dev, cube=cube)
+        self._dense('render_project', torch.int32, n_tracks + 1, dev, seq_ptr=seq_ptr)
+        self._dense('render_project', torch.int32, F * V * 3, dev, out=out)
+        self._ck(self.lib.mbx_render_project(_p(verts), _p(cube), _p(seq_ptr), n_tracks, F, V, int(size), int(ss), _p(out), self._stream()))
+
+    def render_raster(self, vq, verts, faces, size, ss, color, alpha, rgb, face_id=None, depth=None):
+        """vq [F,V,3] i32, verts [F,V,3] f32, faces [Nf,3] i32 -> rgb [F,size,size,3] u8, face_id / depth [F,S,S] i32 or None
+        (mbx_render_raster)"""
+        if vq.dim() != 3 or vq.shape[2] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+            raise RuntimeError(f'libmbx: render_raster needs vq [F,V,3] and faces [Nf,3], got {tuple(vq.shape)} / {tuple(faces.shape)}')
+        F, V, Nf, dev, S = vq.shape[0], vq.shape[1], faces.shape[0], vq.device, int(size) * int(ss)
+        self._dense('render_raster', torch.int32, F * V * 3, dev, vq=vq)
+        self._dense('render_raster', torch.float32, F * V * 3, dev, verts=verts)
+        self._dense('render_raster', torch.int32, Nf * 3, dev, faces=faces)
+        self._dense('render_raster', torch.uint8, F * int(size) * int(size) * 3, dev, rgb=rgb)
+        self._dense('render_raster', torch.int32, F * S * S, dev, face_id=face_id, depth=depth)
+        ws = self._ws(('render', F, Nf), self.lib.mbx_render_raster_ws, F, Nf, device=dev)
+        self._ck(self.lib.mbx_render_raster(_p(vq), _p(verts), _p(faces), F, V, Nf, int(size), int(ss), float(color[0]), float(color[1]),
+                                            float(color[2]), float(alpha), _p(rgb), _p(face_id), _p(depth), _p(ws), ws.numel(), self._stream()))
 
     # ------------------------------------------------------------------ dropout / drop-path (SURVEY 8 a15)
     def dropout(self, x, y, p, seed):

@@ -2,8 +2,9 @@
 hand-written backward.  `smplx` is not imported; the model arrays come from the user's files or module.
 
     SMPLModel                   the arrays: v_template [V,3], shapedirs [V,3,10], posedirs [207,3V], J_regressor [24,V], parents [24],
-                                lbs_weights [V,24] and, where present, J_regressor_h36m [17,V].  `from_npz(path)`, `from_module(m)` (duck-typed:
-                                a `smplx.SMPL` or the reference's `lib.utils.utils_smpl.SMPL` converts), `synthetic(V, seed)` for tests.
+                                lbs_weights [V,24] and, where present, J_regressor_h36m [17,V] and faces [Nf,3] (for render.py).
+                                `from_npz(path)`, `from_module(m)` (duck-typed: a `smplx.SMPL` or the reference's
+                                `lib.utils.utils_smpl.SMPL` converts), `synthetic(V, seed)` for tests.
     SMPLLayer(model)            nn.Module called as the reference calls its layer: `layer(betas=, body_pose=, global_orient=, pose2rot=False)`
                                 -> an object with `.vertices` [F,V,3] in metres and `.joints` [F,24,3]; differentiable in betas and the
                                 rotations through one autograd.Function (`mbx_smpl_fwd` / `mbx_smpl_bwd`).  `forward_kp(betas, rotmat, Q, scale)`
@@ -39,7 +40,7 @@ class SMPLModel:
     """The arrays of one SMPL model, validated, as float32 CPU tensors (`parents`: a tuple of ints).  `Jt` [24,3] = J_regressor . v_template
     and `Jd` [24,3,10] = J_regressor . shapedirs are folded here in float64 (from the stored fp32 arrays) and stored in float32."""
 
-    def __init__(self, v_template, shapedirs, posedirs, J_regressor, parents, lbs_weights, J_regressor_h36m=None):
+    def __init__(self, v_template, shapedirs, posedirs, J_regressor, parents, lbs_weights, J_regressor_h36m=None, faces=None):
         vt, sd, pd = _dense64(v_template), _dense64(shapedirs), _dense64(posedirs)
         jr, w = _dense64(J_regressor), _dense64(lbs_weights)
         if vt.ndim != 2 or vt.shape[1] != 3 or vt.shape[0] < 1:
@@ -79,11 +80,20 @@ class SMPLModel:
             if q.ndim != 2 or q.shape[1] != V or not 1 <= q.shape[0] <= MAX_K:
                 raise ValueError(f'J_regressor_h36m needs to be [1 <= K <= {MAX_K}, {V}], got {q.shape}')
             self.J_regressor_h36m = torch.from_numpy(q).float()
+        self.faces = None                                                    # the triangles (the model files' `f`): only render.py reads them
+        if faces is not None:
+            fa = np.asarray(faces.detach().cpu() if torch.is_tensor(faces) else faces)
+            if fa.ndim != 2 or fa.shape[1] != 3 or fa.shape[0] < 1 or fa.dtype.kind not in 'iu':
+                raise ValueError(f'faces needs to be an integer array [Nf >= 1, 3], got {fa.shape} {fa.dtype}')
+            fa = fa.astype(np.int64)
+            if fa.min() < 0 or fa.max() >= V:
+                raise ValueError(f'faces holds vertex indices outside [0, {V})')
+            self.faces = torch.from_numpy(np.ascontiguousarray(fa.astype(np.int32)))
 
     @classmethod
     def from_npz(cls, path):
         """an .npz with `v_template, shapedirs, posedirs, J_regressor, lbs_weights` (or `weights`), `parents` (or `kintree_table` [2,24]) and
-        optionally `J_regressor_h36m`: what `to_npz` writes, and what the arrays of the SMPL model files are called"""
+        optionally `J_regressor_h36m` and `faces` (or `f`): what `to_npz` writes, and what the arrays of the SMPL model files are called"""
         with np.load(path, allow_pickle=False) as z:
             keys = set(z.files)
             missing = [k for k in ('v_template', 'shapedirs', 'posedirs', 'J_regressor') if k not in keys]
@@ -91,23 +101,27 @@ class SMPLModel:
                 raise ValueError(f'{path}: missing arrays (have {sorted(keys)})')
             parents = z['parents'] if 'parents' in keys else np.asarray(z['kintree_table'])[0].astype(np.int64)
             return cls(z['v_template'], z['shapedirs'], z['posedirs'], z['J_regressor'], parents,
-                       z['lbs_weights'] if 'lbs_weights' in keys else z['weights'], z['J_regressor_h36m'] if 'J_regressor_h36m' in keys else None)
+                       z['lbs_weights'] if 'lbs_weights' in keys else z['weights'], z['J_regressor_h36m'] if 'J_regressor_h36m' in keys else None,
+                       z['faces'] if 'faces' in keys else (z['f'] if 'f' in keys else None))
 
     def to_npz(self, path):
         arrays = dict(v_template=self.v_template.numpy(), shapedirs=self.shapedirs.numpy(), posedirs=self.posedirs.numpy(),
                       J_regressor=self.J_regressor.numpy(), parents=np.asarray(self.parents, np.int64), lbs_weights=self.lbs_weights.numpy())
         if self.J_regressor_h36m is not None:
             arrays['J_regressor_h36m'] = self.J_regressor_h36m.numpy()
+        if self.faces is not None:
+            arrays['faces'] = self.faces.numpy()
         np.savez(path, **arrays)
 
     @classmethod
     def from_module(cls, m):
-        """from any object with `v_template / shapedirs / posedirs / J_regressor / parents / lbs_weights` (and `J_regressor_h36m` where
-        present): a `smplx.SMPL`, or the reference's subclass of it"""
+        """from any object with `v_template / shapedirs / posedirs / J_regressor / parents / lbs_weights` (and `J_regressor_h36m` and
+        `faces` where present): a `smplx.SMPL`, or the reference's subclass of it"""
         missing = [k for k in ('v_template', 'shapedirs', 'posedirs', 'J_regressor', 'parents', 'lbs_weights') if not hasattr(m, k)]
         if missing:
             raise ValueError(f'{type(m).__name__} has no {missing}')
-        return cls(m.v_template, m.shapedirs, m.posedirs, m.J_regressor, m.parents, m.lbs_weights, getattr(m, 'J_regressor_h36m', None))
+        return cls(m.v_template, m.shapedirs, m.posedirs, m.J_regressor, m.parents, m.lbs_weights, getattr(m, 'J_regressor_h36m', None),
+                   getattr(m, 'faces', None))
 
     @classmethod
     def synthetic(cls, V, seed, dense_weights=False):
