@@ -16,6 +16,7 @@
 // launch over [0, F) equals the launches over its single frames bit for bit.  The plain-FMA form of the product (flags bit 1) is kept
 // for the A/B of tools/amass_bench.py (which one is the default and why).
 #include "mbx_common.h"
+#include "smpl_math.h"
 
 #define AM_J 52
 #define AM_C 24            // 16 betas + 8 dmpls
@@ -47,17 +48,6 @@ struct AmassTree { int p[AM_J]; };
 #define AM_LDS_FLOATS (AM_OFF_JR + 64)
 static_assert(AM_OFF_A % 4 == 0 && AM_LDS_FLOATS * 4 <= 160 * 1024, "LDS carve");
 
-// smplx batch_rodrigues: angle = |r + 1e-8|, d = r / angle, R = I + sin K + (1 - cos) K^2; r = 0 gives R = I exactly (mg_rodrigues of smpl.hip)
-__device__ __forceinline__ void am_rodrigues(float r0, float r1, float r2, float (&R)[9]) {
-    const float a0 = r0 + 1e-8f, a1 = r1 + 1e-8f, a2 = r2 + 1e-8f;
-    const float angle = sqrtf(a0 * a0 + a1 * a1 + a2 * a2);
-    const float x = r0 / angle, y = r1 / angle, z = r2 / angle;
-    const float s = sinf(angle), c = 1.0f - cosf(angle);
-    R[0] = 1.0f - c * (y * y + z * z); R[1] = c * (x * y) - s * z;         R[2] = s * y + c * (x * z);
-    R[3] = s * z + c * (x * y);        R[4] = 1.0f - c * (x * x + z * z);  R[5] = c * (y * z) - s * x;
-    R[6] = c * (x * z) - s * y;        R[7] = s * x + c * (y * z);         R[8] = 1.0f - c * (x * x + y * y);
-}
-
 __device__ __forceinline__ int am_feat_at(int k, int f) { return ((k >> 2) * AM_T + f) * 4 + (k & 3); }
 
 template <bool MFMA>
@@ -88,7 +78,7 @@ __global__ __launch_bounds__(AM_NT) void amass_joints_kernel(const float* __rest
             r0 = ps[0]; r1 = ps[1]; r2 = ps[2];
         }
         float R[9];
-        am_rodrigues(r0, r1, r2, R);
+        smplx_rodrigues(r0, r1, r2, R);
         if (k == 0) {
 #pragma unroll
             for (int e = 0; e < 9; ++e) R0[f * 9 + e] = R[e];

@@ -1,16 +1,17 @@
 // The SMPL body model on the device: linear blend skinning as smplx.lbs.lbs evaluates it, forward and hand-written backward (include/mbx.h).
 //   mbx_smpl_pack     : the transposed model table PT [3V,224] = [posedirs^T | shapedirs | 0] the backward reads with one lane per column.
-//   mbx_smpl_fwd      : chain kernel (one thread per frame: joints, the 24 transforms A_j [F,24,12], pf [F,207]) -> vertex kernel (64
-//                       vertices x 32 frames per workgroup; lane = vertex, wave = 8 frames; pose blend, skinning, the tile's share of
-//                       Q x) -> keypoint finalize (tile partials added in tile order).
+// The three forward entries are one path, prepare (if any) -> chain -> vertices -> finish, through the same kernels: the chain kernel (one
+// thread per parameter set: joints, the 24 transforms A_j [F,24,12], pf [F,207]), the vertex kernel smpl_verts_kernel<NP, STITCH> (64
+// vertices x 8 parameter sets per wave, lane = vertex; pose blend, skinning, the tile's share of Q x; NP = 1 or 2 sets meet in one output
+// frame, STITCH: the frame's row comes from dst_frames) and the tile-order keypoint sum sm_kp_sum; hence the same bits from all three.
+//   mbx_smpl_fwd      : chain -> vertices <1, false> -> keypoint finish <1, false> (tile partials added in tile order, scaled).
 //   mbx_mesh_gt       : the mesh targets of MotionSMPL.__getitem__ (lib/data/dataset_mesh.py:63-97) for a batch of clips: prepare kernel (clip
-//                       flip of the 2D input and of theta, Rodrigues into the workspace) -> the chain and vertex kernels of mbx_smpl_fwd ->
-//                       centring kernel (root = scale (Q x)[0] from the tile partials in tile order, subtracted from verts in place and from
-//                       the finished keypoints).
+//                       flip of the 2D input and of theta, Rodrigues into the workspace) -> chain -> vertices <1, false> -> centring kernel
+//                       (root = scale (Q x)[0] by sm_kp_sum, subtracted from verts in place and from the finished keypoints).
 //   mbx_wild_mesh     : the paired SMPL stage of in-the-wild mesh recovery (infer_wild_mesh.py:115-141) for a batch of clips: prepare kernel
-//                       (flip_thetas + Rodrigues of the flipped pass, the theta mean) -> the chain kernel over both parameter sets -> a vertex
-//                       kernel whose waves evaluate both sets of their frames and store the mean once, to the clip's rows of the stitched
-//                       result -> keypoint finish.
+//                       (flip_thetas + Rodrigues of the flipped pass, the theta mean) -> chain over both parameter sets -> vertices
+//                       <2, true>, whose waves evaluate both sets of their frames and store the mean once, to the clip's rows of the
+//                       stitched result (<1, true> without a second pass) -> keypoint finish of the same <NP, STITCH>.
 //   mbx_smpl_bwd      : chain kernel again (nothing but betas and rotmat is saved) -> vertex backward (64 vertices x 16 frames per step;
 //                       phase 1, lane = vertex: vp, T, g, dvp recomputed into LDS; phase 2, lane = output column: d pf / d beta and d A
 //                       accumulated in registers over the workgroup's vertex tiles) -> split sum -> chain backward (one thread per frame).
@@ -19,6 +20,7 @@
 // calls on the same inputs give the same bits.  Frame-uniform operands (pf, A, betas, dkp) are read through wave-uniform addresses.
 #include "mbx_common.h"
 #include "aug_rng.h"
+#include "smpl_math.h"
 
 #define SM_J 24
 #define SM_PF 207          // 23 * 9
@@ -173,11 +175,34 @@ __device__ __forceinline__ void smpl_blend(const float (&w)[SM_J], unsigned mask
     }
 }
 
-__global__ __launch_bounds__(256) void smpl_verts_fwd_kernel(const float* __restrict__ vt, const float* __restrict__ sd, const float* __restrict__ pd,
-                                                             const float* __restrict__ lbsw, const float* __restrict__ Q,
-                                                             const float* __restrict__ betas, const float* __restrict__ Aws,
-                                                             const float* __restrict__ PFws, float scale, float* __restrict__ verts,
-                                                             float* __restrict__ kpart, int F, int V, int K) {
+// the row of frame f (of clip f / T) in the stitched results, -1 where the clip's entry does not fit [0,F)
+__device__ __forceinline__ int wm_row(const int* __restrict__ dst_frames, int f, int T, int F) {
+    const int clip = f / T;
+    const int d = dst_frames[clip];
+    return (d >= 0 && d <= F - T) ? d + (f - clip * T) : -1;
+}
+// (scale a + scale b) * 0.5 with every product and sum rounded: what (a' + b') / 2.0 of the two passes' fp32 tensors gives
+__device__ __forceinline__ float wm_pair(float scale, float a, float b) {
+#pragma clang fp contract(off)
+    const float pa = scale * a;
+    const float pb = scale * b;
+    const float s = pa + pb;
+    return s * 0.5f;
+}
+
+// The vertex kernel: workgroup = 64 vertices (lane = vertex) x 4 waves, SM_FW parameter sets per wave.  nF output frames; betas / Aws /
+// PFws / kpart are indexed by parameter set, NP nF of them: [0,nF) pass A, [nF,2nF) pass B.  NP = 2: a wave's SM_FW sets are SM_FW / 2
+// output frames of pass A and the same frames of pass B; the two x meet in registers and one store writes their mean.  STITCH: frame f
+// goes to row wm_row(f) of the F rows of verts; otherwise to row f (dst_frames, T and F are not read).  The operation order per parameter
+// set is the same in every instantiation.
+template <int NP, bool STITCH>
+__global__ __launch_bounds__(256) void smpl_verts_kernel(const float* __restrict__ vt, const float* __restrict__ sd, const float* __restrict__ pd,
+                                                         const float* __restrict__ lbsw, const float* __restrict__ Q,
+                                                         const float* __restrict__ betas, const float* __restrict__ Aws,
+                                                         const float* __restrict__ PFws, float scale, float* __restrict__ verts,
+                                                         float* __restrict__ kpart, int nF, int V, int K,
+                                                         const int* __restrict__ dst_frames, int T, int F) {
+    constexpr int NO = SM_FW / NP;              // output frames per wave
     __shared__ float qs[32 * 65];
     __shared__ float xs[4][3][64];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -185,7 +210,8 @@ __global__ __launch_bounds__(256) void smpl_verts_fwd_kernel(const float* __rest
     const int v0 = blockIdx.x * SM_VT;
     const bool live = v0 + lane < V;
     const int v = live ? v0 + lane : V - 1;
-    const int f0 = blockIdx.y * (4 * SM_FW) + wave * SM_FW;
+    const int f0 = blockIdx.y * (4 * NO) + wave * NO;
+    const int FC = NP * nF;
     if (kpart) {
         for (int idx = tid; idx < K * 64; idx += 256) {
             const int k = idx >> 6, l = idx & 63;
@@ -199,45 +225,72 @@ __global__ __launch_bounds__(256) void smpl_verts_fwd_kernel(const float* __rest
         w[j] = lbsw[(size_t)v * SM_J + j];
         if (__ballot(w[j] != 0.0f) != 0ull) mask |= 1u << j;
     }
-    int fi[SM_FW];
+    int fi[SM_FW];                              // parameter set of slot i: pass (i / NO), output frame f0 + i % NO
 #pragma unroll
-    for (int i = 0; i < SM_FW; ++i) fi[i] = min(f0 + i, F - 1);
+    for (int i = 0; i < SM_FW; ++i) fi[i] = min(f0 + (i % NO), nF - 1) + (i / NO) * nF;
     float vp[SM_FW][3];
     smpl_vposed<SM_FW>(vt, sd, pd, betas, PFws, fi, v, V, vp);
     __syncthreads();
     const int nout = 3 * K;
 #pragma unroll
-    for (int i = 0; i < SM_FW; ++i) {
-        const bool fl = f0 + i < F;
-        float T[12], x[3];
-        smpl_blend(w, mask, Aws + (size_t)fi[i] * SM_A, T);
+    for (int io = 0; io < NO; ++io) {
+        const bool fl = f0 + io < nF;
+        float x[NP][3];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) x[c] = T[c * 4] * vp[i][0] + T[c * 4 + 1] * vp[i][1] + T[c * 4 + 2] * vp[i][2] + T[c * 4 + 3];
+        for (int p = 0; p < NP; ++p) {
+            const int i = p * NO + io;
+            float Tm[12];
+            smpl_blend(w, mask, Aws + (size_t)fi[i] * SM_A, Tm);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) x[p][c] = Tm[c * 4] * vp[i][0] + Tm[c * 4 + 1] * vp[i][1] + Tm[c * 4 + 2] * vp[i][2] + Tm[c * 4 + 3];
+        }
         if (verts && live && fl) {
-            float* o = verts + ((size_t)fi[i] * V + v) * 3;
-            o[0] = scale * x[0]; o[1] = scale * x[1]; o[2] = scale * x[2];
+            const int row = STITCH ? wm_row(dst_frames, fi[io], T, F) : fi[io];         // wave-uniform
+            if (!STITCH || row >= 0) {
+                float* o = verts + ((size_t)row * V + v) * 3;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) o[c] = NP == 2 ? wm_pair(scale, x[0][c], x[NP - 1][c]) : scale * x[0][c];
+            }
         }
         if (kpart) {
-            xs[wave][0][lane] = x[0]; xs[wave][1][lane] = x[1]; xs[wave][2][lane] = x[2];
-            __syncthreads();
-            for (int o = lane; o < nout; o += 64) {
-                const int k = o / 3, c = o - 3 * k;
-                float s = 0.0f;
-                for (int l = 0; l < 64; ++l) s += qs[k * 65 + l] * xs[wave][c][l];
-                if (fl) kpart[((size_t)blockIdx.x * F + fi[i]) * nout + o] = s;
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                xs[wave][0][lane] = x[p][0]; xs[wave][1][lane] = x[p][1]; xs[wave][2][lane] = x[p][2];
+                __syncthreads();
+                for (int o = lane; o < nout; o += 64) {
+                    const int k = o / 3, c = o - 3 * k;
+                    float s = 0.0f;
+                    for (int l = 0; l < 64; ++l) s += qs[k * 65 + l] * xs[wave][c][l];
+                    if (fl) kpart[((size_t)blockIdx.x * FC + fi[p * NO + io]) * nout + o] = s;
+                }
+                __syncthreads();
             }
-            __syncthreads();
         }
     }
 }
 
+// one (frame, output) record of kpart [tiles][tile_stride]: the tiles' partials added in tile order
+__device__ __forceinline__ float sm_kp_sum(const float* __restrict__ kpart, int nvt, size_t tile_stride, size_t idx) {
+    float s = 0.0f;
+    for (int t = 0; t < nvt; ++t) s += kpart[(size_t)t * tile_stride + idx];
+    return s;
+}
+
+// keypoints, n = nF * nout of them: scale * sum per pass (NP = 2: then the mean, as the vertices form it), to row f or to the clip's rows
+template <int NP, bool STITCH>
 __global__ __launch_bounds__(256) void smpl_kp_finish_kernel(const float* __restrict__ kpart, int nvt, float scale, float* __restrict__ kp,
-                                                             size_t n) {
+                                                             size_t n, int nout, const int* __restrict__ dst_frames, int T, int F) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    float s = 0.0f;
-    for (int t = 0; t < nvt; ++t) s += kpart[(size_t)t * n + i];
-    kp[i] = scale * s;
+    size_t dst = i;
+    if (STITCH) {
+        const int f = (int)(i / nout), o = (int)(i - (size_t)f * nout);
+        const int row = wm_row(dst_frames, f, T, F);
+        if (row < 0) return;
+        dst = (size_t)row * nout + o;
+    }
+    const float sa = sm_kp_sum(kpart, nvt, NP * n, i);
+    kp[dst] = NP == 2 ? wm_pair(scale, sa, sm_kp_sum(kpart, nvt, NP * n, n + i)) : scale * sa;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -258,17 +311,6 @@ __device__ __forceinline__ int mg_joint_src(int j) {      // utils_data.py:61-65
     return j;
 }
 
-// smplx batch_rodrigues: angle = |r + 1e-8|, d = r / angle, R = I + sin K + (1 - cos) K^2; r = 0 gives K = 0 and R = I exactly
-__device__ __forceinline__ void mg_rodrigues(float r0, float r1, float r2, float* __restrict__ R) {
-    const float a0 = r0 + 1e-8f, a1 = r1 + 1e-8f, a2 = r2 + 1e-8f;
-    const float angle = sqrtf(a0 * a0 + a1 * a1 + a2 * a2);
-    const float x = r0 / angle, y = r1 / angle, z = r2 / angle;
-    const float s = sinf(angle), c = 1.0f - cosf(angle);
-    R[0] = 1.0f - c * (y * y + z * z); R[1] = c * (x * y) - s * z;         R[2] = s * y + c * (x * z);
-    R[3] = s * z + c * (x * y);        R[4] = 1.0f - c * (x * x + z * z);  R[5] = c * (y * z) - s * x;
-    R[6] = c * (x * z) - s * y;        R[7] = s * x + c * (y * z);         R[8] = 1.0f - c * (x * x + y * y);
-}
-
 __global__ __launch_bounds__(256) void mesh_gt_prepare_kernel(const float* __restrict__ pose, const float* __restrict__ shape,
                                                               const float* __restrict__ m2d, const unsigned char* __restrict__ flips,
                                                               uint32_t slo, uint32_t shi, float flip_prob, float* __restrict__ x2d,
@@ -287,7 +329,7 @@ __global__ __launch_bounds__(256) void mesh_gt_prepare_kernel(const float* __res
             float* o = theta + (size_t)f * 82 + t * 3;
             o[0] = r0; o[1] = r1; o[2] = r2;
         }
-        if (rot) mg_rodrigues(r0, r1, r2, rot + (size_t)f * 216 + t * 9);
+        if (rot) smplx_rodrigues(r0, r1, r2, rot + (size_t)f * 216 + t * 9);
     } else if (t < SM_J + 17) {
         if (x2d) {
             const int j = t - SM_J;
@@ -306,8 +348,8 @@ __global__ __launch_bounds__(256) void mesh_gt_prepare_kernel(const float* __res
 }
 
 // Centring: workgroup = MG_CF frames x MG_CV vertices.  Every workgroup forms the root of its frames from the tile partials of keypoint 0
-// in tile order (the sum and the product of smpl_kp_finish_kernel), so all workgroups of a frame hold the same bits; verts -= root in
-// place.  The workgroups of the first vertex chunk also finish the keypoints and subtract the root from them.
+// (scale * sm_kp_sum, what smpl_kp_finish_kernel stores), so all workgroups of a frame hold the same bits; verts -= root in place.  The
+// workgroups of the first vertex chunk also finish the keypoints and subtract the root from them.
 __global__ __launch_bounds__(256) void mesh_gt_centre_kernel(const float* __restrict__ kpart, int nvt, int nout, float scale, float* verts,
                                                              float* __restrict__ kp, int F, int V) {
     // no contraction here: scale * s has to round before the root comes off it, as it does where smpl_kp_finish_kernel stores it (a fused
@@ -316,12 +358,11 @@ __global__ __launch_bounds__(256) void mesh_gt_centre_kernel(const float* __rest
     __shared__ float root[MG_CF][3];
     const int tid = threadIdx.x;
     const int f0 = blockIdx.x * MG_CF;          // frame blocks on x: F / 8 of them, up to 2^17; vertex chunks on y: at most 512
+    const size_t n = (size_t)F * nout;
     if (tid < MG_CF * 3) {
         const int i = tid / 3, c = tid - 3 * i;
         const int f = min(f0 + i, F - 1);
-        float s = 0.0f;
-        for (int t = 0; t < nvt; ++t) s += kpart[((size_t)t * F + f) * nout + c];
-        root[i][c] = scale * s;
+        root[i][c] = scale * sm_kp_sum(kpart, nvt, n, (size_t)f * nout + c);
     }
     __syncthreads();
     if (kp && blockIdx.y == 0) {
@@ -329,9 +370,9 @@ __global__ __launch_bounds__(256) void mesh_gt_centre_kernel(const float* __rest
             const int i = idx / nout, o = idx - i * nout;
             const int f = f0 + i;
             if (f < F) {
-                float s = 0.0f;
-                for (int t = 0; t < nvt; ++t) s += kpart[((size_t)t * F + f) * nout + o];
-                kp[(size_t)f * nout + o] = scale * s - root[i][o % 3];
+                const size_t at = (size_t)f * nout + o;
+                const float s = sm_kp_sum(kpart, nvt, n, at);
+                kp[at] = scale * s - root[i][o % 3];
             }
         }
     }
@@ -355,21 +396,6 @@ __global__ __launch_bounds__(256) void mesh_gt_centre_kernel(const float* __rest
 // in-the-wild mesh recovery (mbx_wild_mesh): the model's pass on x (A) and its flipped-back pass on flip_data(x) (B), their mean written
 // once to each clip's rows of the stitched results.  The chain kernel sees 2 nT parameter sets: [0,nT) pass A, [nT,2nT) pass B.
 // ---------------------------------------------------------------------------------------------------------------
-// the row of frame f (of clip f / T) in the stitched results, -1 where the clip's entry does not fit [0,F)
-__device__ __forceinline__ int wm_row(const int* __restrict__ dst_frames, int f, int T, int F) {
-    const int clip = f / T;
-    const int d = dst_frames[clip];
-    return (d >= 0 && d <= F - T) ? d + (f - clip * T) : -1;
-}
-// (scale a + scale b) * 0.5 with every product and sum rounded: what (a' + b') / 2.0 of the two passes' fp32 tensors gives
-__device__ __forceinline__ float wm_pair(float scale, float a, float b) {
-#pragma clang fp contract(off)
-    const float pa = scale * a;
-    const float pb = scale * b;
-    const float s = pa + pb;
-    return s * 0.5f;
-}
-
 // 64 threads per frame: thread = joint (24: flip_thetas + Rodrigues of pass B, the theta mean), shape coefficient (10); all 64 copy pass
 // A's rotations next to pass B's.  theta_b == NULL (single-pass mode, launched for theta alone): theta_a is copied to its rows.
 __global__ __launch_bounds__(256) void wild_mesh_prepare_kernel(const float* __restrict__ rotmat_a, const float* __restrict__ betas_a,
@@ -388,7 +414,7 @@ __global__ __launch_bounds__(256) void wild_mesh_prepare_kernel(const float* __r
         if (theta_b) {
             const float* p = theta_b + (size_t)f * 82 + mg_theta_src(t) * 3;
             const float r0 = p[0], r1 = -p[1], r2 = -p[2];
-            mg_rodrigues(r0, r1, r2, rot2 + (size_t)(nT + f) * 216 + t * 9);
+            smplx_rodrigues(r0, r1, r2, rot2 + (size_t)(nT + f) * 216 + t * 9);
             if (row >= 0) {
                 const float* a = theta_a + (size_t)f * 82 + t * 3;
                 float* o = theta + (size_t)row * 82 + t * 3;
@@ -409,108 +435,6 @@ __global__ __launch_bounds__(256) void wild_mesh_prepare_kernel(const float* __r
             theta[(size_t)row * 82 + 72 + k] = theta_a[(size_t)f * 82 + 72 + k];
         }
     }
-}
-
-// The vertex kernel of the paired stage: smpl_verts_fwd_kernel's tile (64 vertices, lane = vertex, SM_FW parameter sets per wave) and its
-// operation order per parameter set.  PAIR: a wave's SM_FW sets are SM_FW / 2 output frames of pass A and the same frames of pass B; the two
-// x meet in registers and one store writes their mean.  Not PAIR: SM_FW output frames, the bits of smpl_verts_fwd_kernel, stitched.
-// betas / Aws / PFws / kpart are indexed by parameter set (FC = nT or 2 nT of them).
-template <bool PAIR>
-__global__ __launch_bounds__(256) void wild_mesh_verts_kernel(const float* __restrict__ vt, const float* __restrict__ sd, const float* __restrict__ pd,
-                                                              const float* __restrict__ lbsw, const float* __restrict__ Q,
-                                                              const float* __restrict__ betas, const float* __restrict__ Aws,
-                                                              const float* __restrict__ PFws, float scale, const int* __restrict__ dst_frames,
-                                                              float* __restrict__ verts, float* __restrict__ kpart, int nT, int T, int F, int V,
-                                                              int K) {
-    constexpr int NP = PAIR ? 2 : 1;
-    constexpr int NO = SM_FW / NP;              // output frames per wave
-    __shared__ float qs[32 * 65];
-    __shared__ float xs[4][3][64];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int v0 = blockIdx.x * SM_VT;
-    const bool live = v0 + lane < V;
-    const int v = live ? v0 + lane : V - 1;
-    const int f0 = blockIdx.y * (4 * NO) + wave * NO;
-    const int FC = NP * nT;
-    if (kpart) {
-        for (int idx = tid; idx < K * 64; idx += 256) {
-            const int k = idx >> 6, l = idx & 63;
-            qs[k * 65 + l] = (v0 + l < V) ? Q[(size_t)k * V + v0 + l] : 0.0f;
-        }
-    }
-    float w[SM_J];
-    unsigned mask = 0;
-#pragma unroll
-    for (int j = 0; j < SM_J; ++j) {
-        w[j] = lbsw[(size_t)v * SM_J + j];
-        if (__ballot(w[j] != 0.0f) != 0ull) mask |= 1u << j;
-    }
-    int fi[SM_FW];                              // parameter set of slot i: pass (i / NO), output frame f0 + i % NO
-#pragma unroll
-    for (int i = 0; i < SM_FW; ++i) fi[i] = min(f0 + (i % NO), nT - 1) + (i / NO) * nT;
-    float vp[SM_FW][3];
-    smpl_vposed<SM_FW>(vt, sd, pd, betas, PFws, fi, v, V, vp);
-    __syncthreads();
-    const int nout = 3 * K;
-#pragma unroll
-    for (int io = 0; io < NO; ++io) {
-        const bool fl = f0 + io < nT;
-        float x[NP][3];
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-            const int i = p * NO + io;
-            float Tm[12];
-            smpl_blend(w, mask, Aws + (size_t)fi[i] * SM_A, Tm);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) x[p][c] = Tm[c * 4] * vp[i][0] + Tm[c * 4 + 1] * vp[i][1] + Tm[c * 4 + 2] * vp[i][2] + Tm[c * 4 + 3];
-        }
-        if (verts && fl) {
-            const int row = wm_row(dst_frames, fi[io], T, F);           // wave-uniform
-            if (row >= 0 && live) {
-                float* o = verts + ((size_t)row * V + v) * 3;
-                if (PAIR) {
-                    o[0] = wm_pair(scale, x[0][0], x[NP - 1][0]); o[1] = wm_pair(scale, x[0][1], x[NP - 1][1]);
-                    o[2] = wm_pair(scale, x[0][2], x[NP - 1][2]);
-                } else {
-                    o[0] = scale * x[0][0]; o[1] = scale * x[0][1]; o[2] = scale * x[0][2];
-                }
-            }
-        }
-        if (kpart) {
-#pragma unroll
-            for (int p = 0; p < NP; ++p) {
-                xs[wave][0][lane] = x[p][0]; xs[wave][1][lane] = x[p][1]; xs[wave][2][lane] = x[p][2];
-                __syncthreads();
-                for (int o = lane; o < nout; o += 64) {
-                    const int k = o / 3, c = o - 3 * k;
-                    float s = 0.0f;
-                    for (int l = 0; l < 64; ++l) s += qs[k * 65 + l] * xs[wave][c][l];
-                    if (fl) kpart[((size_t)blockIdx.x * FC + fi[p * NO + io]) * nout + o] = s;
-                }
-                __syncthreads();
-            }
-        }
-    }
-}
-
-// keypoints: the tile partials of each pass added in tile order and scaled as smpl_kp_finish_kernel does, then the mean, to the clip's rows
-template <bool PAIR>
-__global__ __launch_bounds__(256) void wild_mesh_kp_finish_kernel(const float* __restrict__ kpart, int nvt, float scale,
-                                                                  const int* __restrict__ dst_frames, float* __restrict__ kp, int nT, int T,
-                                                                  int F, int nout) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const size_t n = (size_t)nT * nout;
-    if (i >= n) return;
-    const int f = (int)(i / nout), o = (int)(i - (size_t)f * nout);
-    const int row = wm_row(dst_frames, f, T, F);
-    if (row < 0) return;
-    const size_t nc = PAIR ? 2 * n : n;                 // one tile's partials
-    float sa = 0.0f, sb = 0.0f;
-    for (int t = 0; t < nvt; ++t) sa += kpart[(size_t)t * nc + i];
-    if (PAIR)
-        for (int t = 0; t < nvt; ++t) sb += kpart[(size_t)t * nc + n + i];
-    kp[(size_t)row * nout + o] = PAIR ? wm_pair(scale, sa, sb) : scale * sa;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -741,18 +665,57 @@ __global__ __launch_bounds__(64) void smpl_chain_bwd_kernel(const float* __restr
 static inline int sm_tiles(int V) { return (V + SM_VT - 1) / SM_VT; }
 static inline int sm_splits(int V) { const int t = sm_tiles(V); return t < SM_SPLITS ? t : SM_SPLITS; }
 static inline bool sm_dims_ok(int F, int V, int K) { return F >= 0 && F <= (1 << 20) && V >= 1 && V <= (1 << 20) && K >= 0 && K <= 32; }
-// float offsets: A [F,288] | pf [F,208] | scratch [288,F] | (fwd) keypoint partials [tiles,F,3K]
-//                                                         | (bwd) d J scratch [72,F] | partials [S,F,512] | sums [F,512]
+
+// The workspace of every entry, for F parameter sets: A [F,288] | pf [F,208] | chain scratch [288,F] | tail.  The tail is
+//   forward : keypoint partials [tiles,F,3K], then what the entry adds (mesh_gt: rotations [F,216]; wild_mesh with pass B: rotations
+//             [F,216] and shapes [F,10] of both passes);
+//   backward: d J scratch [72,F] | partials [S,F,512] | sums [F,512].
+struct SmWs { float *A, *PF, *G, *tail; };
 static inline size_t sm_common_floats(int F) { return (size_t)F * (SM_A + SM_PFS + SM_A); }
+static inline size_t sm_fwd_floats(int F, int V, int K) { return sm_common_floats(F) + (size_t)sm_tiles(V) * F * 3 * K; }
+static inline size_t sm_ws_bytes(size_t floats) { return floats * sizeof(float) + 256; }
+static inline SmWs sm_carve(void* ws, int F) {
+    SmWs w = {};
+    if (!ws) return w;                          // an entry that needs the workspace has refused a null one before it launches
+    w.A = (float*)ws;
+    w.PF = w.A + (size_t)F * SM_A;
+    w.G = w.PF + (size_t)F * SM_PFS;
+    w.tail = w.A + sm_common_floats(F);
+    return w;
+}
 
 extern "C" size_t mbx_smpl_fwd_ws(int F, int V, int K) {
     if (!sm_dims_ok(F, V, K) || F < 1) return 0;
-    return (sm_common_floats(F) + (size_t)sm_tiles(V) * F * 3 * K) * sizeof(float) + 256;
+    return sm_ws_bytes(sm_fwd_floats(F, V, K));
 }
 
 extern "C" size_t mbx_smpl_bwd_ws(int F, int V, int K) {
     if (!sm_dims_ok(F, V, K) || F < 1) return 0;
-    return (sm_common_floats(F) + (size_t)F * 72 + (size_t)(sm_splits(V) + 1) * F * SM_COLS) * sizeof(float) + 256;
+    return sm_ws_bytes(sm_common_floats(F) + (size_t)F * 72 + (size_t)(sm_splits(V) + 1) * F * SM_COLS);
+}
+
+extern "C" size_t mbx_mesh_gt_ws(int F, int V, int K) {
+    if (!sm_dims_ok(F, V, K) || F < 1 || K < 1) return 0;
+    return sm_ws_bytes(sm_fwd_floats(F, V, K) + (size_t)F * 216);
+}
+
+extern "C" size_t mbx_wild_mesh_ws(int nT, int V, int K, int pair) {
+    if (nT < 1 || nT > (1 << 20) / (pair ? 2 : 1)) return 0;
+    const int FC = pair ? 2 * nT : nT;
+    if (!sm_dims_ok(FC, V, K)) return 0;
+    return sm_ws_bytes(sm_fwd_floats(FC, V, K) + (pair ? (size_t)FC * 226 : 0));
+}
+
+// the model arrays every entry takes; Q may be null where no keypoints are asked for
+struct SmModel { const float *v_template, *shapedirs, *posedirs, *Jt, *Jd, *lbs_weights, *Q; };
+static inline bool sm_model_set(const SmModel& m) { return m.v_template && m.shapedirs && m.posedirs && m.Jt && m.Jd && m.lbs_weights; }
+template <class... P>
+static inline uintptr_t sm_or(P... p) { return (uintptr_t(0) | ... | (uintptr_t)p); }
+// the model arrays and the entry's own pointers (rest: sm_or of them) 4-byte aligned, the workspace 16-byte
+static int sm_check_align(const char* who, const SmModel& m, uintptr_t rest, const void* ws) {
+    MBX_CHECK_ARG(((sm_or(m.v_template, m.shapedirs, m.posedirs, m.Jt, m.Jd, m.lbs_weights, m.Q) | rest) & 3) == 0 && ((uintptr_t)ws & 15) == 0,
+                  "%s: pointers must be 4-byte aligned, the workspace 16-byte aligned", who);
+    return 0;
 }
 
 extern "C" int mbx_smpl_pack(const float* shapedirs, const float* posedirs, float* packed_t, int V, void* stream) {
@@ -777,48 +740,57 @@ static int sm_tree(const int* parents, SmplTree& tree, const char* who) {
     return 0;
 }
 
+// The launches the entries are made of; `who` is the entry's name for the step, as a failed launch reports it.
+static int sm_launch_chain(const char* who, hipStream_t s, const SmModel& m, const SmplTree& tree, const float* betas, const float* rotmat,
+                           float scale, const SmWs& w, float* joints, int F) {
+    hipLaunchKernelGGL(smpl_chain_fwd_kernel, dim3((F + 63) / 64), dim3(64), 0, s, betas, rotmat, m.Jt, m.Jd, tree, scale, w.A, w.PF, w.G, joints, F);
+    MBX_LAUNCH_CHECK(who);
+    return 0;
+}
+
+// nF output frames of NP parameter sets each; kpart: the tile partials of K keypoints (null: none); dst_frames / T / F: where STITCH
+template <int NP, bool STITCH>
+static int sm_launch_verts(const char* who, hipStream_t s, const SmModel& m, const float* betas, const SmWs& w, float scale, float* verts,
+                           float* kpart, int nF, int V, int K, const int* dst_frames = nullptr, int T = 0, int F = 0) {
+    constexpr int per_wg = 4 * (SM_FW / NP);
+    hipLaunchKernelGGL((smpl_verts_kernel<NP, STITCH>), dim3(sm_tiles(V), (nF + per_wg - 1) / per_wg), dim3(256), 0, s, m.v_template, m.shapedirs,
+                       m.posedirs, m.lbs_weights, m.Q, betas, (const float*)w.A, (const float*)w.PF, scale, verts, kpart, nF, V, K, dst_frames, T, F);
+    MBX_LAUNCH_CHECK(who);
+    return 0;
+}
+
+template <int NP, bool STITCH>
+static int sm_launch_kp_finish(const char* who, hipStream_t s, const float* kpart, float scale, float* kp, int nF, int V, int K,
+                               const int* dst_frames = nullptr, int T = 0, int F = 0) {
+    const size_t n = (size_t)nF * 3 * K;
+    hipLaunchKernelGGL((smpl_kp_finish_kernel<NP, STITCH>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, kpart, sm_tiles(V), scale, kp, n,
+                       3 * K, dst_frames, T, F);
+    MBX_LAUNCH_CHECK(who);
+    return 0;
+}
+
 extern "C" int mbx_smpl_fwd(const float* v_template, const float* shapedirs, const float* posedirs, const float* Jt, const float* Jd,
                             const int* parents, const float* lbs_weights, const float* Q, int K, const float* betas, const float* rotmat,
                             float scale, float* verts, float* kp, float* joints, int F, int V, void* ws, size_t ws_bytes, void* stream) {
+    const SmModel m = {v_template, shapedirs, posedirs, Jt, Jd, lbs_weights, Q};
     MBX_CHECK_ARG(sm_dims_ok(F, V, K), "smpl_fwd: bad sizes F=%d V=%d K=%d (V >= 1, K <= 32)", F, V, K);
     SmplTree tree;
     if (sm_tree(parents, tree, "smpl_fwd")) return 1;
     if (F == 0) return 0;
-    MBX_CHECK_ARG(v_template && shapedirs && posedirs && Jt && Jd && lbs_weights && betas && rotmat && ws, "smpl_fwd: null pointer");
+    MBX_CHECK_ARG(sm_model_set(m) && betas && rotmat && ws, "smpl_fwd: null pointer");
     MBX_CHECK_ARG(verts || kp || joints, "smpl_fwd: no output");
     MBX_CHECK_ARG(!kp || (Q && K >= 1), "smpl_fwd: kp needs a regressor Q [K,V] with K >= 1");
-    MBX_CHECK_ARG(ws_bytes >= mbx_smpl_fwd_ws(F, V, kp ? K : 0), "smpl_fwd: workspace of %zu bytes, %zu needed", ws_bytes,
-                  mbx_smpl_fwd_ws(F, V, kp ? K : 0));
-    MBX_CHECK_ARG((((uintptr_t)v_template | (uintptr_t)shapedirs | (uintptr_t)posedirs | (uintptr_t)Jt | (uintptr_t)Jd | (uintptr_t)lbs_weights |
-                    (uintptr_t)Q | (uintptr_t)betas | (uintptr_t)rotmat | (uintptr_t)verts | (uintptr_t)kp | (uintptr_t)joints) & 3) == 0 &&
-                      ((uintptr_t)ws & 15) == 0,
-                  "smpl_fwd: pointers must be 4-byte aligned, the workspace 16-byte aligned");
+    const int Kv = kp ? K : 0;
+    MBX_CHECK_ARG(ws_bytes >= mbx_smpl_fwd_ws(F, V, Kv), "smpl_fwd: workspace of %zu bytes, %zu needed", ws_bytes, mbx_smpl_fwd_ws(F, V, Kv));
+    if (sm_check_align("smpl_fwd", m, sm_or(betas, rotmat, verts, kp, joints), ws)) return 1;
     hipStream_t s = (hipStream_t)stream;
-    float* Aws = (float*)ws;
-    float* PFws = Aws + (size_t)F * SM_A;
-    float* G = PFws + (size_t)F * SM_PFS;
-    float* kpart = G + (size_t)F * SM_A;
-    hipLaunchKernelGGL(smpl_chain_fwd_kernel, dim3((F + 63) / 64), dim3(64), 0, s, betas, rotmat, Jt, Jd, tree, scale, Aws, PFws, G, joints, F);
-    MBX_LAUNCH_CHECK("smpl_fwd (chain)");
+    const SmWs w = sm_carve(ws, F);
+    float* kpart = kp ? w.tail : nullptr;
+    if (sm_launch_chain("smpl_fwd (chain)", s, m, tree, betas, rotmat, scale, w, joints, F)) return 1;
     if (!verts && !kp) return 0;
-    const int nvt = sm_tiles(V);
-    hipLaunchKernelGGL(smpl_verts_fwd_kernel, dim3(nvt, (F + 4 * SM_FW - 1) / (4 * SM_FW)), dim3(256), 0, s, v_template, shapedirs, posedirs,
-                       lbs_weights, Q, betas, (const float*)Aws, (const float*)PFws, scale, verts, kp ? kpart : (float*)nullptr, F, V, kp ? K : 0);
-    MBX_LAUNCH_CHECK("smpl_fwd (vertices)");
-    if (kp) {
-        const size_t n = (size_t)F * 3 * K;
-        hipLaunchKernelGGL(smpl_kp_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)kpart, nvt, scale, kp, n);
-        MBX_LAUNCH_CHECK("smpl_fwd (keypoints)");
-    }
+    if (sm_launch_verts<1, false>("smpl_fwd (vertices)", s, m, betas, w, scale, verts, kpart, F, V, Kv)) return 1;
+    if (kp && sm_launch_kp_finish<1, false>("smpl_fwd (keypoints)", s, kpart, scale, kp, F, V, K)) return 1;
     return 0;
-}
-
-// float offsets: the forward's layout with K keypoints (mbx_smpl_fwd_ws less its 256 spare bytes), then the rotation matrices [F,216]
-static inline size_t mg_rot_offset(int F, int V, int K) { return sm_common_floats(F) + (size_t)sm_tiles(V) * F * 3 * K; }
-
-extern "C" size_t mbx_mesh_gt_ws(int F, int V, int K) {
-    if (!sm_dims_ok(F, V, K) || F < 1 || K < 1) return 0;
-    return (mg_rot_offset(F, V, K) + (size_t)F * 216) * sizeof(float) + 256;
 }
 
 extern "C" int mbx_mesh_gt(const float* pose, const float* shape, const float* motion_2d, const unsigned char* flips, uint64_t seed,
@@ -826,6 +798,7 @@ extern "C" int mbx_mesh_gt(const float* pose, const float* shape, const float* m
                            const float* Jd, const int* parents, const float* lbs_weights, const float* Q, int K, float scale, float* x2d,
                            float* theta, float* kp_3d, float* verts, unsigned char* flips_used, int N, int T, int V, void* ws,
                            size_t ws_bytes, void* stream) {
+    const SmModel m = {v_template, shapedirs, posedirs, Jt, Jd, lbs_weights, Q};
     MBX_CHECK_ARG(N >= 0 && T >= 1 && (long long)N * T <= (1 << 20), "mesh_gt: bad sizes N=%d T=%d (T >= 1, N T <= 2^20)", N, T);
     const int F = N * T;
     MBX_CHECK_ARG(sm_dims_ok(F, V, K) && K >= 1, "mesh_gt: bad sizes F=%d V=%d K=%d (V >= 1, 1 <= K <= 32)", F, V, K);
@@ -838,52 +811,32 @@ extern "C" int mbx_mesh_gt(const float* pose, const float* shape, const float* m
     MBX_CHECK_ARG(pose && shape, "mesh_gt: null pointer (pose, shape)");
     MBX_CHECK_ARG(!x2d || motion_2d, "mesh_gt: x2d needs motion_2d");
     MBX_CHECK_ARG(!x2d || x2d != motion_2d, "mesh_gt: x2d must not alias motion_2d (the flip permutes joints)");
-    MBX_CHECK_ARG(!body || (v_template && shapedirs && posedirs && Jt && Jd && lbs_weights && Q && ws),
-                  "mesh_gt: null pointer (kp_3d and verts need the model arrays, Q and a workspace)");
+    MBX_CHECK_ARG(!body || (sm_model_set(m) && Q && ws), "mesh_gt: null pointer (kp_3d and verts need the model arrays, Q and a workspace)");
     MBX_CHECK_ARG(!body || ws_bytes >= mbx_mesh_gt_ws(F, V, K), "mesh_gt: workspace of %zu bytes, %zu needed", ws_bytes, mbx_mesh_gt_ws(F, V, K));
-    MBX_CHECK_ARG((((uintptr_t)pose | (uintptr_t)shape | (uintptr_t)motion_2d | (uintptr_t)v_template | (uintptr_t)shapedirs | (uintptr_t)posedirs |
-                    (uintptr_t)Jt | (uintptr_t)Jd | (uintptr_t)lbs_weights | (uintptr_t)Q | (uintptr_t)x2d | (uintptr_t)theta | (uintptr_t)kp_3d |
-                    (uintptr_t)verts) & 3) == 0 && (!body || ((uintptr_t)ws & 15) == 0),
-                  "mesh_gt: pointers must be 4-byte aligned, the workspace 16-byte aligned");
+    if (sm_check_align("mesh_gt", m, sm_or(pose, shape, motion_2d, x2d, theta, kp_3d, verts), body ? ws : nullptr)) return 1;
     hipStream_t s = (hipStream_t)stream;
     // the vertex kernel forms the partials of the Kv keypoints the caller reads: all K for kp_3d, the root alone for verts
     const int Kv = kp_3d ? K : 1;
-    float* Aws = (float*)ws;
-    float* PFws = body ? Aws + (size_t)F * SM_A : nullptr;
-    float* G = body ? PFws + (size_t)F * SM_PFS : nullptr;
-    float* kpart = body ? G + (size_t)F * SM_A : nullptr;
-    float* rot = body ? Aws + mg_rot_offset(F, V, K) : nullptr;
+    const SmWs w = sm_carve(body ? ws : nullptr, F);
+    float* rot = body ? w.A + sm_fwd_floats(F, V, K) : nullptr;
     hipLaunchKernelGGL(mesh_gt_prepare_kernel, dim3((F + 3) / 4), dim3(256), 0, s, pose, shape, motion_2d, flips, (uint32_t)seed,
                        (uint32_t)(seed >> 32), flip_prob, x2d, theta, rot, flips_used, F, T);
     MBX_LAUNCH_CHECK("mesh_gt (prepare)");
     if (!body) return 0;
-    hipLaunchKernelGGL(smpl_chain_fwd_kernel, dim3((F + 63) / 64), dim3(64), 0, s, shape, (const float*)rot, Jt, Jd, tree, scale, Aws, PFws, G,
-                       (float*)nullptr, F);
-    MBX_LAUNCH_CHECK("mesh_gt (chain)");
-    const int nvt = sm_tiles(V);
-    hipLaunchKernelGGL(smpl_verts_fwd_kernel, dim3(nvt, (F + 4 * SM_FW - 1) / (4 * SM_FW)), dim3(256), 0, s, v_template, shapedirs, posedirs,
-                       lbs_weights, Q, shape, (const float*)Aws, (const float*)PFws, scale, verts, kpart, F, V, Kv);
-    MBX_LAUNCH_CHECK("mesh_gt (vertices)");
+    if (sm_launch_chain("mesh_gt (chain)", s, m, tree, shape, rot, scale, w, nullptr, F)) return 1;
+    if (sm_launch_verts<1, false>("mesh_gt (vertices)", s, m, shape, w, scale, verts, w.tail, F, V, Kv)) return 1;
     const int chunks = verts ? (V + MG_CV - 1) / MG_CV : 1;
-    hipLaunchKernelGGL(mesh_gt_centre_kernel, dim3((F + MG_CF - 1) / MG_CF, chunks), dim3(256), 0, s, (const float*)kpart, nvt, 3 * Kv, scale,
-                       verts, kp_3d, F, V);
+    hipLaunchKernelGGL(mesh_gt_centre_kernel, dim3((F + MG_CF - 1) / MG_CF, chunks), dim3(256), 0, s, (const float*)w.tail, sm_tiles(V), 3 * Kv,
+                       scale, verts, kp_3d, F, V);
     MBX_LAUNCH_CHECK("mesh_gt (centring)");
     return 0;
-}
-
-// float offsets for FC = nT or 2 nT parameter sets: the forward's layout with K keypoints over FC frames, then (pair) the rotation matrices
-// [FC,216] and the shapes [FC,10] of both passes
-extern "C" size_t mbx_wild_mesh_ws(int nT, int V, int K, int pair) {
-    if (nT < 1 || nT > (1 << 20) / (pair ? 2 : 1)) return 0;
-    const int FC = pair ? 2 * nT : nT;
-    if (!sm_dims_ok(FC, V, K)) return 0;
-    return (mg_rot_offset(FC, V, K) + (pair ? (size_t)FC * 226 : 0)) * sizeof(float) + 256;
 }
 
 extern "C" int mbx_wild_mesh(const float* v_template, const float* shapedirs, const float* posedirs, const float* Jt, const float* Jd,
                              const int* parents, const float* lbs_weights, const float* Q, int K, const float* rotmat_a, const float* betas_a,
                              const float* theta_a, const float* theta_b, float scale, const int* dst_frames, int dst_max, int n, int T, int F,
                              float* verts, float* kp, float* theta, int V, void* ws, size_t ws_bytes, void* stream) {
+    const SmModel m = {v_template, shapedirs, posedirs, Jt, Jd, lbs_weights, Q};
     const bool pair = theta_b != nullptr;
     MBX_CHECK_ARG(n >= 0 && T >= 1 && (long long)n * T * (pair ? 2 : 1) <= (1 << 20),
                   "wild_mesh: bad sizes n=%d T=%d (T >= 1, n T <= 2^20, 2 n T with pass B)", n, T);
@@ -898,22 +851,17 @@ extern "C" int mbx_wild_mesh(const float* v_template, const float* shapedirs, co
     MBX_CHECK_ARG(dst_frames && rotmat_a && betas_a, "wild_mesh: null pointer (dst_frames, rotmat_a, betas_a)");
     MBX_CHECK_ARG(!theta || theta_a, "wild_mesh: theta needs theta_a");
     const bool body = verts || kp;
-    MBX_CHECK_ARG(!body || (v_template && shapedirs && posedirs && Jt && Jd && lbs_weights), "wild_mesh: null pointer (model arrays)");
+    MBX_CHECK_ARG(!body || sm_model_set(m), "wild_mesh: null pointer (model arrays)");
     MBX_CHECK_ARG(!kp || (Q && K >= 1), "wild_mesh: kp needs a regressor Q [K,V] with K >= 1");
     MBX_CHECK_ARG(!(body || pair) || ws, "wild_mesh: null workspace");
     const int Kv = kp ? K : 0;
     MBX_CHECK_ARG(!(body || pair) || ws_bytes >= mbx_wild_mesh_ws(nT, V, Kv, pair), "wild_mesh: workspace of %zu bytes, %zu needed", ws_bytes,
                   mbx_wild_mesh_ws(nT, V, Kv, pair));
-    MBX_CHECK_ARG((((uintptr_t)v_template | (uintptr_t)shapedirs | (uintptr_t)posedirs | (uintptr_t)Jt | (uintptr_t)Jd | (uintptr_t)lbs_weights |
-                    (uintptr_t)Q | (uintptr_t)rotmat_a | (uintptr_t)betas_a | (uintptr_t)theta_a | (uintptr_t)theta_b | (uintptr_t)dst_frames |
-                    (uintptr_t)verts | (uintptr_t)kp | (uintptr_t)theta) & 3) == 0 && ((uintptr_t)ws & 15) == 0,
-                  "wild_mesh: pointers must be 4-byte aligned, the workspace 16-byte aligned");
+    if (sm_check_align("wild_mesh", m, sm_or(rotmat_a, betas_a, theta_a, theta_b, dst_frames, verts, kp, theta), ws)) return 1;
     hipStream_t s = (hipStream_t)stream;
-    float* Aws = (float*)ws;
-    float* PFws = Aws + (size_t)FC * SM_A;
-    float* G = PFws + (size_t)FC * SM_PFS;
-    float* kpart = G + (size_t)FC * SM_A;
-    float* rot2 = pair ? Aws + mg_rot_offset(FC, V, Kv) : nullptr;
+    const SmWs w = sm_carve(ws, FC);
+    float* kpart = kp ? w.tail : nullptr;
+    float* rot2 = pair ? w.A + sm_fwd_floats(FC, V, Kv) : nullptr;
     float* betas2 = pair ? rot2 + (size_t)FC * 216 : nullptr;
     if (pair || theta) {
         hipLaunchKernelGGL(wild_mesh_prepare_kernel, dim3((nT + 3) / 4), dim3(256), 0, s, rotmat_a, betas_a, theta_a, theta_b, dst_frames, rot2,
@@ -922,28 +870,13 @@ extern "C" int mbx_wild_mesh(const float* v_template, const float* shapedirs, co
     }
     if (!body) return 0;
     const float* betas = pair ? betas2 : betas_a;
-    const float* rot = pair ? rot2 : rotmat_a;
-    hipLaunchKernelGGL(smpl_chain_fwd_kernel, dim3((FC + 63) / 64), dim3(64), 0, s, betas, rot, Jt, Jd, tree, scale, Aws, PFws, G, (float*)nullptr,
-                       FC);
-    MBX_LAUNCH_CHECK("wild_mesh (chain)");
-    const int nvt = sm_tiles(V);
-    const int per_wg = 4 * (pair ? SM_FW / 2 : SM_FW);
-    const dim3 grid(nvt, (nT + per_wg - 1) / per_wg);
-    if (pair)
-        hipLaunchKernelGGL(wild_mesh_verts_kernel<true>, grid, dim3(256), 0, s, v_template, shapedirs, posedirs, lbs_weights, Q, betas,
-                           (const float*)Aws, (const float*)PFws, scale, dst_frames, verts, kp ? kpart : (float*)nullptr, nT, T, F, V, Kv);
-    else
-        hipLaunchKernelGGL(wild_mesh_verts_kernel<false>, grid, dim3(256), 0, s, v_template, shapedirs, posedirs, lbs_weights, Q, betas,
-                           (const float*)Aws, (const float*)PFws, scale, dst_frames, verts, kp ? kpart : (float*)nullptr, nT, T, F, V, Kv);
-    MBX_LAUNCH_CHECK("wild_mesh (vertices)");
-    if (kp) {
-        const size_t cnt = (size_t)nT * 3 * K;
-        const dim3 g((unsigned)((cnt + 255) / 256));
-        if (pair)
-            hipLaunchKernelGGL(wild_mesh_kp_finish_kernel<true>, g, dim3(256), 0, s, (const float*)kpart, nvt, scale, dst_frames, kp, nT, T, F, 3 * K);
-        else
-            hipLaunchKernelGGL(wild_mesh_kp_finish_kernel<false>, g, dim3(256), 0, s, (const float*)kpart, nvt, scale, dst_frames, kp, nT, T, F, 3 * K);
-        MBX_LAUNCH_CHECK("wild_mesh (keypoints)");
+    if (sm_launch_chain("wild_mesh (chain)", s, m, tree, betas, pair ? rot2 : rotmat_a, scale, w, nullptr, FC)) return 1;
+    if (pair) {
+        if (sm_launch_verts<2, true>("wild_mesh (vertices)", s, m, betas, w, scale, verts, kpart, nT, V, Kv, dst_frames, T, F)) return 1;
+        if (kp && sm_launch_kp_finish<2, true>("wild_mesh (keypoints)", s, kpart, scale, kp, nT, V, K, dst_frames, T, F)) return 1;
+    } else {
+        if (sm_launch_verts<1, true>("wild_mesh (vertices)", s, m, betas, w, scale, verts, kpart, nT, V, Kv, dst_frames, T, F)) return 1;
+        if (kp && sm_launch_kp_finish<1, true>("wild_mesh (keypoints)", s, kpart, scale, kp, nT, V, K, dst_frames, T, F)) return 1;
     }
     return 0;
 }
@@ -952,38 +885,31 @@ extern "C" int mbx_smpl_bwd(const float* v_template, const float* shapedirs, con
                             const float* Jd, const int* parents, const float* lbs_weights, const float* Q, int K, const float* betas,
                             const float* rotmat, float scale, const float* dverts, const float* dkp, const float* djoints, float* drotmat,
                             float* dbetas, int F, int V, void* ws, size_t ws_bytes, void* stream) {
+    const SmModel m = {v_template, shapedirs, posedirs, Jt, Jd, lbs_weights, Q};
     MBX_CHECK_ARG(sm_dims_ok(F, V, K), "smpl_bwd: bad sizes F=%d V=%d K=%d (V >= 1, K <= 32)", F, V, K);
     SmplTree tree;
     if (sm_tree(parents, tree, "smpl_bwd")) return 1;
     if (F == 0) return 0;
-    MBX_CHECK_ARG(v_template && shapedirs && posedirs && packed_t && Jt && Jd && lbs_weights && betas && rotmat && drotmat && dbetas && ws,
-                  "smpl_bwd: null pointer");
+    MBX_CHECK_ARG(sm_model_set(m) && packed_t && betas && rotmat && drotmat && dbetas && ws, "smpl_bwd: null pointer");
     MBX_CHECK_ARG(!dkp || (Q && K >= 1), "smpl_bwd: dkp needs a regressor Q [K,V] with K >= 1");
     MBX_CHECK_ARG(ws_bytes >= mbx_smpl_bwd_ws(F, V, K), "smpl_bwd: workspace of %zu bytes, %zu needed", ws_bytes, mbx_smpl_bwd_ws(F, V, K));
     MBX_CHECK_ARG(drotmat != rotmat && dbetas != betas, "smpl_bwd: a gradient must not alias its input");
-    MBX_CHECK_ARG((((uintptr_t)v_template | (uintptr_t)shapedirs | (uintptr_t)posedirs | (uintptr_t)packed_t | (uintptr_t)Jt | (uintptr_t)Jd |
-                    (uintptr_t)lbs_weights | (uintptr_t)Q | (uintptr_t)betas | (uintptr_t)rotmat | (uintptr_t)dverts | (uintptr_t)dkp |
-                    (uintptr_t)djoints | (uintptr_t)drotmat | (uintptr_t)dbetas) & 3) == 0 && ((uintptr_t)ws & 15) == 0,
-                  "smpl_bwd: pointers must be 4-byte aligned, the workspace 16-byte aligned");
+    if (sm_check_align("smpl_bwd", m, sm_or(packed_t, betas, rotmat, dverts, dkp, djoints, drotmat, dbetas), ws)) return 1;
     hipStream_t s = (hipStream_t)stream;
     const int nvt = sm_tiles(V), S = sm_splits(V);
-    float* Aws = (float*)ws;
-    float* PFws = Aws + (size_t)F * SM_A;
-    float* G = PFws + (size_t)F * SM_PFS;
-    float* DJ = G + (size_t)F * SM_A;
+    const SmWs w = sm_carve(ws, F);
+    float* DJ = w.tail;
     float* part = DJ + (size_t)F * 72;
     float* sums = part + (size_t)S * F * SM_COLS;
-    hipLaunchKernelGGL(smpl_chain_fwd_kernel, dim3((F + 63) / 64), dim3(64), 0, s, betas, rotmat, Jt, Jd, tree, scale, Aws, PFws, G,
-                       (float*)nullptr, F);
-    MBX_LAUNCH_CHECK("smpl_bwd (chain)");
+    if (sm_launch_chain("smpl_bwd (chain)", s, m, tree, betas, rotmat, scale, w, nullptr, F)) return 1;
     hipLaunchKernelGGL(smpl_verts_bwd_kernel, dim3(S, (F + SM_BF - 1) / SM_BF), dim3(256), 0, s, v_template, shapedirs, posedirs, packed_t,
-                       lbs_weights, Q, betas, (const float*)Aws, (const float*)PFws, dverts, dkp, scale, part, F, V, dkp ? K : 0, nvt, S);
+                       lbs_weights, Q, betas, (const float*)w.A, (const float*)w.PF, dverts, dkp, scale, part, F, V, dkp ? K : 0, nvt, S);
     MBX_LAUNCH_CHECK("smpl_bwd (vertices)");
     const size_t n = (size_t)F * SM_COLS;
     hipLaunchKernelGGL(smpl_split_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)part, S, sums, n);
     MBX_LAUNCH_CHECK("smpl_bwd (split sum)");
-    hipLaunchKernelGGL(smpl_chain_bwd_kernel, dim3((F + 63) / 64), dim3(64), 0, s, betas, rotmat, Jt, Jd, tree, scale, (const float*)Aws,
-                       (const float*)sums, djoints, G, DJ, drotmat, dbetas, F);
+    hipLaunchKernelGGL(smpl_chain_bwd_kernel, dim3((F + 63) / 64), dim3(64), 0, s, betas, rotmat, Jt, Jd, tree, scale, (const float*)w.A,
+                       (const float*)sums, djoints, w.G, DJ, drotmat, dbetas, F);
     MBX_LAUNCH_CHECK("smpl_bwd (chain backward)");
     return 0;
 }

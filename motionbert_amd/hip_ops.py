@@ -960,7 +960,8 @@ class HipOps:
 
     # ------------------------------------------------------------------ SMPL body model (csrc/smpl.hip; motionbert_amd/smpl.py)
     def _smpl_model(self, what, m, need_packed):
-        """m: dict of the model tensors (smpl.SMPLModel.tensors()): checked dense f32 on one device; returns (V, device, host parents)"""
+        """m: dict of the model tensors (smpl.SMPLModel.tensors()): checked dense f32 on one device; returns (V, device, args) with args
+        the model's arguments in ABI order: v_template, shapedirs, posedirs[, packed_t], Jt, Jd, parents (host), lbs_weights; Q, K follow"""
         vt = m['v_template']
         if vt.dim() != 2 or vt.shape[1] != 3 or vt.shape[0] < 1:
             raise RuntimeError(f'libmbx: {what} needs v_template [V >= 1, 3], got {tuple(vt.shape)}')
@@ -978,7 +979,19 @@ class HipOps:
         parents = [int(p) for p in m['parents']]
         if len(parents) != 24:
             raise RuntimeError(f'libmbx: {what} needs 24 parents, got {len(parents)}')
-        return V, dev, (C.c_int * 24)(*parents)
+        packed = (_p(m['packed_t']),) if need_packed else ()
+        return V, dev, (_p(vt), _p(m['shapedirs']), _p(m['posedirs']), *packed, _p(m['Jt']), _p(m['Jd']), (C.c_int * 24)(*parents),
+                        _p(m['lbs_weights']))
+
+    @staticmethod
+    def _smpl_q(what, Q, V, need):
+        """the regressor Q [1 <= K <= 32, V] checked; returns K (0 without Q).  need: True where the entry cannot do without Q, else the name of
+        the argument that reads Q where that argument is given (false where it is not)"""
+        if need is True and Q is None or Q is not None and (Q.dim() != 2 or Q.shape[1] != V or not 1 <= Q.shape[0] <= 32):
+            raise RuntimeError(f'libmbx: {what} needs Q [1 <= K <= 32, {V}], got {None if Q is None else tuple(Q.shape)}')
+        if need and Q is None:
+            raise RuntimeError(f'libmbx: {what}: {need} needs the regressor Q')
+        return 0 if Q is None else Q.shape[0]
 
     @staticmethod
     def _smpl_frames(what, betas, rotmat):
@@ -1008,17 +1021,11 @@ class HipOps:
         """model: dict v_template [V,3], shapedirs [V,3,10], posedirs [207,3V], Jt [24,3], Jd [24,3,10], lbs_weights [V,24] f32 on the device
         and parents (24 host ints); Q [K,V] f32 or None; betas [F,10], rotmat [F,24,9] f32; outputs verts [F,V,3] / kp [F,K,3] /
         joints [F,24,3] f32, each may be None; ws: a uint8 workspace of smpl_fwd_ws(F, V, K with kp else 0) (allocated when None)."""
-        V, dev, parents = self._smpl_model('smpl_fwd', model, False)
+        V, dev, margs = self._smpl_model('smpl_fwd', model, False)
         F = self._smpl_frames('smpl_fwd', betas, rotmat)
         if verts is None and kp is None and joints is None:
             raise RuntimeError('libmbx: smpl_fwd: no output')
-        K = 0
-        if Q is not None:
-            if Q.dim() != 2 or Q.shape[1] != V or not 1 <= Q.shape[0] <= 32:
-                raise RuntimeError(f'libmbx: smpl_fwd needs Q [1 <= K <= 32, {V}], got {tuple(Q.shape)}')
-            K = Q.shape[0]
-        if kp is not None and Q is None:
-            raise RuntimeError('libmbx: smpl_fwd: kp needs the regressor Q')
+        K = self._smpl_q('smpl_fwd', Q, V, kp is not None and 'kp')
         self._dense('smpl_fwd', torch.float32, K * V, dev, Q=Q)
         self._dense('smpl_fwd', torch.float32, F * 10, dev, betas=betas)
         self._dense('smpl_fwd', torch.float32, F * 216, dev, rotmat=rotmat)
@@ -1028,22 +1035,15 @@ class HipOps:
         if ws is None:
             ws = self.smpl_fwd_ws(F, V, K if kp is not None else 0, dev)
         self._dense('smpl_fwd', torch.uint8, None, dev, ws=ws)
-        self._ck(self.lib.mbx_smpl_fwd(_p(model['v_template']), _p(model['shapedirs']), _p(model['posedirs']), _p(model['Jt']), _p(model['Jd']),
-                                       parents, _p(model['lbs_weights']), _p(Q), K, _p(betas), _p(rotmat), float(scale), _p(verts), _p(kp),
-                                       _p(joints), F, V, _p(ws), ws.numel(), self._stream()))
+        self._ck(self.lib.mbx_smpl_fwd(*margs, _p(Q), K, _p(betas), _p(rotmat), float(scale), _p(verts), _p(kp), _p(joints), F, V, _p(ws),
+                                       ws.numel(), self._stream()))
 
     def smpl_bwd(self, model, Q, betas, rotmat, scale, dverts, dkp, djoints, drotmat, dbetas, ws=None):
         """the cotangents dverts [F,V,3] / dkp [F,K,3] / djoints [F,24,3] (each may be None: zero) pulled back to drotmat [F,24,9] and
         dbetas [F,10]; model as smpl_fwd plus packed_t [3V,224]."""
-        V, dev, parents = self._smpl_model('smpl_bwd', model, True)
+        V, dev, margs = self._smpl_model('smpl_bwd', model, True)
         F = self._smpl_frames('smpl_bwd', betas, rotmat)
-        K = 0
-        if Q is not None:
-            if Q.dim() != 2 or Q.shape[1] != V or not 1 <= Q.shape[0] <= 32:
-                raise RuntimeError(f'libmbx: smpl_bwd needs Q [1 <= K <= 32, {V}], got {tuple(Q.shape)}')
-            K = Q.shape[0]
-        if dkp is not None and Q is None:
-            raise RuntimeError('libmbx: smpl_bwd: dkp needs the regressor Q')
+        K = self._smpl_q('smpl_bwd', Q, V, dkp is not None and 'dkp')
         if drotmat is None or dbetas is None:
             raise RuntimeError('libmbx: smpl_bwd: drotmat and dbetas are required')
         self._dense('smpl_bwd', torch.float32, K * V, dev, Q=Q)
@@ -1055,10 +1055,8 @@ class HipOps:
         if ws is None:
             ws = self.smpl_bwd_ws(F, V, K, dev)
         self._dense('smpl_bwd', torch.uint8, None, dev, ws=ws)
-        self._ck(self.lib.mbx_smpl_bwd(_p(model['v_template']), _p(model['shapedirs']), _p(model['posedirs']), _p(model['packed_t']),
-                                       _p(model['Jt']), _p(model['Jd']), parents, _p(model['lbs_weights']), _p(Q), K, _p(betas), _p(rotmat),
-                                       float(scale), _p(dverts), _p(dkp), _p(djoints), _p(drotmat), _p(dbetas), F, V, _p(ws), ws.numel(),
-                                       self._stream()))
+        self._ck(self.lib.mbx_smpl_bwd(*margs, _p(Q), K, _p(betas), _p(rotmat), float(scale), _p(dverts), _p(dkp), _p(djoints), _p(drotmat),
+                                       _p(dbetas), F, V, _p(ws), ws.numel(), self._stream()))
 
     # ------------------------------------------------------------------ mesh targets (csrc/smpl.hip; motionbert_amd/mesh.py: mesh_targets)
     def mesh_gt_ws(self, F, V, K, device):
@@ -1068,16 +1066,14 @@ class HipOps:
         """model, Q [K,V] as smpl_fwd takes them; pose [N,T,72], shape [N,T,10] f32, motion_2d [N,T,17,3] f32 or None; flips [N] u8 or None
         (then the flag of clip n is drawn from (seed, n) against flip_prob); outputs x2d [N,T,17,3] / theta [N,T,82] / kp_3d [N,T,K,3] /
         verts [N,T,V,3] f32 and flips_used [N] u8, each may be None; ws: a uint8 workspace of mesh_gt_ws(N T, V, K) (allocated when None)."""
-        V, dev, parents = self._smpl_model('mesh_gt', model, False)
+        V, dev, margs = self._smpl_model('mesh_gt', model, False)
         if pose.dim() != 3 or pose.shape[2] != 72 or pose.shape[1] < 1 or tuple(shape.shape) != tuple(pose.shape[:2]) + (10,):
             raise RuntimeError(f'libmbx: mesh_gt needs pose [N,T >= 1,72] and shape [N,T,10], got {tuple(pose.shape)} / {tuple(shape.shape)}')
         N, T = pose.shape[:2]
         F = N * T
         if x2d is None and theta is None and kp_3d is None and verts is None and flips_used is None:
             raise RuntimeError('libmbx: mesh_gt: no output')
-        if Q is None or Q.dim() != 2 or Q.shape[1] != V or not 1 <= Q.shape[0] <= 32:
-            raise RuntimeError(f'libmbx: mesh_gt needs Q [1 <= K <= 32, {V}], got {None if Q is None else tuple(Q.shape)}')
-        K = Q.shape[0]
+        K = self._smpl_q('mesh_gt', Q, V, True)
         if x2d is not None and motion_2d is None:
             raise RuntimeError('libmbx: mesh_gt: x2d needs motion_2d')
         self._dense('mesh_gt', torch.float32, K * V, dev, Q=Q)
@@ -1091,10 +1087,8 @@ class HipOps:
         if ws is None:
             ws = self.mesh_gt_ws(F, V, K, dev)
         self._dense('mesh_gt', torch.uint8, None, dev, ws=ws)
-        self._ck(self.lib.mbx_mesh_gt(_p(pose), _p(shape), _p(motion_2d), _p(flips), int(seed), float(flip_prob), _p(model['v_template']),
-                                      _p(model['shapedirs']), _p(model['posedirs']), _p(model['Jt']), _p(model['Jd']), parents,
-                                      _p(model['lbs_weights']), _p(Q), K, float(scale), _p(x2d), _p(theta), _p(kp_3d), _p(verts),
-                                      _p(flips_used), N, T, V, _p(ws), ws.numel(), self._stream()))
+        self._ck(self.lib.mbx_mesh_gt(_p(pose), _p(shape), _p(motion_2d), _p(flips), int(seed), float(flip_prob), *margs, _p(Q), K, float(scale),
+                                      _p(x2d), _p(theta), _p(kp_3d), _p(verts), _p(flips_used), N, T, V, _p(ws), ws.numel(), self._stream()))
 
     # ------------------------------------------------------------------ in-the-wild mesh recovery (infer_wild_mesh.py; csrc/smpl.hip, csrc/wild.hip)
     def wild_mesh_ws(self, nT, V, K, pair, device):
@@ -1105,7 +1099,7 @@ class HipOps:
         pass B: theta_b [nT,82] or None (single-pass mode); dst_frames [n] i32 on the device with nT = n T, dst_max its largest entry (host);
         outputs verts [F,V,3] / kp [F,K,3] / theta [F,82] f32, each may be None; ws: a uint8 workspace of wild_mesh_ws (allocated when
         None)."""
-        V, dev, parents = self._smpl_model('wild_mesh', model, False)
+        V, dev, margs = self._smpl_model('wild_mesh', model, False)
         nT = self._smpl_frames('wild_mesh', betas_a, rotmat_a)
         T = int(T)
         n = dst_frames.numel()
@@ -1114,13 +1108,7 @@ class HipOps:
         if verts is None and kp is None and theta is None:
             raise RuntimeError('libmbx: wild_mesh: no output')
         F = (verts if verts is not None else kp if kp is not None else theta).shape[0]
-        K = 0
-        if Q is not None:
-            if Q.dim() != 2 or Q.shape[1] != V or not 1 <= Q.shape[0] <= 32:
-                raise RuntimeError(f'libmbx: wild_mesh needs Q [1 <= K <= 32, {V}], got {tuple(Q.shape)}')
-            K = Q.shape[0]
-        if kp is not None and Q is None:
-            raise RuntimeError('libmbx: wild_mesh: kp needs the regressor Q')
+        K = self._smpl_q('wild_mesh', Q, V, kp is not None and 'kp')
         if theta is not None and theta_a is None:
             raise RuntimeError('libmbx: wild_mesh: theta needs theta_a')
         if n and not 0 <= int(dst_max) <= F - T:
@@ -1139,10 +1127,8 @@ class HipOps:
         if ws is None:
             ws = self.wild_mesh_ws(nT, V, K if kp is not None else 0, pair, dev)
         self._dense('wild_mesh', torch.uint8, None, dev, ws=ws)
-        self._ck(self.lib.mbx_wild_mesh(_p(model['v_template']), _p(model['shapedirs']), _p(model['posedirs']), _p(model['Jt']), _p(model['Jd']),
-                                        parents, _p(model['lbs_weights']), _p(Q), K, _p(rotmat_a), _p(betas_a), _p(theta_a), _p(theta_b),
-                                        float(scale), _p(dst_frames), int(dst_max), n, T, F, _p(verts), _p(kp), _p(theta), V, _p(ws), ws.numel(),
-                                        self._stream()))
+        self._ck(self.lib.mbx_wild_mesh(*margs, _p(Q), K, _p(rotmat_a), _p(betas_a), _p(theta_a), _p(theta_b), float(scale), _p(dst_frames),
+                                        int(dst_max), n, T, F, _p(verts), _p(kp), _p(theta), V, _p(ws), ws.numel(), self._stream()))
 
     def scale_fit(self, ref, kp, seq_ptr, fit):
         """ref [F,17,3] f64, kp [F,17,3] f32, seq_ptr [S+1] i32 -> fit [S,6] f64 = scale, t [3], objective, iterations (< 0: a status)"""
