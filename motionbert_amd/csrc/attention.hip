@@ -24,16 +24,20 @@
 // per lane and are read directly.  No transposed copies exist in LDS.
 // Short sequences (L <= 32: every spatial problem, temporal with T <= 32) run one problem per wave
 // with wave-private LDS, four problems per 256-thread workgroup; longer ones share the tiles across the
-// eight waves of a workgroup, one 32-row query (key) block per wave.  Kernel map:
-//   attn_fwd_kernel<T, HD, SHARED>        forward, both forms
-//   attn_fwd_ragged_kernel<T, HD, SHARED> forward, temporal, clips of different lengths from a table (the same per-problem body)
-//   attn_bwd_small_kernel<T, HD>          backward, L <= 32: dQ, dK, dV from tiles staged once per wave
-//   attn_bwd_fused_kernel<HD>             backward, bf16, 32 < L <= 256: ONE workgroup of 16 waves per problem, Q / K / V / dO
-//                                         staged once, dQ role (8 waves) and dK/dV role (8 waves) concurrently
-//   attn_bwd_dq_kernel / attn_bwd_dkv_kernel   backward, fp32 (tiles twice as large: the four of them do not fit one CU's
-//                                         LDS), dropout, and bf16 beyond the fused kernel's 160 KiB of LDS
-// Sequences longer than 256 run the streamed kernels of attention_stream.hip (K / V or Q / dO through an LDS ring); the device
-// helpers both files use are in attention_common.h.
+// eight waves of a workgroup, one 32-row query (key) block per wave.  Which kernel runs (every one for hd = 32 and 64):
+//   forward    L <= 32         attn_fwd_kernel<T, HD, SHARED = false, DROP>     any dtype, with or without dropout
+//              32 < L <= 256   attn_fwd_kernel<T, HD, SHARED = true, DROP>      the same
+//              ragged          attn_fwd_ragged_kernel<T, HD, SHARED>            temporal, clips of different lengths from a table (the same per-problem
+//                                                                               body); SHARED = the longest clip > 32; never dropout
+//   backward   L <= 32         attn_bwd_small_kernel<T, HD, DROP>               any dtype, with or without dropout: dQ, dK, dV from tiles staged once per
+//                                                                               wave; the row dots (bf16, no dropout) and the planes (fp32) are run-time forms
+//              32 < L <= 256   attn_bwd_fused_kernel<HD, STATS>                 bf16 without dropout: ONE workgroup of 16 waves per problem, Q / K / V / dO
+//                                                                               staged once, dQ role (8 waves) and dK/dV role (8 waves) concurrently;
+//                                                                               STATS = the row dots.  256 rows fit its 160 KiB of LDS (static_assert below)
+//                              attn_bwd_dq_kernel<T, HD, DROP> +                fp32 with or without dropout (tiles twice as large: the four of them do not
+//                              attn_bwd_dkv_kernel<T, HD, DROP>                 fit one CU's LDS), planes included, and bf16 with dropout.  No row dots
+//   L > 256: the streamed kernels of attention_stream.hip (K / V or Q / dO through an LDS ring), every form.
+// The device helpers and the (dtype, hd, dropout) dispatch both files use are in attention_common.h.
 // Outputs never leave a kernel in the accumulator layout (lane = row, 4 consecutive d per register quad: one store
 // instruction would touch 32 rows x 16 bytes).  They are staged through LDS tiles that are dead by then and copied out with
 // eight lanes per 128-byte row segment.
@@ -46,7 +50,6 @@ template <bool SHARED> struct AttnBlock { static constexpr int THREADS = SHARED 
 // the dK/dV kernel needs ~170 VGPRs (two 32x64 accumulators per lane besides the score fragments): eight waves per
 // workgroup would not raise its occupancy, and four waves with eight key blocks each measured faster
 constexpr int MBX_ATTN_KV_THREADS = 256;
-template <bool SHARED> struct AttnBlockKV { static constexpr int THREADS = SHARED ? MBX_ATTN_KV_THREADS : 256, WAVES = THREADS / 64; };
 
 
 // ================================================================================================
@@ -175,10 +178,7 @@ template <typename T, int HD, bool SHARED>
 __global__ __launch_bounds__(AttnBlock<SHARED>::THREADS, sizeof(T) == 2 ? 4 : 1) void attn_fwd_ragged_kernel(const T* __restrict__ qkv, T* __restrict__ o,
                                                        float* __restrict__ lse, const int* __restrict__ clip_tab, int F, int max_len, int J, int H,
                                                        float scale, int nprob, int KP) {
-    MbxDrop dr;
-    dr.seed_lo = dr.seed_hi = dr.thresh = 0u;
-    dr.scale = 1.0f;
-    attn_fwd_body<T, HD, SHARED, false>(qkv, o, lse, H, scale, nprob, KP, dr, [=](int prob, bool& pvalid) {
+    attn_fwd_body<T, HD, SHARED, false>(qkv, o, lse, H, scale, nprob, KP, MbxDrop::off(), [=](int prob, bool& pvalid) {
         Prob P;
         P.h = prob % H;
         const int rest = prob / H, j = rest % J, b = rest / J;
@@ -194,10 +194,10 @@ __global__ __launch_bounds__(AttnBlock<SHARED>::THREADS, sizeof(T) == 2 ? 4 : 1)
 }
 
 // ================================================================================================
-// backward, part 1: dQ   (lane = query)
+// backward, part 1: dQ   (lane = query).  This and part 2: 32 < L <= 256, one problem's tiles shared by the workgroup
 // ================================================================================================
-template <typename T, int HD, bool SHARED, bool DROP = false>
-__global__ __launch_bounds__(AttnBlock<SHARED>::THREADS, (SHARED && sizeof(T) == 2 && !DROP) ? 4 : 1) void attn_bwd_dq_kernel(const T* __restrict__ qkv, const T* __restrict__ o,
+template <typename T, int HD, bool DROP>
+__global__ __launch_bounds__(AttnBlock<true>::THREADS, 1) void attn_bwd_dq_kernel(const T* __restrict__ qkv, const T* __restrict__ o,
                                                           const T* __restrict__ d_o, const float* __restrict__ lse,
                                                           T* __restrict__ dqkv, int Tn, int J, int H, float scale, int mode,
                                                           int nprob, int KP, MbxDrop dr, bf16_t* __restrict__ dq_lo) {
@@ -206,21 +206,19 @@ __global__ __launch_bounds__(AttnBlock<SHARED>::THREADS, (SHARED && sizeof(T) ==
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 5;
     const int C = H * HD, C3 = 3 * C;
-    const int per_prob = 2 * KP * RSTR;
-    int prob = SHARED ? (int)blockIdx.x : (int)blockIdx.x * 4 + wave;
+    int prob = (int)blockIdx.x;
     const bool pvalid = prob < nprob;
     prob = min(prob, nprob - 1);
     const Prob P = decode_prob(prob, mode, Tn, J, H);
-    const int gtid = SHARED ? tid : lane, gsize = SHARED ? AttnBlock<SHARED>::THREADS : 64;
-    char* kt = smem + (SHARED ? 0 : wave * per_prob);
+    char* kt = smem;
     char* vt = kt + KP * RSTR;
     const size_t rstride = (size_t)P.tstep * C3;
     const T* base = qkv + P.tok0 * C3 + (size_t)P.h * HD;
-    fill_two<T, HD>(kt, base + C, rstride, vt, base + 2 * C, rstride, RSTR, P.L, KP, gtid, gsize);
+    fill_two<T, HD>(kt, base + C, rstride, vt, base + 2 * C, rstride, RSTR, P.L, KP, tid, AttnBlock<true>::THREADS);
     __syncthreads();
 
     const int nfr = (P.L + 31) / 32;
-    for (int qb = SHARED ? wave : 0; qb < nfr; qb += SHARED ? AttnBlock<SHARED>::WAVES : 1) {
+    for (int qb = wave; qb < nfr; qb += AttnBlock<true>::WAVES) {
         const int q = qb * 32 + (lane & 31);
         const bool qvalid = pvalid && q < P.L;
         const size_t tok = P.tok0 + (size_t)min(q, P.L - 1) * P.tstep;
@@ -266,8 +264,8 @@ __global__ __launch_bounds__(AttnBlock<SHARED>::THREADS, (SHARED && sizeof(T) ==
 // ================================================================================================
 // backward, part 2: dK, dV   (lane = key)
 // ================================================================================================
-template <typename T, int HD, bool SHARED, bool DROP = false>
-__global__ __launch_bounds__(AttnBlockKV<SHARED>::THREADS, (SHARED && !DROP) ? 2 : 1) void attn_bwd_dkv_kernel(const T* __restrict__ qkv, const T* __restrict__ o,
+template <typename T, int HD, bool DROP>
+__global__ __launch_bounds__(MBX_ATTN_KV_THREADS, DROP ? 1 : 2) void attn_bwd_dkv_kernel(const T* __restrict__ qkv, const T* __restrict__ o,
                                                            const T* __restrict__ d_o, const float* __restrict__ lse,
                                                            T* __restrict__ dqkv, int Tn, int J, int H, float scale, int mode,
                                                            int nprob, int KP, MbxDrop dr, bf16_t* __restrict__ dq_lo) {
@@ -276,13 +274,11 @@ __global__ __launch_bounds__(AttnBlockKV<SHARED>::THREADS, (SHARED && !DROP) ? 2
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 5;
     const int C = H * HD, C3 = 3 * C;
-    const int per_prob = 2 * KP * RSTR + 2 * KP * 4;
-    int prob = SHARED ? (int)blockIdx.x : (int)blockIdx.x * 4 + wave;
+    int prob = (int)blockIdx.x;
     const bool pvalid = prob < nprob;
     prob = min(prob, nprob - 1);
     const Prob P = decode_prob(prob, mode, Tn, J, H);
-    const int gtid = SHARED ? tid : lane, gsize = SHARED ? AttnBlockKV<SHARED>::THREADS : 64;
-    char* qt = smem + (SHARED ? 0 : wave * per_prob);   // Q   [KP][hd]
+    char* qt = smem;                                      // Q   [KP][hd]
     char* dot_ = qt + KP * RSTR;                          // dO  [KP][hd]
     float* lse_s = reinterpret_cast<float*>(dot_ + KP * RSTR);
     float* del_s = lse_s + KP;
@@ -290,11 +286,11 @@ __global__ __launch_bounds__(AttnBlockKV<SHARED>::THREADS, (SHARED && !DROP) ? 2
     const T* qbase = qkv + P.tok0 * C3 + (size_t)P.h * HD;
     const T* dobase = d_o + P.tok0 * C + (size_t)P.h * HD;
     const T* obase = o + P.tok0 * C + (size_t)P.h * HD;
-    fill_two<T, HD>(qt, qbase, rstride, dot_, dobase, ostride, RSTR, P.L, KP, gtid, gsize);
-    // per-query statistics: lse and delta = sum_d dO*O.  KP <= gsize: one row per thread, all 2*HD/4 (8) vector
+    fill_two<T, HD>(qt, qbase, rstride, dot_, dobase, ostride, RSTR, P.L, KP, tid, MBX_ATTN_KV_THREADS);
+    // per-query statistics: lse and delta = sum_d dO*O.  KP <= the workgroup's threads: one row per thread, all 2*HD/4 (8) vector
     // loads of the row in flight together.
     {
-        const int q = gtid;
+        const int q = tid;
         if (q < KP) {
             float l = 0.f, dl = 0.f;
             if (q < P.L) {
@@ -316,7 +312,7 @@ __global__ __launch_bounds__(AttnBlockKV<SHARED>::THREADS, (SHARED && !DROP) ? 2
 
     const int nfr = (P.L + 31) / 32;
     const float c2 = scale * 1.44269504088896341f;
-    for (int kb = SHARED ? wave : 0; kb < nfr; kb += SHARED ? AttnBlockKV<SHARED>::WAVES : 1) {
+    for (int kb = wave; kb < nfr; kb += MBX_ATTN_KV_THREADS / 64) {
         const int key = kb * 32 + (lane & 31);
         const bool kvalid = pvalid && key < P.L;
         const size_t tok = P.tok0 + (size_t)min(key, P.L - 1) * P.tstep;
@@ -870,24 +866,19 @@ static int check_attn_args(const char* who, int B, int T, int J, int H, int hd, 
 // p in [0, 1): 0 = no dropout (the kernels without the mask code)
 static int make_drop(const char* who, float p, uint64_t seed, MbxDrop& dr) {
     MBX_CHECK_ARG(p >= 0.f && p < 1.f, "%s: dropout rate %g outside [0, 1)", who, (double)p);
-    dr.seed_lo = (uint32_t)seed;
-    dr.seed_hi = (uint32_t)(seed >> 32);
-    dr.thresh = p > 0.f ? (uint32_t)fminf(p * 4294967296.0f, 4294967295.0f) : 0u;
-    dr.scale = p > 0.f ? 1.0f / (1.0f - p) : 1.0f;
+    dr = p > 0.f ? MbxDrop{(uint32_t)seed, (uint32_t)(seed >> 32), drop_thresh(p), 1.0f / (1.0f - p)} : MbxDrop::off();
     return 0;
 }
 
-template <typename T, int HD, bool SHARED, bool DROP>
-static int launch_fwd(const void* qkv, void* o, float* lse, int Tn, int J, int H, float scale, int mode, int nprob, int KP, hipStream_t s,
-                      const MbxDrop& dr) {
-    constexpr bool IS_BF = sizeof(T) == 2;
-    const size_t per = (size_t)2 * KP * rm_stride<T>(HD);
-    const size_t shm = SHARED ? per : 4 * per;
-    auto kern = attn_fwd_kernel<T, HD, SHARED, DROP>;
-    if (set_lds(kern, shm, "attn_fwd")) return 1;
-    const int grid = SHARED ? nprob : (nprob + 3) / 4;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(AttnBlock<SHARED>::THREADS), shm, s, (const T*)qkv, (T*)o, lse, Tn, J, H, scale, mode, nprob, KP, dr);
-    MBX_LAUNCH_CHECK("attn_fwd");
+// Either forward kernel (`args`: its arguments) in either form: wave-private tiles, four problems per workgroup of four waves, or one
+// problem's tiles shared by the eight waves of a workgroup.
+template <typename T, int HD, typename K, typename... Args>
+static int launch_fwd(K kern, const char* who, bool shared, int nprob, int KP, hipStream_t s, Args... args) {
+    const size_t per = (size_t)2 * KP * rm_stride<T>(HD), shm = shared ? per : 4 * per;
+    if (set_lds(kern, shm, who)) return 1;
+    const int grid = shared ? nprob : (nprob + 3) / 4, threads = shared ? AttnBlock<true>::THREADS : AttnBlock<false>::THREADS;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), shm, s, args...);
+    MBX_LAUNCH_CHECK(who);
     return 0;
 }
 
@@ -902,27 +893,11 @@ static int attn_fwd_impl(const void* qkv, void* o, float* lse, int B, int T, int
     const int KP = ((L + 31) / 32) * 32;
     const bool shared = KP > 32;
     hipStream_t s = (hipStream_t)stream;
-#define MBX_FWD2(TT, HDV, DR)                                                                        \
-    (shared ? launch_fwd<TT, HDV, true, DR>(qkv, o, lse, T, J, H, scale, mode, nprob, KP, s, dr)       \
-            : launch_fwd<TT, HDV, false, DR>(qkv, o, lse, T, J, H, scale, mode, nprob, KP, s, dr))
-#define MBX_FWD(TT, HDV) (dr.thresh ? MBX_FWD2(TT, HDV, true) : MBX_FWD2(TT, HDV, false))
-    if (dtype == MBX_BF16) return hd == 64 ? MBX_FWD(bf16_t, 64) : MBX_FWD(bf16_t, 32);
-    return hd == 64 ? MBX_FWD(float, 64) : MBX_FWD(float, 32);
-#undef MBX_FWD
-#undef MBX_FWD2
-}
-template <typename T, int HD, bool SHARED>
-static int launch_fwd_ragged(const void* qkv, void* o, float* lse, const int* clip_tab, int F, int max_len, int J, int H, float scale,
-                             int nprob, int KP, hipStream_t s) {
-    const size_t per = (size_t)2 * KP * rm_stride<T>(HD);
-    const size_t shm = SHARED ? per : 4 * per;
-    auto kern = attn_fwd_ragged_kernel<T, HD, SHARED>;
-    if (set_lds(kern, shm, "attn_fwd_ragged")) return 1;
-    const int grid = SHARED ? nprob : (nprob + 3) / 4;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(AttnBlock<SHARED>::THREADS), shm, s, (const T*)qkv, (T*)o, lse, clip_tab, F, max_len, J, H, scale,
-                       nprob, KP);
-    MBX_LAUNCH_CHECK("attn_fwd_ragged");
-    return 0;
+    return dispatch_attn(dtype, hd, dr.thresh != 0, [&](auto tag) {
+        using E = typename decltype(tag)::type;
+        auto kern = shared ? attn_fwd_kernel<E, tag.HD, true, tag.DROP> : attn_fwd_kernel<E, tag.HD, false, tag.DROP>;
+        return launch_fwd<E, tag.HD>(kern, "attn_fwd", shared, nprob, KP, s, (const E*)qkv, (E*)o, lse, T, J, H, scale, mode, nprob, KP, dr);
+    });
 }
 // temporal attention of a ragged batch (mbx.h): per clip the problems, the fragment walk and the arithmetic of mbx_attn_fwd(B = 1, T = frames)
 extern "C" int mbx_attn_fwd_ragged(const void* qkv, void* o, float* lse, const int* clip_tab, int n_clips, int F, int max_len, int J, int H,
@@ -938,19 +913,18 @@ extern "C" int mbx_attn_fwd_ragged(const void* qkv, void* o, float* lse, const i
     MBX_CHECK_ARG((long long)n_clips * J * H < (1ll << 31) - 4, "attn_fwd_ragged: %d clips x %d joints x %d heads exceed 2^31 problems", n_clips, J, H);
     const int nprob = n_clips * J * H;
     const int KP = ((max_len + 31) / 32) * 32;
+    const bool shared = KP > 32;
     hipStream_t s = (hipStream_t)stream;
-#define MBX_FWDR(TT, HDV)                                                                                            \
-    (KP > 32 ? launch_fwd_ragged<TT, HDV, true>(qkv, o, lse, clip_tab, F, max_len, J, H, scale, nprob, KP, s)        \
-             : launch_fwd_ragged<TT, HDV, false>(qkv, o, lse, clip_tab, F, max_len, J, H, scale, nprob, KP, s))
-    if (dtype == MBX_BF16) return hd == 64 ? MBX_FWDR(bf16_t, 64) : MBX_FWDR(bf16_t, 32);
-    return hd == 64 ? MBX_FWDR(float, 64) : MBX_FWDR(float, 32);
-#undef MBX_FWDR
+    return dispatch_attn_type<false>(dtype, hd, [&](auto tag) {      // no dropout: inference
+        using E = typename decltype(tag)::type;
+        auto kern = shared ? attn_fwd_ragged_kernel<E, tag.HD, true> : attn_fwd_ragged_kernel<E, tag.HD, false>;
+        return launch_fwd<E, tag.HD>(kern, "attn_fwd_ragged", shared, nprob, KP, s, (const E*)qkv, (E*)o, lse, clip_tab, F, max_len, J, H, scale,
+                                     nprob, KP);
+    });
 }
 extern "C" int mbx_attn_fwd(const void* qkv, void* o, float* lse, int B, int T, int J, int H, int hd, float scale, int mode,
                             int dtype, void* stream) {
-    MbxDrop dr;
-    make_drop("attn_fwd", 0.f, 0, dr);
-    return attn_fwd_impl(qkv, o, lse, B, T, J, H, hd, scale, mode, dtype, stream, dr);
+    return attn_fwd_impl(qkv, o, lse, B, T, J, H, hd, scale, mode, dtype, stream, MbxDrop::off());
 }
 // mbx_attn_fwd with nn.Dropout(p) on the probabilities (DSTformer.py:96,182,196): o = (mask P / (1 - p)) V, lse of the undropped
 // softmax; the mask is dropmask.keep(flat index in the reference's attn tensor, p, seed)
@@ -961,24 +935,26 @@ extern "C" int mbx_attn_fwd_drop(const void* qkv, void* o, float* lse, int B, in
     return attn_fwd_impl(qkv, o, lse, B, T, J, H, hd, scale, mode, dtype, stream, dr);
 }
 
-template <typename T, int HD, bool SHARED, bool DROP>
+// the dQ + dK/dV pair, 32 < L <= 256: one workgroup per problem in both
+template <typename T, int HD, bool DROP>
 static int launch_bwd(const void* qkv, const void* o, const void* d_o, const float* lse, void* dqkv, int Tn, int J, int H,
                       float scale, int mode, int nprob, int KP, hipStream_t s, const MbxDrop& dr, void* dq_lo) {
-    constexpr bool IS_BF = sizeof(T) == 2;
     const int RSTR = rm_stride<T>(HD);
-    const size_t per_dq = (size_t)2 * KP * RSTR;
-    const size_t per_dkv = (size_t)2 * KP * RSTR + 2 * KP * 4;
-    const int grid = SHARED ? nprob : (nprob + 3) / 4;
-    auto k1 = attn_bwd_dq_kernel<T, HD, SHARED, DROP>;
-    auto k2 = attn_bwd_dkv_kernel<T, HD, SHARED, DROP>;
-    const size_t shm1 = SHARED ? per_dq : 4 * per_dq, shm2 = SHARED ? per_dkv : 4 * per_dkv;
+    const size_t shm1 = (size_t)2 * KP * RSTR, shm2 = shm1 + 2 * KP * 4;
+    auto k1 = attn_bwd_dq_kernel<T, HD, DROP>;
+    auto k2 = attn_bwd_dkv_kernel<T, HD, DROP>;
     if (set_lds(k1, shm1, "attn_bwd_dq") || set_lds(k2, shm2, "attn_bwd_dkv")) return 1;
-    hipLaunchKernelGGL(k1, dim3(grid), dim3(AttnBlock<SHARED>::THREADS), shm1, s, (const T*)qkv, (const T*)o, (const T*)d_o, lse, (T*)dqkv, Tn, J, H, scale, mode, nprob, KP, dr, (bf16_t*)dq_lo);
+    hipLaunchKernelGGL(k1, dim3(nprob), dim3(AttnBlock<true>::THREADS), shm1, s, (const T*)qkv, (const T*)o, (const T*)d_o, lse, (T*)dqkv, Tn, J, H, scale, mode, nprob, KP, dr, (bf16_t*)dq_lo);
     MBX_LAUNCH_CHECK("attn_bwd_dq");
-    hipLaunchKernelGGL(k2, dim3(grid), dim3(AttnBlockKV<SHARED>::THREADS), shm2, s, (const T*)qkv, (const T*)o, (const T*)d_o, lse, (T*)dqkv, Tn, J, H, scale, mode, nprob, KP, dr, (bf16_t*)dq_lo);
+    hipLaunchKernelGGL(k2, dim3(nprob), dim3(MBX_ATTN_KV_THREADS), shm2, s, (const T*)qkv, (const T*)o, (const T*)d_o, lse, (T*)dqkv, Tn, J, H, scale, mode, nprob, KP, dr, (bf16_t*)dq_lo);
     MBX_LAUNCH_CHECK("attn_bwd_dkv");
     return 0;
 }
+
+// LDS of attn_bwd_fused_kernel: the four [KP][hd] bf16 tiles, lse and delta, the row-dot vectors (stats variant).  It runs L <= 256 only, and
+// that always fits: there is no other bf16 backward without dropout for 32 < L <= 256, with or without the row dots.
+constexpr size_t attn_fused_lds(int KP, int hd) { return (size_t)4 * KP * rm_stride<bf16_t>(hd) + 2 * KP * 4 + 3 * hd * 4; }
+static_assert(attn_fused_lds(256, 32) <= 160 * 1024 && attn_fused_lds(256, 64) <= 160 * 1024, "attn_bwd_fused_kernel: a 256-row problem must fit the LDS");
 
 #ifdef MBX_ATTN_TRACE   // (1024 threads = ATTN_TRACE_WAVES waves per problem)
 #define MBX_ATTN_TRACE_SET(s_) mbx_diag_arm(HIP_SYMBOL(g_attn_trace), (size_t)nprob * (ATTN_TRACE_SLOTS + ATTN_TRACE_WAVES) * sizeof(long long), (s_))
@@ -1000,56 +976,40 @@ static int attn_bwd_impl(const void* qkv, const void* o, const void* d_o, const 
     const int KP = ((L + 31) / 32) * 32;
     const bool shared = KP > 32;
     hipStream_t s = (hipStream_t)stream;
-    if (shared && dtype == MBX_BF16 && !dr.thresh) {   // dropout: the dQ + dK/dV pair below (this kernel sits at its 128-VGPR budget: the mask hash spills)
-        const size_t shm = (size_t)4 * KP * rm_stride<bf16_t>(hd) + 2 * KP * 4 + 3 * hd * 4;      // + the row-dot vectors (stats variant)
-        if (shm <= 160 * 1024) {
-#define MBX_BWD_FUSED(HDV)                                                                                            \
-    do {                                                                                                              \
-        auto k = st_part ? attn_bwd_fused_kernel<HDV, true> : attn_bwd_fused_kernel<HDV, false>;                     \
-        if (set_lds(k, shm, "attn_bwd_fused")) return 1;                                                              \
-        MBX_ATTN_TRACE_SET(s);                                                                                        \
-        hipLaunchKernelGGL(k, dim3(nprob), dim3(1024), shm, s, (const bf16_t*)qkv, (const bf16_t*)o, (const bf16_t*)d_o, lse, \
-                           (bf16_t*)dqkv, T, J, H, scale, mode, nprob, KP, st_bias, st_rsum, st_part);                \
-        MBX_LAUNCH_CHECK("attn_bwd_fused");                                                                           \
-        return 0;                                                                                                     \
-    } while (0)
-            if (hd == 64) MBX_BWD_FUSED(64); else MBX_BWD_FUSED(32);
-#undef MBX_BWD_FUSED
-        }
-    }
-    if (!shared) {
-#define MBX_BWD_SMALL2(TT, HDV, DR)                                                                                   \
-    do {                                                                                                              \
-        const size_t shm = (size_t)4 * (4 * 32 * rm_stride<TT>(HDV) + 2 * 32 * 4);                                    \
-        auto k = attn_bwd_small_kernel<TT, HDV, DR>;                                                                  \
-        if (set_lds(k, shm, "attn_bwd_small")) return 1;                                                              \
-        hipLaunchKernelGGL(k, dim3((nprob + 3) / 4), dim3(256), shm, s, (const TT*)qkv, (const TT*)o, (const TT*)d_o, lse, \
-                           (TT*)dqkv, T, J, H, scale, mode, nprob, st_bias, st_rsum, st_part, dr, (bf16_t*)dq_lo);   \
-        MBX_LAUNCH_CHECK("attn_bwd_small");                                                                           \
-        return 0;                                                                                                     \
-    } while (0)
-#define MBX_BWD_SMALL(TT, HDV) do { if (dr.thresh) MBX_BWD_SMALL2(TT, HDV, true); else MBX_BWD_SMALL2(TT, HDV, false); } while (0)
-        if (dtype == MBX_BF16) { if (hd == 64) MBX_BWD_SMALL(bf16_t, 64); else MBX_BWD_SMALL(bf16_t, 32); }
-        else { if (hd == 64) MBX_BWD_SMALL(float, 64); else MBX_BWD_SMALL(float, 32); }
-#undef MBX_BWD_SMALL
-#undef MBX_BWD_SMALL2
-    }
-    MBX_CHECK_ARG(!st_part, "attn_bwd_stats: this shape runs the two-kernel backward, which has no row-dot output");
-#define MBX_BWD2(TT, HDV, DR)                                                                                         \
-    (shared ? launch_bwd<TT, HDV, true, DR>(qkv, o, d_o, lse, dqkv, T, J, H, scale, mode, nprob, KP, s, dr, dq_lo)    \
-            : launch_bwd<TT, HDV, false, DR>(qkv, o, d_o, lse, dqkv, T, J, H, scale, mode, nprob, KP, s, dr, dq_lo))
-#define MBX_BWD(TT, HDV) (dr.thresh ? MBX_BWD2(TT, HDV, true) : MBX_BWD2(TT, HDV, false))
-    if (dtype == MBX_BF16) return hd == 64 ? MBX_BWD(bf16_t, 64) : MBX_BWD(bf16_t, 32);
-    return hd == 64 ? MBX_BWD(float, 64) : MBX_BWD(float, 32);
-#undef MBX_BWD
-#undef MBX_BWD2
+    if (!shared)      // L <= 32: one kernel, one problem per wave; every (dtype, head dim, dropout), the row dots (bf16) and the planes (fp32) inside it
+        return dispatch_attn(dtype, hd, dr.thresh != 0, [&](auto tag) {
+            using E = typename decltype(tag)::type;
+            const size_t shm = (size_t)4 * (4 * 32 * rm_stride<E>(tag.HD) + 2 * 32 * 4);
+            auto k = attn_bwd_small_kernel<E, tag.HD, tag.DROP>;
+            if (set_lds(k, shm, "attn_bwd_small")) return 1;
+            hipLaunchKernelGGL(k, dim3((nprob + 3) / 4), dim3(256), shm, s, (const E*)qkv, (const E*)o, (const E*)d_o, lse, (E*)dqkv, T, J, H, scale,
+                               mode, nprob, st_bias, st_rsum, st_part, dr, (bf16_t*)dq_lo);
+            MBX_LAUNCH_CHECK("attn_bwd_small");
+            return 0;
+        });
+    if (dtype == MBX_BF16 && !dr.thresh)      // bf16 without dropout: one kernel of sixteen waves per problem, STATS = the row dots
+        return dispatch_attn_hd<bf16_t, false>(hd, [&](auto tag) {
+            const size_t shm = attn_fused_lds(KP, tag.HD);
+            auto k = st_part ? attn_bwd_fused_kernel<tag.HD, true> : attn_bwd_fused_kernel<tag.HD, false>;
+            if (set_lds(k, shm, "attn_bwd_fused")) return 1;
+            MBX_ATTN_TRACE_SET(s);
+            hipLaunchKernelGGL(k, dim3(nprob), dim3(1024), shm, s, (const bf16_t*)qkv, (const bf16_t*)o, (const bf16_t*)d_o, lse, (bf16_t*)dqkv, T, J, H,
+                               scale, mode, nprob, KP, st_bias, st_rsum, st_part);
+            MBX_LAUNCH_CHECK("attn_bwd_fused");
+            return 0;
+        });
+    // What is left runs the dQ + dK/dV pair: fp32 (its four tiles do not fit one CU's LDS) and bf16 with dropout (the fused kernel sits at its
+    // 128-VGPR budget: the mask hash spills).  Never the row dots: they come with bf16 and without dropout (above).
+    auto pair = [&](auto tag) {
+        return launch_bwd<typename decltype(tag)::type, tag.HD, tag.DROP>(qkv, o, d_o, lse, dqkv, T, J, H, scale, mode, nprob, KP, s, dr, dq_lo);
+    };
+    if (dtype == MBX_BF16) return dispatch_attn_hd<bf16_t, true>(hd, pair);
+    return dr.thresh ? dispatch_attn_hd<float, true>(hd, pair) : dispatch_attn_hd<float, false>(hd, pair);
 }
 
 extern "C" int mbx_attn_bwd(const void* qkv, const void* o, const void* d_o, const float* lse, void* dqkv, int B, int T, int J,
                             int H, int hd, float scale, int mode, int dtype, void* stream) {
-    MbxDrop dr;
-    make_drop("attn_bwd", 0.f, 0, dr);
-    return attn_bwd_impl(qkv, o, d_o, lse, dqkv, B, T, J, H, hd, scale, mode, dtype, stream, nullptr, nullptr, nullptr, dr);
+    return attn_bwd_impl(qkv, o, d_o, lse, dqkv, B, T, J, H, hd, scale, mode, dtype, stream, nullptr, nullptr, nullptr, MbxDrop::off());
 }
 // fp32 kernels with dq / dk / dv written as the operand planes of the bf16x3 split (dqkv_hi, dqkv_lo bf16 [M, 3C]); p = 0: no dropout
 extern "C" int mbx_attn_bwd_planes(const void* qkv, const void* o, const void* d_o, const float* lse, void* dqkv_hi, void* dqkv_lo, int B,
@@ -1072,7 +1032,5 @@ extern "C" int mbx_attn_bwd_stats(const void* qkv, const void* o, const void* d_
                                   void* stream) {
     MBX_CHECK_ARG(bias_f && rsum && part, "attn_bwd_stats: null pointer");
     MBX_CHECK_ARG((reinterpret_cast<uintptr_t>(part) & 7) == 0, "attn_bwd_stats: part must be 8-byte aligned");
-    MbxDrop dr;
-    make_drop("attn_bwd_stats", 0.f, 0, dr);
-    return attn_bwd_impl(qkv, o, d_o, lse, dqkv, B, T, J, H, hd, scale, mode, MBX_BF16, stream, bias_f, rsum, part, dr);
+    return attn_bwd_impl(qkv, o, d_o, lse, dqkv, B, T, J, H, hd, scale, mode, MBX_BF16, stream, bias_f, rsum, part, MbxDrop::off());
 }

@@ -263,6 +263,20 @@ static int set_lds(K kernel, size_t bytes, const char* who) {
     return bytes > 64 * 1024 ? mbx_set_dyn_lds(reinterpret_cast<const void*>(kernel), bytes, who) : 0;
 }
 
+// runtime (dtype, head dim, dropout) -> compile-time, as dispatch_epi does for epilogues: f(AttnTag<T, HD, DROP>{}) and its return value.
+// The arguments were checked by the caller (check_attn_args).  A launcher whose kernel exists for fewer combinations fixes the other axes
+// itself and calls the narrower helper, so every instantiation is named where it is launched.
+template <typename T, int HD_, bool DROP_> struct AttnTag { typedef T type; static constexpr int HD = HD_; static constexpr bool DROP = DROP_; };
+template <typename T, bool DROP, class F> static inline int dispatch_attn_hd(int hd, F&& f) {
+    return hd == 64 ? f(AttnTag<T, 64, DROP>{}) : f(AttnTag<T, 32, DROP>{});
+}
+template <bool DROP, class F> static inline int dispatch_attn_type(int dtype, int hd, F&& f) {
+    return dtype == MBX_BF16 ? dispatch_attn_hd<bf16_t, DROP>(hd, f) : dispatch_attn_hd<float, DROP>(hd, f);
+}
+template <class F> static inline int dispatch_attn(int dtype, int hd, bool drop, F&& f) {
+    return drop ? dispatch_attn_type<true>(dtype, hd, f) : dispatch_attn_type<false>(dtype, hd, f);
+}
+
 // the streamed kernels for sequences longer than 256 (attention_stream.hip); arguments are checked by the callers in attention.hip
 int mbx_launch_attn_fwd_stream(const void* qkv, void* o, float* lse, int B, int T, int J, int H, int hd, float scale, int mode, int dtype,
                                hipStream_t s, const MbxDrop& dr);

@@ -452,20 +452,15 @@ int mbx_launch_attn_fwd_stream(const void* qkv, void* o, float* lse, int B, int 
     int nprob, nblk;
     if (stream_grid("attn_fwd", B, T, J, H, mode, nprob, nblk)) return 1;
     const dim3 grid((unsigned)(nprob * nblk)), block(MBX_STREAM_THREADS);
-#define MBX_FWD_S(TT, HDV, DR)                                                                                        \
-    do {                                                                                                              \
-        const size_t shm = (size_t)4 * MBX_STREAM_TILE * rm_stride<TT>(HDV);                                          \
-        auto k = attn_fwd_stream_kernel<TT, HDV, DR>;                                                                 \
-        if (set_lds(k, shm, "attn_fwd_stream")) return 1;                                                             \
-        hipLaunchKernelGGL(k, grid, block, shm, s, (const TT*)qkv, (TT*)o, lse, T, J, H, scale, mode, nblk, dr);      \
-        MBX_LAUNCH_CHECK("attn_fwd_stream");                                                                          \
-        return 0;                                                                                                     \
-    } while (0)
-#define MBX_FWD_S2(TT, HDV) do { if (dr.thresh) MBX_FWD_S(TT, HDV, true); else MBX_FWD_S(TT, HDV, false); } while (0)
-    if (dtype == MBX_BF16) { if (hd == 64) MBX_FWD_S2(bf16_t, 64); else MBX_FWD_S2(bf16_t, 32); }
-    else { if (hd == 64) MBX_FWD_S2(float, 64); else MBX_FWD_S2(float, 32); }
-#undef MBX_FWD_S2
-#undef MBX_FWD_S
+    return dispatch_attn(dtype, hd, dr.thresh != 0, [&](auto tag) {
+        using E = typename decltype(tag)::type;
+        const size_t shm = (size_t)4 * MBX_STREAM_TILE * rm_stride<E>(tag.HD);
+        auto k = attn_fwd_stream_kernel<E, tag.HD, tag.DROP>;
+        if (set_lds(k, shm, "attn_fwd_stream")) return 1;
+        hipLaunchKernelGGL(k, grid, block, shm, s, (const E*)qkv, (E*)o, lse, T, J, H, scale, mode, nblk, dr);
+        MBX_LAUNCH_CHECK("attn_fwd_stream");
+        return 0;
+    });
 }
 
 template <typename T, int HD, bool DROP, bool STATS>
@@ -494,12 +489,10 @@ int mbx_launch_attn_bwd_stream(const void* qkv, const void* o, const void* d_o, 
                                float* st_part, const MbxDrop& dr, void* dq_lo) {
     int nprob, nblk;
     if (stream_grid("attn_bwd", B, T, J, H, mode, nprob, nblk)) return 1;
-#define MBX_BWD_S(TT, HDV, DR, ST) \
-    launch_bwd_stream<TT, HDV, DR, ST>(qkv, o, d_o, lse, dqkv, T, J, H, scale, mode, nprob, nblk, s, dr, dq_lo, st_bias, st_rsum, st_part)
-    if (st_part) return hd == 64 ? MBX_BWD_S(bf16_t, 64, false, true) : MBX_BWD_S(bf16_t, 32, false, true);   // bf16, no dropout (attn_bwd_impl)
-#define MBX_BWD_S2(TT, HDV) (dr.thresh ? MBX_BWD_S(TT, HDV, true, false) : MBX_BWD_S(TT, HDV, false, false))
-    if (dtype == MBX_BF16) return hd == 64 ? MBX_BWD_S2(bf16_t, 64) : MBX_BWD_S2(bf16_t, 32);
-    return hd == 64 ? MBX_BWD_S2(float, 64) : MBX_BWD_S2(float, 32);
-#undef MBX_BWD_S2
-#undef MBX_BWD_S
+    auto launch = [&](auto tag, auto stats) {
+        return launch_bwd_stream<typename decltype(tag)::type, tag.HD, tag.DROP, stats.value>(qkv, o, d_o, lse, dqkv, T, J, H, scale, mode, nprob, nblk, s,
+                                                                                             dr, dq_lo, st_bias, st_rsum, st_part);
+    };
+    if (st_part) return dispatch_attn_hd<bf16_t, false>(hd, [&](auto tag) { return launch(tag, std::true_type{}); });   // bf16, no dropout (attn_bwd_impl)
+    return dispatch_attn(dtype, hd, dr.thresh != 0, [&](auto tag) { return launch(tag, std::false_type{}); });
 }

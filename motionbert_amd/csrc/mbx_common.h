@@ -173,7 +173,10 @@ __device__ __forceinline__ bool drop_keep(uint32_t seed_lo, uint32_t seed_hi, ui
 struct MbxDrop {
     uint32_t seed_lo, seed_hi, thresh;
     float scale;      // 1 / (1 - p)
+    static __host__ __device__ MbxDrop off() { return MbxDrop{0u, 0u, 0u, 1.0f}; }
 };
+// the `thresh` of drop_keep for rate p in [0, 1): p * 2^32, saturated; 0 keeps every element
+__host__ __device__ __forceinline__ uint32_t drop_thresh(float p) { return p > 0.f ? (uint32_t)fminf(p * 4294967296.0f, 4294967295.0f) : 0u; }
 
 // ---------------------------------------------------------------- activation math (fp32)
 __device__ __forceinline__ float gelu_erf(float u) { return 0.5f * u * (1.0f + erff(u * 0.70710678118654752440f)); }

@@ -447,7 +447,7 @@ extern "C" int mbx_adamw_step(float* p, const float* g, float* m, float* v, size
 __global__ __launch_bounds__(128) void pool_rep_fwd_kernel(const float* __restrict__ rep, float* __restrict__ pooled, int Mp, int T,
                                                            int J, int R, float p, uint32_t seed_lo, uint32_t seed_hi) {
     const int n = blockIdx.x / J, j = blockIdx.x % J;
-    const uint32_t thresh = p > 0.f ? (uint32_t)fminf(p * 4294967296.0f, 4294967295.0f) : 0u;
+    const uint32_t thresh = drop_thresh(p);
     const float keep_scale = p > 0.f ? 1.0f / (1.0f - p) : 1.0f;
     for (int c = threadIdx.x * 4; c < R; c += 128 * 4) {
         float a[4] = {0.f, 0.f, 0.f, 0.f};
@@ -484,7 +484,7 @@ template <typename T_>
 __global__ __launch_bounds__(256) void tanh_pool_bwd_kernel(const float* __restrict__ dpooled, const float* __restrict__ rep,
                                                             T_* __restrict__ dpre, size_t ntok, int Mp, int T, int J, int R, float p,
                                                             uint32_t seed_lo, uint32_t seed_hi) {
-    const uint32_t thresh = p > 0.f ? (uint32_t)fminf(p * 4294967296.0f, 4294967295.0f) : 0u;
+    const uint32_t thresh = drop_thresh(p);
     const float s = (p > 0.f ? 1.0f / (1.0f - p) : 1.0f) / (float)(Mp * T);
     const int r4 = R >> 2;
     const size_t total = ntok * r4;
@@ -538,12 +538,11 @@ extern "C" int mbx_tanh_pool_bwd(const float* dpooled, const float* rep, void* d
 __device__ __forceinline__ float keep_mul(float p, uint32_t thresh, uint32_t slo, uint32_t shi, uint64_t idx, float scale) {
     return (p > 0.f && !drop_keep(slo, shi, (uint32_t)idx, (uint32_t)(idx >> 32), thresh)) ? 0.f : scale;
 }
-__device__ __forceinline__ uint32_t p_thresh(float p) { return p > 0.f ? (uint32_t)fminf(p * 4294967296.0f, 4294967295.0f) : 0u; }
 
 template <typename T_>
 __global__ __launch_bounds__(256) void dropout_kernel(const T_* __restrict__ x, T_* __restrict__ y, size_t n4, float p, uint32_t slo,
                                                       uint32_t shi) {
-    const uint32_t th = p_thresh(p);
+    const uint32_t th = drop_thresh(p);
     const float sc = 1.0f / (1.0f - p);
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
         float v[4];
@@ -573,7 +572,7 @@ template <typename T_, int MODE>
 __global__ __launch_bounds__(256) void branch_drop_kernel(float* __restrict__ y, const float* __restrict__ x, T_* __restrict__ out_t,
                                                           size_t rows, int C, int rps, float p, uint32_t slo, uint32_t shi,
                                                           float pp, uint32_t plo, uint32_t phi) {
-    const uint32_t th = p_thresh(p), pth = p_thresh(pp);
+    const uint32_t th = drop_thresh(p), pth = drop_thresh(pp);
     const float sc = 1.0f / (1.0f - p), psc = 1.0f / (1.0f - pp);
     const int c4 = C >> 2;
     const size_t total = rows * c4;

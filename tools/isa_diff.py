@@ -1,10 +1,12 @@
 """Is the gfx950 device code of two builds of the kernel library the same, instruction for instruction?
 
-    python tools/isa_diff.py LIB_A LIB_B
+    python tools/isa_diff.py [--rename REGEX=REPL]... LIB_A LIB_B
 
 Unbundles both libraries (llvm-objdump --offloading), disassembles every gfx950 code object (llvm-objdump -d) and compares the two
 listings as plain text.  Prints an md5 per side and the symbols whose listings differ (with the number of differing lines); exit
-status 1 on any difference.  The acceptance check of a refactor: identical device code is unchanged speed by construction."""
+status 1 on any difference.  The acceptance check of a refactor: identical device code is unchanged speed by construction.
+--rename (re.sub on the symbol names of LIB_A, before the comparison) is for a refactor that changes a kernel's template parameters and
+with them its mangled name: the whole listings then differ, and the verdict is `identical per symbol`."""
 import difflib
 import glob
 import hashlib
@@ -42,20 +44,32 @@ def listing(lib):
         m = re.match(r'^[0-9a-f]+ <(.+)>:$', ln)
         if m:
             cur = syms.setdefault(m.group(1), [])
-        elif cur is not None and ln.strip():
+        elif ln.startswith(('== code object', 'Disassembly of section')):
+            cur = None      # the last symbol of a code object ends here, not at the next object's first symbol
+        elif cur is not None and ln.strip() and ln.strip() != '...':      # ('...': zero padding behind a code object's last symbol)
             cur.append(ln.split('//')[0].rstrip())      # per symbol: the instructions without their addresses (code that only moved is the same)
     return syms, text
 
 
 def main():
-    if len(sys.argv) != 3:
+    args, renames = sys.argv[1:], []
+    while len(args) > 1 and args[0] == '--rename':
+        renames.append(args[1].split('=', 1))
+        args = args[2:]
+    if len(args) != 2 or any(len(r) != 2 for r in renames):
         raise SystemExit(__doc__)
-    (sa, ta), (sb, tb) = listing(sys.argv[1]), listing(sys.argv[2])
-    for lib, t in ((sys.argv[1], ta), (sys.argv[2], tb)):
+    (sa, ta), (sb, tb) = listing(args[0]), listing(args[1])
+    for lib, t in ((args[0], ta), (args[1], tb)):
         print(f'{hashlib.md5(t.encode()).hexdigest()}  {lib}  ({len(t.splitlines())} lines)')
     if ta == tb:
         print('identical')
         return 0
+    for pat, repl in renames:
+        renamed = {re.sub(pat, repl, name): ins for name, ins in sa.items()}
+        if len(renamed) != len(sa):
+            raise SystemExit(f'--rename {pat}={repl} maps two symbols of LIB_A to one name')
+        sa = renamed
+    bad = 0
     for name in sorted(set(sa) | set(sb)):
         a, b = sa.get(name), sb.get(name)
         if a is None or b is None:
@@ -63,6 +77,10 @@ def main():
         elif a != b:
             n = sum(1 for d in difflib.unified_diff(a, b, n=0, lineterm='') if d[0] in '+-' and d[:3] not in ('+++', '---'))
             print(f'differs ({len(a)} / {len(b)} instructions, {n} lines of diff): {name}')
+        bad += a != b
+    if renames and not bad:
+        print(f'identical per symbol ({len(sb)} symbols, after the renames)')
+        return 0
     print('DIFFERENT')
     return 1
 
