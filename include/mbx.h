@@ -747,6 +747,42 @@ size_t mbx_render_raster_ws(int F, int Nf);
 int mbx_render_raster(const int* vq, const float* verts, const int* faces, int F, int V, int Nf, int size, int ss, float red, float green,
                       float blue, float alpha, unsigned char* rgb, int* face_id, int* depth, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- skeleton video frames (csrc/skeleton.hip; the view of lib/utils/vismo.py:246-285, motion2video_3d) -- mbx_version() >= 210 --------------
+ * The 3D-skeleton branch of render_and_save in fixed point: bones as capsules, joints as ringed discs, white background; matplotlib's panes,
+ * grid, tick labels and anti-aliasing are not drawn.  S = size ss samples per side (size <= MBX_RENDER_MAX_SIZE, ss 1 or 2).
+ * mbx_skeleton_project: x [F,J,3] f32 on the device (the X3D of infer_wild.py), view15 = 15 doubles in HOST memory: rows 0, 1 and 3 of the
+ * 4 x 4 matrix M of Axes3D.get_proj(), then u_lo, v_hi, inv_w (the left and upper end of the 2D window of the axes and 1 / its width)
+ * -> jq [F,J,2] i32 in 1/MBX_RENDER_SUB of a sample.  Per joint:
+ *   ax = x + 1.0f, ay = y + 1.0f in fp32 (pixel2world_vis_motion on the float32 motion; its factor 512 / 2 is exact); from here on float64,
+ *   every operation rounded on its own:  p = (-256 ax, -256 z, -256 ay), the plotted (-X, -Z, -Y);
+ *   U = ((M00 px + M01 py) + M02 pz) + M03, V from row 1 and W from row 3 likewise;  u = U / W, v = V / W;
+ *   xq = floor(((u - u_lo) inv_w) (16 S)),  yq = floor(((v_hi - v) inv_w) (16 S)): image x right with u, image y down with -v.
+ * A joint with a component that is not finite, with W <= 0 (or not finite), or with |xq| or |yq| > 2^18 gives 2^30 in both components.  One
+ * launch.  F = 0 is a no-op.  Refused: J outside [1, MBX_SKELETON_MAX_JOINTS], a view value that is not finite, size or ss out of range.
+ * mbx_skeleton_raster: jq [F,J,2] i32, bones [Nb,2] i32 (joint indices), colors [Nb,3] u8, radii r_line, r_out, r_in in 1/16 sample
+ * -> rgb [F,size,size,3] u8 and, where given, prim_id [F,S,S] i32 (-1 where empty); every element is written.
+ *   samples     sample (i,j) has its centre at s = (16 j + 8, 16 i + 8).
+ *   primitives  bone k with ends a = jq[bones[k][0]], b = jq[bones[k][1]] gives three, in the reference's plot order (Line3D artists are not
+ *               depth-sorted; later plots cover earlier ones): priority 3k the capsule dist(s, segment ab) <= r_line, 3k + 1 the marker at a,
+ *               3k + 2 the marker at b.  A bone with an index outside [0,J) or an end with |xq| or |yq| > 2^18 contributes nothing.
+ *   capsule     with d = b - a, p = s - a, t = p.d, dd = d.d, r = r_line:  t <= 0: |p|^2 <= r^2;  t >= dd: |s - b|^2 <= r^2;  otherwise
+ *               (px dy - py dx)^2 <= r^2 dd.  a = b is the disc.
+ *   marker      at c: the disc |s - c|^2 <= r_out^2, white where |s - c|^2 <= r_in^2, the bone's colour elsewhere.
+ *   winner      the covering primitive of highest priority: a maximum over a set, independent of any order.  No cover: background, 255.
+ *   ss = 2      pixel = (a + b + c + d + 2) >> 2 of its four samples' channels, in the same launch.
+ *   exactness   every comparison is an integer comparison without overflow: ends within 2^18 and sample centres within [8, 16 (4096 + 31) + 8]
+ *               keep every component of p, d and s - b below 2^19 + 2^10 in magnitude, so |p|^2, t, dd and |px dy - py dx| are below 2^40
+ *               (int64).  r <= MBX_SKELETON_MAX_RADIUS = 2^11 gives r^2 dd < 2^62.  A cross product of magnitude >= 2^31 has a square
+ *               >= 2^62 > r^2 dd and is rejected before squaring; below that its square is < 2^62.
+ * One launch, no workspace, no global atomics, every output element written once.  F = 0 is a no-op.  Refused: J outside
+ * [1, MBX_SKELETON_MAX_JOINTS], Nb outside [1, MBX_SKELETON_MAX_BONES], a radius outside [0, 2^11] or r_in > r_out, size or ss out of range. */
+#define MBX_SKELETON_MAX_JOINTS 32
+#define MBX_SKELETON_MAX_BONES 64
+#define MBX_SKELETON_MAX_RADIUS (1 << 11)
+int mbx_skeleton_project(const float* x, const double* view15, int F, int J, int size, int ss, int* jq, void* stream);
+int mbx_skeleton_raster(const int* jq, const int* bones, const unsigned char* colors, int F, int J, int Nb, int r_line, int r_out, int r_in,
+                        int size, int ss, unsigned char* rgb, int* prim_id, void* stream);
+
 /* ---- measurement aid (bench.py`roofline.sustained_mfma_tflops`; not part of the model) --------------------------------------------
  * The bf16 MFMA rate the part sustains under its power cap with nothing but v_mfma_f32_32x32x16_bf16 in the loop (pseudo-random
  * operands; n_wg workgroups of 4 waves, `iters` x 16 MFMAs per wave).  ws: >= mbx_mfma_probe_ws(n_wg) bytes = a float sink

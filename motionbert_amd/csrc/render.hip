@@ -13,18 +13,15 @@
 //                             of faces is complete.  Every lane owns a 2 x 2 quad of samples and keeps their four minimum keys
 //                             (depth << 32 | face) in registers: the winner is a minimum over a set, independent of any order.  The 64-bit
 //                             divide of the depth runs for covered samples only, as a reciprocal estimate with an exact integer correction.
-//                             The tile's colours go through LDS and leave as whole dwords where the image rows allow it.
-#include "mbx_common.h"
+//                             The tile's colours go through LDS and leave as whole dwords where the image rows allow it (render_tile.h).
+#include "render_tile.h"
 #include <math.h>
 
 #pragma clang fp contract(off)
 
-#define RD_SUB MBX_RENDER_SUB
 #define RD_ZQ MBX_RENDER_ZQ
 #define RD_GUARD (1 << 17)
 #define RD_OUTSIDE (1 << 30)          // what a non-finite or far-away coordinate projects to: outside the guard in x, y and z
-#define RD_TILE 32                    // samples per tile edge; a lane owns a 2 x 2 quad: 16 x 16 quads = RD_THREADS
-#define RD_THREADS 256
 #define RD_LIST 512                   // face records in LDS; consumed as soon as fewer than RD_THREADS slots are left
 #define RD_EMPTY_BOX 0x000000ffu      // tx0 = 255 > tx1 = 0: meets no tile
 #define RD_EMPTY_KEY 0x7fffffffffffffffull
@@ -197,7 +194,7 @@ __global__ __launch_bounds__(RD_THREADS) void render_tile_kernel(const int* __re
                                                                   int Nf, int V, int S, int size, int ss, int tiles, unsigned char* __restrict__ rgb,
                                                                   int* __restrict__ face_id, int* __restrict__ depth) {
     __shared__ RdRec list[RD_LIST];
-    __shared__ unsigned stage[RD_TILE * RD_TILE * 3 / 4];
+    __shared__ unsigned stage[RD_STAGE_WORDS];
     __shared__ int wave_count[RD_THREADS / MBX_WAVE];
     __shared__ int list_count;
     const int tid = threadIdx.x, lane = tid & (MBX_WAVE - 1), wave = tid / MBX_WAVE;
@@ -283,8 +280,6 @@ __global__ __launch_bounds__(RD_THREADS) void render_tile_kernel(const int* __re
     }
 
     // resolve: colours into the staging tile, the optional sample buffers straight out
-    const int PW = RD_TILE / ss;                                             // pixels per tile edge
-    unsigned char* st = (unsigned char*)stage;
     unsigned col[4];
     const uint2* frec = face_rec + (size_t)f * Nf;
 #pragma unroll
@@ -298,34 +293,7 @@ __global__ __launch_bounds__(RD_THREADS) void render_tile_kernel(const int* __re
             if (depth) depth[o] = (int)(best[s] >> 32);
         }
     }
-    if (ss == 2) {
-        unsigned char* p = st + (qy * PW + qx) * 3;
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-            p[c] = (unsigned char)(((col[0] >> 8 * c & 255u) + (col[1] >> 8 * c & 255u) + (col[2] >> 8 * c & 255u) + (col[3] >> 8 * c & 255u) + 2u) >> 2);
-    } else {
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            unsigned char* p = st + ((2 * qy + (s >> 1)) * PW + 2 * qx + (s & 1)) * 3;
-            p[0] = (unsigned char)(col[s] & 255u); p[1] = (unsigned char)(col[s] >> 8 & 255u); p[2] = (unsigned char)(col[s] >> 16 & 255u);
-        }
-    }
-    __syncthreads();
-    const int px0 = tx * PW, py0 = ty * PW;
-    const int pw = min(PW, size - px0), ph = min(PW, size - py0);            // the part of the tile inside the image (>= 1: the grid covers S)
-    unsigned char* out = rgb + ((size_t)f * size * size) * 3;
-    if (pw == PW && (size & 3) == 0 && ((uintptr_t)rgb & 3) == 0) {          // whole rows of 3 PW bytes at a 4-byte aligned address: dword stores
-        const int dpr = 3 * PW / 4;
-        for (int e = tid; e < ph * dpr; e += RD_THREADS) {
-            const int row = e / dpr, d = e % dpr;
-            *(unsigned*)(out + ((size_t)(py0 + row) * size + px0) * 3 + 4 * d) = stage[row * dpr + d];
-        }
-    } else {
-        for (int e = tid; e < ph * pw * 3; e += RD_THREADS) {
-            const int row = e / (pw * 3), b = e % (pw * 3);
-            out[((size_t)(py0 + row) * size + px0) * 3 + b] = st[row * PW * 3 + b];
-        }
-    }
+    rd_store_tile(col, stage, tid, qx, qy, tx, ty, f, size, ss, rgb);
 }
 
 extern "C" size_t mbx_render_raster_ws(int F, int Nf) {

@@ -132,6 +132,8 @@ SIGNATURES = {
     'mbx_render_project': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     'mbx_render_raster_ws': (_sz, [_i, _i]),
     'mbx_render_raster': (_i, [_vp, _vp, _vp] + [_i] * 5 + [_f] * 4 + [_vp, _vp, _vp, _vp, _sz, _vp]),
+    'mbx_skeleton_project': (_i, [_vp, C.POINTER(C.c_double), _i, _i, _i, _i, _vp, _vp]),
+    'mbx_skeleton_raster': (_i, [_vp, _vp, _vp] + [_i] * 8 + [_vp, _vp, _vp]),
     'mbx_rows_n_pack_bytes': (_sz, [_i, _i]),
     'mbx_rows_lnbwd_t': (_i, [_vp] * 6 + [_i, _i, _i, _vp]),
     'mbx_rows_n_pack_many': (_i, [_i64p, _i, _i, _i, _vp]),
@@ -1185,6 +1187,31 @@ class HipOps:
         ws = self._ws(('render', F, Nf), self.lib.mbx_render_raster_ws, F, Nf, device=dev)
         self._ck(self.lib.mbx_render_raster(_p(vq), _p(verts), _p(faces), F, V, Nf, int(size), int(ss), float(color[0]), float(color[1]),
                                             float(color[2]), float(alpha), _p(rgb), _p(face_id), _p(depth), _p(ws), ws.numel(), self._stream()))
+
+    # ------------------------------------------------------------------ skeleton video frames (motionbert_amd/render.py)
+    def skeleton_project(self, x, view, size, ss, jq):
+        """x [F,J,3] f32 on the device, view: 15 float64 values on the host (rows 0, 1, 3 of M, u_lo, v_hi, inv_w) -> jq [F,J,2] i32
+        (mbx_skeleton_project)"""
+        if x.dim() != 3 or x.shape[2] != 3 or len(view) != 15:
+            raise RuntimeError(f'libmbx: skeleton_project needs x [F,J,3] and a view of 15 values, got {tuple(x.shape)} / {len(view)}')
+        F, J, dev = x.shape[0], x.shape[1], x.device
+        self._dense('skeleton_project', torch.float32, F * J * 3, dev, x=x)
+        self._dense('skeleton_project', torch.int32, F * J * 2, dev, jq=jq)
+        self._ck(self.lib.mbx_skeleton_project(_p(x), (C.c_double * 15)(*[float(v) for v in view]), F, J, int(size), int(ss), _p(jq), self._stream()))
+
+    def skeleton_raster(self, jq, bones, colors, radii, size, ss, rgb, prim_id=None):
+        """jq [F,J,2] i32, bones [Nb,2] i32, colors [Nb,3] u8, radii = (r_line, r_out, r_in) in 1/16 sample -> rgb [F,size,size,3] u8,
+        prim_id [F,S,S] i32 or None (mbx_skeleton_raster)"""
+        if jq.dim() != 3 or jq.shape[2] != 2 or bones.dim() != 2 or bones.shape[1] != 2 or len(radii) != 3:
+            raise RuntimeError(f'libmbx: skeleton_raster needs jq [F,J,2], bones [Nb,2] and three radii, got {tuple(jq.shape)} / {tuple(bones.shape)} / {radii!r}')
+        F, J, Nb, dev, S = jq.shape[0], jq.shape[1], bones.shape[0], jq.device, int(size) * int(ss)
+        self._dense('skeleton_raster', torch.int32, F * J * 2, dev, jq=jq)
+        self._dense('skeleton_raster', torch.int32, Nb * 2, dev, bones=bones)
+        self._dense('skeleton_raster', torch.uint8, Nb * 3, dev, colors=colors)
+        self._dense('skeleton_raster', torch.uint8, F * int(size) * int(size) * 3, dev, rgb=rgb)
+        self._dense('skeleton_raster', torch.int32, F * S * S, dev, prim_id=prim_id)
+        self._ck(self.lib.mbx_skeleton_raster(_p(jq), _p(bones), _p(colors), F, J, Nb, int(radii[0]), int(radii[1]), int(radii[2]), int(size), int(ss),
+                                              _p(rgb), _p(prim_id), self._stream()))
 
     # ------------------------------------------------------------------ dropout / drop-path (SURVEY 8 a15)
     def dropout(self, x, y, p, seed):

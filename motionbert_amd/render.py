@@ -1,15 +1,22 @@
-"""Mesh video frames on the device (csrc/render.hip): the last line of infer_wild_mesh.py, `render_and_save` -> `vismo.motion2video_mesh`,
-as compute.  An Instinct has no graphics pipeline; the frames are drawn by an exact fixed-point tile rasteriser instead (include/mbx.h has
-the definition: orthographic along +z, image x right with mesh x, image y down with mesh y, inside the bounding cube of the whole motion,
-z-buffered and flat-shaded, white background).
+"""Video frames on the device: the last lines of infer_wild_mesh.py and infer_wild.py, `render_and_save` -> `vismo.motion2video_mesh`
+(csrc/render.hip) and `vismo.motion2video_3d` (csrc/skeleton.hip), as compute.  An Instinct has no graphics pipeline; the frames are drawn
+by exact fixed-point tile rasterisers instead (include/mbx.h has the definitions.  The mesh: orthographic along +z, image x right with mesh
+x, image y down with mesh y, inside the bounding cube of the whole motion, z-buffered and flat-shaded, white background.  The skeleton: the
+reference's perspective 3D axes as one constant matrix, bones and joints in the reference's plot order, white background).
 
     frame_cube(verts, seq_lens=None)        [n_tracks,4] = (cx, cy, cz, 1 / (2 R)) per track over ALL its frames, torch operations on the device
     render_mesh(verts, faces, ...)          verts [F,V,3] + faces [Nf,3] -> {'rgb': uint8 [F,size,size,3]} (+ the test hooks 'face_id', 'depth',
                                             'vq') as device tensors
     render_chunks(verts, faces, ...)        generator of host uint8 [n,size,size,3] arrays, `chunk` frames at a time through two pinned
                                             buffers: 4,960 frames at 1024 x 1024 are 15.6 GB and cannot be one tensor
+    render_skeleton(x3d, ...)               x3d [F,J,3] (the X3D of `wild.infer`, device tensor or host array) -> {'rgb': uint8 [F,size,size,3]}
+                                            (+ the test hooks 'prim_id', 'jq'): the reference's 3D axes view as the constant SKELETON_VIEW, bones as
+                                            capsules and joints as ringed discs in the reference's plot order, exact in integers
+    skeleton_chunks(x3d, ...)               the same frames through the pipeline of render_chunks
+    skeleton_radii(size, ss)                the reference's line and marker widths scaled to the image
 
-Not here: video encoding, the skeleton videos of `motion2video_3d`, smooth shading, other cameras, several persons in one frame.
+Not here: video encoding, the 2D overlay of `motion2video`, matplotlib's panes, grid and anti-aliasing, smooth shading, other mesh cameras,
+several persons in one frame.
 
 There is no CPU path: without an injected kernel provider (`ops=`), tensors that are not on a ROCm device raise."""
 from __future__ import annotations
@@ -21,6 +28,8 @@ from . import hip_ops
 
 MAX_SIZE, SUB, ZQ = 2048, 16, 1 << 20
 WANT_KEYS = ('rgb', 'face_id', 'depth', 'vq')
+SKELETON_WANT_KEYS = ('rgb', 'prim_id', 'jq')
+MAX_JOINTS, MAX_BONES, MAX_RADIUS = 32, 64, 1 << 11
 CUBE_SLACK = 1.0 + 2.0 ** -16
 MESH_COLOR, MESH_ALPHA = (166, 188, 218), 0.9      # vismo.py:323: the face colour of the reference's surface, alpha 0.9 over white
 
@@ -123,25 +132,13 @@ def render_mesh(verts, faces, cube=None, seq_lens=None, size: int = 1024, ss: in
     return {k: res[k] for k in want}
 
 
-def render_chunks(verts, faces, cube=None, seq_lens=None, size: int = 1024, ss: int = 1, color=MESH_COLOR, alpha: float = MESH_ALPHA,
-                  chunk: int = 32, ops=None):
-    """A generator of host uint8 arrays [n,size,size,3], n <= `chunk` frames at a time, in frame order: the frames of `render_mesh` without
-    ever holding them all.  The cube is that of the whole motion (per track), whatever the chunking.  On the device two frame buffers and two
-    pinned host buffers alternate: the copy of one chunk runs on a side stream under the render of the next, and the host waits once per
-    chunk, for that chunk's copy.  An array is valid until the generator is advanced again (its buffer is then reused)."""
-    where = 'render.render_chunks'
-    _, lens, prov = _check(verts, faces, cube, seq_lens, size, ss, color, alpha, ('rgb',), ops, where)
-    if not isinstance(chunk, int) or chunk < 1:
-        raise ValueError(f'{where}: chunk must be a positive int, got {chunk!r}')
-    F, dev = verts.shape[0], verts.device
-    if F == 0:
-        return
-    verts, faces = verts.contiguous(), faces.contiguous()
-    cube = (frame_cube(verts, lens) if cube is None else cube).contiguous()
-    ptr = _seq_ptr(lens, dev)
+def _pipeline(F, chunk, size, dev, span):
+    """The frames [F,size,size,3] of `span(a, b, rgb)` (which launches the render of frames a .. b - 1 into the device tensor rgb) as host
+    arrays, `chunk` frames at a time.  On the device two frame buffers and two pinned host buffers alternate: the copy of one chunk runs on a
+    side stream under the render of the next, and the host waits once per chunk, for that chunk's copy."""
     spans = [(a, min(a + chunk, F)) for a in range(0, F, chunk)]
     n_buf = min(2, len(spans))
-    piped = verts.is_cuda
+    piped = dev.type == 'cuda'
     dbuf = [torch.empty(min(chunk, F), size, size, 3, dtype=torch.uint8, device=dev) for _ in range(n_buf)]
     hbuf = [torch.empty(min(chunk, F), size, size, 3, dtype=torch.uint8, pin_memory=True) for _ in range(n_buf)] if piped else dbuf
     side = torch.cuda.Stream(device=dev) if piped else None
@@ -153,7 +150,7 @@ def render_chunks(verts, faces, cube=None, seq_lens=None, size: int = 1024, ss: 
         rgb = dbuf[k][:b - a]
         if copied[k] is not None:
             torch.cuda.current_stream(dev).wait_event(copied[k])      # the copy that last read this device buffer
-        _render(prov, verts[a:b], faces, cube, (ptr - a).clamp_(0, b - a), size, ss, color, alpha, rgb, ('rgb',))
+        span(a, b, rgb)
         if side is not None:
             side.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(side):
@@ -168,3 +165,151 @@ def render_chunks(verts, faces, cube=None, seq_lens=None, size: int = 1024, ss: 
         if copied[i % n_buf] is not None:
             copied[i % n_buf].synchronize()
         yield hbuf[i % n_buf][:b - a].numpy()
+
+
+def render_chunks(verts, faces, cube=None, seq_lens=None, size: int = 1024, ss: int = 1, color=MESH_COLOR, alpha: float = MESH_ALPHA,
+                  chunk: int = 32, ops=None):
+    """A generator of host uint8 arrays [n,size,size,3], n <= `chunk` frames at a time, in frame order: the frames of `render_mesh` without
+    ever holding them all.  The cube is that of the whole motion (per track), whatever the chunking.  The frames come through `_pipeline`:
+    an array is valid until the generator is advanced again (its buffer is then reused)."""
+    where = 'render.render_chunks'
+    _, lens, prov = _check(verts, faces, cube, seq_lens, size, ss, color, alpha, ('rgb',), ops, where)
+    if not isinstance(chunk, int) or chunk < 1:
+        raise ValueError(f'{where}: chunk must be a positive int, got {chunk!r}')
+    F, dev = verts.shape[0], verts.device
+    if F == 0:
+        return
+    verts, faces = verts.contiguous(), faces.contiguous()
+    cube = (frame_cube(verts, lens) if cube is None else cube).contiguous()
+    ptr = _seq_ptr(lens, dev)
+
+    def span(a, b, rgb):
+        _render(prov, verts[a:b], faces, cube, (ptr - a).clamp_(0, b - a), size, ss, color, alpha, rgb, ('rgb',))
+    yield from _pipeline(F, chunk, size, dev, span)
+
+
+# ------------------------------------------------------------------------------------------------ skeleton frames (csrc/skeleton.hip)
+# vismo.py:262-269: Axes3D with limits x [-512, 0], y [-256, 256], z [-512, 0], view_init(elev=12, azim=80), default perspective.  With fixed
+# limits and a fixed view Axes3D.get_proj() is one constant matrix M (matplotlib 3.10.8; tests/golden/skeleton_view.npz holds it as the
+# reference's own run gave it): rows 0, 1 and 3 here, then the 2D window of a 3D axes, [-0.95 / dist, 0.9 / dist] at dist = 10, as u_lo, v_hi
+# and 1 / width.  The tightly cropped image of the reference is that axes rectangle.
+SKELETON_VIEW = tuple(float.fromhex(h) for h in (
+    '-0x1.2c21c35e6b437p-9', '0x1.a75eec7dd4bbdp-12', '0x0.0p+0', '-0x1.2c21c35e6b439p-1',
+    '-0x1.60184ec9e1feep-14', '-0x1.f33519d378183p-12', '0x1.bf2737751c729p-10', '0x1.a925b2887e52dp-2',
+    '-0x1.9e1e7f32e9c01p-12', '-0x1.2592c2d6c7b64p-9', '-0x1.7c2e6ed07e176p-12', '0x1.39cb6623f9304p+3')) + (-0.095, 0.09, 1 / 0.185)
+# vismo.py:252-258: the plot order, and the colours by the reference's membership lists
+SKELETON_BONES = ((0, 1), (1, 2), (2, 3), (0, 4), (4, 5), (5, 6), (0, 7), (7, 8), (8, 9), (8, 11), (8, 14), (9, 10), (11, 12), (12, 13), (14, 15),
+                  (15, 16))
+_LEFT, _RIGHT = ((8, 11), (11, 12), (12, 13), (0, 4), (4, 5), (5, 6)), ((8, 14), (14, 15), (15, 16), (0, 1), (1, 2), (2, 3))
+COLOR_LEFT, COLOR_RIGHT, COLOR_MID = (0x02, 0x31, 0x5E), (0x2F, 0x70, 0xAF), (0x00, 0x45, 0x7E)
+SKELETON_COLORS = tuple(COLOR_LEFT if b in _LEFT else COLOR_RIGHT if b in _RIGHT else COLOR_MID for b in SKELETON_BONES)
+REF_FRAME_PX = 924          # the reference's cropped frame: 0.77 of 10 inches at 120 dpi
+
+
+def _round_div(num, den):
+    return (2 * num + den) // (2 * den)
+
+
+def skeleton_radii(size: int, ss: int = 1):
+    """(r_line, r_out, r_in) in 1/16 sample: vismo.py:276 draws lw = 3 pt, markersize = 3 pt and markeredgewidth = 2 pt at 120 dpi (5, 5 and
+    10/3 px) in a 924-px frame: line width 5 size / 924 px, marker outer diameter (5 + 10/3) size / 924 px, inner (5 - 10/3) size / 924 px.
+    Half of each, in 1/16 of a sample (ss samples per pixel), rounded to nearest."""
+    k = 16 * ss * size
+    return _round_div(5 * k, 2 * REF_FRAME_PX), _round_div(25 * k, 6 * REF_FRAME_PX), _round_div(5 * k, 6 * REF_FRAME_PX)
+
+
+def _table(t, dtype, cols, most, name, dev, where):
+    """a small per-bone table as a contiguous device tensor [n,cols]: a tensor as it is, host data uploaded"""
+    if not isinstance(t, torch.Tensor):
+        a = np.asarray(t)
+        if a.ndim != 2 or a.shape[1] != cols or a.dtype.kind not in 'iu' or (a.size and (a.min() < torch.iinfo(dtype).min or a.max() > torch.iinfo(dtype).max)):
+            raise ValueError(f'{where}: {name} must be integers [n,{cols}] that fit {dtype}, got {a.shape} {a.dtype}')
+        t = torch.from_numpy(a.astype(np.uint8 if dtype == torch.uint8 else np.int32)).to(dev)
+    if t.dtype != dtype or t.dim() != 2 or t.shape[1] != cols or not 1 <= t.shape[0] <= most or t.device != dev:
+        raise ValueError(f'{where}: {name} must be a {dtype} tensor [1 <= n <= {most},{cols}] on {dev}, got {tuple(t.shape)} {t.dtype} on {t.device}')
+    return t.contiguous()
+
+
+def _check_skeleton(x3d, size, ss, view, bones, colors, radii, want, ops, where):
+    if isinstance(x3d, np.ndarray):                      # the result of `wild.infer` as it comes: uploaded once
+        if x3d.dtype != np.float32:
+            raise ValueError(f'{where}: x3d must be float32 [F, J, 3], got {x3d.shape} {x3d.dtype}')
+        x3d = torch.from_numpy(np.ascontiguousarray(x3d))
+        if ops is None:
+            if not torch.cuda.is_available():
+                raise RuntimeError(f'motionbert_amd.{where} runs on the ROCm device; there is no CPU path')
+            x3d = x3d.cuda()
+    if (not isinstance(x3d, torch.Tensor) or x3d.dtype != torch.float32 or x3d.dim() != 3 or x3d.shape[2] != 3
+            or not 1 <= x3d.shape[1] <= MAX_JOINTS):
+        raise ValueError(f'{where}: x3d must be a float32 tensor or array [F, 1 <= J <= {MAX_JOINTS}, 3], got '
+                         f'{tuple(x3d.shape) if hasattr(x3d, "shape") else type(x3d).__name__} {getattr(x3d, "dtype", "")}')
+    if not isinstance(size, int) or not 1 <= size <= MAX_SIZE:
+        raise ValueError(f'{where}: size must be an int in [1, {MAX_SIZE}], got {size!r}')
+    if ss not in (1, 2):
+        raise ValueError(f'{where}: ss must be 1 or 2, got {ss!r}')
+    view = SKELETON_VIEW if view is None else tuple(float(v) for v in np.asarray(view, np.float64).reshape(-1))
+    if len(view) != 15 or not all(np.isfinite(view)):
+        raise ValueError(f'{where}: view must be 15 finite values (rows 0, 1, 3 of M, u_lo, v_hi, inv_w), got {len(view)}')
+    radii = skeleton_radii(size, ss) if radii is None else tuple(radii)
+    if (len(radii) != 3 or not all(isinstance(r, (int, np.integer)) for r in radii)
+            or not (0 <= radii[0] <= MAX_RADIUS and 0 <= radii[2] <= radii[1] <= MAX_RADIUS)):
+        raise ValueError(f'{where}: radii must be ints (r_line, r_out, r_in) with 0 <= r_line <= {MAX_RADIUS} and 0 <= r_in <= r_out <= {MAX_RADIUS}, '
+                         f'got {radii!r}')
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(k not in SKELETON_WANT_KEYS for k in want):
+        raise ValueError(f'{where}: want must name some of {SKELETON_WANT_KEYS}, got {want!r}')
+    dev = x3d.device
+    if colors is None and bones is not None:
+        raise ValueError(f'{where}: colors must be given with bones, one colour for each')
+    bones = _table(SKELETON_BONES if bones is None else bones, torch.int32, 2, MAX_BONES, 'bones', dev, where)
+    colors = _table(SKELETON_COLORS if colors is None else colors, torch.uint8, 3, MAX_BONES, 'colors', dev, where)
+    if colors.shape[0] != bones.shape[0]:
+        raise ValueError(f'{where}: colors must give one colour for each of the {bones.shape[0]} bones, got {colors.shape[0]}')
+    prov = hip_ops.provider(ops, 'motionbert_amd.' + where, x3d)
+    return x3d.contiguous(), view, bones, colors, tuple(int(r) for r in radii), want, prov
+
+
+def _render_skeleton(prov, x3d, view, bones, colors, radii, size, ss, rgb, want):
+    F, J, S, dev = x3d.shape[0], x3d.shape[1], size * ss, x3d.device
+    jq = torch.empty(F, J, 2, dtype=torch.int32, device=dev)
+    res = {'rgb': rgb, 'jq': jq, 'prim_id': torch.empty(F, S, S, dtype=torch.int32, device=dev) if 'prim_id' in want else None}
+    if F:
+        prov.skeleton_project(x3d, view, size, ss, jq)
+        prov.skeleton_raster(jq, bones, colors, radii, size, ss, rgb, res['prim_id'])
+    return res
+
+
+def render_skeleton(x3d, size: int = 1024, ss: int = 1, view=None, bones=None, colors=None, radii=None, out=None, want=('rgb',), ops=None):
+    """x3d [F,J,3] float32, a device tensor or a host array (uploaded once): the X3D of `wild.infer` -> a dict of device tensors: 'rgb' uint8
+    [F,size,size,3] and, where `want` names them, the test hooks 'prim_id' int32 [F,S,S] (S = size ss; the winning primitive 3 bone + (0 the
+    line, 1 / 2 the marker at the first / second end), -1 where empty) and 'jq' int32 [F,J,2] (the projected joints).  `view`: 15 float64
+    values (default SKELETON_VIEW, the reference's axes); `bones` [Nb,2] / `colors` [Nb,3]: joint pairs in plot order and their colours
+    (default: the 16 H36M bones in the reference's colours); `radii` = (r_line, r_out, r_in) in 1/16 sample (default `skeleton_radii`).
+    `ss = 2` averages 2 x 2 samples per pixel.  `out`: a uint8 [F,size,size,3] tensor to write 'rgb' into.  Two kernel calls; F = 0
+    returns empty tensors without a launch.  A dict of tracks is the caller's loop."""
+    where = 'render.render_skeleton'
+    x3d, view, bones, colors, radii, want, prov = _check_skeleton(x3d, size, ss, view, bones, colors, radii, want, ops, where)
+    F, dev = x3d.shape[0], x3d.device
+    if out is None:
+        out = torch.empty(F, size, size, 3, dtype=torch.uint8, device=dev)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (F, size, size, 3) or not out.is_contiguous()
+          or out.device != dev):
+        raise ValueError(f'{where}: out must be a contiguous uint8 tensor [{F},{size},{size},3] on {dev}')
+    res = _render_skeleton(prov, x3d, view, bones, colors, radii, size, ss, out, want)
+    return {k: res[k] for k in want}
+
+
+def skeleton_chunks(x3d, size: int = 1024, ss: int = 1, view=None, bones=None, colors=None, radii=None, chunk: int = 32, ops=None):
+    """A generator of host uint8 arrays [n,size,size,3], n <= `chunk` frames at a time, in frame order: the frames of `render_skeleton`
+    through `_pipeline`, without ever holding them all.  An array is valid until the generator is advanced again."""
+    where = 'render.skeleton_chunks'
+    x3d, view, bones, colors, radii, _, prov = _check_skeleton(x3d, size, ss, view, bones, colors, radii, ('rgb',), ops, where)
+    if not isinstance(chunk, int) or chunk < 1:
+        raise ValueError(f'{where}: chunk must be a positive int, got {chunk!r}')
+    F = x3d.shape[0]
+    if F == 0:
+        return
+
+    def span(a, b, rgb):
+        _render_skeleton(prov, x3d[a:b], view, bones, colors, radii, size, ss, rgb, ('rgb',))
+    yield from _pipeline(F, chunk, size, x3d.device, span)
