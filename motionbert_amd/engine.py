@@ -164,6 +164,24 @@ def grad_bucket(name: str, depth: int) -> int:
     return depth + 1
 
 
+# The N-resident row-owner kernels (gemm_rows_n.hip) address every tensor as a wave-uniform 64-bit base plus ONE unsigned 32-bit byte
+# offset per lane, so each of their [M, .] tensors has to stay below this many bytes.  The C entries refuse more (mbx_rows_lnbwd_t,
+# mbx_rows_resid_ln); the same limits are restated here -- once -- because the choice of the sequencing is made per forward, BEFORE
+# anything runs: a refusal in backward would come after the forward has dropped what the tile kernels need.  tests/test_row_limits.py
+# pins both functions to the library's checks at the boundary.
+ROW_OFFSET_LIMIT = 1 << 32
+
+
+def rows_lnbwd_fits(M: int, N: int, K: int) -> bool:
+    """mbx_rows_lnbwd_t takes M rows: xhat / dres / dx_t bf16 [M, N] and dy bf16 [M, K] inside the 32-bit offsets."""
+    return M * N * 2 < ROW_OFFSET_LIMIT and M * K * 2 < ROW_OFFSET_LIMIT
+
+
+def rows_resid_ln_fits(M: int, N: int, K: int) -> bool:
+    """mbx_rows_resid_ln takes M rows: resid / y fp32 [M, N] and a bf16 [M, K] inside the 32-bit offsets."""
+    return M * N * 4 < ROW_OFFSET_LIMIT and M * K * 2 < ROW_OFFSET_LIMIT
+
+
 class Drops(namedtuple('Drops', 'p seed_branch seed_act p_path seed_path p_attn seed_attn')):
     """Active dropout of one sub-layer (`Engine._drops`): rates and mask seeds of proj_drop / the MLP drops (on the branch output, after
     the activation), of DropPath and of the dropout on the attention probabilities."""
@@ -247,6 +265,14 @@ class Engine:
         self.Pk_proj: Dict[str, str] = {}           # MLP -> the proj Linear packed in front of it (derived from ORDER)
         self.proj_mlp = sw.proj_mlp and hasattr(ops, 'proj_mlp_fused_fwd')      # A/B switch: 0 = proj + residual as its own GEMM
 
+    def _choose_row_kernels(self):
+        """The row-owner kernels serve a bounded row count (ROW_OFFSET_LIMIT): whether they run is a matter of THIS pass's M and of the
+        longest contraction each of them meets -- dX of qkv: 3 C, dX of fc1 and fc2 itself: hidden.  Beyond the limit the tile kernels run,
+        in forward and backward alike, exactly as with the A/B switch off.  Decided once per pass, where its weights are prepared."""
+        cfg = self.cfg
+        self.lnbwd_rows = bool(self.rows_lnbwd and rows_lnbwd_fits(self.M, cfg.C, max(3 * cfg.C, cfg.hidden)))
+        self.resid_rows = bool(self.rows_resid_ln and rows_resid_ln_fits(self.M, cfg.C, max(cfg.C, cfg.hidden)))
+
     def _streams(self):
         """(main, side) streams for the dual-stream schedule, or (None, None)."""
         if not (self.dual and self.dev.type == 'cuda'):
@@ -319,7 +345,7 @@ class Engine:
         `.data` in a pure inference process still needs `hip_ops.get().weight_cache.clear()`."""
         if need_grad or not hasattr(self.ops, 'weight_cache') or self.dev.type != 'cuda' or torch.cuda.is_current_stream_capturing():
             return None
-        return (tuple((p.data_ptr(), p._version) for p in self.P.values()), self.T, self.fold, self.rawln, self.proj_mlp, self.x3, self.rows_resid_ln)
+        return (tuple((p.data_ptr(), p._version) for p in self.P.values()), self.T, self.fold, self.rawln, self.proj_mlp, self.x3, self.resid_rows)
 
     def prepare_weights(self, need_grad: bool):
         """T-typed copies of every Linear weight (and their transposes when a backward follows); with LayerNorm folding the
@@ -327,6 +353,7 @@ class Engine:
         on the kernel provider and reused as long as no parameter changed: an inference call then launches no fold / pack kernels
         (at depth 5 they were ~60 small launches per forward, as many as a B = 1 forward has kernels of its own)."""
         cfg, ops, P = self.cfg, self.ops, self.P
+        self._choose_row_kernels()
         if need_grad and hasattr(ops, 'weight_cache') and self.dev.type == 'cuda':
             # a training step follows: whatever it does to the parameters -- also through `p.data`, which bumps no version counter
             # (legacy optimizers, EMA code, a replayed graph) -- the next no-grad forward must not find this forward's prepared set
@@ -354,11 +381,11 @@ class Engine:
             fn, ft, self.Bf, self.Rs = ops.fold_norm_weights(P, pairs, need_grad, self.T)
             self.Wn.update(fn)
             self.Wt.update(ft)
-            if self.rows_resid_ln and not self.rawln:
+            if self.resid_rows and not self.rawln:
                 # proj / fc2 of the first three sub-layers of every Block (the fourth feeds the fusion, not a LayerNorm)
                 lins = [f'{pre}.{mod}.{LINEARS[typ][1]}' for pre, _, sub, typ, _, mod, _ in sublayers(cfg) if sub < 3]
                 self.Pf = dict(zip(lins, ops.rows_n_pack_many([self.Wn[lin] for lin in lins])))
-            if need_grad and self.rows_lnbwd and self.gstream_allowed:
+            if need_grad and self.lnbwd_rows and self.gstream_allowed:
                 # (not for the first sub-layer of a Block whose input gradient leaves in fp32 with the other stream's gradient added --
                 # MBX_BLOCK_GRAD_T=0: the tile kernel's epilogue)
                 first = {f'{pre}.{mod}.qkv' for pre, _, sub, _, _, mod, _ in sublayers(cfg) if sub == 0 and not (self.block_grad_t and cfg.att_fuse)}
@@ -526,8 +553,8 @@ class Engine:
         cfg, ops, P = self.cfg, self.ops, self.P
         y = self._f(self.M, cfg.C)
         drop = dm is not None and dm.branch      # proj_drop / MLP drop + DropPath on the branch (DSTformer.py:84,148-149,241-242)
-        # (the kernel addresses its 2-KiB rows with 32-bit offsets: beyond 2^21 rows the tile kernel + LayerNorm take over)
-        if self.fold and nxt is not None and lin in self.Pf and self.M < (1 << 21) and not drop:
+        # (the kernel addresses its rows with 32-bit offsets: beyond `resid_rows` the tile kernel + LayerNorm take over)
+        if self.fold and nxt is not None and lin in self.Pf and self.resid_rows and not drop:
             xn, mean, rstd = self._op(self.M, cfg.C), self._f(self.M), self._f(self.M)
             ops.rows_resid_ln(a, self.Pf[lin], P[lin + '.bias'], x, y, xn, mean, rstd, cfg.eps)
             return y, (xn, mean, rstd)
@@ -591,7 +618,7 @@ class Engine:
         # the derivative instead of the pre-activation where backward will run the row-owner tail (every MLP of a Block does: never the
         # first sub-layer, so bf16 gradient in and out and no second summand)
         save_d = bool(need_grad and self.fold and self.gelu_d and self.gstream_allowed and not self.recompute and not mlp_drop
-                      and lin in self.Pn and self.M < (1 << 22))
+                      and lin in self.Pn and self.lnbwd_rows)
         if save_d:
             ops.gemm_nt_gelu_d(xn, self.Wn[lin], self.Bf[lin], u, g)
         else:
@@ -655,7 +682,7 @@ class Engine:
                 ops.average_bwd(dh, d_st, d_ts, d_st_t, d_ts_t)
             pair = dh = None
             # this level's Blocks hand their input gradients down T-typed when the row-owner tail can take their first sub-layer
-            out_t = bool(self.block_grad_t and self.gstream and cfg.att_fuse and (i > 0 or self.drop_seed is None) and self.M < (1 << 22)
+            out_t = bool(self.block_grad_t and self.gstream and cfg.att_fuse and (i > 0 or self.drop_seed is None) and self.lnbwd_rows
                          and all(f'{st}.{i}.{ORDER[kind][0][2]}.qkv' in self.Pn for st, kind in STREAMS))
             main, side = self._streams()
             if out_t:
@@ -777,7 +804,7 @@ class Engine:
 
     def _rows_tail_ok(self, lin, dy_t, extra, need_t) -> bool:
         """The row-owner LayerNorm-backward GEMM serves a folded pair whose gradient arrives and leaves in the operand type only."""
-        return bool(self.rows_lnbwd and self.gstream and need_t and dy_t is not None and extra is None and lin in self.Pn and self.M < (1 << 22))
+        return bool(self.lnbwd_rows and self.gstream and need_t and dy_t is not None and extra is None and lin in self.Pn)
 
     def _fold_tail(self, dY, part, sv, lin, norm, dy, dy_t, extra, need_t):
         """Folded (LayerNorm -> Linear) pair, backward from the Linear's output gradient dY and its row dots `part`: weight

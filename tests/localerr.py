@@ -278,10 +278,16 @@ def _seq_back(x, mode_temporal):
 
 def attn_mask(B, T, J, H, temporal, drop, device):
     """keep / (1 - p) over the reference's attn tensor, in this module's problem-major layout ([B,J,H,T,T] temporal -- the reference's
-    is [B,H,J,T,T] -- and [B,T,H,J,J] spatial); None without dropout"""
+    is [B,H,J,T,T] -- and [B,T,H,J,J] spatial); None without dropout.  drop = (p, seed) or (p, seed, clips): the B clips given are the
+    clips of those numbers in a LARGER batch, over whose attention tensor the mask index runs (tests/test_gpu_big_rows.py)"""
     if drop is None or drop[0] <= 0:
         return None
-    from motionbert_amd.dropmask import mask_like
+    from motionbert_amd.dropmask import keep, mask_like
+    if len(drop) > 2:
+        per = H * J * T * T if temporal else T * H * J * J      # elements of one clip: the batch index is outermost in both layouts
+        idx = torch.tensor(list(drop[2]), dtype=torch.int64, device=device)[:, None] * per + torch.arange(per, dtype=torch.int64, device=device)[None, :]
+        m = (keep(idx, drop[0], drop[1]).float() / (1.0 - drop[0])).double()      # (in fp32 first, as mask_like on an fp32 tensor)
+        return m.reshape(B, H, J, T, T).permute(0, 2, 1, 3, 4) if temporal else m.reshape(B, T, H, J, J)
     if temporal:
         return mask_like(torch.empty(B, H, J, T, T, device=device), drop[0], drop[1]).permute(0, 2, 1, 3, 4).double()
     return mask_like(torch.empty(B, T, H, J, J, device=device), drop[0], drop[1]).double()
