@@ -65,6 +65,10 @@ int mbx_prep_weights(const int64_t* desc, int n_desc, int max_n, int max_k, int 
  * x [B,T,J,Din] f32, w [C,Din], b [C], pos [J,C], temp [>=T,C]  ->  h [M,C] f32 */
 int mbx_embed_fwd(const float* x, const float* w, const float* b, const float* pos, const float* temp,
                   float* h, int B, int T, int J, int Din, int C, void* stream);
+/* mbx_embed_fwd plus the plain normalisation of its rows (the folded path's level-0 operand) in one launch: h [M,C] f32 as above,
+ * xhat bf16 [M,C], mean / rstd [M] -- bit for bit what mbx_layernorm_fwd(h, NULL, NULL, eps, xhat, ..., bf16) gives.  Din <= 4, C <= 1024. */
+int mbx_embed_ln_fwd(const float* x, const float* w, const float* b, const float* pos, const float* temp, float eps, float* h,
+                     void* xhat, float* mean, float* rstd, int B, int T, int J, int Din, int C, void* stream);
 /* dh [M,C] -> dw [C,Din], db [C], dpos [J,C], dtemp [T,C] (rows >= T untouched), dx [M,Din] or NULL.
  * ws: >= mbx_embed_bwd_ws(T,J,Din,C) bytes. */
 size_t mbx_embed_bwd_ws(int T, int J, int Din, int C);

@@ -56,7 +56,7 @@ int mbx_cu_count() {
     g_cus[dev].store(c, std::memory_order_relaxed);
     return c;
 }
-extern "C" int mbx_version(void) { return 210; }
+extern "C" int mbx_version(void) { return 220; }
 
 static inline int clamp_grid(size_t want, int cap) { return (int)(want < (size_t)cap ? (want ? want : 1) : (size_t)cap); }
 
@@ -65,13 +65,22 @@ static inline int clamp_grid(size_t want, int cap) { return (int)(want < (size_t
 // Vector kernel: a lane owns 4 consecutive columns (one 16-B load per partial row); a block is CL column lanes x
 // PL = 256/CL part lanes, every part lane keeps four loads in flight, the part lanes are folded through LDS.
 // CL = 64 for wide outputs (weight-gradient tiles: few partial rows, 10^5..10^6 columns), CL = 16 for narrow ones
-// (LayerNorm dgamma/dbeta: 10^3 partial rows, 10^3 columns).  Columns >= split go to out1 (two outputs, one launch).
-// The scalar kernel below remains for outputs whose width or offset is not a multiple of 4.
+// (LayerNorm dgamma/dbeta: 10^3 partial rows, 10^3 columns).  One launch serves up to three outputs (ColOut): columns
+// [0, split0) go to out[0], [split0, split1) to out[1], [split1, nvalid) to out[2]; columns in [nvalid, ncols) are padding of the
+// partial row (read, never stored).  The scalar kernel below has the same shape (16 column lanes x 16 part lanes, eight loads in
+// flight each) and serves outputs whose width or offset is not a multiple of 4.
 // ------------------------------------------------------------------------------------------------
+struct ColOut {
+    float* out[3];
+    int split0, split1, nvalid;
+};
+static inline ColOut col_out(float* o0, int ncols) { return ColOut{{o0, nullptr, nullptr}, ncols, ncols, ncols}; }
+__device__ __forceinline__ float* col_dst(const ColOut& o, int c) {
+    return c < o.split0 ? o.out[0] + c : c < o.split1 ? o.out[1] + (c - o.split0) : o.out[2] + (c - o.split1);
+}
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 template <int CL>
-__global__ __launch_bounds__(256) void colsum4_kernel(const float* __restrict__ part, int nparts, size_t stride, int ncols,
-                                                      float* __restrict__ out0, float* __restrict__ out1, int split) {
+__global__ __launch_bounds__(256) void colsum4_kernel(const float* __restrict__ part, int nparts, size_t stride, int ncols, ColOut o) {
     constexpr int PLW = 64 / CL, PL = 4 * PLW;
     __shared__ float4 red[PL][CL];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -90,61 +99,68 @@ __global__ __launch_bounds__(256) void colsum4_kernel(const float* __restrict__ 
     }
     red[pl][cl] = (a0 + a1) + (a2 + a3);
     __syncthreads();
-    if (pl == 0 && c < ncols) {
+    if (pl == 0 && c < o.nvalid) {
         float4 t = red[0][cl];
 #pragma unroll
         for (int q = 1; q < PL; ++q) t += red[q][cl];
-        float* o = c < split ? out0 + c : out1 + (c - split);
-        if ((reinterpret_cast<uintptr_t>(o) & 15) == 0) {
-            *reinterpret_cast<float4*>(o) = t;
+        float* d = col_dst(o, c);      // (the splits are multiples of 4: the four columns of a lane have one destination)
+        if (c + 3 < o.nvalid && (reinterpret_cast<uintptr_t>(d) & 15) == 0) {
+            *reinterpret_cast<float4*>(d) = t;
         } else {
-            o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = t.w;
+            const float tv[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (c + e < o.nvalid) d[e] = tv[e];
         }
     }
 }
-__global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ part, int nparts, int stride, int col0,
-                                                     int ncols, float* __restrict__ out) {
-    __shared__ float red[4][64];
-    const int cl = threadIdx.x & 63, grp = threadIdx.x >> 6;
-    const int c = blockIdx.x * 64 + cl;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+__global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ part, int nparts, size_t stride, int ncols, ColOut o) {
+    __shared__ float red[16][17];
+    const int cl = threadIdx.x & 15, pl = threadIdx.x >> 4;
+    const int c = blockIdx.x * 16 + cl;
+    float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (c < ncols) {
-        const float* p = part + col0 + c;
-        int i = grp;
-        for (; i + 12 < nparts; i += 16) {
-            s0 += p[(size_t)i * stride];
-            s1 += p[(size_t)(i + 4) * stride];
-            s2 += p[(size_t)(i + 8) * stride];
-            s3 += p[(size_t)(i + 12) * stride];
+        const float* p = part + c;
+        int i = pl;
+        for (; i + 7 * 16 < nparts; i += 8 * 16) {
+            float v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = p[(size_t)(i + u * 16) * stride];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) s[u] += v[u];
         }
-        for (; i < nparts; i += 4) s0 += p[(size_t)i * stride];
+        for (; i < nparts; i += 16) s[0] += p[(size_t)i * stride];
     }
-    red[grp][cl] = (s0 + s1) + (s2 + s3);
+    red[pl][cl] = ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
     __syncthreads();
-    if (grp == 0 && c < ncols) out[c] = (red[0][cl] + red[1][cl]) + (red[2][cl] + red[3][cl]);
+    if (pl == 0 && c < o.nvalid) {
+        float t = red[0][cl];
+#pragma unroll
+        for (int q = 1; q < 16; ++q) t += red[q][cl];
+        *col_dst(o, c) = t;
+    }
 }
-// two outputs: columns [0, split) -> out0, [split, ncols) -> out1 (pass split = ncols, out1 = nullptr for one output)
-static int launch_colsum2(const float* part, int nparts, int stride, int col0, int ncols, float* out0, float* out1, int split,
-                          hipStream_t s) {
-    const bool vec = ncols % 4 == 0 && col0 % 4 == 0 && stride % 4 == 0 && split % 4 == 0 &&
+// ncols columns of the partial rows from column col0 on, distributed as `o` says
+static int launch_colsum_out(const float* part, int nparts, int stride, int col0, int ncols, const ColOut& o, hipStream_t s) {
+    const bool vec = ncols % 4 == 0 && col0 % 4 == 0 && stride % 4 == 0 && o.split0 % 4 == 0 && o.split1 % 4 == 0 &&
                      (reinterpret_cast<uintptr_t>(part + col0) & 15) == 0;
     if (!vec) {
-        hipLaunchKernelGGL(colsum_kernel, dim3((split + 63) / 64), dim3(256), 0, s, part, nparts, stride, col0, split, out0);
-        if (ncols > split)
-            hipLaunchKernelGGL(colsum_kernel, dim3((ncols - split + 63) / 64), dim3(256), 0, s, part, nparts, stride, col0 + split,
-                               ncols - split, out1);
+        hipLaunchKernelGGL(colsum_kernel, dim3((ncols + 15) / 16), dim3(256), 0, s, part + col0, nparts, (size_t)stride, ncols, o);
     } else if (ncols / 4 >= 64 * 512) {
-        hipLaunchKernelGGL(colsum4_kernel<64>, dim3((ncols / 4 + 63) / 64), dim3(256), 0, s, part + col0, nparts, (size_t)stride, ncols,
-                           out0, out1, split);
+        hipLaunchKernelGGL(colsum4_kernel<64>, dim3((ncols / 4 + 63) / 64), dim3(256), 0, s, part + col0, nparts, (size_t)stride, ncols, o);
     } else {
-        hipLaunchKernelGGL(colsum4_kernel<16>, dim3((ncols / 4 + 15) / 16), dim3(256), 0, s, part + col0, nparts, (size_t)stride, ncols,
-                           out0, out1, split);
+        hipLaunchKernelGGL(colsum4_kernel<16>, dim3((ncols / 4 + 15) / 16), dim3(256), 0, s, part + col0, nparts, (size_t)stride, ncols, o);
     }
     MBX_LAUNCH_CHECK("colsum");
     return 0;
 }
+// two outputs: columns [0, split) -> out0, [split, ncols) -> out1
+static int launch_colsum2(const float* part, int nparts, int stride, int col0, int ncols, float* out0, float* out1, int split,
+                          hipStream_t s) {
+    return launch_colsum_out(part, nparts, stride, col0, ncols, ColOut{{out0, out1, nullptr}, split, ncols, ncols}, s);
+}
 int mbx_launch_colsum(const float* part, int nparts, int stride, int col0, int ncols, float* out, hipStream_t s) {
-    return launch_colsum2(part, nparts, stride, col0, ncols, out, nullptr, ncols, s);
+    return launch_colsum_out(part, nparts, stride, col0, ncols, col_out(out, ncols), s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -421,13 +437,19 @@ extern "C" int mbx_embed_fwd_tta_ragged(const float* x, const int* perm, const f
 }
 
 // ------------------------------------------------------------------------------------------------
-// embedding backward.  One block per frame index t: a thread owns channel c and walks (j, b);
-// dtemp[t,c] is final, dpos / dw / db leave one partial row per t (folded by colsum).
+// embedding backward.  One block of 1024 threads per (frame index t, group of QB channel quads): a thread owns one channel quad
+// and one of NS = 1024/QB slices of the work of frame t; dtemp[t,c] is final, dpos / dw / db leave one partial row per t (folded by
+// one colsum launch with three outputs).
 // partial row layout: [J*C | C*Din | C]
 // ------------------------------------------------------------------------------------------------
 #define EMB_MAXDIN 4
-// 256 threads = (C/4 channel quads) x (256 / (C/4) slices of the clip range); 16-byte loads, eight clips in flight per
-// thread; the slices are folded through LDS.  (The scalar one-clip-at-a-time walk of round 1 took 1.05 ms at 64 clips.)
+// The slices take whole joints first (slice sl owns joints sl, sl + NS, ... below J - J % NS and walks every clip of them: its dpos
+// sums are complete, nothing to fold), then the J % NS joints left over are split by clip (slice sl takes clips sl, sl + NS, ...)
+// and folded through LDS, so that every slice loads the same number of rows and the main loop has no barrier.  16-byte loads, eight
+// rows in flight per thread.  QB = C/4 up to 256 (a block reads whole rows up to C = 1024) and never below 64, so that a slice is
+// whole waves: the joint, the clip and the rows of x are wave-uniform and x comes through the scalar cache instead of three vector
+// loads per row.  Sixteen waves per block keep a CU busy with the one block per t it gets (243 blocks at 243 frames).
+// (Rounds 1-6: 256 threads per t and a barrier per joint, 1.1 TB/s; 256-thread blocks of 32 quads with per-lane x loads: 2.4 TB/s.)
 // dh_a / dh_b (round 5): the incoming gradient as the sum of two bf16 tensors (the input gradients of the two Blocks of level 0, as
 // their row-owner LayerNorm-backward kernels leave them) instead of one fp32 tensor
 __device__ __forceinline__ float4 embed_dh4(const float* __restrict__ dh, const bf16_t* __restrict__ dh_a, const bf16_t* __restrict__ dh_b, size_t o) {
@@ -437,81 +459,96 @@ __device__ __forceinline__ float4 embed_dh4(const float* __restrict__ dh, const 
     load4<bf16_t>(dh_b + o, v);
     return make_float4(u[0] + v[0], u[1] + v[1], u[2] + v[2], u[3] + v[3]);
 }
-__global__ __launch_bounds__(256) void embed_bwd_kernel(const float* __restrict__ dh, const float* __restrict__ x,
-                                                        float* __restrict__ dtemp, float* __restrict__ part, int B, int T,
-                                                        int J, int Din, int C, const bf16_t* __restrict__ dh_a = nullptr,
-                                                        const bf16_t* __restrict__ dh_b = nullptr) {
-    __shared__ float4 red[256][1 + EMB_MAXDIN];
-    const int t = blockIdx.x;
-    const int stride = J * C + C * Din + C;
-    float* prow = part + (size_t)t * stride;
-    const int nq = C / 4, ns = max(256 / nq, 1);          // channel quads, clip slices (C % 4 == 0 checked on the host)
-    for (int q0 = 0; q0 < nq; q0 += 256) {                // C <= 1024: one pass
-        const int q = q0 + (int)threadIdx.x % min(nq, 256), sl = (int)threadIdx.x / min(nq, 256);
-        const bool act = q < nq && sl < ns;
-        const int c = q * 4;
-        float4 at = make_float4(0.f, 0.f, 0.f, 0.f), aw[EMB_MAXDIN];
+__device__ __forceinline__ void add4(float4& a, const float4& b) { a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w; }
+// clips b0, b0 + bs, ... < B of token (t, j), channels c .. c+3: ap += dh, aw[k] += dh x[k]
+__device__ __forceinline__ void embed_bwd_walk(const float* __restrict__ dh, const bf16_t* __restrict__ dh_a, const bf16_t* __restrict__ dh_b,
+                                               const float* __restrict__ x, int B, int T, int J, int Din, int C, int t, int j, int c,
+                                               int b0, int bs, float4& ap, float4 (&aw)[EMB_MAXDIN]) {
+    for (; b0 < B; b0 += 8 * bs) {
+        float4 g[8];
 #pragma unroll
-        for (int k = 0; k < EMB_MAXDIN; ++k) aw[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int j = 0; j < J; ++j) {
-            float4 ap = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (act) {
-                for (int b0 = sl; b0 < B; b0 += 8 * ns) {
-                    float4 g[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const int b = min(b0 + u * ns, B - 1);
-                        g[u] = embed_dh4(dh, dh_a, dh_b, (((size_t)b * T + t) * J + j) * C + c);
-                    }
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const int b = b0 + u * ns;
-                        const float on = b < B ? 1.f : 0.f;
-                        const size_t m = ((size_t)min(b, B - 1) * T + t) * J + j;
-                        ap.x = fmaf(on, g[u].x, ap.x); ap.y = fmaf(on, g[u].y, ap.y); ap.z = fmaf(on, g[u].z, ap.z); ap.w = fmaf(on, g[u].w, ap.w);
-#pragma unroll
-                        for (int k = 0; k < EMB_MAXDIN; ++k)
-                            if (k < Din) {
-                                const float xv = on * x[m * Din + k];
-                                aw[k].x = fmaf(g[u].x, xv, aw[k].x); aw[k].y = fmaf(g[u].y, xv, aw[k].y);
-                                aw[k].z = fmaf(g[u].z, xv, aw[k].z); aw[k].w = fmaf(g[u].w, xv, aw[k].w);
-                            }
-                    }
-                }
-            }
-            // fold the clip slices of this joint (fixed order), slice 0 writes the dpos partial
-            red[threadIdx.x][0] = ap;
-            __syncthreads();
-            if (act && sl == 0) {
-                for (int s2 = 1; s2 < ns; ++s2) {
-                    const float4 o = red[threadIdx.x + s2 * nq][0];
-                    ap.x += o.x; ap.y += o.y; ap.z += o.z; ap.w += o.w;
-                }
-                *reinterpret_cast<float4*>(prow + (size_t)j * C + c) = ap;
-                at.x += ap.x; at.y += ap.y; at.z += ap.z; at.w += ap.w;
-            }
-            __syncthreads();
+        for (int u = 0; u < 8; ++u) {
+            const int b = min(b0 + u * bs, B - 1);
+            g[u] = embed_dh4(dh, dh_a, dh_b, (((size_t)b * T + t) * J + j) * C + c);
         }
 #pragma unroll
-        for (int k = 0; k < EMB_MAXDIN; ++k) red[threadIdx.x][1 + k] = aw[k];
-        __syncthreads();
-        if (act && sl == 0) {
-            *reinterpret_cast<float4*>(dtemp + (size_t)t * C + c) = at;
-            *reinterpret_cast<float4*>(prow + (size_t)J * C + (size_t)C * Din + c) = at;
+        for (int u = 0; u < 8; ++u) {
+            const int b = b0 + u * bs;
+            const float on = b < B ? 1.f : 0.f;
+            const size_t m = ((size_t)min(b, B - 1) * T + t) * J + j;
+            ap.x = fmaf(on, g[u].x, ap.x); ap.y = fmaf(on, g[u].y, ap.y); ap.z = fmaf(on, g[u].z, ap.z); ap.w = fmaf(on, g[u].w, ap.w);
 #pragma unroll
             for (int k = 0; k < EMB_MAXDIN; ++k)
                 if (k < Din) {
-                    float4 w4 = aw[k];
-                    for (int s2 = 1; s2 < ns; ++s2) {
-                        const float4 o = red[threadIdx.x + s2 * nq][1 + k];
-                        w4.x += o.x; w4.y += o.y; w4.z += o.z; w4.w += o.w;
-                    }
-                    float* d = prow + (size_t)J * C + (size_t)c * Din + k;
-                    d[0] = w4.x; d[Din] = w4.y; d[2 * Din] = w4.z; d[3 * Din] = w4.w;
+                    const float xv = on * x[m * Din + k];
+                    aw[k].x = fmaf(g[u].x, xv, aw[k].x); aw[k].y = fmaf(g[u].y, xv, aw[k].y);
+                    aw[k].z = fmaf(g[u].z, xv, aw[k].z); aw[k].w = fmaf(g[u].w, xv, aw[k].w);
                 }
         }
-        __syncthreads();
     }
+}
+// sum of v over the NS slices (fixed order), valid in slice 0; every thread of the block calls it
+template <int QB, int NS>
+__device__ __forceinline__ float4 embed_bwd_fold(float4 v, float4 (&red)[NS][QB], int sl, int ql) {
+    red[sl][ql] = v;
+    __syncthreads();
+    if (sl == 0)
+        for (int s2 = 1; s2 < NS; ++s2) add4(v, red[s2][ql]);
+    __syncthreads();
+    return v;
+}
+template <int QB, int NS>
+__global__ __launch_bounds__(QB * NS) void embed_bwd_kernel(const float* __restrict__ dh, const float* __restrict__ x,
+                                                            float* __restrict__ dtemp, float* __restrict__ part, int B, int T,
+                                                            int J, int Din, int C, const bf16_t* __restrict__ dh_a,
+                                                            const bf16_t* __restrict__ dh_b) {
+    __shared__ float4 red[NS][QB];
+    const int t = blockIdx.x, cgrp = blockIdx.y;
+    const int stride = J * C + C * Din + C;
+    float* prow = part + (size_t)t * stride;
+    const int ql = (int)threadIdx.x % QB;
+    // (a slice is whole waves when QB is a multiple of 64: the joint and the rows of x are the same for all lanes)
+    const int sl = QB % 64 == 0 ? __builtin_amdgcn_readfirstlane((int)threadIdx.x / QB) : (int)threadIdx.x / QB;
+    const int q = cgrp * QB + ql;
+    const bool act = q < C / 4;                            // (C % 4 == 0 checked on the host)
+    const int c = act ? q * 4 : 0;
+    const int jfull = J - J % NS;
+    float4 at = make_float4(0.f, 0.f, 0.f, 0.f), aw[EMB_MAXDIN];
+#pragma unroll
+    for (int k = 0; k < EMB_MAXDIN; ++k) aw[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (act) {
+        for (int j = sl; j < jfull; j += NS) {
+            float4 ap = make_float4(0.f, 0.f, 0.f, 0.f);
+            embed_bwd_walk(dh, dh_a, dh_b, x, B, T, J, Din, C, t, j, c, 0, 1, ap, aw);
+            *reinterpret_cast<float4*>(prow + (size_t)j * C + c) = ap;
+            add4(at, ap);
+        }
+    }
+    // the joints left over: every slice takes its clips, slice 0 folds them and writes the dpos partial
+    for (int j = jfull; j < J; ++j) {
+        float4 ap = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (act) embed_bwd_walk(dh, dh_a, dh_b, x, B, T, J, Din, C, t, j, c, sl, NS, ap, aw);
+        ap = embed_bwd_fold<QB, NS>(ap, red, sl, ql);
+        if (act && sl == 0) {
+            *reinterpret_cast<float4*>(prow + (size_t)j * C + c) = ap;
+            add4(at, ap);
+        }
+    }
+    // the slices' dtemp / db and dw sums
+    at = embed_bwd_fold<QB, NS>(at, red, sl, ql);
+    if (act && sl == 0) {
+        *reinterpret_cast<float4*>(dtemp + (size_t)t * C + c) = at;
+        *reinterpret_cast<float4*>(prow + (size_t)J * C + (size_t)C * Din + c) = at;
+    }
+#pragma unroll
+    for (int k = 0; k < EMB_MAXDIN; ++k)
+        if (k < Din) {
+            const float4 w4 = embed_bwd_fold<QB, NS>(aw[k], red, sl, ql);
+            if (act && sl == 0) {
+                float* d = prow + (size_t)J * C + (size_t)c * Din + k;
+                d[0] = w4.x; d[Din] = w4.y; d[2 * Din] = w4.z; d[3 * Din] = w4.w;
+            }
+        }
 }
 // dx[m,k] = sum_c dh[m,c] w[c,k]  (one wave per token)
 __global__ __launch_bounds__(256) void embed_bwd_dx_kernel(const float* __restrict__ dh, const float* __restrict__ w,
@@ -542,11 +579,14 @@ static int launch_embed_bwd(const float* dh, const bf16_t* dh_a, const bf16_t* d
     hipStream_t s = (hipStream_t)stream;
     float* part = (float*)ws;
     const int stride = J * C + C * Din + C;
-    hipLaunchKernelGGL(embed_bwd_kernel, dim3(T), dim3(256), 0, s, dh, x, dtemp, part, B, T, J, Din, C, dh_a, dh_b);
+    const int nq = C / 4;
+#define EMBED_BWD_LAUNCH(QBV, NSV)                                                                                                  \
+    hipLaunchKernelGGL((embed_bwd_kernel<QBV, NSV>), dim3(T, (nq + QBV - 1) / QBV), dim3(QBV * NSV), 0, s, dh, x, dtemp, part, B, T, J, Din, \
+                       C, dh_a, dh_b)
+    if (nq >= 256) EMBED_BWD_LAUNCH(256, 4); else if (nq >= 128) EMBED_BWD_LAUNCH(128, 8); else EMBED_BWD_LAUNCH(64, 16);
     MBX_LAUNCH_CHECK("embed_bwd");
-    if (mbx_launch_colsum(part, T, stride, 0, J * C, dpos, s)) return 1;
-    if (mbx_launch_colsum(part, T, stride, J * C, C * Din, dw, s)) return 1;
-    if (mbx_launch_colsum(part, T, stride, J * C + C * Din, C, db, s)) return 1;
+    // one finalize launch, three outputs: dpos [J*C] | dw [C*Din] | db [C]
+    if (launch_colsum_out(part, T, stride, 0, stride, ColOut{{dpos, dw, db}, J * C, J * C + C * Din, stride}, s)) return 1;
     if (dx) {
         const int M = B * T * J;
         hipLaunchKernelGGL(embed_bwd_dx_kernel, dim3(clamp_grid((M + 3) / 4, 2048)), dim3(256), 0, s, dh, w, dx, M, Din, C, dh_a, dh_b);
@@ -702,6 +742,85 @@ static int launch_layernorm_fwd(const float* x, const float* gamma, const float*
         if (full) { LN_FWD_LAUNCH(float, true); } else { LN_FWD_LAUNCH(float, false); }
     }
     MBX_LAUNCH_CHECK("layernorm_fwd");
+    return 0;
+}
+
+// Embedding + the plain normalisation (no gamma / beta) of its own rows, for the folded path: level 0 reads h only to normalise it, so
+// the rows are normalised where they are made (one wave per row, two rows per iteration).  h is embed_fwd's (the same
+// fma chain over k and the same association), xhat / mean / rstd are ln_fwd_row's on those values: the bits of the two launches.
+template <int VPL, bool FULL>
+__device__ __forceinline__ void embed_row(const float* __restrict__ x, const float* __restrict__ pos, const float* __restrict__ temp,
+                                          const float (&wv)[VPL][4][EMBF_MAXDIN], const float (&bb)[VPL][4], int row, int T, int J, int Din,
+                                          int C, int lane, float* __restrict__ h, float4 (&raw)[VPL]) {
+    const int j = row % J, t = (row / J) % T;
+    float xv[EMBF_MAXDIN];
+#pragma unroll
+    for (int kk = 0; kk < EMBF_MAXDIN; ++kk) xv[kk] = kk < Din ? x[(size_t)row * Din + kk] : 0.f;
+    ROW_LOOP(k) {
+        const int c = ROW_C(k);
+        raw[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (FULL || c < C) {
+            const float4 pp = ld4(pos + (size_t)j * C + c), tt = ld4(temp + (size_t)t * C + c);
+            float a[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int kk = 0; kk < EMBF_MAXDIN; ++kk)
+                if (kk < Din) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) a[e] = fmaf(xv[kk], wv[k][e][kk], a[e]);
+                }
+            raw[k] = make_float4(((a[0] + bb[k][0]) + pp.x) + tt.x, ((a[1] + bb[k][1]) + pp.y) + tt.y, ((a[2] + bb[k][2]) + pp.z) + tt.z,
+                                 ((a[3] + bb[k][3]) + pp.w) + tt.w);
+            *reinterpret_cast<float4*>(h + (size_t)row * C + c) = raw[k];
+        }
+    }
+}
+template <int VPL, bool FULL>
+__global__ __launch_bounds__(256) void embed_ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                           const float* __restrict__ b, const float* __restrict__ pos,
+                                                           const float* __restrict__ temp, float eps, float* __restrict__ h,
+                                                           bf16_t* __restrict__ xhat, float* __restrict__ mean, float* __restrict__ rstd,
+                                                           int M, int T, int J, int Din, int C) {
+    const int lane = threadIdx.x & 63;
+    float wv[VPL][4][EMBF_MAXDIN], bb[VPL][4], g[VPL][4], bt[VPL][4];
+    ROW_LOOP(k) {
+        const int c = ROW_C(k);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            g[k][e] = 1.f; bt[k][e] = 0.f; bb[k][e] = 0.f;
+#pragma unroll
+            for (int kk = 0; kk < EMBF_MAXDIN; ++kk) wv[k][e][kk] = (kk < Din && (FULL || c < C)) ? w[(size_t)(c + e) * Din + kk] : 0.f;
+        }
+        if (FULL || c < C) load4<float>(b + c, bb[k]);
+    }
+    const float invC = 1.0f / (float)C;
+    for (int row0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 2; row0 < M; row0 += gridDim.x * 8) {      // two consecutive rows
+        const int row1 = row0 + 1;
+        float4 ra[VPL], rb[VPL];
+        embed_row<VPL, FULL>(x, pos, temp, wv, bb, row0, T, J, Din, C, lane, h, ra);
+        if (row1 < M) embed_row<VPL, FULL>(x, pos, temp, wv, bb, row1, T, J, Din, C, lane, h, rb);
+        ln_fwd_row<bf16_t, VPL, FULL>(ra, g, bt, eps, invC, xhat, mean, rstd, row0, C, lane);
+        if (row1 < M) ln_fwd_row<bf16_t, VPL, FULL>(rb, g, bt, eps, invC, xhat, mean, rstd, row1, C, lane);
+    }
+}
+#define EMBED_LN_LAUNCH(VPLV, FULLV)                                                                                              \
+    hipLaunchKernelGGL((embed_ln_fwd_kernel<VPLV, FULLV>), dim3(grid), dim3(256), 0, (hipStream_t)stream, x, w, b, pos, temp, eps, h, \
+                       (bf16_t*)xhat, mean, rstd, M, T, J, Din, C)
+extern "C" int mbx_embed_ln_fwd(const float* x, const float* w, const float* b, const float* pos, const float* temp, float eps, float* h,
+                                void* xhat, float* mean, float* rstd, int B, int T, int J, int Din, int C, void* stream) {
+    MBX_CHECK_ARG(x && w && b && pos && temp && h && xhat && mean && rstd, "embed_ln_fwd: null pointer");
+    MBX_CHECK_ARG(B > 0 && T > 0 && J > 0 && Din > 0 && Din <= EMBF_MAXDIN && C > 0 && C % 4 == 0 && C <= 1024,
+                  "embed_ln_fwd: bad shape (need dim_in <= %d, C %% 4 == 0, C <= 1024)", EMBF_MAXDIN);
+    MBX_CHECK_ARG((size_t)B * T * J < ((size_t)1 << 31), "embed_ln_fwd: %zu rows do not fit a 32-bit row index", (size_t)B * T * J);
+    const int M = B * T * J;
+    const int grid = clamp_grid((M + 3) / 4, LN_BLOCKS);
+    const int vpl = vpl_for(C);
+    const bool full = C == vpl * 256;
+    switch (vpl) {
+        case 1: if (full) { EMBED_LN_LAUNCH(1, true); } else { EMBED_LN_LAUNCH(1, false); } break;
+        case 2: if (full) { EMBED_LN_LAUNCH(2, true); } else { EMBED_LN_LAUNCH(2, false); } break;
+        default: if (full) { EMBED_LN_LAUNCH(4, true); } else { EMBED_LN_LAUNCH(4, false); } break;
+    }
+    MBX_LAUNCH_CHECK("embed_ln_fwd");
     return 0;
 }
 
@@ -1365,33 +1484,57 @@ extern "C" int mbx_average_bwd(const float* dh, float* d_st, float* d_ts, void* 
 // head: Linear(R -> Dout), Dout <= 8 (skinny: VALU dot products, wave reduction)
 // ------------------------------------------------------------------------------------------------
 #define HEAD_MAXD 8
+// rows in flight per wave: a wave takes RU consecutive rows per iteration and issues every load of them before the first dot
+// product (one row at a time left both kernels at 2.7 TB/s).  Forward: four rows of up to 512 channels; backward: six (at 512 channels two
+// waves per SIMD fit either way: the weight-gradient accumulators take the registers)
+#define HEAD_RU(VPL) ((VPL) <= 2 ? 4 : (VPL) == 4 ? 2 : 1)
+#define HEAD_BWD_RU(VPL) ((VPL) <= 2 ? 6 : HEAD_RU(VPL))
 template <int VPL>
 __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__ rep, const float* __restrict__ w,
                                                        const float* __restrict__ b, float* __restrict__ out, int M, int R,
                                                        int Dout) {
+    constexpr int RU = HEAD_RU(VPL);
     const int lane = threadIdx.x & 63;
-    for (int row = blockIdx.x * 4 + (threadIdx.x >> 6); row < M; row += gridDim.x * 4) {
-        float v[VPL][4];
-        ROW_LOOP(k) {
-            const int c = ROW_C(k);
-            if (c < R) load4<float>(rep + (size_t)row * R + c, v[k]);
+    for (int row0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * RU; row0 < M; row0 += gridDim.x * 4 * RU) {      // RU consecutive rows
+        float v[RU][VPL][4];
+#pragma unroll
+        for (int u = 0; u < RU; ++u) {
+            const int row = min(row0 + u, M - 1);      // (rows past M: a second read of the last row, never stored)
+            ROW_LOOP(k) {
+                const int c = ROW_C(k);
+                if (c < R) load4<float>(rep + (size_t)row * R + c, v[u][k]);
+            }
         }
-        float mine = 0.f;
+        float mine[RU];
+#pragma unroll
+        for (int u = 0; u < RU; ++u) mine[u] = 0.f;
         for (int i = 0; i < Dout; ++i) {
-            float a = 0.f;
+            float a[RU];
+#pragma unroll
+            for (int u = 0; u < RU; ++u) a[u] = 0.f;
             ROW_LOOP(k) {
                 const int c = ROW_C(k);
                 if (c < R) {
                     float ww[4];
                     load4<float>(w + (size_t)i * R + c, ww);
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) a = fmaf(v[k][e], ww[e], a);
+                    for (int u = 0; u < RU; ++u)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) a[u] = fmaf(v[u][k][e], ww[e], a[u]);
                 }
             }
-            a = wave_sum(a) + b[i];
-            if (lane == i) mine = a;
+            const float bi = b[i];
+#pragma unroll
+            for (int u = 0; u < RU; ++u) {
+                const float t = wave_sum(a[u]) + bi;
+                if (lane == i) mine[u] = t;
+            }
         }
-        if (lane < Dout) out[(size_t)row * Dout + lane] = mine;
+#pragma unroll
+        for (int u = 0; u < RU; ++u) {
+            const int row = row0 + u;
+            if (row < M && lane < Dout) out[(size_t)row * Dout + lane] = mine[u];
+        }
     }
 }
 extern "C" int mbx_head_fwd(const float* rep, const float* w, const float* b, float* out, int M, int R, int Dout,
@@ -1430,40 +1573,68 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
                 for (int e = 0; e < 4; ++e) gw[j][k][e] = 0.f;
             }
         }
-        for (int row = blockIdx.x * 4 + wave; row < M; row += gridDim.x * 4) {
-            float dvg[DG];
+        // RU rows in flight: all their loads first, then the rows one after another in row order; the weight rows of dpre are loaded
+        // once per iteration
+        constexpr int RU = HEAD_BWD_RU(VPL);
+        for (int row0 = (blockIdx.x * 4 + wave) * RU; row0 < M; row0 += gridDim.x * 4 * RU) {
+            float r[RU][VPL][4], dvg[RU][DG];
+            int rows[RU];
 #pragma unroll
-            for (int j = 0; j < DG; ++j) dvg[j] = i0 + j < Dout ? dout[(size_t)row * Dout + i0 + j] : 0.f;
+            for (int u = 0; u < RU; ++u) {
+                const int row = min(row0 + u, M - 1);      // (rows past M: read again, neither summed nor stored)
+                ROW_LOOP(k) {
+                    const int c = ROW_C(k);
+                    if (c < R) load4<float>(rep + (size_t)row * R + c, r[u][k]);
+                }
 #pragma unroll
-            for (int j = 0; j < DG; ++j) gbv[j] += dvg[j];
-            float dv[HEAD_MAXD];
-            if (i0 == 0) {
-#pragma unroll
-                for (int q = 0; q < HEAD_MAXD; ++q) dv[q] = q < DG ? dvg[q < DG ? q : 0] : (q < Dout ? dout[(size_t)row * Dout + q] : 0.f);
+                for (int j = 0; j < DG; ++j) dvg[u][j] = i0 + j < Dout ? dout[(size_t)row * Dout + i0 + j] : 0.f;
+                rows[u] = row;
             }
-            ROW_LOOP(k) {
-                const int c = ROW_C(k);
-                if (c < R) {
-                    float r[4];
-                    load4<float>(rep + (size_t)row * R + c, r);
 #pragma unroll
-                    for (int j = 0; j < DG; ++j)
+            for (int u = 0; u < RU; ++u) {
+                if (row0 + u < M) {
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) gw[j][k][e] = fmaf(dvg[j], r[e], gw[j][k][e]);
-                    if (i0 == 0) {      // dpre = (dout . w) (1 - rep^2): all Dout weights, once
-                        float o[4] = {0.f, 0.f, 0.f, 0.f};
+                    for (int j = 0; j < DG; ++j) gbv[j] += dvg[u][j];
+                    ROW_LOOP(k) {
+                        const int c = ROW_C(k);
+                        if (c < R) {
+#pragma unroll
+                            for (int j = 0; j < DG; ++j)
+#pragma unroll
+                                for (int e = 0; e < 4; ++e) gw[j][k][e] = fmaf(dvg[u][j], r[u][k][e], gw[j][k][e]);
+                        }
+                    }
+                }
+            }
+            if (i0 == 0) {      // dpre = (dout . w) (1 - rep^2): all Dout weights, once
+                ROW_LOOP(k) {
+                    const int c = ROW_C(k);
+                    if (c < R) {
+                        float o[RU][4];
+#pragma unroll
+                        for (int u = 0; u < RU; ++u)
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) o[u][e] = 0.f;
 #pragma unroll
                         for (int q = 0; q < HEAD_MAXD; ++q) {
                             if (q < Dout) {
                                 float ww[4];
                                 load4<float>(w + (size_t)q * R + c, ww);
 #pragma unroll
-                                for (int e = 0; e < 4; ++e) o[e] = fmaf(dv[q], ww[e], o[e]);
+                                for (int u = 0; u < RU; ++u) {
+                                    // (the first group's gradients are in registers; dim_out > 4 reads the others where it needs them)
+                                    const float dq = q < DG ? dvg[u][q < DG ? q : 0] : dout[(size_t)rows[u] * Dout + q];
+#pragma unroll
+                                    for (int e = 0; e < 4; ++e) o[u][e] = fmaf(dq, ww[e], o[u][e]);
+                                }
                             }
                         }
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) o[e] *= (1.0f - r[e] * r[e]);
-                        store4<T>(dpre + (size_t)row * R + c, o);
+                        for (int u = 0; u < RU; ++u) {
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) o[u][e] *= (1.0f - r[u][k][e] * r[u][k][e]);
+                            if (row0 + u < M) store4<T>(dpre + (size_t)(row0 + u) * R + c, o[u]);
+                        }
                     }
                 }
             }
@@ -1503,9 +1674,8 @@ extern "C" int mbx_head_bwd(const float* dout, const float* rep, const float* w,
         return mbx_set_error("head_bwd: unknown dtype %d", dtype);
     }
     MBX_LAUNCH_CHECK("head_bwd");
-    if (mbx_launch_colsum(part, grid, n, 0, Dout * R, dw, s)) return 1;
-    if (mbx_launch_colsum(part, grid, n, Dout * R, Dout, db, s)) return 1;
-    return 0;
+    // one finalize launch: dw [Dout*R] | db (the first Dout of the row's 8)
+    return launch_colsum_out(part, grid, n, 0, n, ColOut{{dw, db, nullptr}, Dout * R, n, Dout * R + Dout}, s);
 }
 
 // tanh backward on the representation path: dpre = drep * (1 - rep^2)

@@ -445,7 +445,13 @@ class Engine:
         self.rawln = not need_grad and self.fold and self.drop_seed is None and self.rawln_allowed and self._can('can_fuse_mlp')
         self.prepare_weights(need_grad)
         h = self._f(M, C)
-        if ragged is not None and tta_perm is not None:
+        pos_drop = self.drop_seed is not None and cfg.drop > 0
+        ln0 = None      # (xhat, mean, rstd) of h when the embedding kernel normalises its own rows (folded path, plain batch, no pos_drop)
+        if (hasattr(ops, 'embed_ln_fwd') and self.fold and not self.rawln and not pos_drop and ragged is None and tta_perm is None
+                and self._can('can_embed_ln')):
+            ln0 = (self._t(M, C), self._f(M), self._f(M))
+            ops.embed_ln_fwd(x, P['joints_embed.weight'], P['joints_embed.bias'], P['pos_embed'], P['temp_embed'], cfg.eps, h, *ln0, B, T, J)
+        elif ragged is not None and tta_perm is not None:
             ops.embed_fwd_tta_ragged(x, tta_perm, P['joints_embed.weight'], P['joints_embed.bias'], P['pos_embed'], P['temp_embed'], frame_t, h, T, J)
         elif ragged is not None:
             ops.embed_fwd_ragged(x, P['joints_embed.weight'], P['joints_embed.bias'], P['pos_embed'], P['temp_embed'], frame_t, h, T, J)
@@ -453,7 +459,7 @@ class Engine:
             ops.embed_fwd_tta(x, tta_perm, P['joints_embed.weight'], P['joints_embed.bias'], P['pos_embed'], P['temp_embed'], h, B // 2, T, J)
         else:
             ops.embed_fwd(x, P['joints_embed.weight'], P['joints_embed.bias'], P['pos_embed'], P['temp_embed'], h, B, T, J)
-        if self.drop_seed is not None and cfg.drop > 0:      # pos_drop (DSTformer.py:337)
+        if pos_drop:      # (DSTformer.py:337)
             from .dropmask import site_seed
             ops.dropout(h, h, cfg.drop, site_seed(self.drop_seed, -1, 0, 0, 1))
         saved: Dict[str, Any] = dict(x=x, levels=[], return_rep=return_rep)
@@ -463,7 +469,7 @@ class Engine:
         if self.fold and not self.rawln:
             # folded: both Blocks of a level read the SAME plain normalisation of h (their gamma / beta live in their own weights) -- one
             # launch for level 0 too, as the fusion kernel provides one xhat for the later levels
-            ln_st = ln_ts = self._layernorm(h, None)
+            ln_st = ln_ts = ln0 if ln0 is not None else self._layernorm(h, None)
         for i in range(cfg.depth):
             if side is not None:
                 side.wait_stream(main)

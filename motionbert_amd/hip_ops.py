@@ -29,6 +29,7 @@ SIGNATURES = {
     'mbx_version': (_i, []),
     'mbx_prep_weights': (_i, [_i64p, _i, _i, _i, _i, _vp]),
     'mbx_embed_fwd': (_i, [_vp] * 6 + [_i] * 5 + [_vp]),
+    'mbx_embed_ln_fwd': (_i, [_vp] * 5 + [_f] + [_vp] * 4 + [_i] * 5 + [_vp]),
     'mbx_embed_bwd_ws': (_sz, [_i] * 4),
     'mbx_embed_bwd': (_i, [_vp] * 8 + [_i] * 5 + [_vp, _vp]),
     'mbx_embed_bwd_pair': (_i, [_vp] * 9 + [_i] * 5 + [_vp, _vp]),
@@ -491,6 +492,18 @@ class HipOps:
     def embed_fwd(self, x, w, b, pos, temp, h, B, T, J):
         self._ck(self.lib.mbx_embed_fwd(_p(x), _p(w), _p(b), _p(pos), _p(temp), _p(h), B, T, J, x.shape[-1], h.shape[-1],
                                         self._stream()))
+
+    @staticmethod
+    def can_embed_ln(tdtype, cfg) -> bool:
+        """mbx_embed_ln_fwd writes a bf16 xhat and keeps the embedding weights in registers: bf16, dim_in <= 4, dim_feat <= 1024."""
+        return tdtype == torch.bfloat16 and cfg.dim_in <= 4 and cfg.C <= 1024 and cfg.C % 4 == 0
+
+    def embed_ln_fwd(self, x, w, b, pos, temp, eps, h, xhat, mean, rstd, B, T, J):
+        """embed_fwd and the plain normalisation of its rows (layernorm_fwd(h, None, None)) in one launch; xhat bf16"""
+        if xhat.dtype != torch.bfloat16:
+            raise RuntimeError('libmbx: embed_ln_fwd writes a bf16 xhat')
+        self._ck(self.lib.mbx_embed_ln_fwd(_p(x), _p(w), _p(b), _p(pos), _p(temp), float(eps), _p(h), _p(xhat), _p(mean), _p(rstd), B, T, J,
+                                           x.shape[-1], h.shape[-1], self._stream()))
 
     def embed_bwd(self, dh, x, w, dw, db, dpos, dtemp, dx, B, T, J):
         Din, Cc = x.shape[-1], dh.shape[-1]
