@@ -787,6 +787,72 @@ int mbx_skeleton_project(const float* x, const double* view15, int F, int J, int
 int mbx_skeleton_raster(const int* jq, const int* bones, const unsigned char* colors, int F, int J, int Nb, int r_line, int r_out, int r_in,
                         int size, int ss, unsigned char* rgb, int* prim_id, void* stream);
 
+/* ---- video files from the device (csrc/jpeg.hip; motionbert_amd/video.py) -- mbx_version() >= 230 -------------------------------------------
+ * Baseline JPEG (ITU-T T.81, 8 bit, three components, one interleaved scan, the Annex K Huffman tables) exactly as libjpeg's default path
+ * computes it: the file equals the one libjpeg-turbo writes for the same pixels, quality, subsampling and restart interval, byte for byte.
+ * All arithmetic is int32.  sub: 0 = 4:4:4 (MCU 8 x 8: Y Cb Cr), 1 = 4:2:0 (MCU 16 x 16: Y00 Y01 Y10 Y11 Cb Cr); MCUs in raster order;
+ * n_mcu = ceil(W / m) ceil(H / m) with m = 8 or 16.
+ * mbx_jpeg_blocks: rgb [F,H,W,3] u8 -> coef [F, n_mcu, blocks per MCU, 64] i16, quantised, in zigzag order.
+ *   colour     Y = (19595 R + 38470 G + 7471 B + 32768) >> 16,  Cb = (-11059 R - 21709 G + 32768 B + 8421375) >> 16,
+ *              Cr = (32768 R - 27439 G - 5329 B + 8421375) >> 16
+ *   padding    a sample outside the image is the nearest one inside (last column, then last row)
+ *   4:2:0      chroma: rows padded to an even count, columns to a multiple of 16; c = (a + b + c + d + bias) >> 2 over each 2 x 2, bias 1 in
+ *              even output columns and 2 in odd ones; only then the last downsampled row is repeated down to the MCU height.  A luma block
+ *              of an MCU wholly beyond ceil(W / 8) block columns or ceil(H / 8) block rows is a dummy: AC 0, DC that of the preceding block
+ *              of the MCU; in a dummy bottom row both blocks take the DC of the block in front of the row
+ *   DCT        samples - 128, then MBX_JPEG_FDCT_PASS over the rows (first) and over the columns: the Loeffler-Ligtenberg-Moschytz
+ *              butterfly of libjpeg's slow-integer method, 13 constant bits, 2 pass-1 bits; the result is 8 times the DCT
+ *   quantise   q = clamp((base s + 50) / 100, 1, 255) with s = 5000 / quality below 50, else 200 - 2 quality, base = the Annex K table;
+ *              coef = sign(c) ((|c| + (8 q >> 1)) / (8 q))
+ * mbx_jpeg_entropy_sizes, then mbx_jpeg_entropy: coef as above -> F complete JFIF files back to back in data, file f at offsets[f] ..
+ * offsets[f+1] - 1 (offsets [F+1] i64 on the device).  A file is the header of mbx_jpeg_header (MBX_JPEG_HEADER_BYTES: SOI, APP0 JFIF 1.01, two
+ * DQT, SOF0, four DHT, DRI, SOS), the scan and EOI.  The scan: restart intervals of `restart` MCUs, RSTn with n = interval index mod 8 between
+ * them; per interval the DC predictors start at 0, every block is DC difference, then (run, size) symbols with ZRL only in front of a later
+ * non-zero coefficient and EOB unless coefficient 63 is non-zero; 0x00 after every 0xFF byte; the interval padded to a byte with 1-bits.
+ *   sizing     nothing is truncated and no buffer is sized by a guess: mbx_jpeg_entropy_sizes codes every interval without storing it, counts
+ *              its bytes after stuffing and leaves the offsets on the device; the caller reads offsets[F] -- the ONE host synchronisation of
+ *              an encode -- allocates data and calls mbx_jpeg_entropy with the same coef, parameters and ws, which codes the intervals again
+ *              straight into place.  data_bytes is checked against every store.
+ *   worst case a block is at most MBX_JPEG_MAX_BLOCK_BITS = 22 + 63 (16 + 10) bits: the longest DC code with its 11 bits, and 63 coefficients
+ *              of the longest AC code with 10 bits each (a ZRL stands for 16 zeros in fewer bits than 16 such coefficients; without a zero
+ *              there is no EOB).  The kernel's LDS buffer holds that many bits for every block of a piece.  Coefficients outside the baseline
+ *              range (a DC difference beyond +-2047, an AC beyond +-1023) are clamped to it, so the bound holds for any input
+ *   ws         >= mbx_jpeg_entropy_ws(F, H, W, sub, restart) bytes, 16-byte aligned; ws_bytes is checked
+ * F = 0 is a no-op.  Refused, not clamped: H or W outside [1, MBX_JPEG_MAX_SIZE], F > MBX_JPEG_MAX_FRAMES, quality outside [1, 100], restart
+ * outside [1, 65535], sub other than 0 or 1, a small ws or data.  Everything is launched on the caller's stream. */
+#define MBX_JPEG_MAX_SIZE 2048
+#define MBX_JPEG_MAX_FRAMES 65535
+#define MBX_JPEG_HEADER_BYTES 629
+#define MBX_JPEG_MAX_BLOCK_BITS (22 + 63 * 26)
+#define MBX_JPEG_DESCALE(x, n) (((x) + (1 << ((n) - 1))) >> (n))
+/* one pass over int d[8], in place; `first`: the row pass (outputs scaled up by 2 bits), else the column pass (scaled back down) */
+#define MBX_JPEG_FDCT_PASS(d, first)                                                                        \
+    do {                                                                                                    \
+        const int n_ = (first) ? 11 : 15;                                                                   \
+        const int t0_ = d[0] + d[7], t7_ = d[0] - d[7], t1_ = d[1] + d[6], t6_ = d[1] - d[6];               \
+        const int t2_ = d[2] + d[5], t5_ = d[2] - d[5], t3_ = d[3] + d[4], t4_ = d[3] - d[4];               \
+        const int t10_ = t0_ + t3_, t13_ = t0_ - t3_, t11_ = t1_ + t2_, t12_ = t1_ - t2_;                   \
+        d[0] = (first) ? (t10_ + t11_) << 2 : MBX_JPEG_DESCALE(t10_ + t11_, 2);                             \
+        d[4] = (first) ? (t10_ - t11_) << 2 : MBX_JPEG_DESCALE(t10_ - t11_, 2);                             \
+        const int za_ = (t12_ + t13_) * 4433;                                                               \
+        d[2] = MBX_JPEG_DESCALE(za_ + t13_ * 6270, n_);                                                     \
+        d[6] = MBX_JPEG_DESCALE(za_ - t12_ * 15137, n_);                                                    \
+        const int z5_ = (t4_ + t6_ + t5_ + t7_) * 9633;                                                     \
+        const int z1_ = -(t4_ + t7_) * 7373, z2_ = -(t5_ + t6_) * 20995;                                    \
+        const int z3_ = -(t4_ + t6_) * 16069 + z5_, z4_ = -(t5_ + t7_) * 3196 + z5_;                        \
+        d[7] = MBX_JPEG_DESCALE(t4_ * 2446 + z1_ + z3_, n_);                                                \
+        d[5] = MBX_JPEG_DESCALE(t5_ * 16819 + z2_ + z4_, n_);                                               \
+        d[3] = MBX_JPEG_DESCALE(t6_ * 25172 + z2_ + z3_, n_);                                               \
+        d[1] = MBX_JPEG_DESCALE(t7_ * 12299 + z1_ + z4_, n_);                                               \
+    } while (0)
+int mbx_jpeg_header(int H, int W, int quality, int sub, int restart, unsigned char* out);      /* out: MBX_JPEG_HEADER_BYTES of HOST memory */
+int mbx_jpeg_blocks(const unsigned char* rgb, int F, int H, int W, int quality, int sub, short* coef, void* stream);
+size_t mbx_jpeg_entropy_ws(int F, int H, int W, int sub, int restart);
+int mbx_jpeg_entropy_sizes(const short* coef, int F, int H, int W, int sub, int quality, int restart, long long* offsets, void* ws,
+                           size_t ws_bytes, void* stream);
+int mbx_jpeg_entropy(const short* coef, int F, int H, int W, int sub, int quality, int restart, const long long* offsets, unsigned char* data,
+                     long long data_bytes, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- measurement aid (bench.py`roofline.sustained_mfma_tflops`; not part of the model) --------------------------------------------
  * The bf16 MFMA rate the part sustains under its power cap with nothing but v_mfma_f32_32x32x16_bf16 in the loop (pseudo-random
  * operands; n_wg workgroups of 4 waves, `iters` x 16 MFMAs per wave).  ws: >= mbx_mfma_probe_ws(n_wg) bytes = a float sink

@@ -135,6 +135,11 @@ SIGNATURES = {
     'mbx_render_raster': (_i, [_vp, _vp, _vp] + [_i] * 5 + [_f] * 4 + [_vp, _vp, _vp, _vp, _sz, _vp]),
     'mbx_skeleton_project': (_i, [_vp, C.POINTER(C.c_double), _i, _i, _i, _i, _vp, _vp]),
     'mbx_skeleton_raster': (_i, [_vp, _vp, _vp] + [_i] * 8 + [_vp, _vp, _vp]),
+    'mbx_jpeg_header': (_i, [_i] * 5 + [_vp]),
+    'mbx_jpeg_blocks': (_i, [_vp] + [_i] * 5 + [_vp, _vp]),
+    'mbx_jpeg_entropy_ws': (_sz, [_i] * 5),
+    'mbx_jpeg_entropy_sizes': (_i, [_vp] + [_i] * 6 + [_vp, _vp, _sz, _vp]),
+    'mbx_jpeg_entropy': (_i, [_vp] + [_i] * 6 + [_vp, _vp, C.c_longlong, _vp, _sz, _vp]),
     'mbx_rows_n_pack_bytes': (_sz, [_i, _i]),
     'mbx_rows_lnbwd_t': (_i, [_vp] * 6 + [_i, _i, _i, _vp]),
     'mbx_rows_n_pack_many': (_i, [_i64p, _i, _i, _i, _vp]),
@@ -1225,6 +1230,43 @@ class HipOps:
         self._dense('skeleton_raster', torch.int32, F * S * S, dev, prim_id=prim_id)
         self._ck(self.lib.mbx_skeleton_raster(_p(jq), _p(bones), _p(colors), F, J, Nb, int(radii[0]), int(radii[1]), int(radii[2]), int(size), int(ss),
                                               _p(rgb), _p(prim_id), self._stream()))
+
+    # ------------------------------------------------------------------ video files (motionbert_amd/video.py)
+    @staticmethod
+    def _jpeg_blocks(H, W, sub):
+        m = 16 if sub else 8
+        return -(-H // m) * -(-W // m) * (6 if sub else 3)
+
+    def jpeg_ws(self, F, H, W, sub, restart, device):
+        """the workspace that jpeg_sizes fills and jpeg_emit reads (mbx_jpeg_entropy_ws)"""
+        return self._ws(('jpeg', F, H, W, sub, restart), self.lib.mbx_jpeg_entropy_ws, F, H, W, int(sub), int(restart), device=device)
+
+    def jpeg_blocks(self, rgb, quality, sub, coef):
+        """rgb [F,H,W,3] u8 -> coef [F, n_mcu, blocks per MCU, 64] i16, quantised, zigzag (mbx_jpeg_blocks)"""
+        if rgb.dim() != 4 or rgb.shape[3] != 3:
+            raise RuntimeError(f'libmbx: jpeg_blocks needs rgb [F,H,W,3], got {tuple(rgb.shape)}')
+        F, H, W, dev = rgb.shape[0], rgb.shape[1], rgb.shape[2], rgb.device
+        self._dense('jpeg_blocks', torch.uint8, F * H * W * 3, dev, rgb=rgb)
+        self._dense('jpeg_blocks', torch.int16, F * self._jpeg_blocks(H, W, sub) * 64, dev, coef=coef)
+        self._ck(self.lib.mbx_jpeg_blocks(_p(rgb), F, H, W, int(quality), int(sub), _p(coef), self._stream()))
+
+    def jpeg_sizes(self, coef, H, W, sub, quality, restart, offsets, ws):
+        """coef [F, ...] i16 -> offsets [F+1] i64 on the device: where every file will lie (mbx_jpeg_entropy_sizes); no host read"""
+        F, dev = coef.shape[0], coef.device
+        self._dense('jpeg_sizes', torch.int16, F * self._jpeg_blocks(H, W, sub) * 64, dev, coef=coef)
+        self._dense('jpeg_sizes', torch.int64, F + 1, dev, offsets=offsets)
+        self._dense('jpeg_sizes', torch.uint8, None, dev, ws=ws)
+        self._ck(self.lib.mbx_jpeg_entropy_sizes(_p(coef), F, int(H), int(W), int(sub), int(quality), int(restart), _p(offsets), _p(ws), ws.numel(),
+                                                 self._stream()))
+
+    def jpeg_emit(self, coef, H, W, sub, quality, restart, offsets, data, ws):
+        """the files themselves into data [offsets[F]] u8, with the coef, parameters and ws of jpeg_sizes (mbx_jpeg_entropy)"""
+        F, dev = coef.shape[0], coef.device
+        self._dense('jpeg_emit', torch.int16, F * self._jpeg_blocks(H, W, sub) * 64, dev, coef=coef)
+        self._dense('jpeg_emit', torch.int64, F + 1, dev, offsets=offsets)
+        self._dense('jpeg_emit', torch.uint8, None, dev, data=data, ws=ws)
+        self._ck(self.lib.mbx_jpeg_entropy(_p(coef), F, int(H), int(W), int(sub), int(quality), int(restart), _p(offsets), _p(data), data.numel(),
+                                           _p(ws), ws.numel(), self._stream()))
 
     # ------------------------------------------------------------------ dropout / drop-path (SURVEY 8 a15)
     def dropout(self, x, y, p, seed):

@@ -15,7 +15,9 @@ reference's perspective 3D axes as one constant matrix, bones and joints in the 
     skeleton_chunks(x3d, ...)               the same frames through the pipeline of render_chunks
     skeleton_radii(size, ss)                the reference's line and marker widths scaled to the image
 
-Not here: video encoding, the 2D overlay of `motion2video`, matplotlib's panes, grid and anti-aliasing, smooth shading, other mesh cameras,
+The file itself -- the frames compressed on the device and written as Motion-JPEG -- is motionbert_amd.video (`mesh_video`, `skeleton_video`).
+
+Not here: the 2D overlay of `motion2video`, matplotlib's panes, grid and anti-aliasing, smooth shading, other mesh cameras,
 several persons in one frame.
 
 There is no CPU path: without an injected kernel provider (`ops=`), tensors that are not on a ROCm device raise."""
