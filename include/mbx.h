@@ -787,6 +787,37 @@ int mbx_skeleton_project(const float* x, const double* view15, int F, int J, int
 int mbx_skeleton_raster(const int* jq, const int* bones, const unsigned char* colors, int F, int J, int Nb, int r_line, int r_out, int r_in,
                         int size, int ss, unsigned char* rgb, int* prim_id, void* stream);
 
+/* ---- crowd video frames (csrc/scene.hip; every tracked person of a video frame in one image) -- mbx_version() >= 240 ---------------------------
+ * The skeletons of mbx_skeleton_raster, any number per frame, in an image of W x H pixels (1 <= W, H <= MBX_RENDER_MAX_SIZE, W != H allowed, ss 1
+ * or 2), over one colour or over the frames of the video.  The reference draws one person; this has no counterpart there.
+ * mbx_scene_project: x [R,J,C] f32 on the device, C = 2 or 3, in video pixels (the output of in-the-wild inference with pixel coordinates; z is
+ * not used: inside one skeleton the plot order decides, as above) -> jq [R,J,2] i32 in 1/MBX_RENDER_SUB of a sample.  In float64:
+ *   xq = floor(double(x) (16 ss) + 0.5), yq likewise: the product is exact, the sum is rounded once.
+ * A joint with a component that is not finite or with |xq| or |yq| > 2^18 gives 2^30 in both components.  One launch.  R = 0 is a no-op.
+ * mbx_scene_raster: jq [R,J,2] i32; the scene table frame_ptr [Fv+1] i32, rows [n_entries] i32, person [n_entries] i32: video frame f shows the
+ * entries k = frame_ptr[f] .. frame_ptr[f+1] - 1 in drawing order, entry k is the skeleton jq[rows[k]] in the colours palette[person[k]];
+ * bones [Nb,2] i32; palette [P,Nb,3] u8 (P = 1: everybody in row 0, person is not looked at); radii as above; the background: bg_frames u8
+ * [bg_n,H,W,3] with bg_n = Fv or 1 (frame 0 for every video frame), or, with bg_frames null, the colour bg_rgb = r | g << 8 | b << 16
+ * -> rgb [Fv,H,W,3] u8 and, where given, prim_id [Fv, H ss, W ss] i32; every element is written exactly once.
+ *   coverage    samples, primitives, capsule and marker exactly as in mbx_skeleton_raster: the same int64 comparisons (csrc/skeleton_prim.h).
+ *               The bound stated there holds unchanged: W, H <= 2048 and ss <= 2 keep every sample centre within [8, 16 (4096 + 31) + 8].
+ *   winner      with rank = k - frame_ptr[f], the covering primitive with the largest id = rank 3 Nb + priority: a later person covers an
+ *               earlier one, inside a person the plot order decides.  A marker's white centre counts as white.  prim_id = that id, -1 where
+ *               nothing covers.  Ranks from 2^23 on are not drawn (the id is an int32).
+ *   background  a sample that nothing covers takes the colour, or the pixel of the background frame that holds it.
+ *   ss = 2      pixel = (a + b + c + d + 2) >> 2 of its four samples' channels, uncovered samples counting with the background pixel.
+ *   skipped     an entry with rows[k] outside [0,R) or, for P > 1, person[k] outside [0,P); frame_ptr values are cut to [0, n_entries] and
+ *               to ascending order.  The tables live on the device: the host cannot check them without a synchronisation.
+ * One workgroup per tile of 32 x 32 samples walks its frame's list MBX_SCENE_CHUNK persons at a time: one lane per person tests the box of
+ * the person's drawn joints, grown by the largest radius, against the tile; only the survivors' primitives are set up and tested.  Nothing
+ * caps the list.  One launch, no workspace, no global atomics.  Fv = 0 is a no-op; R = 0 or an empty table writes the background.  Refused: J,
+ * Nb, radii as in mbx_skeleton_raster, W, H or ss out of range, P < 1, n_entries > 2^30, bg_n other than 1 or Fv, a colour beyond 0xffffff. */
+#define MBX_SCENE_CHUNK 64
+int mbx_scene_project(const float* x, int R, int J, int C, int ss, int* jq, void* stream);
+int mbx_scene_raster(const int* jq, const int* frame_ptr, const int* rows, const int* person, int n_entries, const int* bones,
+                     const unsigned char* palette, int Fv, int R, int J, int Nb, int P, int r_line, int r_out, int r_in, int W, int H, int ss,
+                     const unsigned char* bg_frames, int bg_n, int bg_rgb, unsigned char* rgb, int* prim_id, void* stream);
+
 /* ---- video files from the device (csrc/jpeg.hip; motionbert_amd/video.py) -- mbx_version() >= 230 -------------------------------------------
  * Baseline JPEG (ITU-T T.81, 8 bit, three components, one interleaved scan, the Annex K Huffman tables) exactly as libjpeg's default path
  * computes it: the file equals the one libjpeg-turbo writes for the same pixels, quality, subsampling and restart interval, byte for byte.

@@ -4,7 +4,9 @@ from .evaluate import H36MEvaluator, pose_errors  # noqa: F401  (motionbert_amd.
 from .oneshot import OneShotEvaluator, OneShotStep, supcon_loss  # noqa: F401  (one-shot recognition: train_action_1shot.py)
 from .mesh import (MeshEvaluator, MeshLoss, MeshRegressor, MeshStep, SMPLRegressor, compute_error, compute_error_frames,  # noqa: F401
                    rot6d_to_rotmat_theta)                      # (mesh recovery: train_mesh.py)
+from .render import render_scene, scene_chunks, scene_table, track_palette  # noqa: F401  (every tracked person in one video frame)
+from .video import scene_video  # noqa: F401
 
 __all__ = ['DSTformer', 'H36MEvaluator', 'pose_errors', 'OneShotEvaluator', 'OneShotStep', 'supcon_loss', 'MeshEvaluator', 'MeshLoss',
-           'MeshRegressor', 'MeshStep', 'SMPLRegressor', 'compute_error', 'compute_error_frames', 'rot6d_to_rotmat_theta']
+           'MeshRegressor', 'MeshStep', 'SMPLRegressor', 'compute_error', 'compute_error_frames', 'rot6d_to_rotmat_theta', 'render_scene', 'scene_chunks', 'scene_table', 'track_palette', 'scene_video']
 __version__ = '0.1.0'

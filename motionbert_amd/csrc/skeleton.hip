@@ -7,19 +7,17 @@
 //                          up the frame's primitives (per bone: the capsule and the two markers) in LDS, each with the answer whether its box
 //                          meets the tile; a tile that none meets writes background and leaves.  Every lane owns a 2 x 2 quad of samples and
 //                          reads the records as broadcasts; the winner of a sample is the covering primitive of highest priority, a maximum
-//                          over a set.  The tile leaves through render_tile.h, as the mesh rasteriser's tiles do.
+//                          over a set.  The tile leaves through render_tile.h, as the mesh rasteriser's tiles do.  The primitive, its set-up
+//                          and its coverage test are in skeleton_prim.h, which scene.hip (any number of people per frame) shares.
 // Exactness.  Ends inside the guard |q| <= SK_GUARD = 2^18 and sample centres in [8, 16 (4096 + 31) + 8] give |s - a|, |b - a| < 2^19 + 2^10 per
 // component, so |p|^2, t, dd < 2^40 and the cross product is below 2^40 in magnitude: all int64.  r <= 2^11: r^2 dd < 2^62.  A cross product
 // of magnitude >= 2^31 has a square >= 2^62 > r^2 dd and is rejected before squaring; below that the square is < 2^62.  No product overflows.
-#include "render_tile.h"
+#include "skeleton_prim.h"
 #include <math.h>
 
 #pragma clang fp contract(off)
 
-#define SK_GUARD (1 << 18)
-#define SK_OUTSIDE (1 << 30)          // a joint that is not drawn: both components
 #define SK_MAX_PRIMS (3 * MBX_SKELETON_MAX_BONES)
-#define SK_WHITE 0x00ffffffu
 
 struct SkView {
     double m[12];                     // rows 0, 1 and 3 of the projection matrix
@@ -68,15 +66,6 @@ extern "C" int mbx_skeleton_project(const float* x, const double* view15, int F,
 // ---------------------------------------------------------------------------------------------------------------
 // tiles
 // ---------------------------------------------------------------------------------------------------------------
-struct SkPrim {                       // the capsule dist(s, [a, a + d]) <= r; a marker is the capsule with d = 0
-    int ax, ay, dx, dy;
-    long long dd, r2, r2dd;
-    int rin2;                         // a marker is white where |s - a|^2 <= rin2; -1: a capsule
-    unsigned col;
-    int hit;                          // the primitive is drawn and its box meets this tile
-    int pad;
-};
-
 __global__ __launch_bounds__(RD_THREADS) void skeleton_tile_kernel(const int* __restrict__ jq, const int* __restrict__ bones,
                                                                     const unsigned char* __restrict__ colors, int J, int Nb, int r_line, int r_out,
                                                                     int r_in, int S, int size, int ss, int tiles, unsigned char* __restrict__ rgb,
@@ -101,20 +90,10 @@ __global__ __launch_bounds__(RD_THREADS) void skeleton_tile_kernel(const int* __
         if ((unsigned)ia < (unsigned)J && (unsigned)ib < (unsigned)J) {
             const int* fj = jq + (size_t)f * 2 * J;
             const int ax = fj[2 * ia], ay = fj[2 * ia + 1], bx = fj[2 * ib], by = fj[2 * ib + 1];
-            if (min(min(ax, ay), min(bx, by)) >= -SK_GUARD && max(max(ax, ay), max(bx, by)) <= SK_GUARD) {      // the sentinel is outside
-                const int rad = part == 0 ? r_line : r_out;
-                r.ax = part == 2 ? bx : ax; r.ay = part == 2 ? by : ay;
-                r.dx = part == 0 ? bx - ax : 0; r.dy = part == 0 ? by - ay : 0;
-                r.dd = (long long)r.dx * r.dx + (long long)r.dy * r.dy;
-                r.r2 = (long long)rad * rad;
-                r.r2dd = r.r2 * r.dd;
-                r.rin2 = part == 0 ? -1 : r_in * r_in;
-                r.col = (unsigned)colors[3 * k] | (unsigned)colors[3 * k + 1] << 8 | (unsigned)colors[3 * k + 2] << 16;
-                // the sample centres of this tile span [c0, c0 + RD_SUB (RD_TILE - 1)] per axis
-                const int cx0 = tx * RD_TILE * RD_SUB + RD_SUB / 2, cy0 = ty * RD_TILE * RD_SUB + RD_SUB / 2, span = RD_SUB * (RD_TILE - 1);
-                r.hit = min(r.ax, r.ax + r.dx) - rad <= cx0 + span && max(r.ax, r.ax + r.dx) + rad >= cx0 &&
-                        min(r.ay, r.ay + r.dy) - rad <= cy0 + span && max(r.ay, r.ay + r.dy) + rad >= cy0;
-            }
+            if (sk_drawn(ax, ay, bx, by))
+                sk_setup(r, part, ax, ay, bx, by, r_line, r_out, r_in,
+                         (unsigned)colors[3 * k] | (unsigned)colors[3 * k + 1] << 8 | (unsigned)colors[3 * k + 2] << 16, tx * RD_TILE * RD_SUB + RD_SUB / 2,
+                         ty * RD_TILE * RD_SUB + RD_SUB / 2);
         }
         prims[tid] = r;
         if (r.hit) any_hit = 1;
@@ -128,18 +107,8 @@ __global__ __launch_bounds__(RD_THREADS) void skeleton_tile_kernel(const int* __
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 const int px = (sx + (s & 1)) * RD_SUB + RD_SUB / 2 - r.ax, py = (sy + (s >> 1)) * RD_SUB + RD_SUB / 2 - r.ay;
-                const long long pp = (long long)px * px + (long long)py * py;
-                const long long td = (long long)px * r.dx + (long long)py * r.dy;
-                bool cov;
-                if (td <= 0) {
-                    cov = pp <= r.r2;
-                } else if (td >= r.dd) {
-                    const int ex = px - r.dx, ey = py - r.dy;
-                    cov = (long long)ex * ex + (long long)ey * ey <= r.r2;
-                } else {
-                    const long long c = (long long)px * r.dy - (long long)py * r.dx;
-                    cov = c > -(1ll << 31) && c < (1ll << 31) && c * c <= r.r2dd;
-                }
+                long long pp;
+                const bool cov = sk_covers(r, px, py, pp);
                 const int key = 2 * k + (pp <= (long long)r.rin2 ? 1 : 0);
                 best[s] = cov ? max(best[s], key) : best[s];
             }

@@ -135,6 +135,8 @@ SIGNATURES = {
     'mbx_render_raster': (_i, [_vp, _vp, _vp] + [_i] * 5 + [_f] * 4 + [_vp, _vp, _vp, _vp, _sz, _vp]),
     'mbx_skeleton_project': (_i, [_vp, C.POINTER(C.c_double), _i, _i, _i, _i, _vp, _vp]),
     'mbx_skeleton_raster': (_i, [_vp, _vp, _vp] + [_i] * 8 + [_vp, _vp, _vp]),
+    'mbx_scene_project': (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    'mbx_scene_raster': (_i, [_vp] * 4 + [_i] + [_vp, _vp] + [_i] * 11 + [_vp, _i, _i, _vp, _vp, _vp]),
     'mbx_jpeg_header': (_i, [_i] * 5 + [_vp]),
     'mbx_jpeg_blocks': (_i, [_vp] + [_i] * 5 + [_vp, _vp]),
     'mbx_jpeg_entropy_ws': (_sz, [_i] * 5),
@@ -1230,6 +1232,46 @@ class HipOps:
         self._dense('skeleton_raster', torch.int32, F * S * S, dev, prim_id=prim_id)
         self._ck(self.lib.mbx_skeleton_raster(_p(jq), _p(bones), _p(colors), F, J, Nb, int(radii[0]), int(radii[1]), int(radii[2]), int(size), int(ss),
                                               _p(rgb), _p(prim_id), self._stream()))
+
+    # ------------------------------------------------------------------ crowd video frames (motionbert_amd/render.py)
+    def scene_project(self, x, ss, jq):
+        """x [R,J,2|3] f32 on the device, in video pixels -> jq [R,J,2] i32 (mbx_scene_project)"""
+        if x.dim() != 3 or x.shape[2] not in (2, 3):
+            raise RuntimeError(f'libmbx: scene_project needs x [R,J,2|3], got {tuple(x.shape)}')
+        R, J, C_, dev = x.shape[0], x.shape[1], x.shape[2], x.device
+        self._dense('scene_project', torch.float32, R * J * C_, dev, x=x)
+        self._dense('scene_project', torch.int32, R * J * 2, dev, jq=jq)
+        self._ck(self.lib.mbx_scene_project(_p(x), R, J, C_, int(ss), _p(jq), self._stream()))
+
+    def scene_raster(self, jq, frame_ptr, rows, person, bones, palette, radii, width, height, ss, background, rgb, prim_id=None):
+        """jq [R,J,2] i32, the scene table (frame_ptr [Fv+1], rows [n], person [n], i32), bones [Nb,2] i32, palette [P,Nb,3] u8, radii = (r_line,
+        r_out, r_in), background: three ints or u8 frames [Fv or 1,H,W,3] -> rgb [Fv,H,W,3] u8, prim_id [Fv, H ss, W ss] i32 or None
+        (mbx_scene_raster)"""
+        if (jq.dim() != 3 or jq.shape[2] != 2 or bones.dim() != 2 or bones.shape[1] != 2 or palette.dim() != 3 or palette.shape[1:] != (bones.shape[0], 3)
+                or frame_ptr.dim() != 1 or frame_ptr.numel() < 1 or rows.dim() != 1 or len(radii) != 3):
+            raise RuntimeError(f'libmbx: scene_raster needs jq [R,J,2], frame_ptr [Fv+1], rows [n], bones [Nb,2], palette [P,Nb,3] and three radii, got '
+                               f'{tuple(jq.shape)} / {tuple(frame_ptr.shape)} / {tuple(rows.shape)} / {tuple(bones.shape)} / {tuple(palette.shape)} / {radii!r}')
+        R, J, Nb, P, Fv, n, dev = jq.shape[0], jq.shape[1], bones.shape[0], palette.shape[0], frame_ptr.numel() - 1, rows.numel(), jq.device
+        W, H, ss = int(width), int(height), int(ss)
+        self._dense('scene_raster', torch.int32, R * J * 2, dev, jq=jq)
+        self._dense('scene_raster', torch.int32, Fv + 1, dev, frame_ptr=frame_ptr)
+        self._dense('scene_raster', torch.int32, n, dev, rows=rows, person=person)
+        self._dense('scene_raster', torch.int32, Nb * 2, dev, bones=bones)
+        self._dense('scene_raster', torch.uint8, P * Nb * 3, dev, palette=palette)
+        self._dense('scene_raster', torch.uint8, Fv * H * W * 3, dev, rgb=rgb)
+        self._dense('scene_raster', torch.int32, Fv * H * ss * W * ss, dev, prim_id=prim_id)
+        if isinstance(background, torch.Tensor):
+            if background.dim() != 4 or background.shape[0] not in (1, Fv):
+                raise RuntimeError(f'libmbx: scene_raster: background frames must be [{Fv} or 1,{H},{W},3], got {tuple(background.shape)}')
+            bg_n, bg_rgb = background.shape[0], 0
+            self._dense('scene_raster', torch.uint8, bg_n * H * W * 3, dev, background=background)
+        else:
+            r, g, b = (int(c) for c in background)
+            if not all(0 <= c <= 255 for c in (r, g, b)):
+                raise RuntimeError(f'libmbx: scene_raster: a background colour is three values in [0, 255], got {background!r}')
+            background, bg_n, bg_rgb = None, 1, r | g << 8 | b << 16
+        self._ck(self.lib.mbx_scene_raster(_p(jq), _p(frame_ptr), _p(rows), _p(person), n, _p(bones), _p(palette), Fv, R, J, Nb, P, int(radii[0]),
+                                           int(radii[1]), int(radii[2]), W, H, ss, _p(background), bg_n, bg_rgb, _p(rgb), _p(prim_id), self._stream()))
 
     # ------------------------------------------------------------------ video files (motionbert_amd/video.py)
     @staticmethod

@@ -14,11 +14,19 @@ reference's perspective 3D axes as one constant matrix, bones and joints in the 
                                             capsules and joints as ringed discs in the reference's plot order, exact in integers
     skeleton_chunks(x3d, ...)               the same frames through the pipeline of render_chunks
     skeleton_radii(size, ss)                the reference's line and marker widths scaled to the image
+    scene_table(frame_ids, ...)             the frames of every track (`wild.read_alphapose(frames=True)`) -> (frame_ptr, rows, person): who is
+                                            in which video frame, in drawing order (host, numpy)
+    render_scene(x3d, table, W, H, ...)     every tracked person of a video frame in one image of W x H pixels (csrc/scene.hip): x3d in video
+                                            pixels (`wild.infer(..., pixel=True)`: the dict of tracks, or a device tensor [R,J,2|3]) -> {'rgb': uint8
+                                            [Fv,H,W,3]} (+ 'prim_id', 'jq'), over a colour or over the video's own frames
+    scene_chunks(x3d, table, W, H, ...)     the same frames through the pipeline of render_chunks
+    track_palette(n)                        n distinct colour rows [n,16,3] for the persons of a scene, from an integer formula
 
-The file itself -- the frames compressed on the device and written as Motion-JPEG -- is motionbert_amd.video (`mesh_video`, `skeleton_video`).
+The file itself -- the frames compressed on the device and written as Motion-JPEG -- is motionbert_amd.video (`mesh_video`, `skeleton_video`, `scene_video`).
 
-Not here: the 2D overlay of `motion2video`, matplotlib's panes, grid and anti-aliasing, smooth shading, other mesh cameras,
-several persons in one frame.
+Not here: the 2D overlay of `motion2video`, matplotlib's panes, grid and anti-aliasing, smooth shading, other mesh cameras, several meshes
+in one frame, decoding the input video (the caller brings its frames as a tensor), track labels or text, ordering persons by estimated depth
+(the caller passes `order` to `scene_table`).
 
 There is no CPU path: without an injected kernel provider (`ops=`), tensors that are not on a ROCm device raise."""
 from __future__ import annotations
@@ -135,14 +143,15 @@ def render_mesh(verts, faces, cube=None, seq_lens=None, size: int = 1024, ss: in
 
 
 def _pipeline(F, chunk, size, dev, span):
-    """The frames [F,size,size,3] of `span(a, b, rgb)` (which launches the render of frames a .. b - 1 into the device tensor rgb) as host
+    """The frames [F,size,size,3] (`size` an int) or [F,H,W,3] (`size` = (H, W)) of `span(a, b, rgb)` (which launches the render of frames a .. b - 1 into the device tensor rgb) as host
     arrays, `chunk` frames at a time.  On the device two frame buffers and two pinned host buffers alternate: the copy of one chunk runs on a
     side stream under the render of the next, and the host waits once per chunk, for that chunk's copy."""
+    H, W = (size, size) if isinstance(size, int) else size
     spans = [(a, min(a + chunk, F)) for a in range(0, F, chunk)]
     n_buf = min(2, len(spans))
     piped = dev.type == 'cuda'
-    dbuf = [torch.empty(min(chunk, F), size, size, 3, dtype=torch.uint8, device=dev) for _ in range(n_buf)]
-    hbuf = [torch.empty(min(chunk, F), size, size, 3, dtype=torch.uint8, pin_memory=True) for _ in range(n_buf)] if piped else dbuf
+    dbuf = [torch.empty(min(chunk, F), H, W, 3, dtype=torch.uint8, device=dev) for _ in range(n_buf)]
+    hbuf = [torch.empty(min(chunk, F), H, W, 3, dtype=torch.uint8, pin_memory=True) for _ in range(n_buf)] if piped else dbuf
     side = torch.cuda.Stream(device=dev) if piped else None
     copied = [None] * n_buf
 
@@ -288,7 +297,8 @@ def render_skeleton(x3d, size: int = 1024, ss: int = 1, view=None, bones=None, c
     values (default SKELETON_VIEW, the reference's axes); `bones` [Nb,2] / `colors` [Nb,3]: joint pairs in plot order and their colours
     (default: the 16 H36M bones in the reference's colours); `radii` = (r_line, r_out, r_in) in 1/16 sample (default `skeleton_radii`).
     `ss = 2` averages 2 x 2 samples per pixel.  `out`: a uint8 [F,size,size,3] tensor to write 'rgb' into.  Two kernel calls; F = 0
-    returns empty tensors without a launch.  A dict of tracks is the caller's loop."""
+    returns empty tensors without a launch.  One person per frame, in the reference's own view; every tracked person of a video frame in one
+    image is `render_scene`."""
     where = 'render.render_skeleton'
     x3d, view, bones, colors, radii, want, prov = _check_skeleton(x3d, size, ss, view, bones, colors, radii, want, ops, where)
     F, dev = x3d.shape[0], x3d.device
@@ -315,3 +325,224 @@ def skeleton_chunks(x3d, size: int = 1024, ss: int = 1, view=None, bones=None, c
     def span(a, b, rgb):
         _render_skeleton(prov, x3d[a:b], view, bones, colors, radii, size, ss, rgb, ('rgb',))
     yield from _pipeline(F, chunk, size, x3d.device, span)
+
+
+# ------------------------------------------------------------------------------------------------ crowd frames (csrc/scene.hip)
+SCENE_WANT_KEYS = ('rgb', 'prim_id', 'jq')
+SCENE_CHUNK = 64                    # MBX_SCENE_CHUNK: the persons a tile culls at a time (the tests place their cases around it)
+MAX_PERSONS_PER_FRAME = 1 << 23     # prim_id packs rank 3 Nb + primitive into an int32
+
+
+def scene_table(frame_ids, n_frames=None, order=None):
+    """Who is in which video frame.  `frame_ids`: the dict idx -> int64 [F_idx] of `wild.read_alphapose(by_track=True, frames=True)`, or a
+    list of such arrays: the video frame of every row of every track.  Tracks count in the dict's order (the track ordinal), rows count
+    through the concatenated tracks, as the rows of the concatenated output of `wild.infer` do.  Returns numpy int32 arrays
+    `(frame_ptr [Fv+1], rows [R], person [R])`: video frame f shows the rows `rows[frame_ptr[f]:frame_ptr[f+1]]` in drawing order (a later
+    one is drawn on top) and `person[k]` is the track ordinal of entry k, its palette row.  Fv = `n_frames`, or 1 + the largest frame id.
+    Drawing order: ascending track ordinal, or, with `order` (a float array [R], one value per row), ascending `order`, stable: for
+    example each row's lowest image point, so that nearer people cover farther ones.  ValueError on negative ids, ids >= n_frames, an
+    `order` that is not finite or not [R], and on more than 2^23 persons in one frame."""
+    where = 'render.scene_table'
+    tracks = list(frame_ids.values()) if isinstance(frame_ids, dict) else list(frame_ids)
+    ids = []
+    for n, t in enumerate(tracks):
+        a = np.asarray(t)
+        if a.ndim != 1 or (a.size and a.dtype.kind not in 'iu'):
+            raise ValueError(f'{where}: the frame ids of track {n} must be a 1-D integer array, got {a.shape} {a.dtype}')
+        ids.append(a.astype(np.int64))
+    frame = np.concatenate(ids) if ids else np.zeros(0, np.int64)
+    person = np.concatenate([np.full(a.size, n, np.int64) for n, a in enumerate(ids)]) if ids else np.zeros(0, np.int64)
+    R = frame.size
+    if R and frame.min() < 0:
+        raise ValueError(f'{where}: negative frame id {int(frame.min())}')
+    if n_frames is None:
+        Fv = int(frame.max()) + 1 if R else 0
+    else:
+        Fv = int(n_frames)
+        if Fv < 0 or (R and frame.max() >= Fv):
+            raise ValueError(f'{where}: frame id {int(frame.max()) if R else None} with n_frames = {n_frames!r}')
+    if Fv >= 2 ** 31 - 1 or R >= 2 ** 31:
+        raise ValueError(f'{where}: {Fv} frames / {R} rows do not fit the int32 table')
+    if order is None:
+        by = np.argsort(frame, kind='stable')                                # rows come in track order already
+    else:
+        order = np.asarray(order)
+        if order.shape != (R,) or order.dtype.kind not in 'fiu' or not np.isfinite(order).all():
+            raise ValueError(f'{where}: order must be {R} finite values, one per row, got {order.shape} {order.dtype}')
+        by = np.lexsort((order.astype(np.float64), frame))                   # stable: by frame, then by order, then by row
+    count = np.bincount(frame, minlength=Fv) if R else np.zeros(Fv, np.int64)
+    if count.size and count.max() > MAX_PERSONS_PER_FRAME:
+        raise ValueError(f'{where}: {int(count.max())} persons in frame {int(count.argmax())}, at most {MAX_PERSONS_PER_FRAME}')
+    frame_ptr = np.concatenate([[0], np.cumsum(count)]).astype(np.int32)
+    return frame_ptr, by.astype(np.int32), person[by].astype(np.int32)
+
+
+def _hsv(h, s, v):
+    """integer HSV -> RGB: h in [0, 360), s and v in [0, 255]; floor divisions only"""
+    k, rem = divmod(h, 60)
+    p, q, t = v * (255 - s) // 255, v * (255 * 60 - s * rem) // (255 * 60), v * (255 * 60 - s * (60 - rem)) // (255 * 60)
+    return ((v, t, p), (q, v, p), (p, v, t), (p, q, v), (t, p, v), (v, p, q))[k]
+
+
+def track_palette(n: int, bones=None):
+    """n distinct colour rows for the persons of a scene -> numpy uint8 [n,Nb,3] (`bones` default: the 16 H36M bones).  Person i takes the hue
+    137 i mod 360 (the golden angle in whole degrees: 360 hues before one repeats) at one of four saturation / value levels (i // 360), the
+    middle bones in that colour, the left ones darker and the right ones paler, as the reference's three blues are.  Integer arithmetic with
+    floor divisions only: no RNG and no rounding that numpy and another machine could see differently.  No colour is white.  ValueError for n
+    outside [0, 1440]."""
+    if not isinstance(n, (int, np.integer)) or not 0 <= n <= 1440:
+        raise ValueError(f'render.track_palette: n must be an int in [0, 1440], got {n!r}')
+    bones = SKELETON_BONES if bones is None else [tuple(int(j) for j in b) for b in np.asarray(bones).reshape(-1, 2)]
+    out = np.zeros((n, len(bones), 3), np.uint8)
+    for i in range(n):
+        h, level = (137 * i) % 360, i // 360
+        s, v = 230 - 40 * level, 235 - 25 * level
+        mid, left, right = _hsv(h, s, v), _hsv(h, s, v * 3 // 5), _hsv(h, s * 3 // 5, v)
+        for k, b in enumerate(bones):
+            out[i, k] = left if b in _LEFT else right if b in _RIGHT else mid
+    return out
+
+
+def _check_scene(x3d, table, width, height, ss, bones, palette, radii, background, want, ops, where):
+    """-> (x [R,J,C] on the device, (frame_ptr, rows, person) int32 tensors, bones, palette [P,Nb,3], radii, background (a triple of ints or a
+    uint8 tensor [Fv or 1,H,W,3]), want, provider)"""
+    if isinstance(x3d, dict):                            # the result of `wild.infer` for a dict of tracks: concatenated in its order
+        parts = [v if isinstance(v, np.ndarray) else np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v) for v in x3d.values()]
+        if not parts or any(a.dtype != np.float32 or a.ndim != 3 or a.shape[1:] != parts[0].shape[1:] for a in parts):
+            raise ValueError(f'{where}: x3d as a dict must hold float32 arrays [F_idx, J, 2|3] of one J, got '
+                             f'{[(a.shape, str(a.dtype)) for a in parts][:4]}')
+        x3d = np.concatenate(parts)
+    if isinstance(x3d, np.ndarray):
+        if x3d.dtype != np.float32:
+            raise ValueError(f'{where}: x3d must be float32 [R, J, 2|3], got {x3d.shape} {x3d.dtype}')
+        x3d = torch.from_numpy(np.ascontiguousarray(x3d))
+        if ops is None:
+            if not torch.cuda.is_available():
+                raise RuntimeError(f'motionbert_amd.{where} runs on the ROCm device; there is no CPU path')
+            x3d = x3d.cuda()
+    if (not isinstance(x3d, torch.Tensor) or x3d.dtype != torch.float32 or x3d.dim() != 3 or x3d.shape[2] not in (2, 3)
+            or not 1 <= x3d.shape[1] <= MAX_JOINTS):
+        raise ValueError(f'{where}: x3d must be a dict of tracks, or a float32 tensor or array [R, 1 <= J <= {MAX_JOINTS}, 2|3], got '
+                         f'{tuple(x3d.shape) if hasattr(x3d, "shape") else type(x3d).__name__} {getattr(x3d, "dtype", "")}')
+    dev = x3d.device
+    for name, v in (('width', width), ('height', height)):
+        if not isinstance(v, int) or not 1 <= v <= MAX_SIZE:
+            raise ValueError(f'{where}: {name} must be an int in [1, {MAX_SIZE}], got {v!r}')
+    if ss not in (1, 2):
+        raise ValueError(f'{where}: ss must be 1 or 2, got {ss!r}')
+    if not isinstance(table, (tuple, list)) or len(table) != 3:
+        raise ValueError(f'{where}: table must be (frame_ptr, rows, person) as scene_table gives it')
+    tab = []
+    for name, t in zip(('frame_ptr', 'rows', 'person'), table):
+        if not isinstance(t, torch.Tensor):
+            a = np.asarray(t)
+            if a.ndim != 1 or a.dtype != np.int32:
+                raise ValueError(f'{where}: table {name} must be a 1-D int32 array, got {a.shape} {a.dtype}')
+            t = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        if t.dtype != torch.int32 or t.dim() != 1 or t.device != dev:
+            raise ValueError(f'{where}: table {name} must be a 1-D int32 tensor on {dev}, got {tuple(t.shape)} {t.dtype} on {t.device}')
+        tab.append(t.contiguous())
+    if tab[0].numel() < 1 or tab[1].numel() != tab[2].numel():
+        raise ValueError(f'{where}: table of {tab[0].numel()} frame_ptr / {tab[1].numel()} rows / {tab[2].numel()} person entries')
+    Fv = tab[0].numel() - 1
+    radii = skeleton_radii(min(width, height), ss) if radii is None else tuple(radii)
+    if (len(radii) != 3 or not all(isinstance(r, (int, np.integer)) for r in radii)
+            or not (0 <= radii[0] <= MAX_RADIUS and 0 <= radii[2] <= radii[1] <= MAX_RADIUS)):
+        raise ValueError(f'{where}: radii must be ints (r_line, r_out, r_in) with 0 <= r_line <= {MAX_RADIUS} and 0 <= r_in <= r_out <= {MAX_RADIUS}, '
+                         f'got {radii!r}')
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(k not in SCENE_WANT_KEYS for k in want):
+        raise ValueError(f'{where}: want must name some of {SCENE_WANT_KEYS}, got {want!r}')
+    if palette is None and bones is not None:
+        raise ValueError(f'{where}: palette must be given with bones, one colour for each')
+    bones = _table(SKELETON_BONES if bones is None else bones, torch.int32, 2, MAX_BONES, 'bones', dev, where)
+    if palette is None:
+        palette = np.array(SKELETON_COLORS, np.uint8)[None]
+    if not isinstance(palette, torch.Tensor):
+        a = np.asarray(palette)
+        if a.ndim != 3 or a.dtype.kind not in 'iu' or (a.size and (a.min() < 0 or a.max() > 255)):
+            raise ValueError(f'{where}: palette must be integers in [0, 255] [P,Nb,3], got {a.shape} {a.dtype}')
+        palette = torch.from_numpy(a.astype(np.uint8)).to(dev)
+    if palette.dtype != torch.uint8 or palette.dim() != 3 or palette.shape[0] < 1 or tuple(palette.shape[1:]) != (bones.shape[0], 3) or palette.device != dev:
+        raise ValueError(f'{where}: palette must be a uint8 tensor [P >= 1,{bones.shape[0]},3] on {dev}, got {tuple(palette.shape)} {palette.dtype} '
+                         f'on {palette.device}')
+    if background is None:
+        background = (255, 255, 255)
+    if isinstance(background, np.ndarray) and background.ndim == 4:
+        background = torch.from_numpy(np.ascontiguousarray(background)).to(dev)
+    if isinstance(background, torch.Tensor):
+        if (background.dtype != torch.uint8 or background.dim() != 4 or background.shape[0] not in (1, Fv)
+                or tuple(background.shape[1:]) != (height, width, 3) or background.device != dev):
+            raise ValueError(f'{where}: background frames must be a uint8 tensor [{Fv} or 1,{height},{width},3] on {dev}, got '
+                             f'{tuple(background.shape)} {background.dtype} on {background.device}')
+        background = background.contiguous()
+    else:
+        background = tuple(background)
+        if len(background) != 3 or not all(isinstance(c, (int, np.integer)) and 0 <= c <= 255 for c in background):
+            raise ValueError(f'{where}: background must be three ints in [0, 255] or uint8 frames [{Fv} or 1,{height},{width},3], got {background!r}')
+        background = tuple(int(c) for c in background)
+    prov = hip_ops.provider(ops, 'motionbert_amd.' + where, x3d)
+    return x3d.contiguous(), tuple(tab), bones, palette.contiguous(), tuple(int(r) for r in radii), background, want, prov
+
+
+def _render_scene(prov, jq, tab, a, b, bones, palette, radii, width, height, ss, background, rgb, want):
+    """video frames a .. b - 1: frame_ptr[a:b+1] keeps its offsets into the whole rows / person, so a span of frames is the same table"""
+    Fv = tab[0].numel() - 1
+    if isinstance(background, torch.Tensor) and background.shape[0] == Fv and Fv != 1:
+        background = background[a:b]
+    prim_id = torch.empty(b - a, height * ss, width * ss, dtype=torch.int32, device=tab[0].device) if 'prim_id' in want else None
+    if b > a:
+        prov.scene_raster(jq, tab[0][a:b + 1], tab[1], tab[2], bones, palette, radii, width, height, ss, background, rgb, prim_id)
+    return prim_id
+
+
+def _project_scene(prov, x, ss):
+    jq = torch.empty(x.shape[0], x.shape[1], 2, dtype=torch.int32, device=x.device)
+    if x.shape[0]:
+        prov.scene_project(x, ss, jq)
+    return jq
+
+
+def render_scene(x3d, table, width: int, height: int, ss: int = 1, bones=None, palette=None, radii=None, background=None, out=None, want=('rgb',),
+                 ops=None):
+    """Every tracked person of a video frame in one image.  `x3d`: the dict idx -> float32 [F_idx,J,2|3] of `wild.infer(..., pixel=True)` (host
+    arrays, concatenated in the dict's order and uploaded once) or a device tensor [R,J,2|3], in video pixels; z is not used.  `table` =
+    (frame_ptr, rows, person) as `scene_table` gives it for the same tracks (arrays are uploaded, device tensors taken as they are).  Returns a
+    dict of device tensors: 'rgb' uint8 [Fv,height,width,3] and, where `want` names them, the test hooks 'prim_id' int32 [Fv, height ss,
+    width ss] (rank in the frame's list x 3 Nb + the primitive of `render_skeleton`; -1 where empty) and 'jq' int32 [R,J,2].
+    `bones` [Nb,2] and `palette` [P,Nb,3] (or [1,Nb,3] for everybody): default the 16 H36M bones and the reference's three colours for
+    everybody (`track_palette(n)` gives one row per person); `radii` default `skeleton_radii(min(width, height), ss)`; `background`: three
+    ints (default white) or uint8 frames [Fv or 1,height,width,3], an array or a device tensor: the video's own frames.  A later entry of a
+    frame's list covers an earlier one.  Table entries that name no row of x3d or no row of the palette are not drawn.  Two kernel calls;
+    Fv = 0 returns empty frames without drawing (the projection runs only where 'jq' is wanted)."""
+    where = 'render.render_scene'
+    x, tab, bones, palette, radii, background, want, prov = _check_scene(x3d, table, width, height, ss, bones, palette, radii, background, want, ops,
+                                                                        where)
+    Fv, dev = tab[0].numel() - 1, x.device
+    if out is None:
+        out = torch.empty(Fv, height, width, 3, dtype=torch.uint8, device=dev)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (Fv, height, width, 3) or not out.is_contiguous()
+          or out.device != dev):
+        raise ValueError(f'{where}: out must be a contiguous uint8 tensor [{Fv},{height},{width},3] on {dev}')
+    res = {'rgb': out, 'jq': _project_scene(prov, x, ss) if Fv or 'jq' in want else None}
+    res['prim_id'] = _render_scene(prov, res['jq'], tab, 0, Fv, bones, palette, radii, width, height, ss, background, out, want)
+    return {k: res[k] for k in want}
+
+
+def scene_chunks(x3d, table, width: int, height: int, ss: int = 1, bones=None, palette=None, radii=None, background=None, chunk: int = 32, ops=None):
+    """A generator of host uint8 arrays [n,height,width,3], n <= `chunk` video frames at a time, in frame order: the frames of `render_scene`
+    through `_pipeline`, without ever holding them all.  Background frames given per video frame are sliced per chunk.  An array is valid
+    until the generator is advanced again."""
+    where = 'render.scene_chunks'
+    x, tab, bones, palette, radii, background, _, prov = _check_scene(x3d, table, width, height, ss, bones, palette, radii, background, ('rgb',), ops,
+                                                                     where)
+    if not isinstance(chunk, int) or chunk < 1:
+        raise ValueError(f'{where}: chunk must be a positive int, got {chunk!r}')
+    Fv = tab[0].numel() - 1
+    if Fv == 0:
+        return
+    jq = _project_scene(prov, x, ss)
+
+    def span(a, b, rgb):
+        _render_scene(prov, jq, tab, a, b, bones, palette, radii, width, height, ss, background, rgb, ('rgb',))
+    yield from _pipeline(Fv, chunk, (height, width), x.device, span)

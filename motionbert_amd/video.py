@@ -11,6 +11,7 @@ cross the host link.
                                                       idx1); `.write(host_bytes, offsets)`, `.close()`, a context manager; at most 2^31 - 1 bytes
     mesh_video(path, verts, faces, fps, ...)          render.render_mesh + encode_jpeg + MJPEGWriter, `chunk` frames at a time -> (frames, bytes)
     skeleton_video(path, x3d, fps, ...)               render.render_skeleton likewise
+    scene_video(path, x3d, table, W, H, fps, ...)     render.render_scene likewise: every tracked person in one video of the input's size
 
 One host synchronisation per encode: the sizes of the files are computed on the device first, the host reads their total and allocates, then the
 bytes are emitted straight into place.  In the *_video functions that wait falls under the copy of the chunk before.
@@ -246,12 +247,14 @@ def _video_pipeline(writer, prov, F, chunk, H, W, dev, span, quality, sub, resta
 
 
 def _run(path, fps, F, chunk, size, dev, span, prov, quality, subsampling, restart, where):
+    """`size`: an int (square frames) or (H, W)"""
+    H, W = (size, size) if isinstance(size, int) else size
     if not isinstance(chunk, int) or not 1 <= chunk <= MAX_FRAMES:
         raise ValueError(f'{where}: chunk must be an int in [1, {MAX_FRAMES}], got {chunk!r}')
-    restart = _check_coding(size, size, quality, subsampling, restart, where)
-    with MJPEGWriter(path, size, size, fps) as writer:
+    restart = _check_coding(H, W, quality, subsampling, restart, where)
+    with MJPEGWriter(path, W, H, fps) as writer:
         if F:
-            _video_pipeline(writer, prov, F, chunk, size, size, dev, span, quality, SUBSAMPLINGS.index(subsampling), restart)
+            _video_pipeline(writer, prov, F, chunk, H, W, dev, span, quality, SUBSAMPLINGS.index(subsampling), restart)
         frames = writer.frames
     return frames, writer.bytes
 
@@ -283,3 +286,18 @@ def skeleton_video(path, x3d, fps: float, quality: int = 90, subsampling: str = 
     def span(a, b, rgb):
         R._render_skeleton(prov, x3d[a:b], view, bones, colors, radii, size, ss, rgb, ('rgb',))
     return _run(path, fps, x3d.shape[0], chunk, size, x3d.device, span, prov, quality, subsampling, restart, where)
+
+
+def scene_video(path, x3d, table, width: int, height: int, fps: float, quality: int = 90, subsampling: str = '420', background=None, chunk: int = 32,
+                restart=None, ss: int = 1, bones=None, palette=None, radii=None, ops=None):
+    """The frames of `render.render_scene(x3d, table, width, height, ...)` as the Motion-JPEG AVI file `path` -> (frames, bytes of the file): every
+    tracked person in one video of the input's size; see `mesh_video`.  Background frames given per video frame are sliced per chunk."""
+    where = 'video.scene_video'
+    x, tab, bones, palette, radii, background, _, prov = R._check_scene(x3d, table, width, height, ss, bones, palette, radii, background, ('rgb',), ops,
+                                                                       where)
+    Fv = tab[0].numel() - 1
+    jq = R._project_scene(prov, x, ss) if Fv else None
+
+    def span(a, b, rgb):
+        R._render_scene(prov, jq, tab, a, b, bones, palette, radii, width, height, ss, background, rgb, ('rgb',))
+    return _run(path, fps, Fv, chunk, (height, width), x.device, span, prov, quality, subsampling, restart, where)

@@ -5,6 +5,8 @@
     poses = infer(model, kp)                                          # [F,17,3] float32, numpy
     tracks = read_alphapose('alphapose-results.json', by_track=True)  # idx -> [F_idx,26,3]
     poses = infer(model, tracks, vid_size=(1920, 1080), pixel=True)   # idx -> [F_idx,17,3], every tracked person in one pass
+    tracks, frame_ids = read_alphapose('alphapose-results.json', by_track=True, frames=True)      # + idx -> the video frame of every row:
+                                                                      # render.scene_table / render_scene / video.scene_video draw them all
 
 The reference runs one clip per forward at batch 1, two forwards per clip for the flip, two deep copies in `flip_data`, a `.cpu()` per
 clip, a numpy input stage on the host and one person per run (`--focus`).  Here the detections are uploaded once, `mbx_wild_input`
@@ -35,6 +37,7 @@ from __future__ import annotations
 
 import json
 import math
+import os
 from collections import OrderedDict
 from contextlib import nullcontext as _nullcontext
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -51,14 +54,30 @@ ROOTREL, GT_2D, OUT_PIXEL = 1, 2, 4      # flags of mbx_wild_output
 
 
 # ---------------------------------------------------------------------------------------------------------------- host: the JSON
-def read_alphapose(json_path, focus=None, by_track: bool = False):
+def _frame_id(image_id, json_path, n) -> int:
+    """the video frame an AlphaPose item belongs to: its `image_id` as an int, or the decimal file stem of a string"""
+    if isinstance(image_id, int) and not isinstance(image_id, bool):
+        return image_id
+    if isinstance(image_id, str):
+        stem = os.path.splitext(os.path.basename(image_id))[0]
+        if stem.isascii() and stem.isdigit():
+            return int(stem)
+    raise ValueError(f'{json_path}: item {n} has image_id {image_id!r}; an int or a file name with a decimal stem expected')
+
+
+def read_alphapose(json_path, focus=None, by_track: bool = False, frames: bool = False):
     """The detections of an AlphaPose result file (Halpe-26): items in file order, `keypoints` reshaped to [-1,3], float64
     (dataset_wild.py:67-76).  `focus`: only the items with that `idx`, as the reference filters.  Returns [F,26,3]; with
     `by_track=True` an ordered dict idx -> [F_idx,26,3], the keys in order of first appearance, file order inside a track.
-    ValueError on a joint count other than 26, on non-finite values and on an empty selection."""
+    ValueError on a joint count other than 26, on non-finite values and on an empty selection.
+    `frames=True` returns `(detections, frame_ids)`: the video frame of every row, int64 [F] (with `by_track=True` a dict idx -> int64
+    [F_idx]), from each item's `image_id`: an int, or a string whose file stem is a decimal number ('17.jpg' -> 17).  ValueError, naming the
+    item, on any other `image_id` and where the frame ids of a track do not rise strictly in file order.  It is what `render.scene_table`
+    takes to put every track of a crowd back into the frames of the video."""
     with open(json_path, 'r') as f:
         results = json.load(f)
     tracks: Dict[object, List[np.ndarray]] = OrderedDict()
+    ids: Dict[object, List[int]] = OrderedDict()
     for n, item in enumerate(results):
         if focus is not None and item['idx'] != focus:
             continue
@@ -68,11 +87,18 @@ def read_alphapose(json_path, focus=None, by_track: bool = False):
         if not np.isfinite(kpts).all():
             raise ValueError(f'{json_path}: item {n} has non-finite keypoints')
         tracks.setdefault(item['idx'] if by_track else None, []).append(kpts)
+        if frames:
+            seen = ids.setdefault(item['idx'] if by_track else None, [])
+            frame = _frame_id(item.get('image_id'), json_path, n)
+            if seen and frame <= seen[-1]:
+                raise ValueError(f'{json_path}: item {n} is frame {frame} after frame {seen[-1]} of the same track; frame ids must rise strictly')
+            seen.append(frame)
     if not tracks:
         raise ValueError(f'{json_path}: no detections' + ('' if focus is None else f' with idx == {focus!r}'))
     if by_track:
-        return OrderedDict((k, np.stack(v)) for k, v in tracks.items())
-    return np.stack(tracks[None])
+        det = OrderedDict((k, np.stack(v)) for k, v in tracks.items())
+        return (det, OrderedDict((k, np.asarray(v, dtype=np.int64)) for k, v in ids.items())) if frames else det
+    return (np.stack(tracks[None]), np.asarray(ids[None], dtype=np.int64)) if frames else np.stack(tracks[None])
 
 
 # ---------------------------------------------------------------------------------------------------------------- host: plans
