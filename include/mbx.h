@@ -884,6 +884,74 @@ int mbx_jpeg_entropy_sizes(const short* coef, int F, int H, int W, int sub, int 
 int mbx_jpeg_entropy(const short* coef, int F, int H, int W, int sub, int quality, int restart, const long long* offsets, unsigned char* data,
                      long long data_bytes, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- reading video on the device (csrc/jpeg_dec.hip; motionbert_amd/video.py) -- mbx_version() >= 250 ------------------------------------------
+ * Baseline JPEG decoded exactly as libjpeg's default path decodes it (jpeg_idct_islow, do_fancy_upsampling, 16-bit colour tables): the
+ * pixels equal the ones libjpeg-turbo gives, with no tolerance.  Accepted (the host parser, video.parse_jpeg, refuses the rest before a
+ * launch): SOF0, 8 bit, three components in one interleaved scan, luma sampling 1x1 (sub 0, 4:4:4), 2x2 (sub 1, 4:2:0) or 2x1 (sub 2,
+ * 4:2:2: MCU 16 x 8, Y0 Y1 Cb Cr) with chroma 1x1, 8-bit DQT, the file's Huffman tables or Annex K where it has none, DRI or not.
+ * All frames of a call share geometry, tables and restart interval.  restart = 0: no DRI, the frame is one interval; n_int =
+ * ceil(n_mcu / restart) otherwise, and interval k covers MCUs k restart .. k restart + restart - 1.
+ * mbx_jpeg_dec_tables (host to host): dht [6][272] u8 = (bits [16], vals [256]) of the DC and the AC table of components 0, 1, 2, or NULL
+ *   for Annex K -> out [6][MBX_JPEG_DEC_TABLE_WORDS]: per table an 8-bit look-ahead (256 x u16: length << 8 | symbol, 0: longer), maxcode
+ *   [18] and valoffset [18] i32 (libjpeg's), vals [256] u8.  Refused: more than 256 symbols, more codes than a length has, a DC symbol > 15.
+ * mbx_jpeg_dec_index: data u8 [data_bytes] (the files back to back, on the device), scans i64 [F,2] = where every frame's entropy-coded
+ *   bytes start and where its EOI marker lies (absolute, from the host parser; clamped into the buffer) -> pos i64 [F, n_int + 1] and
+ *   status i32 [F, n_int].  An RSTn is 0xFF followed by 0xD0 .. 0xD7; marker k closes interval k, which is data[pos[k] .. pos[k+1] - 3];
+ *   pos[0] = the start, pos[n_int] = the EOI's position + 2.  Unless the frame has n_int - 1 markers with n = k mod 8, every interval of
+ *   it gets MBX_JPEG_DEC_MARKERS, else MBX_JPEG_DEC_OK.
+ * mbx_jpeg_dec_entropy: T.81 F.2.2 per interval -> coef i16 [F, n_mcu, blocks per MCU, 64] in zigzag order (the layout mbx_jpeg_blocks
+ *   writes) and status.  Predictors start at 0; 0xFF 0x00 is one byte 0xFF; a DC value is stored modulo 2^16.  coef is zeroed first; an
+ *   interval whose status is not OK on entry is left zero.  A malformed interval has a defined result: its status is the first of
+ *     MBX_JPEG_DEC_TRUNCATED  the interval ends inside a symbol        MBX_JPEG_DEC_BAD_CODE  no such Huffman code, or an AC symbol (r, 0)
+ *     MBX_JPEG_DEC_RUN        a run or a ZRL passes coefficient 63                            with r other than 0 (EOB) and 15 (ZRL)
+ *     MBX_JPEG_DEC_LEFTOVER   all blocks decoded and 8 or more bits are left
+ *   and the block the error lies in and all later blocks of the interval are zero.  libjpeg's resynchronisation is not reproduced.
+ * mbx_jpeg_dec_pixels: coef, q u8 [3][64] (HOST memory: the quantisation table of each component in zigzag order, no entry 0) -> rgb u8
+ *   [F,H,W,3] at any address.  ws >= mbx_jpeg_dec_ws(F, H, W, sub) bytes holds the component planes, whole MCUs wide and high.
+ *   IDCT       multiply by the table, un-zigzag, MBX_JPEG_IDCT_PASS over the columns (shift 11) and then over the rows (shift 18) in
+ *              64-bit arithmetic (libjpeg's JLONG), then sample = limit[v & 1023] with limit = 128 .. 255, 255 x 384, 0 x 384, 0 .. 127
+ *   upsample   chroma has dh = ceil(H / v) real rows and dw = ceil(W / h) real columns c; nothing beyond them is read.  dw <= 2:
+ *              replicated.  4:2:2: out[2i] = (3 c[i] + c[i-1] + 1) >> 2, out[2i+1] = (3 c[i] + c[i+1] + 2) >> 2, the first and the last
+ *              output copies.  4:2:0: s = 3 c[r] + c[r-1] (even output row) or 3 c[r] + c[r+1] (odd), rows clamped to [0, dh - 1];
+ *              out[2i] = (3 s[i] + s[i-1] + 8) >> 4, out[2i+1] = (3 s[i] + s[i+1] + 7) >> 4, first (4 s[0] + 8) >> 4, last (4 s[dw-1] + 7) >> 4
+ *   colour     R = Y + ((91881 (Cr - 128) + 32768) >> 16), B = Y + ((116130 (Cb - 128) + 32768) >> 16),
+ *              G = Y + ((-22554 (Cb - 128) + 32768 - 46802 (Cr - 128)) >> 16), arithmetic shifts, clamped to [0, 255]
+ * F = 0 is a no-op.  Refused, not clamped: sizes outside the encoder's limits, sub outside 0 .. 2, restart outside [0, 65535], a small ws,
+ * misaligned pointers.  Everything is launched on the caller's stream. */
+#define MBX_JPEG_DEC_TABLE_WORDS 228
+#define MBX_JPEG_DEC_OK 0
+#define MBX_JPEG_DEC_TRUNCATED 1
+#define MBX_JPEG_DEC_BAD_CODE 2
+#define MBX_JPEG_DEC_RUN 3
+#define MBX_JPEG_DEC_LEFTOVER 4
+#define MBX_JPEG_DEC_MARKERS 5
+/* one pass of jpeg_idct_islow over long long d[8] (dequantised), in place: the butterfly of MBX_JPEG_FDCT_PASS backwards */
+#define MBX_JPEG_IDCT_PASS(d, shift)                                                                        \
+    do {                                                                                                    \
+        const long long r_ = 1ll << ((shift) - 1);                                                          \
+        const long long za_ = (d[2] + d[6]) * 4433;                                                         \
+        const long long e2_ = za_ - d[6] * 15137, e3_ = za_ + d[2] * 6270;                                  \
+        const long long e0_ = (d[0] + d[4]) * 8192, e1_ = (d[0] - d[4]) * 8192;                             \
+        const long long t10_ = e0_ + e3_, t13_ = e0_ - e3_, t11_ = e1_ + e2_, t12_ = e1_ - e2_;             \
+        const long long z5_ = (d[7] + d[3] + d[5] + d[1]) * 9633;                                           \
+        const long long z1_ = -(d[7] + d[1]) * 7373, z2_ = -(d[5] + d[3]) * 20995;                          \
+        const long long z3_ = -(d[7] + d[3]) * 16069 + z5_, z4_ = -(d[5] + d[1]) * 3196 + z5_;              \
+        const long long o0_ = d[7] * 2446 + z1_ + z3_, o1_ = d[5] * 16819 + z2_ + z4_;                      \
+        const long long o2_ = d[3] * 25172 + z2_ + z3_, o3_ = d[1] * 12299 + z1_ + z4_;                     \
+        d[0] = (t10_ + o3_ + r_) >> (shift); d[7] = (t10_ - o3_ + r_) >> (shift);                           \
+        d[1] = (t11_ + o2_ + r_) >> (shift); d[6] = (t11_ - o2_ + r_) >> (shift);                           \
+        d[2] = (t12_ + o1_ + r_) >> (shift); d[5] = (t12_ - o1_ + r_) >> (shift);                           \
+        d[3] = (t13_ + o0_ + r_) >> (shift); d[4] = (t13_ - o0_ + r_) >> (shift);                           \
+    } while (0)
+int mbx_jpeg_dec_tables(const unsigned char* dht, unsigned* out);                               /* both HOST memory */
+int mbx_jpeg_dec_index(const unsigned char* data, long long data_bytes, const long long* scans, int F, int n_int, long long* pos, int* status,
+                       void* stream);
+int mbx_jpeg_dec_entropy(const unsigned char* data, long long data_bytes, const long long* pos, const unsigned* tables, int F, int H, int W,
+                         int sub, int restart, short* coef, int* status, void* stream);
+size_t mbx_jpeg_dec_ws(int F, int H, int W, int sub);
+int mbx_jpeg_dec_pixels(const short* coef, const unsigned char* q, int F, int H, int W, int sub, unsigned char* rgb, void* ws, size_t ws_bytes,
+                        void* stream);
+
 /* ---- measurement aid (bench.py`roofline.sustained_mfma_tflops`; not part of the model) --------------------------------------------
  * The bf16 MFMA rate the part sustains under its power cap with nothing but v_mfma_f32_32x32x16_bf16 in the loop (pseudo-random
  * operands; n_wg workgroups of 4 waves, `iters` x 16 MFMAs per wave).  ws: >= mbx_mfma_probe_ws(n_wg) bytes = a float sink

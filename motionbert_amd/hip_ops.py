@@ -13,6 +13,7 @@ import threading
 from itertools import accumulate
 from typing import Dict, List, Optional
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -142,6 +143,11 @@ SIGNATURES = {
     'mbx_jpeg_entropy_ws': (_sz, [_i] * 5),
     'mbx_jpeg_entropy_sizes': (_i, [_vp] + [_i] * 6 + [_vp, _vp, _sz, _vp]),
     'mbx_jpeg_entropy': (_i, [_vp] + [_i] * 6 + [_vp, _vp, C.c_longlong, _vp, _sz, _vp]),
+    'mbx_jpeg_dec_tables': (_i, [_vp, _vp]),
+    'mbx_jpeg_dec_index': (_i, [_vp, C.c_longlong, _vp, _i, _i, _vp, _vp, _vp]),
+    'mbx_jpeg_dec_entropy': (_i, [_vp, C.c_longlong, _vp, _vp] + [_i] * 5 + [_vp, _vp, _vp]),
+    'mbx_jpeg_dec_ws': (_sz, [_i] * 4),
+    'mbx_jpeg_dec_pixels': (_i, [_vp, _vp] + [_i] * 4 + [_vp, _vp, _sz, _vp]),
     'mbx_rows_n_pack_bytes': (_sz, [_i, _i]),
     'mbx_rows_lnbwd_t': (_i, [_vp] * 6 + [_i, _i, _i, _vp]),
     'mbx_rows_n_pack_many': (_i, [_i64p, _i, _i, _i, _vp]),
@@ -1309,6 +1315,63 @@ class HipOps:
         self._dense('jpeg_emit', torch.uint8, None, dev, data=data, ws=ws)
         self._ck(self.lib.mbx_jpeg_entropy(_p(coef), F, int(H), int(W), int(sub), int(quality), int(restart), _p(offsets), _p(data), data.numel(),
                                            _p(ws), ws.numel(), self._stream()))
+
+    # ------------------------------------------------------------------ reading video (motionbert_amd/video.py)
+    JPEG_DEC_TABLE_WORDS = 228
+
+    @staticmethod
+    def _jpeg_dec_blocks(H, W, sub):
+        h, v = (1, 1) if sub == 0 else (2, 2) if sub == 1 else (2, 1)
+        return -(-H // (8 * v)) * -(-W // (8 * h)) * (h * v + 2)
+
+    def jpeg_dec_tables(self, dht):
+        """(bits [16], vals [256]) of the DC and AC table of each component, uint8 [6,272] on the host, or None for Annex K -> the decode
+        tables as a host int32 tensor [6, 228] (mbx_jpeg_dec_tables); a set that is no Huffman table raises ValueError"""
+        out = np.zeros((6, self.JPEG_DEC_TABLE_WORDS), np.uint32)
+        if dht is not None:
+            dht = np.ascontiguousarray(dht, np.uint8)
+            if dht.shape != (6, 272):
+                raise RuntimeError(f'libmbx: jpeg_dec_tables needs uint8 [6,272], got {dht.shape}')
+        if self.lib.mbx_jpeg_dec_tables(None if dht is None else dht.ctypes.data, out.ctypes.data) != 0:
+            raise ValueError('libmbx: ' + self.lib.mbx_last_error().decode())
+        return torch.from_numpy(out.view(np.int32))
+
+    def jpeg_dec_ws(self, F, H, W, sub, device):
+        """the component planes mbx_jpeg_dec_pixels writes between its two launches (mbx_jpeg_dec_ws)"""
+        return self._ws(('jpeg_dec', F, H, W, sub), self.lib.mbx_jpeg_dec_ws, F, H, W, int(sub), device=device)
+
+    def jpeg_dec_index(self, data, scans, n_int, pos, status):
+        """data u8 [n], scans i64 [F,2] -> pos i64 [F, n_int + 1], status i32 [F, n_int] (mbx_jpeg_dec_index)"""
+        F, dev = scans.shape[0], data.device
+        self._dense('jpeg_dec_index', torch.uint8, None, dev, data=data)
+        self._dense('jpeg_dec_index', torch.int64, F * 2, dev, scans=scans)
+        self._dense('jpeg_dec_index', torch.int64, F * (n_int + 1), dev, pos=pos)
+        self._dense('jpeg_dec_index', torch.int32, F * n_int, dev, status=status)
+        self._ck(self.lib.mbx_jpeg_dec_index(_p(data), data.numel(), _p(scans), F, int(n_int), _p(pos), _p(status), self._stream()))
+
+    def jpeg_dec_entropy(self, data, pos, tables, H, W, sub, restart, coef, status):
+        """the restart intervals pos names -> coef i16 [F, n_mcu, blocks per MCU, 64], zigzag, and status (mbx_jpeg_dec_entropy)"""
+        F, dev = coef.shape[0], data.device
+        n_mcu = self._jpeg_dec_blocks(H, W, sub) // (3 if sub == 0 else 6 if sub == 1 else 4)
+        n_int = -(-n_mcu // restart) if restart else 1
+        self._dense('jpeg_dec_entropy', torch.uint8, None, dev, data=data)
+        self._dense('jpeg_dec_entropy', torch.int64, F * (n_int + 1), dev, pos=pos)
+        self._dense('jpeg_dec_entropy', torch.int32, 6 * self.JPEG_DEC_TABLE_WORDS, dev, tables=tables)
+        self._dense('jpeg_dec_entropy', torch.int16, F * self._jpeg_dec_blocks(H, W, sub) * 64, dev, coef=coef)
+        self._dense('jpeg_dec_entropy', torch.int32, F * n_int, dev, status=status)
+        self._ck(self.lib.mbx_jpeg_dec_entropy(_p(data), data.numel(), _p(pos), _p(tables), F, int(H), int(W), int(sub), int(restart), _p(coef),
+                                               _p(status), self._stream()))
+
+    def jpeg_dec_pixels(self, coef, q, H, W, sub, rgb, ws):
+        """coef, q (uint8 [3,64] on the host: each component's table, zigzag order) -> rgb u8 [F,H,W,3] (mbx_jpeg_dec_pixels)"""
+        F, dev = coef.shape[0], coef.device
+        q = np.ascontiguousarray(q, np.uint8)
+        if q.shape != (3, 64):
+            raise RuntimeError(f'libmbx: jpeg_dec_pixels needs q uint8 [3,64], got {q.shape}')
+        self._dense('jpeg_dec_pixels', torch.int16, F * self._jpeg_dec_blocks(H, W, sub) * 64, dev, coef=coef)
+        self._dense('jpeg_dec_pixels', torch.uint8, F * H * W * 3, dev, rgb=rgb)
+        self._dense('jpeg_dec_pixels', torch.uint8, None, dev, ws=ws)
+        self._ck(self.lib.mbx_jpeg_dec_pixels(_p(coef), q.ctypes.data, F, int(H), int(W), int(sub), _p(rgb), _p(ws), ws.numel(), self._stream()))
 
     # ------------------------------------------------------------------ dropout / drop-path (SURVEY 8 a15)
     def dropout(self, x, y, p, seed):

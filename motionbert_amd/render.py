@@ -25,8 +25,8 @@ reference's perspective 3D axes as one constant matrix, bones and joints in the 
 The file itself -- the frames compressed on the device and written as Motion-JPEG -- is motionbert_amd.video (`mesh_video`, `skeleton_video`, `scene_video`).
 
 Not here: the 2D overlay of `motion2video`, matplotlib's panes, grid and anti-aliasing, smooth shading, other mesh cameras, several meshes
-in one frame, decoding the input video (the caller brings its frames as a tensor), track labels or text, ordering persons by estimated depth
-(the caller passes `order` to `scene_table`).
+in one frame, track labels or text, ordering persons by estimated depth (the caller passes `order` to `scene_table`).  The input video behind
+a scene is read by motionbert_amd.video (`MJPEGReader`, Motion-JPEG in AVI; csrc/jpeg_dec.hip) and passed as `background=`.
 
 There is no CPU path: without an injected kernel provider (`ops=`), tensors that are not on a ROCm device raise."""
 from __future__ import annotations
@@ -468,6 +468,14 @@ def _check_scene(x3d, table, width, height, ss, bones, palette, radii, backgroun
                          f'on {palette.device}')
     if background is None:
         background = (255, 255, 255)
+    if isinstance(background, _ReaderFrames):
+        background = background.reader
+    if hasattr(background, 'read') and hasattr(background, 'frames'):          # a video.MJPEGReader: the video's own frames, decoded per span
+        if background.frames != Fv or (background.height, background.width) != (height, width):
+            raise ValueError(f'{where}: the background video has {background.frames} frames of {background.height} x {background.width}, the scene '
+                             f'{Fv} of {height} x {width}')
+        prov = hip_ops.provider(ops, 'motionbert_amd.' + where, x3d)
+        return x3d.contiguous(), tuple(tab), bones, palette.contiguous(), tuple(int(r) for r in radii), _ReaderFrames(background, dev, ops), want, prov
     if isinstance(background, np.ndarray) and background.ndim == 4:
         background = torch.from_numpy(np.ascontiguousarray(background)).to(dev)
     if isinstance(background, torch.Tensor):
@@ -485,10 +493,25 @@ def _check_scene(x3d, table, width, height, ss, bones, palette, radii, backgroun
     return x3d.contiguous(), tuple(tab), bones, palette.contiguous(), tuple(int(r) for r in radii), background, want, prov
 
 
+class _ReaderFrames:
+    """The background frames of a span from a video.MJPEGReader: decoded into one buffer that grows to the largest span asked for, just before
+    the span's render and on its stream, so the whole background never exists on the device."""
+
+    def __init__(self, reader, dev, ops):
+        self.reader, self.dev, self.ops, self.buf = reader, dev, ops, None
+
+    def span(self, a, b):
+        if self.buf is None or self.buf.shape[0] < b - a:
+            self.buf = torch.empty(b - a, self.reader.height, self.reader.width, 3, dtype=torch.uint8, device=self.dev)
+        return self.reader.read(a, b, device=self.dev, out=self.buf[:b - a], ops=self.ops)
+
+
 def _render_scene(prov, jq, tab, a, b, bones, palette, radii, width, height, ss, background, rgb, want):
     """video frames a .. b - 1: frame_ptr[a:b+1] keeps its offsets into the whole rows / person, so a span of frames is the same table"""
     Fv = tab[0].numel() - 1
-    if isinstance(background, torch.Tensor) and background.shape[0] == Fv and Fv != 1:
+    if isinstance(background, _ReaderFrames):
+        background = background.span(a, b) if b > a else (255, 255, 255)
+    elif isinstance(background, torch.Tensor) and background.shape[0] == Fv and Fv != 1:
         background = background[a:b]
     prim_id = torch.empty(b - a, height * ss, width * ss, dtype=torch.int32, device=tab[0].device) if 'prim_id' in want else None
     if b > a:
@@ -512,7 +535,8 @@ def render_scene(x3d, table, width: int, height: int, ss: int = 1, bones=None, p
     width ss] (rank in the frame's list x 3 Nb + the primitive of `render_skeleton`; -1 where empty) and 'jq' int32 [R,J,2].
     `bones` [Nb,2] and `palette` [P,Nb,3] (or [1,Nb,3] for everybody): default the 16 H36M bones and the reference's three colours for
     everybody (`track_palette(n)` gives one row per person); `radii` default `skeleton_radii(min(width, height), ss)`; `background`: three
-    ints (default white) or uint8 frames [Fv or 1,height,width,3], an array or a device tensor: the video's own frames.  A later entry of a
+    ints (default white), uint8 frames [Fv or 1,height,width,3] (an array or a device tensor), or a `video.MJPEGReader` of Fv frames of that
+    size: the video's own frames, decoded on the device.  A later entry of a
     frame's list covers an earlier one.  Table entries that name no row of x3d or no row of the palette are not drawn.  Two kernel calls;
     Fv = 0 returns empty frames without drawing (the projection runs only where 'jq' is wanted)."""
     where = 'render.render_scene'
@@ -531,7 +555,8 @@ def render_scene(x3d, table, width: int, height: int, ss: int = 1, bones=None, p
 
 def scene_chunks(x3d, table, width: int, height: int, ss: int = 1, bones=None, palette=None, radii=None, background=None, chunk: int = 32, ops=None):
     """A generator of host uint8 arrays [n,height,width,3], n <= `chunk` video frames at a time, in frame order: the frames of `render_scene`
-    through `_pipeline`, without ever holding them all.  Background frames given per video frame are sliced per chunk.  An array is valid
+    through `_pipeline`, without ever holding them all.  Background frames given per video frame are sliced per chunk; those of a
+    `video.MJPEGReader` are decoded per chunk into one chunk-sized buffer, just before the chunk's render.  An array is valid
     until the generator is advanced again."""
     where = 'render.scene_chunks'
     x, tab, bones, palette, radii, background, _, prov = _check_scene(x3d, table, width, height, ss, bones, palette, radii, background, ('rgb',), ops,

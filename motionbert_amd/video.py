@@ -16,12 +16,27 @@ cross the host link.
 One host synchronisation per encode: the sizes of the files are computed on the device first, the host reads their total and allocates, then the
 bytes are emitted straight into place.  In the *_video functions that wait falls under the copy of the chunk before.
 
-Not here: inter-frame codecs, optimised Huffman tables, progressive / 12-bit / grayscale JPEG, AVI beyond 2 GB (OpenDML), audio, decoding.  No AVI
-reader exists where this was developed: the container is checked field by field against its specification and has not been played.
+Reading is the other half (csrc/jpeg_dec.hip): the compressed bytes cross the host link and the frames are decoded where they are used.
+
+    parse_jpeg(bytes)                                 the header facts of one baseline JFIF frame, on the host; raises ValueError naming the marker
+                                                      of anything the decoder does not take
+    decode_jpeg(data, offsets, device)                F files -> rgb uint8 [F,H,W,3] on the device, every pixel the one libjpeg's default path
+                                                      decodes (include/mbx.h has the definition); one host synchronisation, the status read
+    MJPEGReader(path)                                 RIFF 'AVI ' with an MJPG video stream: `.width .height .fps .frames`, `.read(a, b, device)`,
+                                                      `.chunks(chunk, device)` (the upload of the next chunk under the decode of this one)
+    scene_video(..., background=reader)               the video's own frames behind the skeletons, decoded chunk by chunk
+
+Not here: inter-frame codecs, optimised Huffman tables when writing, progressive / arithmetic / 12-bit / grayscale / CMYK JPEG, libjpeg's error
+recovery (a malformed restart interval raises), AVI beyond 2 GB (OpenDML: not written, refused when read), audio.  `MJPEGReader` opens the
+files `MJPEGWriter` writes and gives back their frames; no third-party player or writer (ffmpeg, cv2, imageio) has been available where
+this was developed, so files written by ffmpeg are handled by construction (file-specific Huffman tables, frames without DHT, 4:2:2, no
+restart markers, file-relative index offsets, `LIST 'rec '`, `JUNK`) and by hand-built variants in the tests, not by a test on such a file.
 
 There is no CPU path: without an injected kernel provider (`ops=`), tensors that are not on a ROCm device raise."""
 from __future__ import annotations
 
+import mmap
+import re
 import struct
 
 import numpy as np
@@ -176,6 +191,422 @@ class MJPEGWriter:
         self.close()
 
 
+# ------------------------------------------------------------------------------------------------ reading: the header of a frame
+DEC_SUBSAMPLINGS = ('444', '420', '422')          # the index is the `sub` of the decoder's C ABI
+DEC_STATUS = ('ok', 'the interval ends inside a symbol', 'no such Huffman code', 'a run past coefficient 63', 'whole bytes left over',
+              'the restart markers of the frame are not the expected ones')
+_MARKERS = {0xc0: 'SOF0', 0xc1: 'SOF1', 0xc2: 'SOF2', 0xc3: 'SOF3', 0xc4: 'DHT', 0xc5: 'SOF5', 0xc6: 'SOF6', 0xc7: 'SOF7', 0xc8: 'JPG', 0xc9: 'SOF9',
+            0xca: 'SOF10', 0xcb: 'SOF11', 0xcc: 'DAC', 0xcd: 'SOF13', 0xce: 'SOF14', 0xcf: 'SOF15', 0xd8: 'SOI', 0xd9: 'EOI', 0xda: 'SOS', 0xdb: 'DQT',
+            0xdc: 'DNL', 0xdd: 'DRI', 0xde: 'DHP', 0xdf: 'EXP', 0xfe: 'COM', 0x01: 'TEM'}
+_NEXT_MARKER = re.compile(rb'\xff[^\x00\xd0-\xd7\xff]')          # inside a scan: 0xFF that is neither stuffed, nor RSTn, nor a fill byte
+
+
+def _marker(m):
+    return _MARKERS.get(m) or (f'APP{m - 0xe0}' if 0xe0 <= m <= 0xef else f'RST{m - 0xd0}' if 0xd0 <= m <= 0xd7 else f'marker {m:#04x}')
+
+
+def parse_jpeg(data):
+    """The header facts of one JPEG file (`bytes`, or anything `bytes()` takes) as the decoder needs them, on the host: a dict with H, W,
+    subsampling ('444', '420' or '422'), restart (the interval in MCUs; 0: none), q (uint8 [3,64]: each component's quantisation table in
+    zigzag order), dht (uint8 [6,272]: bits [16] and vals [256] of the DC and the AC table of each component; None where the file brings no
+    Huffman table, as an AVI 'MJPG' frame may: Annex K applies) and scan = (the first entropy-coded byte, the position of EOI).
+    Accepted: baseline sequential (SOF0), 8 bit, three components in one interleaved scan, luma sampling 1x1, 2x1 or 2x2 with chroma 1x1,
+    8-bit DQT, DRI or not; APPn and COM are skipped.  Everything else raises ValueError naming the marker: SOF1 and above, DAC (arithmetic
+    coding), 12 bit, a 16-bit DQT, one or four components, other sampling factors, a second scan, DNL, no SOI or no EOI."""
+    where = 'video.parse_jpeg'
+    data = data if isinstance(data, bytes) else data.tobytes() if isinstance(data, np.ndarray) else bytes(data)
+    if data[:2] != b'\xff\xd8':
+        raise ValueError(f'{where}: SOI: the file does not start with it')
+    p, q, huff, restart, comps, size = 2, {}, {}, 0, None, None
+    while True:
+        while p + 1 < len(data) and data[p] == 0xff and data[p + 1] == 0xff:          # fill bytes
+            p += 1
+        if p + 4 > len(data):
+            raise ValueError(f'{where}: SOS: the file ends at byte {len(data)} before a scan')
+        if data[p] != 0xff:
+            raise ValueError(f'{where}: no marker at byte {p}')
+        m, n = data[p + 1], struct.unpack('>H', data[p + 2:p + 4])[0]
+        name, seg = _marker(m), data[p + 4:p + 2 + n]
+        if m in (0xd8, 0xd9) or 0xd0 <= m <= 0xd7 or m == 0x01:
+            raise ValueError(f'{where}: {name} at byte {p}, before a scan')
+        if n < 2 or len(seg) != n - 2:
+            raise ValueError(f'{where}: {name} at byte {p} runs past the end of the file')
+        if m == 0xdb:
+            while seg:
+                if seg[0] >> 4:
+                    raise ValueError(f'{where}: DQT: table {seg[0] & 15} has 16-bit entries')
+                if len(seg) < 65 or (seg[0] & 15) > 3:
+                    raise ValueError(f'{where}: DQT: a short table, or an id above 3')
+                q[seg[0] & 15], seg = np.frombuffer(seg[1:65], np.uint8), seg[65:]
+        elif m == 0xc0:
+            if comps is not None:
+                raise ValueError(f'{where}: SOF0: a second frame header')
+            if len(seg) < 6 or seg[0] != 8:
+                raise ValueError(f'{where}: SOF0: {seg[0] if seg else "?"} bit samples (8 bit only)')
+            if seg[5] != 3 or len(seg) != 15:
+                raise ValueError(f'{where}: SOF0: {seg[5]} components (three only)')
+            size = struct.unpack('>HH', seg[1:5])
+            comps = [(seg[6 + 3 * i], seg[7 + 3 * i], seg[8 + 3 * i]) for i in range(3)]
+            if comps[0][1] not in (0x11, 0x21, 0x22) or comps[1][1] != 0x11 or comps[2][1] != 0x11:
+                raise ValueError(f'{where}: SOF0: sampling factors {[hex(c[1]) for c in comps]} (luma 1x1, 2x1 or 2x2 with chroma 1x1 only)')
+        elif 0xc1 <= m <= 0xcf and m != 0xc4:
+            raise ValueError(f'{where}: {name}: only baseline sequential Huffman-coded JPEG (SOF0) is decoded')
+        elif m == 0xc4:
+            while seg:
+                k = sum(seg[1:17])
+                if len(seg) < 17 + k or k > 256 or (seg[0] >> 4) > 1 or (seg[0] & 15) > 3:
+                    raise ValueError(f'{where}: DHT: a short table, a class above 1 or an id above 3')
+                huff[seg[0]], seg = (seg[1:17], seg[17:17 + k]), seg[17 + k:]
+        elif m == 0xdd:
+            if len(seg) != 2:
+                raise ValueError(f'{where}: DRI of {len(seg)} bytes')
+            restart = struct.unpack('>H', seg)[0]
+        elif m == 0xda:
+            if comps is None:
+                raise ValueError(f'{where}: SOS before SOF0')
+            if not seg or seg[0] != 3 or len(seg) != 10 or [seg[1 + 2 * i] for i in range(3)] != [c[0] for c in comps]:
+                raise ValueError(f'{where}: SOS: a scan of {seg[0] if seg else "?"} components (one interleaved scan of the three only)')
+            if tuple(seg[7:10]) != (0, 63, 0):
+                raise ValueError(f'{where}: SOS: spectral selection {tuple(seg[7:10])} (a baseline scan has 0, 63, 0)')
+            select = [seg[2 + 2 * i] for i in range(3)]
+            p += 2 + n
+            break
+        elif m == 0xdc:
+            raise ValueError(f'{where}: DNL is not taken')
+        elif not (0xe0 <= m <= 0xef or m == 0xfe):
+            raise ValueError(f'{where}: {name} at byte {p} is not taken')
+        p += 2 + n
+    H, W = size
+    if not (1 <= H <= MAX_SIZE and 1 <= W <= MAX_SIZE):
+        raise ValueError(f'{where}: SOF0: a frame of {H} x {W}: height and width must be in [1, {MAX_SIZE}] (DNL is not taken)')
+    for c in comps:
+        if c[2] not in q:
+            raise ValueError(f'{where}: DQT: table {c[2]} of component {c[0]} is missing')
+    dht = None
+    if huff:
+        dht = np.zeros((6, 272), np.uint8)
+        for c, s in enumerate(select):
+            for a, key in enumerate((s >> 4, 0x10 | (s & 15))):
+                if key not in huff:
+                    raise ValueError(f'{where}: DHT: the {"AC" if a else "DC"} table {key & 15} of component {comps[c][0]} is missing')
+                bits, vals = huff[key]
+                dht[2 * c + a, :16], dht[2 * c + a, 16:16 + len(vals)] = list(bits), list(vals)
+    end = _NEXT_MARKER.search(data, p)
+    if end is None:
+        raise ValueError(f'{where}: EOI: the scan runs to the end of the file')
+    if data[end.start() + 1] != 0xd9:
+        raise ValueError(f'{where}: {_marker(data[end.start() + 1])} after the scan at byte {end.start()} (one scan only)')
+    return dict(H=H, W=W, subsampling={0x11: '444', 0x22: '420', 0x21: '422'}[comps[0][1]], restart=restart, q=np.stack([q[c[2]] for c in comps]),
+                dht=dht, scan=(p, end.start()))
+
+
+def dec_geometry(H: int, W: int, subsampling: str):
+    """(MCU columns, MCU rows, blocks per MCU) of a frame that is read"""
+    h, v = {'444': (1, 1), '420': (2, 2), '422': (2, 1)}[subsampling]
+    return -(-W // (8 * h)), -(-H // (8 * v)), h * v + 2
+
+
+# ------------------------------------------------------------------------------------------------ reading: frames
+def _host_files(data, offsets, where):
+    """-> (host uint8 array of all files back to back, int64 offsets [F+1], the device tensor if `data` was one)"""
+    if isinstance(data, (list, tuple)):
+        if offsets is not None or not all(isinstance(b, (bytes, bytearray, memoryview)) for b in data):
+            raise ValueError(f'{where}: a list of frames holds `bytes` and takes no offsets')
+        off = np.concatenate([[0], np.cumsum([len(b) for b in data])]).astype(np.int64)
+        host = np.empty(int(off[-1]), np.uint8)
+        for f, b in enumerate(data):
+            host[off[f]:off[f + 1]] = np.frombuffer(b, np.uint8)
+        return host, off, None
+    if isinstance(data, np.ndarray):
+        data = torch.from_numpy(np.ascontiguousarray(data))
+    if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or data.dim() != 1 or offsets is None:
+        raise ValueError(f'{where}: data must be a list of `bytes`, or a 1-D uint8 tensor with offsets [F+1]')
+    off = np.asarray(offsets.cpu() if isinstance(offsets, torch.Tensor) else offsets).astype(np.int64)
+    if off.ndim != 1 or off.size < 1 or off[0] < 0 or off[-1] > data.numel() or (np.diff(off) < 0).any():
+        raise ValueError(f'{where}: offsets {off.tolist()[:6]} do not frame files inside {data.numel()} bytes')
+    return (data.cpu() if data.is_cuda else data).contiguous().numpy(), off, data.contiguous() if data.is_cuda else None
+
+
+def _decode(prov, host, off, dev, dev_data, want, out, where, size=None):
+    """F files host[off[f]:off[f+1]] -> the dict of `want`.  dev_data: the same bytes on the device where they are there already, else they
+    are uploaded here, once.  Consecutive frames that share geometry, quantisation and Huffman tables and restart interval go through the
+    kernels together.  Nothing is launched before every header is parsed; the ONE host synchronisation is the read of the status."""
+    F = len(off) - 1
+    facts = [parse_jpeg(host[off[f]:off[f + 1]]) for f in range(F)]
+    if F and any((p['H'], p['W']) != (facts[0]['H'], facts[0]['W']) for p in facts):
+        raise ValueError(f'{where}: the frames have different sizes: {sorted({(p["H"], p["W"]) for p in facts})}')
+    if F and size is not None and (facts[0]['H'], facts[0]['W']) != tuple(size):
+        raise ValueError(f'{where}: frames of {facts[0]["H"]} x {facts[0]["W"]} where {size[0]} x {size[1]} are expected')
+    H, W = (facts[0]['H'], facts[0]['W']) if F else (size or (0, 0))
+    if out is None:
+        out = torch.empty(F, H, W, 3, dtype=torch.uint8, device=dev)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (F, H, W, 3) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f'{where}: out must be a contiguous uint8 tensor [{F},{H},{W},3] on {dev}')
+    res = dict(rgb=out, coef=None, status=None, pos=None)
+    if F == 0:
+        return {k: res[k] for k in want}
+
+    def key(p):
+        return (p['subsampling'], p['restart'], p['q'].tobytes(), None if p['dht'] is None else p['dht'].tobytes())
+    groups, a = [], 0
+    for f in range(1, F + 1):
+        if f == F or key(facts[f]) != key(facts[a]):
+            groups.append((a, f))
+            a = f
+    if len(groups) > 1 and any(k in want for k in ('coef', 'status', 'pos')):
+        raise ValueError(f'{where}: the test hooks {want!r} need frames that share subsampling, tables and restart interval')
+    tables = [prov.jpeg_dec_tables(facts[a]['dht']) for a, _ in groups]              # host; a bad table raises before any launch
+    scans = np.array([[off[f] + p['scan'][0], off[f] + p['scan'][1]] for f, p in enumerate(facts)], np.int64)
+    if dev_data is None:
+        dev_data = torch.from_numpy(host).to(dev, non_blocking=True) if dev.type == 'cuda' else torch.from_numpy(host)
+    scans_dev = torch.from_numpy(scans).to(dev)
+    stats = []
+    for (a, b), tab in zip(groups, tables):
+        p = facts[a]
+        sub = DEC_SUBSAMPLINGS.index(p['subsampling'])
+        mx, my, bpm = dec_geometry(H, W, p['subsampling'])
+        n_int = -(-mx * my // p['restart']) if p['restart'] else 1
+        pos = torch.empty(b - a, n_int + 1, dtype=torch.int64, device=dev)
+        status = torch.empty(b - a, n_int, dtype=torch.int32, device=dev)
+        coef = torch.empty(b - a, mx * my, bpm, 64, dtype=torch.int16, device=dev)
+        prov.jpeg_dec_index(dev_data, scans_dev[a:b], n_int, pos, status)
+        prov.jpeg_dec_entropy(dev_data, pos, tab.to(dev), H, W, sub, p['restart'], coef, status)
+        if 'rgb' in want:
+            prov.jpeg_dec_pixels(coef, p['q'], H, W, sub, out[a:b], prov.jpeg_dec_ws(b - a, H, W, sub, dev))
+        stats.append(status)
+        res.update(coef=coef, status=status, pos=pos)
+    flat = torch.cat([s.reshape(-1) for s in stats]).cpu().numpy()                    # the one host synchronisation
+    if flat.any() and 'status' not in want:
+        i = int(np.nonzero(flat)[0][0])
+        for (a, b), s in zip(groups, stats):
+            if i < s.numel():
+                raise ValueError(f'{where}: frame {a + i // s.shape[1]}, restart interval {i % s.shape[1]} of {s.shape[1]}: status {flat[i]} '
+                                 f'({DEC_STATUS[flat[i]] if 0 <= flat[i] < len(DEC_STATUS) else "unknown"}); {int((flat != 0).sum())} intervals in all')
+            i, flat = i - s.numel(), flat[s.numel():]
+    return {k: res[k] for k in want}
+
+
+def decode_jpeg(data, offsets=None, device=None, want=('rgb',), out=None, ops=None):
+    """F baseline JPEG files -> rgb uint8 [F,H,W,3] on the device, every pixel the one libjpeg's default path decodes.  `data`: a list of
+    `bytes`, or a 1-D uint8 tensor or array (host or device) that holds the files back to back with `offsets` [F+1]; all frames must have
+    one size; what `parse_jpeg` refuses raises before anything is launched.  `device`: where to decode (default: that of a device tensor,
+    else the current ROCm device).  Host bytes are uploaded once; a device tensor is also read back once, for its headers.  With the
+    default `want` the result is the rgb tensor (`out`, where one is given); any other `want` gives a dict: 'coef' (int16 [F, n_mcu, blocks
+    per MCU, 64], zigzag: the encoder's layout), 'pos' and 'status' (then a malformed interval does not raise) are test hooks.  ONE host
+    synchronisation, the read of the status: an interval that is malformed raises ValueError naming frame, interval and code."""
+    where = 'video.decode_jpeg'
+    plain = want == ('rgb',) or want == 'rgb'
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(k not in ('rgb', 'coef', 'status', 'pos') for k in want):
+        raise ValueError(f"{where}: want must name some of ('rgb', 'coef', 'status', 'pos'), got {want!r}")
+    host, off, dev_data = _host_files(data, offsets, where)
+    device = _dec_device(dev_data.device if device is None and dev_data is not None else device, ops, where)
+    if dev_data is not None and dev_data.device != device:
+        dev_data = None
+    prov = hip_ops.provider(ops, 'motionbert_amd.' + where)
+    res = _decode(prov, host, off, device, dev_data, want, out, where)
+    return res['rgb'] if plain else res
+
+
+# ------------------------------------------------------------------------------------------------ reading: the container
+class MJPEGReader:
+    """The Motion-JPEG video stream of an AVI 1.0 file.  The constructor walks RIFF 'AVI ': `avih`, the first `strl` whose `strh` is 'vids' with
+    handler or compression 'MJPG' (either case) and its `strf`; other streams are ignored.  The frames are located through `idx1` (offsets
+    relative to the 'movi' fourcc or to the file: whichever names the stream's chunk, as players decide it), or by walking `movi` when there
+    is no index; `LIST 'rec '` is descended, `JUNK` and everything else skipped; a chunk of length 0 repeats the frame before it.
+    `.width .height .fps .frames`; `.frame_bytes(f)`; `.read(a, b, device)` -> uint8 [b - a, height, width, 3] on the device;
+    `.chunks(chunk, device)` yields them `chunk` at a time.  A context manager.  OpenDML files (a RIFF 'AVIX' after the first) are refused."""
+
+    def __init__(self, path):
+        self.path = path
+        self.file = open(path, 'rb')
+        try:
+            self.map = mmap.mmap(self.file.fileno(), 0, access=mmap.ACCESS_READ)
+        except ValueError:
+            self.file.close()
+            raise ValueError(f'MJPEGReader: {path} is empty')
+        try:
+            self._walk()
+        except Exception:
+            self.close()
+            raise
+
+    def _chunks(self, a, b):
+        """(fourcc, payload start, size as the chunk states it) of the chunks in [a, b)"""
+        d = self.map
+        while a + 8 <= b:
+            cid, size = d[a:a + 4], struct.unpack('<I', d[a + 4:a + 8])[0]
+            yield cid, a + 8, size
+            a += 8 + size + (size & 1)
+
+    def _walk(self):
+        d, n = self.map, len(self.map)
+        if n < 12 or d[:4] != b'RIFF' or d[8:12] != b'AVI ':
+            raise ValueError(f'MJPEGReader: {self.path} is no RIFF \'AVI \' file')
+        end = min(n, 8 + struct.unpack('<I', d[4:8])[0])
+        for cid, at, size in self._chunks(end + (end & 1), n):
+            if cid == b'RIFF' and d[at:at + 4] == b'AVIX':
+                raise ValueError(f'MJPEGReader: {self.path} is an OpenDML file (RIFF \'AVIX\'); only AVI 1.0 is read')
+        avih = stream = strf = movi = idx1 = None
+        n_streams = 0
+        for cid, at, size in self._chunks(12, end):
+            if cid == b'LIST' and d[at:at + 4] == b'hdrl':
+                for c2, a2, s2 in self._chunks(at + 4, min(at + size, end)):
+                    if c2 == b'avih':
+                        avih = d[a2:a2 + s2]
+                    elif c2 == b'LIST' and d[a2:a2 + 4] == b'strl':
+                        strh = fmt = None
+                        for c3, a3, s3 in self._chunks(a2 + 4, min(a2 + s2, end)):
+                            strh, fmt = (d[a3:a3 + s3], fmt) if c3 == b'strh' else (strh, d[a3:a3 + s3]) if c3 == b'strf' else (strh, fmt)
+                        if stream is None and strh is not None and len(strh) >= 36 and strh[:4] == b'vids':
+                            codecs = {strh[4:8].upper(), fmt[16:20].upper() if fmt is not None and len(fmt) >= 20 else b''}
+                            if b'MJPG' not in codecs:
+                                raise ValueError(f'MJPEGReader: the video stream of {self.path} is {strh[4:8]!r} / '
+                                                 f'{fmt[16:20] if fmt is not None else b""!r}, not MJPG')
+                            stream, strf, head = n_streams, fmt, strh
+                        n_streams += 1
+            elif cid == b'LIST' and d[at:at + 4] == b'movi':
+                movi = (at, min(at + size, end))                                   # from the 'movi' fourcc to the end of the list
+            elif cid == b'idx1':
+                idx1 = (at, min(size, end - at))
+        if stream is None or movi is None:
+            raise ValueError(f'MJPEGReader: {self.path} has no MJPG video stream, or no \'movi\' list')
+        scale, rate = struct.unpack('<II', head[20:28])
+        if scale == 0 or rate == 0:
+            if avih is None or len(avih) < 4 or struct.unpack('<I', avih[:4])[0] == 0:
+                raise ValueError(f'MJPEGReader: {self.path} names no frame rate')
+            scale, rate = struct.unpack('<I', avih[:4])[0], 1000000
+        self.fps = rate / scale
+        if strf is not None and len(strf) >= 12:
+            w, h = struct.unpack('<ii', strf[4:12])
+            self.width, self.height = w, abs(h)
+        elif avih is not None and len(avih) >= 40:
+            self.width, self.height = struct.unpack('<II', avih[32:40])
+        else:
+            raise ValueError(f'MJPEGReader: {self.path} names no frame size')
+        ids = (b'%02ddc' % stream, b'%02ddb' % stream)
+        self.index = []                                                  # (start, size) of every frame's payload in the file
+        if idx1 is not None and idx1[1] >= 16:
+            ent = np.frombuffer(d[idx1[0]:idx1[0] + idx1[1] - idx1[1] % 16], np.dtype([('id', 'S4'), ('flags', '<u4'), ('at', '<u4'), ('size', '<u4')]))
+            ent = ent[(ent['id'] == ids[0]) | (ent['id'] == ids[1])]
+            if len(ent):
+                first = int(ent['at'][0])
+                if d[movi[0] + first:movi[0] + first + 4] in ids:
+                    base = movi[0]
+                elif d[first:first + 4] in ids:
+                    base = 0
+                else:
+                    raise ValueError(f'MJPEGReader: the index of {self.path} points at no chunk of the video stream, relative to \'movi\' or to the file')
+                self.index = [(base + int(a) + 8, int(s)) for a, s in zip(ent['at'], ent['size'])]
+        else:
+            def walk(a, b):
+                for cid, at, size in self._chunks(a, b):
+                    if cid == b'LIST' and d[at:at + 4] == b'rec ':
+                        walk(at + 4, min(at + size, b))
+                    elif cid in ids:
+                        self.index.append((at, size))
+            walk(movi[0] + 4, movi[1])
+        for f, (at, size) in enumerate(self.index):
+            if at + size > n:
+                raise ValueError(f'MJPEGReader: frame {f} of {self.path} ({size} bytes at {at}) runs past the end of the file')
+            if size == 0:
+                if f == 0:
+                    raise ValueError(f'MJPEGReader: the first frame of {self.path} is empty')
+                self.index[f] = self.index[f - 1]
+        self.frames = len(self.index)
+        if self.frames > 0 and not (1 <= self.width <= MAX_SIZE and 1 <= self.height <= MAX_SIZE):
+            raise ValueError(f'MJPEGReader: frames of {self.height} x {self.width}: height and width must be in [1, {MAX_SIZE}]')
+
+    def frame_bytes(self, f: int) -> bytes:
+        at, size = self.index[f]
+        return self.map[at:at + size]
+
+    def _span(self, a, b, where):
+        if not (isinstance(a, int) and isinstance(b, int) and 0 <= a <= b <= self.frames):
+            raise ValueError(f'{where}: frames {a!r} .. {b!r} of {self.frames}')
+        if self.map is None:
+            raise ValueError(f'{where}: the file is closed')
+
+    def _gather(self, a, b, buf=None):
+        """the payloads of frames a .. b - 1 back to back -> (host uint8 array, offsets); into the pinned tensor `buf` where it is large enough"""
+        off = np.concatenate([[0], np.cumsum([self.index[f][1] for f in range(a, b)])]).astype(np.int64)
+        host = np.empty(int(off[-1]), np.uint8) if buf is None else buf.numpy()[:int(off[-1])]
+        for f in range(a, b):
+            at, size = self.index[f]
+            host[off[f - a]:off[f - a + 1]] = np.frombuffer(self.map, np.uint8, size, at)
+        return host, off
+
+    def read(self, a: int = 0, b=None, device=None, out=None, ops=None):
+        """frames a .. b - 1 (default: to the end) -> uint8 [b - a, height, width, 3] on the device (`out` where given)"""
+        where = 'video.MJPEGReader.read'
+        b = self.frames if b is None else b
+        self._span(a, b, where)
+        device = _dec_device(device, ops, where)
+        host, off = self._gather(a, b)
+        return _decode(hip_ops.provider(ops, 'motionbert_amd.' + where), host, off, device, None, ('rgb',), out, where, (self.height, self.width))['rgb']
+
+    def chunks(self, chunk: int = 32, device=None, ops=None):
+        """A generator of device tensors uint8 [n, height, width, 3], n <= `chunk` frames at a time, in frame order.  The structure of
+        render._pipeline turned round: the compressed bytes of chunk i + 1 are gathered into one of two pinned buffers and uploaded on a
+        side stream under the decode of chunk i.  A tensor is valid until the generator is advanced twice."""
+        where = 'video.MJPEGReader.chunks'
+        if not isinstance(chunk, int) or chunk < 1:
+            raise ValueError(f'{where}: chunk must be a positive int, got {chunk!r}')
+        device = _dec_device(device, ops, where)
+        prov = hip_ops.provider(ops, 'motionbert_amd.' + where)
+        spans = [(a, min(a + chunk, self.frames)) for a in range(0, self.frames, chunk)]
+        self._span(0, self.frames, where)
+        piped = device.type == 'cuda'
+        room = max((sum(self.index[f][1] for f in range(a, b)) for a, b in spans), default=0)
+        n_buf = min(2, len(spans))
+        hbuf = [torch.empty(room, dtype=torch.uint8, pin_memory=piped) for _ in range(n_buf)]
+        dbuf = [torch.empty(room, dtype=torch.uint8, device=device) for _ in range(n_buf)] if piped else hbuf
+        rgb = [torch.empty(min(chunk, self.frames), self.height, self.width, 3, dtype=torch.uint8, device=device) for _ in range(n_buf)]
+        side = torch.cuda.Stream(device=device) if piped else None
+
+        def upload(i):
+            (a, b), k = spans[i], i % n_buf
+            host, off = self._gather(a, b, hbuf[k])                      # the decode that last read dbuf[k] has been waited for (its status)
+            if not piped:
+                return host, off, None
+            with torch.cuda.stream(side):
+                dbuf[k][:host.size].copy_(hbuf[k][:host.size], non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record(side)
+            return host, off, ev
+
+        ahead = upload(0) if spans else None
+        for i, (a, b) in enumerate(spans):
+            (host, off, ev), k = ahead, i % n_buf
+            ahead = upload(i + 1) if i + 1 < len(spans) else None
+            if ev is not None:
+                torch.cuda.current_stream(device).wait_event(ev)
+            yield _decode(prov, host, off, device, dbuf[k][:host.size], ('rgb',), rgb[k][:b - a], where, (self.height, self.width))['rgb']
+
+    def close(self):
+        if getattr(self, 'map', None) is not None:
+            self.map.close()
+            self.map = None
+        self.file.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _dec_device(device, ops, where):
+    if device is None:
+        device = torch.device('cuda', torch.cuda.current_device()) if ops is None and torch.cuda.is_available() else torch.device('cpu')
+    device = torch.device(device)
+    if ops is None and device.type != 'cuda':
+        raise RuntimeError(f'motionbert_amd.{where} runs on the ROCm device; there is no CPU path')
+    if device.type == 'cuda' and device.index is None:                   # 'cuda' and 'cuda:0' compare unequal
+        device = torch.device('cuda', torch.cuda.current_device())
+    return device
+
+
 # ------------------------------------------------------------------------------------------------ render, encode, copy, write
 def _video_pipeline(writer, prov, F, chunk, H, W, dev, span, quality, sub, restart):
     """The frames of `span(a, b, rgb)` (which launches the render of frames a .. b - 1 into the device tensor rgb) into `writer`, `chunk` frames
@@ -291,7 +722,9 @@ def skeleton_video(path, x3d, fps: float, quality: int = 90, subsampling: str = 
 def scene_video(path, x3d, table, width: int, height: int, fps: float, quality: int = 90, subsampling: str = '420', background=None, chunk: int = 32,
                 restart=None, ss: int = 1, bones=None, palette=None, radii=None, ops=None):
     """The frames of `render.render_scene(x3d, table, width, height, ...)` as the Motion-JPEG AVI file `path` -> (frames, bytes of the file): every
-    tracked person in one video of the input's size; see `mesh_video`.  Background frames given per video frame are sliced per chunk."""
+    tracked person in one video of the input's size; see `mesh_video`.  Background frames given per video frame are sliced per chunk; an
+    `MJPEGReader` as `background` (the input video: as many frames, of this size) is decoded chunk by chunk into one chunk-sized buffer just
+    before the chunk's render, so the whole background never exists on the device."""
     where = 'video.scene_video'
     x, tab, bones, palette, radii, background, _, prov = R._check_scene(x3d, table, width, height, ss, bones, palette, radii, background, ('rgb',), ops,
                                                                        where)
