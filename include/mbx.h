@@ -952,6 +952,37 @@ size_t mbx_jpeg_dec_ws(int F, int H, int W, int sub);
 int mbx_jpeg_dec_pixels(const short* coef, const unsigned char* q, int F, int H, int W, int sub, unsigned char* rgb, void* ws, size_t ws_bytes,
                         void* stream);
 
+/* ---- Huffman decoding inside a restart interval (csrc/jpeg_sync.hip) -- mbx_version() >= 260 -----------------------------------------------------
+ * mbx_jpeg_dec_entropy_sync gives the coef and status of mbx_jpeg_dec_entropy, in every coefficient and status word and for every input,
+ * malformed scans included, with many lanes per interval: the self-synchronising decode (Klein & Wiseman; Weissenberger & Schmidt).
+ * State (p, k, z): p the position of the next bit in the RAW bytes of the interval (stuffed bytes counted), k the block inside the MCU, z the
+ * next zigzag index (0: a DC symbol is next).  The interval's bytes are cut into subsequences of MBX_JPEG_SYNC_BYTES at fixed offsets from
+ * its start; a subsequence that would begin on the 00 of an FF 00 pair begins one byte later; it owns the symbols whose first bit lies in
+ * it, and its exit is the state at the first symbol at or behind its end.  MBX_JPEG_SYNC_CHUNK subsequences are a chunk, one workgroup.
+ *   speculate  each lane decodes its subsequence from (its first bit, 0, 0), chunk 0's first from the true (0, 0, 0); then lane i takes lane
+ *              i - 1's exit and decodes again while that changes (at most MBX_JPEG_SYNC_CHUNK rounds).  The decode is LENIENT: where no code
+ *              matches, one bit on with the state unchanged; a DC symbol s takes s & 15 bits; EOB ends the block; every other AC symbol
+ *              (r, s) takes s bits and r + 1 coefficients, and a block ends at coefficient 63.  Behind the interval's end the bits are 0.
+ *   verify     chunk c >= 1 starts lane 0 from the exit stored for chunk c - 1 and repeats the rounds; an interval all of whose chunks
+ *              reproduce their stored exit has true exits throughout; otherwise route = 1.
+ *   scan       exclusive sums over the subsequences of (blocks completed, DC differences per component mod 2^32).
+ *   write      each lane decodes again from its true entry with the checks of mbx_jpeg_dec_entropy and stores at (block from the scan, z),
+ *              every store checked against the interval's block count; the lane that completes the last block applies the LEFTOVER rule.
+ *              route = 2 where a check fails, where the bytes end before the blocks do, or where the interval is empty.
+ *   fall back  an interval with route != 0 is zeroed again and decoded by the lane of mbx_jpeg_dec_entropy, which defines its result.
+ * route i32 [F, n_int] (out): 0 decoded in parallel (or status was not OK on entry: nothing is decoded), 1, 2 as above, 3 the interval is
+ * longer than max_interval_bytes.  max_interval_bytes (0 .. 2^27, from the host's parsed scan lengths) sizes the grid and ws
+ * (>= mbx_jpeg_dec_sync_ws(F, n_int, max_interval_bytes) bytes, 16-byte aligned); a longer interval never touches ws.  route is a property
+ * of the bytes, the tables and the two constants.  F = 0 is a no-op; refused: null pointers, a small ws, sizes as mbx_jpeg_dec_entropy. */
+#ifndef MBX_JPEG_SYNC_BYTES
+#define MBX_JPEG_SYNC_BYTES 256       /* 128, 256 and 512 were measured: profiles/jpeg_sync_bench.txt */
+#endif
+#define MBX_JPEG_SYNC_CHUNK 256
+size_t mbx_jpeg_dec_sync_ws(int F, int n_int, long long max_interval_bytes);
+int mbx_jpeg_dec_entropy_sync(const unsigned char* data, long long data_bytes, const long long* pos, const unsigned* tables, int F, int H, int W,
+                              int sub, int restart, long long max_interval_bytes, short* coef, int* status, int* route, void* ws,
+                              size_t ws_bytes, void* stream);
+
 /* ---- measurement aid (bench.py`roofline.sustained_mfma_tflops`; not part of the model) --------------------------------------------
  * The bf16 MFMA rate the part sustains under its power cap with nothing but v_mfma_f32_32x32x16_bf16 in the loop (pseudo-random
  * operands; n_wg workgroups of 4 waves, `iters` x 16 MFMAs per wave).  ws: >= mbx_mfma_probe_ws(n_wg) bytes = a float sink

@@ -18,8 +18,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OBJ = os.path.join(HERE, 'csrc', '_obj')
 LIB = os.path.join(HERE, 'libmbx.so')
-SOURCES = ['elementwise.hip', 'gemm.hip', 'gemm_pipe.hip', 'mlp_fused.hip', 'gemm_rows.hip', 'gemm_rows_n.hip', 'attention.hip', 'attention_stream.hip', 'train_step.hip', 'augment.hip', 'pose_eval.hip', 'oneshot.hip', 'mesh.hip', 'smpl.hip', 'action.hip', 'wild.hip', 'motion2d.hip', 'amass.hip', 'render.hip', 'skeleton.hip', 'scene.hip', 'jpeg.hip', 'jpeg_dec.hip', 'probe.hip']
-HEADERS = [os.path.join(CSRC, 'mbx_common.h'), os.path.join(CSRC, 'mbx_diag.h'), os.path.join(CSRC, 'attention_common.h'), os.path.join(CSRC, 'gelu_fast.h'), os.path.join(CSRC, 'lds_stream.h'), os.path.join(CSRC, 'pose_solve.h'), os.path.join(CSRC, 'aug_rng.h'), os.path.join(CSRC, 'aug2d_point.h'), os.path.join(CSRC, 'smpl_math.h'), os.path.join(CSRC, 'render_tile.h'), os.path.join(CSRC, 'skeleton_prim.h'), os.path.join(CSRC, 'jpeg_tables.h'), os.path.join(os.path.dirname(HERE), 'include', 'mbx.h')]
+SOURCES = ['elementwise.hip', 'gemm.hip', 'gemm_pipe.hip', 'mlp_fused.hip', 'gemm_rows.hip', 'gemm_rows_n.hip', 'attention.hip', 'attention_stream.hip', 'train_step.hip', 'augment.hip', 'pose_eval.hip', 'oneshot.hip', 'mesh.hip', 'smpl.hip', 'action.hip', 'wild.hip', 'motion2d.hip', 'amass.hip', 'render.hip', 'skeleton.hip', 'scene.hip', 'jpeg.hip', 'jpeg_dec.hip', 'jpeg_sync.hip', 'probe.hip']
+HEADERS = [os.path.join(CSRC, 'mbx_common.h'), os.path.join(CSRC, 'mbx_diag.h'), os.path.join(CSRC, 'attention_common.h'), os.path.join(CSRC, 'gelu_fast.h'), os.path.join(CSRC, 'lds_stream.h'), os.path.join(CSRC, 'pose_solve.h'), os.path.join(CSRC, 'aug_rng.h'), os.path.join(CSRC, 'aug2d_point.h'), os.path.join(CSRC, 'smpl_math.h'), os.path.join(CSRC, 'render_tile.h'), os.path.join(CSRC, 'skeleton_prim.h'), os.path.join(CSRC, 'jpeg_tables.h'), os.path.join(CSRC, 'jpeg_dec_common.h'), os.path.join(os.path.dirname(HERE), 'include', 'mbx.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-Wno-unused-result']
 
 

@@ -56,7 +56,7 @@ int mbx_cu_count() {
     g_cus[dev].store(c, std::memory_order_relaxed);
     return c;
 }
-extern "C" int mbx_version(void) { return 250; }
+extern "C" int mbx_version(void) { return 260; }
 
 static inline int clamp_grid(size_t want, int cap) { return (int)(want < (size_t)cap ? (want ? want : 1) : (size_t)cap); }
 

@@ -12,13 +12,15 @@
 //                          of parallel work, ONE LANE per interval, one wave per workgroup.  The loop's body is one symbol, so the 64
 //                          intervals of a wave run in step, each with its own bit reader, predictors and (MCU, block, coefficient)
 //                          position, and diverge only inside a symbol.  The tables are staged in LDS once per workgroup.
-//                          Coefficients are zero unless a lane stores them.
+//                          Coefficients are zero unless a lane stores them.  The lane's body lives in jpeg_dec_common.h, because it is also the
+//                          fallback of mbx_jpeg_dec_entropy_sync (jpeg_sync.hip): the self-synchronising decode INSIDE an interval, for the
+//                          frames without restart markers that are one interval, and one lane here.
 //   mbx_jpeg_dec_pixels  : two launches.  jpeg_idct_kernel: eight lanes per block, dequantise and un-zigzag through LDS, columns, then
 //                          rows through the 72-word pitch of the encoder's stage A, the range-limit table, eight samples per lane as one
 //                          8-byte store into the component planes of the workspace (padded to whole MCUs).  jpeg_colour_kernel: four
 //                          consecutive pixels per lane, fancy upsampling read from the planes (the halo of a block is its neighbour's
 //                          samples, which only exist once every block of the frame is done), colour, three 4-byte stores.
-#include "mbx_common.h"
+#include "jpeg_dec_common.h"
 #include "jpeg_tables.h"
 
 #define JI_THREADS 256
@@ -28,26 +30,8 @@
 #define JP_BLOCKS (JP_THREADS / 8)
 #define JP_PITCH 72                   // words per block in LDS: 64 + 8, so that the column pass of four blocks covers 32 banks
 #define JC_THREADS 256
-#define TW MBX_JPEG_DEC_TABLE_WORDS
 
 namespace {
-
-struct DGeo {                         // a frame's MCU grid; sub 0 = 4:4:4, 1 = 4:2:0, 2 = 4:2:2
-    int H, W, sub, mx, my, n_mcu, bpm, hs, vs, dw, dh, cw, yw;
-    long long frame_bytes, y_bytes, c_bytes;
-};
-inline DGeo make_dgeo(int H, int W, int sub) {
-    DGeo g;
-    g.H = H; g.W = W; g.sub = sub;
-    g.hs = sub ? 2 : 1; g.vs = sub == 1 ? 2 : 1;
-    g.mx = (W + 8 * g.hs - 1) / (8 * g.hs); g.my = (H + 8 * g.vs - 1) / (8 * g.vs);
-    g.n_mcu = g.mx * g.my; g.bpm = g.hs * g.vs + 2;
-    g.dw = (W + g.hs - 1) / g.hs; g.dh = (H + g.vs - 1) / g.vs;       // the real chroma samples
-    g.cw = g.mx * 8; g.yw = g.mx * 8 * g.hs;                            // plane widths, whole MCUs
-    g.y_bytes = (long long)g.n_mcu * g.hs * g.vs * 64; g.c_bytes = (long long)g.n_mcu * 64;
-    g.frame_bytes = g.y_bytes + 2 * g.c_bytes;
-    return g;
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // the restart markers of every frame
@@ -109,60 +93,8 @@ __global__ __launch_bounds__(JI_THREADS) void jpeg_index_kernel(const unsigned c
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// entropy decoding: one lane per restart interval
+// entropy decoding: one lane per restart interval (the body: jpeg_decode_interval, jpeg_dec_common.h)
 // ---------------------------------------------------------------------------------------------------------------
-struct BitReader {
-    const unsigned char* data;
-    long long at, end;                // the next byte, the interval's end: every read is checked against it
-    unsigned long long acc;           // the low n bits are the next bits of the stream
-    int n;
-    __device__ __forceinline__ void fill() {
-        while (n <= 48 && at < end) {
-            const unsigned b = data[at++];
-            if (b == 0xffu && at < end && data[at] == 0u) ++at;          // the stuffed byte
-            acc = (acc << 8) | b;
-            n += 8;
-        }
-    }
-    __device__ __forceinline__ unsigned peek(int k) const {             // the next k <= 16 bits; zeros behind the end
-        return (unsigned)(n >= k ? acc >> (n - k) : acc << (k - n)) & ((1u << k) - 1u);
-    }
-};
-
-// one Huffman symbol, or a negative status; the caller has filled the reader.  t: the table in LDS (look 256 x u16 | maxcode 18 |
-// valoffset 18 | vals 256 x u8)
-__device__ __forceinline__ int jpeg_symbol(BitReader& r, const unsigned* __restrict__ t) {
-    const unsigned short* look = reinterpret_cast<const unsigned short*>(t);
-    const int* maxcode = reinterpret_cast<const int*>(t + 128);
-    const int* valoff = maxcode + 18;
-    const unsigned char* vals = reinterpret_cast<const unsigned char*>(t + 164);
-    const unsigned e = look[r.peek(8)];
-    int len = (int)(e >> 8), sym = (int)(e & 255u);
-    if (len < 1 || len > 8) {
-        const int code = (int)r.peek(16);
-        for (len = 9; len <= 16; ++len)
-            if ((code >> (16 - len)) <= maxcode[len]) break;
-        if (len > 16) return r.n < 16 ? -MBX_JPEG_DEC_TRUNCATED : -MBX_JPEG_DEC_BAD_CODE;
-        sym = vals[((code >> (16 - len)) + valoff[len]) & 255];
-    }
-    if (len > r.n) return -MBX_JPEG_DEC_TRUNCATED;
-    r.n -= len;
-    return sym;
-}
-
-// `s` <= 15 more bits, sign-extended as T.81 F.2.2.1 (EXTEND); ok false where the interval ends first.  No refill: a filled reader holds
-// 49 bits or all there are, a symbol and its bits take at most 16 + 15
-__device__ __forceinline__ int jpeg_receive_extend(BitReader& r, int s, bool& ok) {
-    if (s == 0) return 0;
-    if (s > r.n) { ok = false; return 0; }
-    const int v = (int)((r.acc >> (r.n - s)) & ((1u << s) - 1u));
-    r.n -= s;
-    return v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
-}
-
-// The lanes of a wave are kept in step by making the SYMBOL the loop's body: one trip decodes one Huffman symbol with its extra bits,
-// whether it is a DC difference or an AC (run, size), and then advances the lane's own (MCU, block, coefficient) state.  Nested loops over
-// MCUs, blocks and coefficients would let every lane sit in another loop, and the wave would walk them one after the other.
 __global__ __launch_bounds__(JD_THREADS) void jpeg_entropy_dec_kernel(const unsigned char* __restrict__ data, long long data_bytes,
                                                                       const long long* __restrict__ pos, const unsigned* __restrict__ tables,
                                                                       DGeo g, int restart, int n_int, long long n_all, short* __restrict__ coef,
@@ -173,64 +105,7 @@ __global__ __launch_bounds__(JD_THREADS) void jpeg_entropy_dec_kernel(const unsi
     const long long t = (long long)blockIdx.x * JD_THREADS + threadIdx.x;
     if (t >= n_all) return;
     if (status[t] != MBX_JPEG_DEC_OK) return;                            // the frame's markers are wrong: its coefficients stay zero
-    const int f = (int)(t / n_int), iv = (int)(t % n_int);
-    const long long* p = pos + (size_t)f * (n_int + 1) + iv;
-    BitReader r;
-    r.data = data;
-    r.at = p[0] < 0 ? 0 : p[0] > data_bytes ? data_bytes : p[0];
-    r.end = p[1] - 2 < r.at ? r.at : p[1] - 2 > data_bytes ? data_bytes : p[1] - 2;
-    r.acc = 0; r.n = 0;
-    const int per = restart ? restart : g.n_mcu;
-    const long long m0 = (long long)iv * per;
-    const int m1 = (int)(m0 + per < g.n_mcu ? m0 + per : g.n_mcu);
-    const int ny = g.bpm - 2;
-    unsigned pred0 = 0u, pred1 = 0u, pred2 = 0u;                          // wrap; only the low 16 bits are stored
-    int st = MBX_JPEG_DEC_OK;
-    int m = (int)m0, k = 0, z = 0;                                       // the next symbol belongs to coefficient z of block k of MCU m; z = 0: the DC
-    short* blk = coef + ((size_t)f * g.n_mcu + m) * g.bpm * 64;
-    bool busy = m < m1;
-    while (busy) {
-        r.fill();
-        const int c = k < ny ? 0 : k - ny + 1;
-        const bool dc = z == 0;
-        bool ok = true;
-        const int s = jpeg_symbol(r, tab + (2 * c + (dc ? 0 : 1)) * TW);
-        if (s < 0) st = -s;
-        else if (dc) {
-            const int d = jpeg_receive_extend(r, s & 15, ok);          // the tables hold no DC symbol above 15 (mbx_jpeg_dec_tables)
-            if (!ok) st = MBX_JPEG_DEC_TRUNCATED;
-            else {
-                const unsigned v = (c == 0 ? pred0 : c == 1 ? pred1 : pred2) + (unsigned)d;
-                pred0 = c == 0 ? v : pred0; pred1 = c == 1 ? v : pred1; pred2 = c == 2 ? v : pred2;
-                blk[0] = (short)v;
-                z = 1;
-            }
-        } else if (s == 0) z = 64;                                       // EOB
-        else {
-            z += s >> 4;
-            if (s & 15) {
-                if (z > 63) st = MBX_JPEG_DEC_RUN;
-                else {
-                    const int v = jpeg_receive_extend(r, s & 15, ok);
-                    if (!ok) st = MBX_JPEG_DEC_TRUNCATED;
-                    else blk[z] = (short)v;
-                }
-            } else if ((s >> 4) != 15) st = MBX_JPEG_DEC_BAD_CODE;       // (r, 0) other than EOB and ZRL is no baseline symbol
-            else if (z > 63) st = MBX_JPEG_DEC_RUN;                      // a ZRL whose zeros pass 63
-            ++z;
-        }
-        if (st != MBX_JPEG_DEC_OK) {                                     // the block the error lies in is zero like those behind it
-            uint4* b4 = reinterpret_cast<uint4*>(blk);
-            for (int j = 0; j < 8; ++j) b4[j] = make_uint4(0u, 0u, 0u, 0u);
-            busy = false;
-        } else if (z >= 64) {                                            // the next block
-            z = 0;
-            blk += 64;
-            if (++k == g.bpm) { k = 0; busy = ++m < m1; }
-        }
-    }
-    if (st == MBX_JPEG_DEC_OK && (r.n >= 8 || r.at < r.end)) st = MBX_JPEG_DEC_LEFTOVER;
-    status[t] = st;
+    jpeg_decode_interval(data, data_bytes, pos, tab, g, restart, n_int, t, coef, status);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

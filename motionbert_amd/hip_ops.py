@@ -147,6 +147,8 @@ SIGNATURES = {
     'mbx_jpeg_dec_index': (_i, [_vp, C.c_longlong, _vp, _i, _i, _vp, _vp, _vp]),
     'mbx_jpeg_dec_entropy': (_i, [_vp, C.c_longlong, _vp, _vp] + [_i] * 5 + [_vp, _vp, _vp]),
     'mbx_jpeg_dec_ws': (_sz, [_i] * 4),
+    'mbx_jpeg_dec_sync_ws': (_sz, [_i, _i, C.c_longlong]),
+    'mbx_jpeg_dec_entropy_sync': (_i, [_vp, C.c_longlong, _vp, _vp] + [_i] * 5 + [C.c_longlong, _vp, _vp, _vp, _vp, _sz, _vp]),
     'mbx_jpeg_dec_pixels': (_i, [_vp, _vp] + [_i] * 4 + [_vp, _vp, _sz, _vp]),
     'mbx_rows_n_pack_bytes': (_sz, [_i, _i]),
     'mbx_rows_lnbwd_t': (_i, [_vp] * 6 + [_i, _i, _i, _vp]),
@@ -1361,6 +1363,29 @@ class HipOps:
         self._dense('jpeg_dec_entropy', torch.int32, F * n_int, dev, status=status)
         self._ck(self.lib.mbx_jpeg_dec_entropy(_p(data), data.numel(), _p(pos), _p(tables), F, int(H), int(W), int(sub), int(restart), _p(coef),
                                                _p(status), self._stream()))
+
+    JPEG_SYNC_MAX_BYTES = 1 << 27
+
+    def jpeg_dec_sync_ws(self, F, n_int, max_interval_bytes, device):
+        """the lane states, chunk exits and sums of jpeg_dec_entropy_sync (mbx_jpeg_dec_sync_ws)"""
+        if not 0 <= int(max_interval_bytes) <= self.JPEG_SYNC_MAX_BYTES:
+            raise RuntimeError(f'libmbx: jpeg_dec_sync_ws: max_interval_bytes {max_interval_bytes} (0 .. {self.JPEG_SYNC_MAX_BYTES})')
+        n = int(self.lib.mbx_jpeg_dec_sync_ws(int(F), int(n_int), int(max_interval_bytes)))   # not cached: the longest scan differs in every call
+        return torch.empty(max(n, 16), dtype=torch.uint8, device=device)
+
+    def jpeg_dec_entropy_sync(self, data, pos, tables, H, W, sub, restart, max_interval_bytes, coef, status, route, ws):
+        """jpeg_dec_entropy with many lanes per interval: the same coef and status, and route i32 [F, n_int]: 0 where the interval was
+        decoded in parallel, else why the one-lane body decoded it (mbx_jpeg_dec_entropy_sync)"""
+        F, dev = coef.shape[0], data.device
+        n_mcu = self._jpeg_dec_blocks(H, W, sub) // (3 if sub == 0 else 6 if sub == 1 else 4)
+        n_int = -(-n_mcu // restart) if restart else 1
+        self._dense('jpeg_dec_entropy_sync', torch.uint8, None, dev, data=data, ws=ws)
+        self._dense('jpeg_dec_entropy_sync', torch.int64, F * (n_int + 1), dev, pos=pos)
+        self._dense('jpeg_dec_entropy_sync', torch.int32, 6 * self.JPEG_DEC_TABLE_WORDS, dev, tables=tables)
+        self._dense('jpeg_dec_entropy_sync', torch.int16, F * self._jpeg_dec_blocks(H, W, sub) * 64, dev, coef=coef)
+        self._dense('jpeg_dec_entropy_sync', torch.int32, F * n_int, dev, status=status, route=route)
+        self._ck(self.lib.mbx_jpeg_dec_entropy_sync(_p(data), data.numel(), _p(pos), _p(tables), F, int(H), int(W), int(sub), int(restart),
+                                                    int(max_interval_bytes), _p(coef), _p(status), _p(route), _p(ws), ws.numel(), self._stream()))
 
     def jpeg_dec_pixels(self, coef, q, H, W, sub, rgb, ws):
         """coef, q (uint8 [3,64] on the host: each component's table, zigzag order) -> rgb u8 [F,H,W,3] (mbx_jpeg_dec_pixels)"""

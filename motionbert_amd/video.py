@@ -21,8 +21,10 @@ Reading is the other half (csrc/jpeg_dec.hip): the compressed bytes cross the ho
     parse_jpeg(bytes)                                 the header facts of one baseline JFIF frame, on the host; raises ValueError naming the marker
                                                       of anything the decoder does not take
     decode_jpeg(data, offsets, device)                F files -> rgb uint8 [F,H,W,3] on the device, every pixel the one libjpeg's default path
-                                                      decodes (include/mbx.h has the definition); one host synchronisation, the status read
-    MJPEGReader(path)                                 RIFF 'AVI ' with an MJPG video stream: `.width .height .fps .frames`, `.read(a, b, device)`,
+                                                      decodes (include/mbx.h has the definition); one host synchronisation, the status read.
+                                                      entropy='auto' | 'interval' | 'sync': one lane per restart interval, or the parallel
+                                                      decode inside an interval (csrc/jpeg_sync.hip) that frames without DRI need
+    MJPEGReader(path, entropy)                              RIFF 'AVI ' with an MJPG video stream: `.width .height .fps .frames`, `.read(a, b, device)`,
                                                       `.chunks(chunk, device)` (the upload of the next chunk under the decode of this one)
     scene_video(..., background=reader)               the video's own frames behind the skeletons, decoded chunk by chunk
 
@@ -327,7 +329,21 @@ def _host_files(data, offsets, where):
     return (data.cpu() if data.is_cuda else data).contiguous().numpy(), off, data.contiguous() if data.is_cuda else None
 
 
-def _decode(prov, host, off, dev, dev_data, want, out, where, size=None):
+ENTROPY = ('auto', 'interval', 'sync')
+
+
+def _entropy_route(entropy, prov, where):
+    """`entropy` checked against the provider: 'auto' is 'interval' where the provider has no jpeg_dec_entropy_sync; 'sync' then raises"""
+    if entropy not in ENTROPY:
+        raise ValueError(f'{where}: entropy must be one of {ENTROPY}, got {entropy!r}')
+    if not (hasattr(prov, 'jpeg_dec_entropy_sync') and hasattr(prov, 'jpeg_dec_sync_ws')):
+        if entropy == 'sync':
+            raise RuntimeError(f"{where}: entropy='sync' needs a provider with jpeg_dec_entropy_sync and jpeg_dec_sync_ws; {type(prov).__name__} has none")
+        return 'interval'
+    return entropy
+
+
+def _decode(prov, host, off, dev, dev_data, want, out, where, size=None, entropy='auto'):
     """F files host[off[f]:off[f+1]] -> the dict of `want`.  dev_data: the same bytes on the device where they are there already, else they
     are uploaded here, once.  Consecutive frames that share geometry, quantisation and Huffman tables and restart interval go through the
     kernels together.  Nothing is launched before every header is parsed; the ONE host synchronisation is the read of the status."""
@@ -342,7 +358,8 @@ def _decode(prov, host, off, dev, dev_data, want, out, where, size=None):
         out = torch.empty(F, H, W, 3, dtype=torch.uint8, device=dev)
     elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (F, H, W, 3) or not out.is_contiguous() or out.device != dev:
         raise ValueError(f'{where}: out must be a contiguous uint8 tensor [{F},{H},{W},3] on {dev}')
-    res = dict(rgb=out, coef=None, status=None, pos=None)
+    res = dict(rgb=out, coef=None, status=None, pos=None, route=None)
+    entropy = _entropy_route(entropy, prov, where)
     if F == 0:
         return {k: res[k] for k in want}
 
@@ -353,14 +370,14 @@ def _decode(prov, host, off, dev, dev_data, want, out, where, size=None):
         if f == F or key(facts[f]) != key(facts[a]):
             groups.append((a, f))
             a = f
-    if len(groups) > 1 and any(k in want for k in ('coef', 'status', 'pos')):
+    if len(groups) > 1 and any(k in want for k in ('coef', 'status', 'pos', 'route')):
         raise ValueError(f'{where}: the test hooks {want!r} need frames that share subsampling, tables and restart interval')
     tables = [prov.jpeg_dec_tables(facts[a]['dht']) for a, _ in groups]              # host; a bad table raises before any launch
     scans = np.array([[off[f] + p['scan'][0], off[f] + p['scan'][1]] for f, p in enumerate(facts)], np.int64)
     if dev_data is None:
         dev_data = torch.from_numpy(host).to(dev, non_blocking=True) if dev.type == 'cuda' else torch.from_numpy(host)
     scans_dev = torch.from_numpy(scans).to(dev)
-    stats = []
+    stats, routes = [], []
     for (a, b), tab in zip(groups, tables):
         p = facts[a]
         sub = DEC_SUBSAMPLINGS.index(p['subsampling'])
@@ -370,12 +387,22 @@ def _decode(prov, host, off, dev, dev_data, want, out, where, size=None):
         status = torch.empty(b - a, n_int, dtype=torch.int32, device=dev)
         coef = torch.empty(b - a, mx * my, bpm, 64, dtype=torch.int16, device=dev)
         prov.jpeg_dec_index(dev_data, scans_dev[a:b], n_int, pos, status)
-        prov.jpeg_dec_entropy(dev_data, pos, tab.to(dev), H, W, sub, p['restart'], coef, status)
+        route = torch.zeros(b - a, n_int, dtype=torch.int32, device=dev)
+        if entropy == 'sync' or (entropy == 'auto' and n_int == 1):      # a frame that is one interval would be one lane of the other route
+            longest = max(q['scan'][1] - q['scan'][0] for q in facts[a:b])          # the host's parsed scan lengths bound every interval
+            prov.jpeg_dec_entropy_sync(dev_data, pos, tab.to(dev), H, W, sub, p['restart'], longest, coef, status, route,
+                                       prov.jpeg_dec_sync_ws(b - a, n_int, longest, dev))
+        else:
+            prov.jpeg_dec_entropy(dev_data, pos, tab.to(dev), H, W, sub, p['restart'], coef, status)
         if 'rgb' in want:
             prov.jpeg_dec_pixels(coef, p['q'], H, W, sub, out[a:b], prov.jpeg_dec_ws(b - a, H, W, sub, dev))
         stats.append(status)
+        routes.append(route)
         res.update(coef=coef, status=status, pos=pos)
-    flat = torch.cat([s.reshape(-1) for s in stats]).cpu().numpy()                    # the one host synchronisation
+    both = torch.cat([s.reshape(-1) for s in stats + routes]).cpu().numpy()           # the one host synchronisation: status and route together
+    flat = both[:both.size // 2]
+    if 'route' in want:
+        res['route'] = torch.from_numpy(both[both.size // 2:].reshape(routes[-1].shape).copy())
     if flat.any() and 'status' not in want:
         i = int(np.nonzero(flat)[0][0])
         for (a, b), s in zip(groups, stats):
@@ -386,25 +413,29 @@ def _decode(prov, host, off, dev, dev_data, want, out, where, size=None):
     return {k: res[k] for k in want}
 
 
-def decode_jpeg(data, offsets=None, device=None, want=('rgb',), out=None, ops=None):
+def decode_jpeg(data, offsets=None, device=None, want=('rgb',), out=None, ops=None, entropy='auto'):
     """F baseline JPEG files -> rgb uint8 [F,H,W,3] on the device, every pixel the one libjpeg's default path decodes.  `data`: a list of
     `bytes`, or a 1-D uint8 tensor or array (host or device) that holds the files back to back with `offsets` [F+1]; all frames must have
     one size; what `parse_jpeg` refuses raises before anything is launched.  `device`: where to decode (default: that of a device tensor,
     else the current ROCm device).  Host bytes are uploaded once; a device tensor is also read back once, for its headers.  With the
     default `want` the result is the rgb tensor (`out`, where one is given); any other `want` gives a dict: 'coef' (int16 [F, n_mcu, blocks
-    per MCU, 64], zigzag: the encoder's layout), 'pos' and 'status' (then a malformed interval does not raise) are test hooks.  ONE host
-    synchronisation, the read of the status: an interval that is malformed raises ValueError naming frame, interval and code."""
+    per MCU, 64], zigzag: the encoder's layout), 'pos', 'status' (then a malformed interval does not raise) and 'route' (int32 [F, n_int] on
+    the host: how mbx_jpeg_dec_entropy_sync decoded each interval, zeros on the other route) are test hooks.  `entropy`: 'interval' decodes
+    one restart interval per lane; 'sync' decodes inside the intervals in parallel (csrc/jpeg_sync.hip), with the same result for every
+    input; 'auto' takes 'sync' for the frames that are one interval (no DRI, or one that covers the frame), 'interval' otherwise and where
+    the provider has no jpeg_dec_entropy_sync.  ONE host synchronisation, the read of the status (and route): an interval that is malformed
+    raises ValueError naming frame, interval and code."""
     where = 'video.decode_jpeg'
     plain = want == ('rgb',) or want == 'rgb'
     want = (want,) if isinstance(want, str) else tuple(want)
-    if not want or any(k not in ('rgb', 'coef', 'status', 'pos') for k in want):
-        raise ValueError(f"{where}: want must name some of ('rgb', 'coef', 'status', 'pos'), got {want!r}")
+    if not want or any(k not in ('rgb', 'coef', 'status', 'pos', 'route') for k in want):
+        raise ValueError(f"{where}: want must name some of ('rgb', 'coef', 'status', 'pos', 'route'), got {want!r}")
     host, off, dev_data = _host_files(data, offsets, where)
     device = _dec_device(dev_data.device if device is None and dev_data is not None else device, ops, where)
     if dev_data is not None and dev_data.device != device:
         dev_data = None
     prov = hip_ops.provider(ops, 'motionbert_amd.' + where)
-    res = _decode(prov, host, off, device, dev_data, want, out, where)
+    res = _decode(prov, host, off, device, dev_data, want, out, where, entropy=entropy)
     return res['rgb'] if plain else res
 
 
@@ -415,10 +446,13 @@ class MJPEGReader:
     relative to the 'movi' fourcc or to the file: whichever names the stream's chunk, as players decide it), or by walking `movi` when there
     is no index; `LIST 'rec '` is descended, `JUNK` and everything else skipped; a chunk of length 0 repeats the frame before it.
     `.width .height .fps .frames`; `.frame_bytes(f)`; `.read(a, b, device)` -> uint8 [b - a, height, width, 3] on the device;
-    `.chunks(chunk, device)` yields them `chunk` at a time.  A context manager.  OpenDML files (a RIFF 'AVIX' after the first) are refused."""
+    `.chunks(chunk, device)` yields them `chunk` at a time.  `entropy`: as `decode_jpeg`'s, for every read.  A context manager.  OpenDML files
+    (a RIFF 'AVIX' after the first) are refused."""
 
-    def __init__(self, path):
-        self.path = path
+    def __init__(self, path, entropy='auto'):
+        if entropy not in ENTROPY:
+            raise ValueError(f'MJPEGReader: entropy must be one of {ENTROPY}, got {entropy!r}')
+        self.path, self.entropy = path, entropy
         self.file = open(path, 'rb')
         try:
             self.map = mmap.mmap(self.file.fileno(), 0, access=mmap.ACCESS_READ)
@@ -543,7 +577,8 @@ class MJPEGReader:
         self._span(a, b, where)
         device = _dec_device(device, ops, where)
         host, off = self._gather(a, b)
-        return _decode(hip_ops.provider(ops, 'motionbert_amd.' + where), host, off, device, None, ('rgb',), out, where, (self.height, self.width))['rgb']
+        return _decode(hip_ops.provider(ops, 'motionbert_amd.' + where), host, off, device, None, ('rgb',), out, where, (self.height, self.width),
+                       self.entropy)['rgb']
 
     def chunks(self, chunk: int = 32, device=None, ops=None):
         """A generator of device tensors uint8 [n, height, width, 3], n <= `chunk` frames at a time, in frame order.  The structure of
@@ -581,7 +616,7 @@ class MJPEGReader:
             ahead = upload(i + 1) if i + 1 < len(spans) else None
             if ev is not None:
                 torch.cuda.current_stream(device).wait_event(ev)
-            yield _decode(prov, host, off, device, dbuf[k][:host.size], ('rgb',), rgb[k][:b - a], where, (self.height, self.width))['rgb']
+            yield _decode(prov, host, off, device, dbuf[k][:host.size], ('rgb',), rgb[k][:b - a], where, (self.height, self.width), self.entropy)['rgb']
 
     def close(self):
         if getattr(self, 'map', None) is not None:
