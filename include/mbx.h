@@ -377,6 +377,10 @@ int mbx_flip_average(const float* out2, const int* perm, float* out, int B, int 
  *   e2 = mean_j |a p_j R + t - g_j|, (a, R, t) the optimal similarity transform of p onto g    (lib/model/loss.py:16-51  p_mpjpe)
  * e1, e2 [N,T] f64; all arithmetic after the f32 loads is f64.  The 3x3 decomposition is a fixed 8 sweeps of cyclic Jacobi on H^T H
  * with the third singular vectors taken as cross products (planar poses are fine; no data-dependent loop, terminates on NaN input).
+ * Accuracy of e2, in the singular values s0 >= s1 of H = X0^T Y0 (centred gt, centred pred): 1e-10 relative against a LAPACK SVD where
+ * s1 / s0 >= 1e-3, which every human pose is; for a needle-shaped pose below that the roll about the needle's axis degrades and e2 is
+ * off by at most (2 s1 |X0| + 2 min(|X0_T|, a |Y0_T|)) / sqrt(J), the transverse extents (csrc/pose_solve.h); a pose exactly on a line
+ * and J = 2 (H of rank one) give the reference's value to rounding.  e2 is finite for every pair of finite poses of non-zero extent.
  * 1 < J <= 64.  pred / gt / x need 4-byte alignment only.  A frame whose pred or gt has zero extent (all joints equal) gives e2 = NaN,
  * the reference's 0/0; a non-finite e1 is dropped by mbx_eval_reduce as the reference's `e1_all[idx] > 0` drops it. */
 int mbx_pose_errors(const float* pred, const float* gt, const float* hw, const float* factor, const float* x, int x_channels, int rootrel,
@@ -481,7 +485,8 @@ int mbx_mesh_param_loss(const float* pred_theta, const float* gt_theta, int loss
  *   err[3] PA-MPJPE, 17 joints: after rigid_align's similarity transform of the prediction onto the target   ('pa_mpjpe_17j')
  *   err[4] PA-MPJPE, 14 joints                                       ('pa_mpjpe')
  * One workgroup per frame streams the vertices with 4-byte loads (frame bases need no more alignment).  The 3x3 decomposition is the
- * fixed-sweep Jacobi of mbx_pose_errors (csrc/pose_solve.h).  A frame whose predicted joints have zero extent gives NaN in rows 3 / 4
+ * fixed-sweep Jacobi of mbx_pose_errors (csrc/pose_solve.h), with its accuracy: rows 3 / 4 agree with the reference to 1e-10 relative
+ * where s1 / s0 >= 1e-3, within the transverse extent of the thinner pose below that, and are finite down to rank one.  A frame whose predicted joints have zero extent gives NaN in rows 3 / 4
  * as the reference's 0 / 0 does; a target of zero extent alone gives the reference's scale 0.  1 <= V. */
 int mbx_mesh_errors(const float* verts_p, const float* verts_g, const float* kp_p, const float* kp_g, double* err, int F, int V,
                     void* stream);

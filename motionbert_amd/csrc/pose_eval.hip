@@ -22,7 +22,8 @@
 // right vectors give u_i = H v_i / s_i; the third pair is v2 = v0 x v1, u2 = u0 x u1.  With both triples right-handed
 // R = sum_i v_i u_i^T has det +1 -- the reference's matrix after its flip -- and the signed third singular value is
 // u2 . H v2 (= det-sign * s2, and 0 for a planar pose, whose third vectors a division could not give).
-// A frame whose pred or gt has zero extent divides 0 by 0 as the reference does: e2 is NaN there.
+// A frame whose pred or gt has zero extent divides 0 by 0 as the reference does: e2 is NaN there.  Every other pair of finite poses
+// gives a finite e2, a pose on a line and J = 2 (H of rank one) included; pose_solve.h states the accuracy below s1 / s0 = 1e-3.
 // ---------------------------------------------------------------------------------------------------------------
 #define PE_FRAMES 64
 

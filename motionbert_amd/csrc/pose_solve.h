@@ -1,5 +1,19 @@
 // The 3x3 decomposition behind every Procrustes alignment of the library (pose_eval.hip: mbx_pose_errors; mesh.hip: mbx_mesh_errors).
-// fp64, a fixed number of operations: no data-dependent loop, terminates on NaN input.
+// fp64, a fixed number of operations: no data-dependent loop, terminates on NaN input (NaN in, NaN out).
+//
+// Domain and accuracy, in the singular values s0 >= s1 >= |s2| of H.  For every finite H with s0 > 0 the result is a proper rotation
+// (orthogonal to rounding, det +1) and a finite ssum:
+//   s1 / s0 >= 1e-3          the aligned error agrees with a LAPACK SVD to 1e-10 of the larger of itself and the rms joint distance from
+//                            the centroid (measured on the MI355X: 5e-13, profiles/procrustes_parity.txt).  Every human pose is here;
+//                            s2 may be anything, 0 (a planar pose) and negative (a mirrored one) included.
+//   2^-26 < s1 / s0 < 1e-3   a needle.  The right vectors come from H^T H, whose squaring leaves v1, v2 with a relative error of about
+//                            2^-52 (s0 / s1)^2: the roll about the needle's axis degrades and is lost at the lower end.  u0, v0, the
+//                            orthogonality of R and s0 are not affected, so the aligned error is off by at most
+//                                (2 s1 |X0| + 2 min(|X0_T|, a |Y0_T|)) / sqrt(J)
+//                            with X0_T, Y0_T the parts of the centred poses transverse to their leading axes (tests/procerr.py derives it).
+//   s1 / s0 <= 2^-26         rank one: a pose on a line, or J = 2.  u1 is chosen orthogonal to u0 and s1 counts as 0.  The bound above
+//                            holds; for an exactly collinear pose it is 0 and the result is the reference's to rounding.
+// Taking V from H itself (one-sided Jacobi) would remove the middle band.
 #pragma once
 
 // one Jacobi rotation of the symmetric 3x3 matrix in the (p, q) plane; r is the third index.  V's columns p and q follow.
@@ -62,8 +76,20 @@ __device__ __forceinline__ void pe_rotation(double h00, double h01, double h02, 
     double u01 = h00 * v01 + h01 * v11 + h02 * v21, u11 = h10 * v01 + h11 * v11 + h12 * v21, u21 = h20 * v01 + h21 * v11 + h22 * v21;
     const double dot = u00 * u01 + u10 * u11 + u20 * u21;
     u01 -= dot * u00; u11 -= dot * u10; u21 -= dot * u20;
-    const double sv1 = sqrt(u01 * u01 + u11 * u11 + u21 * u21);
-    u01 /= sv1; u11 /= sv1; u21 /= sv1;
+    double sv1 = sqrt(u01 * u01 + u11 * u11 + u21 * u21);
+    // rank one.  v1 is an eigenvector of H^T H, whose eigenvalues carry an error of 2^-52 lambda_0: at lambda_1 <= 2^-52 lambda_0, that is
+    // s1 <= 2^-26 s0, v1 holds no information and H v1 is rounding noise or exactly 0 (a pose on a line, J = 2).  Then u1 is any unit
+    // vector orthogonal to u0 -- u0 x e_k, k the axis of u0's smallest component, of length >= sqrt(2/3) before it is normalised -- and
+    // s1 counts as 0.  Computed for every frame and selected: no branch.  Written as !(sv1 > thr * sv0), so that a NaN takes the
+    // fallback and comes out of it as the NaN of u0.
+    const double ax = fabs(u00), ay = fabs(u10), az = fabs(u20);
+    const bool kx = ax <= ay && ax <= az, ky = ay <= az;
+    double f0 = kx ? 0.0 : (ky ? -u20 : u10), f1 = kx ? u20 : (ky ? 0.0 : -u00), f2 = kx ? -u10 : (ky ? u00 : 0.0);
+    const double fn = sqrt(f0 * f0 + f1 * f1 + f2 * f2);
+    f0 /= fn; f1 /= fn; f2 /= fn;
+    const bool rank_one = !(sv1 > 0x1p-26 * sv0);
+    u01 = rank_one ? f0 : u01 / sv1; u11 = rank_one ? f1 : u11 / sv1; u21 = rank_one ? f2 : u21 / sv1;
+    sv1 = rank_one ? 0.0 * sv0 : sv1;          // (0 * NaN = NaN)
     const double u02 = u10 * u21 - u20 * u11, u12 = u20 * u01 - u00 * u21, u22 = u00 * u11 - u10 * u01;
     const double w0 = h00 * v02 + h01 * v12 + h02 * v22, w1 = h10 * v02 + h11 * v12 + h12 * v22, w2 = h20 * v02 + h21 * v12 + h22 * v22;
     const double sv2 = u02 * w0 + u12 * w1 + u22 * w2;     // signed: negative when the best orthogonal map is a reflection

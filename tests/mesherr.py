@@ -306,8 +306,9 @@ def err_ratio(got, ref):
 # ------------------------------------------------------------------------------------------------ the fp64 kernel's own algebra
 def _align_model(A, B, corrupt=None):
     """mean |aligned_j - B_j| the way mbx_mesh_errors forms it (csrc/pose_solve.h): right vectors from the eigen-decomposition of H^T H
-    (the kernel: 8 Jacobi sweeps), u_i = H v_i / s_i for the two leading ones, the third pair as cross products, the signed third
-    singular value u2 . H v2.  A = prediction, B = target, [n,3] float64."""
+    (the kernel: 8 Jacobi sweeps; tests/procerr.py models those), u_i = H v_i / s_i for the two leading ones, with the kernel's guard for a
+    rank-one H (procerr.rank_one_guard), the third pair as cross products, the signed third singular value u2 . H v2.
+    A = prediction, B = target, [n,3] float64."""
     with np.errstate(divide='ignore', invalid='ignore'):
         Y0, X0 = A - A.mean(0), B - B.mean(0)
         nx, ny = (X0 ** 2).sum(), (Y0 ** 2).sum()
@@ -324,8 +325,8 @@ def _align_model(A, B, corrupt=None):
         u0 = u0 / s0
         u1 = H @ v1
         u1 = u1 - (u0 @ u1) * u0
-        s1 = np.linalg.norm(u1)
-        u1 = u1 / s1
+        from tests import procerr                # (procerr reads rigid_align64 from this module)
+        u1, s1 = procerr.rank_one_guard(u0, u1, s0, np.linalg.norm(u1))
         u2 = np.cross(u0, u1)
         s2 = u2 @ (H @ v2)
         if corrupt == 'no_reflection_fix' and s2 < 0:
