@@ -31,6 +31,7 @@ as row constants in its epilogue (mbx_rows_gemm_nk_ln), the MLP as ONE kernel (m
 """
 from __future__ import annotations
 
+import functools
 from collections import namedtuple
 from dataclasses import dataclass
 from typing import Any, ClassVar, Dict, List, Optional
@@ -79,7 +80,7 @@ class Switches:
     """The A/B switches of the sequencing: one `MBX_*` environment variable each, every one ON by default.
     They are read ONCE, when this module is imported (`SWITCHES`); a test or a tool that flips one afterwards calls
     `reload_switches()` (or patches `engine.SWITCHES` with `Switches.from_env({...})`).  What each one selects is described where
-    `Engine.__init__` consumes it."""
+    it is decided: in `_plan` (the scheduling ones, dual_stream and x3_planes, in `Engine.__init__`)."""
     x3_planes: bool       # MBX_X3_PLANES      bf16x3: producers write the operand planes themselves (0: every operand through mbx_split_bf16)
     dual_stream: bool     # MBX_DUAL_STREAM    the ts Block of a level on a second HIP stream
     fold_ln: bool         # MBX_FOLD_LN        LayerNorm folded into the Linear it feeds (bf16)
@@ -182,6 +183,128 @@ def rows_resid_ln_fits(M: int, N: int, K: int) -> bool:
     return M * N * 4 < ROW_OFFSET_LIMIT and M * K * 2 < ROW_OFFSET_LIMIT
 
 
+@dataclass(frozen=True)
+class Caps:
+    """What a pass may use: every A/B switch ANDed with the provider's capability, as the engine holds them when the pass is prepared
+    (`Engine.__init__`; model.py lowers fold / gelu_d / recompute afterwards)."""
+    fold: bool = False             # LayerNorm folded into the Linear it feeds: bf16 without dropout only (Engine.__init__)
+    x3: bool = False               # precision bf16x3 (the plain weights then come as operand planes)
+    recompute: bool = False        # low-memory mode
+    gelu_d: bool = False           # fc1 may save gelu'(u)
+    grad_stream: bool = False      # gradient of the residual stream in the operand type
+    rows_lnbwd: bool = False       # mbx_rows_lnbwd_t
+    rows_resid_ln: bool = False    # mbx_rows_resid_ln
+    block_grad_t: bool = False     # ... and the operand-typed gradient across Block boundaries
+    proj_mlp: bool = False         # mbx_proj_mlp_fused_fwd
+    fuse_ln: bool = False          # mbx_fuse_ln_fwd
+
+
+class SubPlan(namedtuple('SubPlan', 'lin_in lin_out front save tail')):
+    """One sub-layer of the plan.
+    lin_in   'ln'    tile GEMM on the output of a LayerNorm (its own, or the one that came with x from its producer)
+             'raw'   row-owner GEMM / fused MLP straight from the fp32 rows (no-grad sequencing)
+    lin_out  'tile'  proj / fc2 as a tile GEMM with the residual epilogue
+             'rows'  mbx_rows_resid_ln: residual GEMM + the plain normalisation for the next sub-layer
+             'deferred'  the proj is left to the MLP kernel that follows;  'fused'  the MLP is one kernel (`front`: the proj it runs first)
+    save     what an MLP keeps for GELU': 'u' the pre-activation, 'd' the derivative itself (None: attention, no backward)
+    tail     backward from the Linear-in's output gradient: 'plain' (dX GEMM + LayerNorm backward), 'fold' (tile dX GEMM with the folded
+             LayerNorm backward as its epilogue, row dots from the core) or 'rows' (mbx_rows_lnbwd_t; no row dots).  The FIRST sub-layer
+             of a Block is only eligible for 'rows': it takes it when its caller wants the operand-typed gradient alone and adds nothing."""
+
+
+@dataclass(frozen=True)
+class Plan:
+    """Which kernel serves every sub-layer of one pass: decided once (`plan_pass`), read by every sequencing method."""
+    fold: bool              # folded sequencing (else plain: fp32-class modes, dropout)
+    gstream: bool           # backward: the gradient of the residual stream travels in the operand type inside a Block
+    sub: Dict[tuple, SubPlan]      # (block prefix, sub) -> SubPlan
+    out_t: tuple            # per level: the Blocks hand their input gradients down operand-typed, as a pair
+    embed_norm: bool        # the embedding's rows come with ONE plain normalisation for both Blocks of level 0
+    fuse_norm: tuple        # per level, what the fusion kernel normalises: None, 'xhat' (one plain normalisation for both Blocks of the
+                            # next level), 'pair' (their two LayerNorms) or 'norm' (the final one)
+    pack_f: tuple           # proj / fc2 in the fragment order of mbx_rows_resid_ln           (lin_out 'rows')
+    pack_n: tuple           # transposed folded qkv / fc1 in the order of mbx_rows_lnbwd_t    (tail 'rows')
+    pack_k: tuple           # no-grad: ('mlp', module, proj in front or None) / ('qkv', Linear, None) in packing order
+    formats: tuple          # everything above that selects a prepared-weight format (key of the weight cache)
+
+
+def plan_pass(cfg: ModelCfg, caps: Caps, M: int, need_grad: bool, rawln: bool) -> Plan:
+    """The plan of a pass over M rows: a pure function of its arguments (and of ROW_OFFSET_LIMIT)."""
+    return _plan(cfg, caps, M, need_grad, rawln, ROW_OFFSET_LIMIT)
+
+
+@functools.lru_cache(maxsize=64)      # (building it takes ~65 us at depth 5, 3 % of a one-clip no-grad forward; a hit under 1 us)
+def _plan(cfg, caps, M, need_grad, rawln, _limit):
+    # The folded sequencing (round 3, bf16 path; include/mbx.h "LayerNorm folded into the Linear it feeds"): the LayerNorm kernels write
+    # the plain normalisation xhat, the affine part lives in the qkv / fc1 weights, and the LayerNorm BACKWARD runs as the epilogue of the
+    # dX GEMM -- 40 LayerNorm-backward launches and the saved fp32 sub-layer inputs disappear.  Never with dropout (the masks sit between
+    # the producer and the row dots) nor in the fp32-class modes (bf16 kernels only): the engine grants `caps.fold` only without them, so
+    # NOTHING below asks about dropout or bf16x3 -- every folded, row-owner or no-grad entry implies that there is neither.
+    fold = caps.fold
+    rawln = rawln and fold
+    # Gradient residual stream in the operand type BETWEEN the four sub-layers of a Block (round 4; fp32 arithmetic in the kernels): the
+    # folded LayerNorm-backward GEMM reads its dres as bf16 and writes ONLY the bf16 dx, which is the stream and the next GEMMs' operand
+    # at once -- 4 instead of 12 bytes per element and launch.  Numerics: tools/gradstream_numerics.py / profiles/r04_gradstream_numerics.txt.
+    gstream = fold and caps.grad_stream
+    # The row-owner kernels serve a bounded row count (ROW_OFFSET_LIMIT): whether they run is a matter of THIS pass's M and of the longest
+    # contraction each of them meets -- dX of qkv: 3 C, dX of fc1 and fc2 itself: hidden.  Beyond it the tile kernels run, in forward and
+    # backward alike, exactly as with the A/B switch off.
+    # Round 5, backward: inside a Block (bf16 gradient stream in and out, no second summand) the folded LayerNorm backward is the epilogue
+    # of a row-owner GEMM that takes both row means from its own accumulators (mbx_rows_lnbwd_t): the producers of dY -- attention
+    # backward, the GELU' GEMM -- run WITHOUT their row dots there, and no row-constant launch is needed.
+    lnbwd_rows = need_grad and gstream and caps.rows_lnbwd and rows_lnbwd_fits(M, cfg.C, max(3 * cfg.C, cfg.hidden))
+    # ... and ACROSS Block boundaries: the first sub-layer of a Block then takes the row-owner tail too (no row dots, no row constants,
+    # bf16 out), and the fusion backward of the level below (the embedding backward below level 0) reads the two Blocks' input gradients
+    # as a bf16 pair and adds them (same bytes as one fp32 tensor).  Numerics: profiles/r05_boundary_numerics.txt.  Otherwise a Block's
+    # input gradient leaves in fp32 with the other stream's gradient added: the tile kernel's epilogue.
+    first_rows = lnbwd_rows and caps.block_grad_t and cfg.att_fuse
+    # Round 5, forward: the residual GEMM (proj / fc2) of a sub-layer that is followed by a LayerNorm runs on the same row-owner shape
+    # and leaves the plain normalisation of its output rows with them (mbx_rows_resid_ln): three of the four LayerNorm launches of a
+    # Block -- each a second read of the fp32 rows -- disappear.  Folded sequencing only (the kernel writes xhat, not gamma xhat + beta);
+    # the fourth sub-layer feeds the fusion, not a LayerNorm.
+    resid_rows = fold and not rawln and caps.rows_resid_ln and rows_resid_ln_fits(M, cfg.C, max(cfg.C, cfg.hidden))
+    sub, pack_f, pack_k, rows_in = {}, [], [], set()
+    for stream, kind in STREAMS:
+        order = ORDER[kind]
+        for i in range(cfg.depth):
+            pre, front = f'{stream}.{i}', None
+            for s, (typ, _, mod, _) in enumerate(order):
+                if rawln and typ == 'attn':
+                    # no-grad: proj + residual run inside the MLP kernel that follows the attention in its Block
+                    defer = caps.proj_mlp and s + 1 < len(order) and order[s + 1][0] == 'mlp'
+                    front = f'{pre}.{mod}.proj' if defer else None
+                    sp = SubPlan('raw', 'deferred' if defer else 'tile', None, None, None)
+                elif rawln:
+                    sp, front = SubPlan('raw', 'fused', front, None, None), None
+                    pack_k.append(('mlp', f'{pre}.{mod}', sp.front))
+                else:
+                    tail = None if not need_grad else 'plain' if not fold else 'rows' if lnbwd_rows and (s > 0 or first_rows) else 'fold'
+                    # Round 5 (VERDICT r4 item 5): where the row-owner tail takes the row means, the GELU' epilogue no longer has to
+                    # produce the dot of du with the pre-activation: fc1's forward epilogue saves gelu'(u) -- from the fp32 accumulator
+                    # -- INSTEAD of u (same bytes) and the backward epilogue is one multiply (mbx_gemm_nt_gelu_d / mbx_gemm_nt_mul).
+                    # Never for a first sub-layer, whose tail still depends on its caller; recompute rebuilds g from u.
+                    save = None if typ == 'attn' or not need_grad else 'd' if tail == 'rows' and s > 0 and caps.gelu_d and not caps.recompute else 'u'
+                    sp = SubPlan('ln', 'rows' if resid_rows and s + 1 < len(order) else 'tile', None, save, tail)
+                sub[pre, s] = sp
+                if sp.lin_out == 'rows':
+                    pack_f.append(f'{pre}.{mod}.{LINEARS[typ][1]}')
+                if sp.tail == 'rows':
+                    rows_in.add(f'{pre}.{mod}.{LINEARS[typ][0]}')
+            if rawln:      # the Block is complete: its two qkv
+                pack_k += [('qkv', f'{pre}.{a}.qkv', None) for a in ('attn_s', 'attn_t')]
+    out_t = tuple(all(sub[f'{stream}.{i}', 0].tail == 'rows' for stream, _ in STREAMS) for i in range(cfg.depth))
+    # the fusion kernel also normalises its output for its consumers: the first LayerNorm of both Blocks of the next level (folded: ONE
+    # plain normalisation, no gamma / beta, serves both) or the final `norm`; no-grad: the next level's consumers read the fp32 rows
+    fuse_norm = tuple(None if not (cfg.att_fuse and caps.fuse_ln) else 'norm' if i + 1 == cfg.depth else None if rawln else
+                      'xhat' if fold else 'pair' for i in range(cfg.depth))
+    pack_f, pack_k = tuple(pack_f), tuple(pack_k)
+    pack_n = tuple(lin for lin, _ in folded_pairs(cfg) if lin in rows_in)
+    # folded: both Blocks of a level read the SAME plain normalisation of h (their gamma / beta live in their own weights) -- one launch
+    # for level 0 too, or none where the embedding kernel normalises its own rows
+    return Plan(fold=fold, gstream=gstream, sub=sub, out_t=out_t, embed_norm=fold and not rawln, fuse_norm=fuse_norm,
+                pack_f=pack_f, pack_n=pack_n, pack_k=pack_k, formats=(fold, caps.x3, pack_f, pack_k))
+
+
 class Drops(namedtuple('Drops', 'p seed_branch seed_act p_path seed_path p_attn seed_attn')):
     """Active dropout of one sub-layer (`Engine._drops`): rates and mask seeds of proj_drop / the MLP drops (on the branch output, after
     the activation), of DropPath and of the dropout on the attention probabilities."""
@@ -222,56 +345,34 @@ class Engine:
         # (Measured and dropped: the weight-gradient GEMMs on a third stream -- 137.0 -> 136.0 ms per step at 64 clips, but the
         # operands stay alive until that stream catches up (record_stream), which at 256 clips (231 GiB resident) sends the
         # allocator into retries: 421 -> 37 clips/s.)
-        # LayerNorm folding (round 3, bf16 path; include/mbx.h "LayerNorm folded into the Linear it feeds"): the LayerNorm kernels
-        # write the plain normalisation xhat, the affine part lives in the qkv / fc1 weights, and the LayerNorm BACKWARD runs as the
-        # epilogue of the dX GEMM from row dots the attention-backward / GELU' kernels emit -- 40 LayerNorm-backward launches and the
-        # saved fp32 sub-layer inputs disappear.  Off with dropout (the masks sit between the producer and the row dots), in the
-        # fp32-class modes (bf16 kernels only), or by request (model.fold_ln = False / MBX_FOLD_LN=0: the A/B switch).
+        # What the plan of a pass may use (`Caps`, `_plan` says what each is for): A/B switch AND the provider's capability.  `fold`
+        # also by request (model.fold_ln = False), `gelu_d` likewise; model.py lowers both, and sets `recompute`, after construction.
         self.fold = sw.fold_ln and not x3 and drop_seed is None and self._can('can_fold')
-        # Gradient residual stream in the operand type BETWEEN the four sub-layers of a Block (round 4; fp32 at the Block boundaries,
-        # fp32 arithmetic in the kernels): the folded LayerNorm-backward GEMM reads its dres as bf16 and writes ONLY the bf16 dx, which
-        # is the stream and the next GEMMs' operand at once -- 4 instead of 12 bytes per element and launch.  Numerics:
-        # tools/gradstream_numerics.py / profiles/r04_gradstream_numerics.txt (every gate unchanged).  MBX_GRAD_STREAM=0: the A/B switch.
         self.gstream_allowed = sw.grad_stream and bool(getattr(ops, 'grad_stream_t', False))
-        self.gstream = False      # decided per backward (the folded sequencing only)
+        self.rows_lnbwd = sw.rows_lnbwd and self._can('can_rows_lnbwd')
+        self.rows_resid_ln = sw.rows_resid_ln and self._can('can_rows_resid_ln')
+        self.block_grad_t = sw.block_grad_t and self.rows_lnbwd and hasattr(ops, 'fuse_bwd_pair') and hasattr(ops, 'embed_bwd_pair')
+        self.gelu_d = sw.gelu_d and self.rows_lnbwd and self._can('can_gelu_d')
+        self.proj_mlp = sw.proj_mlp and hasattr(ops, 'proj_mlp_fused_fwd')      # 0 = proj + residual as its own GEMM
+        self.rawln_allowed = sw.rawln      # A/B switch: 0 = the training sequencing without saves
+        # State of a pass; complete here, so that a caller may drive a Block without `forward()` (bench.py): it sets dev / B / Tlen / M
+        # (and rawln, grads) itself and calls prepare_weights(), which makes the plan.
+        self.rawln = False        # no-grad sequencing of a Block (decided per forward): raw-operand LayerNorm + fused MLP, see the module docstring
+        self.gstream = False      # read by nothing (the plan has it); kept assignable for bench.py, which still sets it
+        self.ragged = None        # (clip_tab, n_clips, max_len) of a ragged batch
+        self.plan: Optional[Plan] = None
+        self.grads = None
         self.Bf: Dict[str, torch.Tensor] = {}
         self.Rs: Dict[str, torch.Tensor] = {}
-        # Round 5: inside a Block (bf16 gradient stream in and out, no second summand) the folded LayerNorm backward runs as the
-        # epilogue of a row-owner GEMM that takes both row means from its own accumulators (mbx_rows_lnbwd_t): the producers of dY --
-        # attention backward, the GELU' GEMM -- run WITHOUT their row dots there, and no row-constant launch is needed.  The first
-        # sub-layer of a Block (fp32 out, the other block's gradient added) keeps the tile kernel.  MBX_ROWS_LNBWD=0: the A/B switch.
-        self.rows_lnbwd = sw.rows_lnbwd and self._can('can_rows_lnbwd')
-        self.Pn: Dict[str, torch.Tensor] = {}       # transposed folded weights in the fragment order of mbx_rows_lnbwd_t
-        # Round 5: the FORWARD residual GEMM (proj / fc2) of a sub-layer that is followed by a LayerNorm runs on the same row-owner shape
-        # and leaves the plain normalisation of its output rows with them (mbx_rows_resid_ln): three of the four LayerNorm launches of a
-        # Block -- each a second read of the fp32 rows -- disappear.  Folded sequencing only (the kernel writes xhat, not gamma xhat +
-        # beta), no dropout on the branch.  MBX_ROWS_RESID_LN=0: the A/B switch.
-        self.rows_resid_ln = sw.rows_resid_ln and self._can('can_rows_resid_ln')
-        self.Pf: Dict[str, torch.Tensor] = {}       # proj / fc2 weights of those sub-layers in the fragment order of the row-owner kernels
-        # Round 5: the gradient of the residual stream stays in the operand type ACROSS Block boundaries too: the first
-        # sub-layer of a Block then also takes the row-owner LayerNorm backward (no row dots, no row constants, bf16 out), and the fusion
-        # backward of the level below reads the two Blocks' input gradients as a bf16 pair and adds them (same bytes as one fp32 tensor).
-        # Numerics: four realisations on both reference-minted fixtures, every frozen gate (profiles/r05_boundary_numerics.txt).
-        # The embedding backward reads level 0's pair the same way (mbx_embed_bwd_pair).  MBX_BLOCK_GRAD_T=0: the A/B switch.
-        self.block_grad_t = sw.block_grad_t and self.rows_lnbwd and hasattr(ops, 'fuse_bwd_pair') and hasattr(ops, 'embed_bwd_pair')
-        # Round 5: with the row means taken by that kernel the GELU' epilogue no longer has to produce the dot of
-        # du with the pre-activation, so fc1's forward epilogue saves gelu'(u) -- taken from the fp32 accumulator -- INSTEAD of u (same
-        # bytes) and the backward epilogue is one multiply (mbx_gemm_nt_gelu_d / mbx_gemm_nt_mul).  MBX_GELU_D=0: the A/B switch.
-        self.gelu_d = sw.gelu_d and self.rows_lnbwd and self._can('can_gelu_d')
-        # no-grad sequencing of a Block (decided per forward): raw-operand LayerNorm + fused MLP, see the module docstring
-        self.rawln = False
-        self.rawln_allowed = sw.rawln      # A/B switch: 0 = the training sequencing without saves
-        self.Pk: Dict[str, torch.Tensor] = {}       # fc1 / fc2 of every MLP (with the proj in front of it) in the fragment order of the fused kernels
-        self.Pk_proj: Dict[str, str] = {}           # MLP -> the proj Linear packed in front of it (derived from ORDER)
-        self.proj_mlp = sw.proj_mlp and hasattr(ops, 'proj_mlp_fused_fwd')      # A/B switch: 0 = proj + residual as its own GEMM
+        self.Pn: Dict[str, torch.Tensor] = {}       # plan.pack_n: transposed folded weights in the fragment order of mbx_rows_lnbwd_t
+        self.Pf: Dict[str, torch.Tensor] = {}       # plan.pack_f: proj / fc2 in the fragment order of the row-owner kernels
+        self.Pk: Dict[str, torch.Tensor] = {}       # plan.pack_k: fc1 / fc2 of every MLP (with the proj in front of it) and every qkv, fused kernels' order
 
-    def _choose_row_kernels(self):
-        """The row-owner kernels serve a bounded row count (ROW_OFFSET_LIMIT): whether they run is a matter of THIS pass's M and of the
-        longest contraction each of them meets -- dX of qkv: 3 C, dX of fc1 and fc2 itself: hidden.  Beyond the limit the tile kernels run,
-        in forward and backward alike, exactly as with the A/B switch off.  Decided once per pass, where its weights are prepared."""
-        cfg = self.cfg
-        self.lnbwd_rows = bool(self.rows_lnbwd and rows_lnbwd_fits(self.M, cfg.C, max(3 * cfg.C, cfg.hidden)))
-        self.resid_rows = bool(self.rows_resid_ln and rows_resid_ln_fits(self.M, cfg.C, max(cfg.C, cfg.hidden)))
+    def _make_plan(self, need_grad: bool) -> Plan:
+        caps = Caps(fold=self.fold, x3=self.x3, recompute=self.recompute, gelu_d=self.gelu_d,
+                    grad_stream=self.gstream_allowed, rows_lnbwd=self.rows_lnbwd, rows_resid_ln=self.rows_resid_ln,
+                    block_grad_t=self.block_grad_t, proj_mlp=self.proj_mlp, fuse_ln=hasattr(self.ops, 'fuse_ln_fwd'))
+        return plan_pass(self.cfg, caps, self.M, need_grad, self.rawln)
 
     def _streams(self):
         """(main, side) streams for the dual-stream schedule, or (None, None)."""
@@ -321,7 +422,7 @@ class Engine:
 
     def _norm_in(self, x, pre, norm, ln):
         """(GEMM operand, mean, rstd) of a sub-layer's LayerNorm; `ln` when LayerNorm(x) came with x from its producer."""
-        xn, mean, rstd = ln if ln is not None else self._layernorm(x, None if self.fold else f'{pre}.{norm}')
+        xn, mean, rstd = ln if ln is not None else self._layernorm(x, None if self.plan.fold else f'{pre}.{norm}')
         return self._mm(xn), mean, rstd
 
     def _mm(self, t):
@@ -345,15 +446,15 @@ class Engine:
         `.data` in a pure inference process still needs `hip_ops.get().weight_cache.clear()`."""
         if need_grad or not hasattr(self.ops, 'weight_cache') or self.dev.type != 'cuda' or torch.cuda.is_current_stream_capturing():
             return None
-        return (tuple((p.data_ptr(), p._version) for p in self.P.values()), self.T, self.fold, self.rawln, self.proj_mlp, self.x3, self.resid_rows)
+        return (tuple((p.data_ptr(), p._version) for p in self.P.values()), self.T, self.plan.formats)
 
     def prepare_weights(self, need_grad: bool):
         """T-typed copies of every Linear weight (and their transposes when a backward follows); with LayerNorm folding the
         qkv / fc1 weights are W diag(gamma) and come with their folded bias and row sums.  Under no_grad the prepared set is kept
         on the kernel provider and reused as long as no parameter changed: an inference call then launches no fold / pack kernels
         (at depth 5 they were ~60 small launches per forward, as many as a B = 1 forward has kernels of its own)."""
-        cfg, ops, P = self.cfg, self.ops, self.P
-        self._choose_row_kernels()
+        ops, P = self.ops, self.P
+        self.plan = self._make_plan(need_grad)      # (every call: a caller may have changed M or rawln since the last one)
         if need_grad and hasattr(ops, 'weight_cache') and self.dev.type == 'cuda':
             # a training step follows: whatever it does to the parameters -- also through `p.data`, which bumps no version counter
             # (legacy optimizers, EMA code, a replayed graph) -- the next no-grad forward must not find this forward's prepared set
@@ -365,47 +466,35 @@ class Engine:
             # same storage + same versions is not enough: a NEW model built after the old one died gets the same addresses and the
             # same (small) version numbers from the allocator -- the entry must be about these very tensor objects
             if hit is not None and hit[0] == key and len(hit[1]) == len(P) and all(r() is p for r, p in zip(hit[1], P.values())):
-                self.Wn, self.Wt, self.Bf, self.Rs, self.Pk, self.Pk_proj, self.Pf = hit[2]
+                self.Wn, self.Wt, self.Bf, self.Rs, self.Pk, self.Pf = hit[2]
                 return
         self._prepare_weights(need_grad)
         if key is not None:
             import weakref
-            ops.weight_cache[self.dev.index] = (key, [weakref.ref(p) for p in P.values()], (self.Wn, self.Wt, self.Bf, self.Rs, self.Pk, self.Pk_proj, self.Pf))
+            ops.weight_cache[self.dev.index] = (key, [weakref.ref(p) for p in P.values()], (self.Wn, self.Wt, self.Bf, self.Rs, self.Pk, self.Pf))
 
     def _prepare_weights(self, need_grad: bool):
-        cfg, ops, P = self.cfg, self.ops, self.P
-        if self.fold:
-            pairs = folded_pairs(cfg)
-            folded = {l for l, _ in pairs}
-            self.Wn, self.Wt = ops.prep_weights(P, [n for n in linear_names(cfg) if n not in folded], self.T, need_grad)
-            fn, ft, self.Bf, self.Rs = ops.fold_norm_weights(P, pairs, need_grad, self.T)
-            self.Wn.update(fn)
-            self.Wt.update(ft)
-            if self.resid_rows and not self.rawln:
-                # proj / fc2 of the first three sub-layers of every Block (the fourth feeds the fusion, not a LayerNorm)
-                lins = [f'{pre}.{mod}.{LINEARS[typ][1]}' for pre, _, sub, typ, _, mod, _ in sublayers(cfg) if sub < 3]
-                self.Pf = dict(zip(lins, ops.rows_n_pack_many([self.Wn[lin] for lin in lins])))
-            if need_grad and self.lnbwd_rows and self.gstream_allowed:
-                # (not for the first sub-layer of a Block whose input gradient leaves in fp32 with the other stream's gradient added --
-                # MBX_BLOCK_GRAD_T=0: the tile kernel's epilogue)
-                first = {f'{pre}.{mod}.qkv' for pre, _, sub, _, _, mod, _ in sublayers(cfg) if sub == 0 and not (self.block_grad_t and cfg.att_fuse)}
-                lins = [lin for lin, _ in pairs if lin not in first]
-                self.Pn = dict(zip(lins, ops.rows_n_pack_many([ft[lin] for lin in lins])))
-            if self.rawln:
-                before = None      # the sub-layer in front of the current one in its Block: (typ, module)
-                for blk, _, sub, typ, _, m, _ in sublayers(cfg):
-                    pre = f'{blk}.{m}'
-                    if typ == 'mlp' and self.proj_mlp and before is not None and before[0] == 'attn':
-                        # the proj that runs in front of this MLP in the same kernel: the attention right before it in ORDER
-                        self.Pk_proj[pre] = f'{blk}.{before[1]}.proj'
-                        self.Pk[pre] = ops.proj_mlp_pack_weights(self.Wn[self.Pk_proj[pre]], self.Wn[pre + '.fc1'], self.Wn[pre + '.fc2'])
-                    elif typ == 'mlp':
-                        self.Pk[pre] = ops.mlp_pack_weights(self.Wn[pre + '.fc1'], self.Wn[pre + '.fc2'])
-                    before = (typ, m) if sub < 3 else None
-                    for a in ('attn_s', 'attn_t') if sub == 3 else ():      # the Block is complete: its two qkv
-                        self.Pk[f'{blk}.{a}.qkv'] = ops.rows_pack_nk(self.Wn[f'{blk}.{a}.qkv'])
-        else:
+        cfg, ops, P, plan = self.cfg, self.ops, self.P, self.plan
+        if not plan.fold:
             self.Wn, self.Wt = ops.prep_weights(P, linear_names(cfg), self.T, need_grad, x3=self.x3)
+            return
+        pairs = folded_pairs(cfg)
+        folded = {l for l, _ in pairs}
+        self.Wn, self.Wt = ops.prep_weights(P, [n for n in linear_names(cfg) if n not in folded], self.T, need_grad)
+        fn, ft, self.Bf, self.Rs = ops.fold_norm_weights(P, pairs, need_grad, self.T)
+        self.Wn.update(fn)
+        self.Wt.update(ft)
+        if plan.pack_f:
+            self.Pf = dict(zip(plan.pack_f, ops.rows_n_pack_many([self.Wn[lin] for lin in plan.pack_f])))
+        if plan.pack_n:
+            self.Pn = dict(zip(plan.pack_n, ops.rows_n_pack_many([ft[lin] for lin in plan.pack_n])))
+        for what, name, front in plan.pack_k:
+            if what == 'qkv':
+                self.Pk[name] = ops.rows_pack_nk(self.Wn[name])
+            elif front is not None:
+                self.Pk[name] = ops.proj_mlp_pack_weights(self.Wn[front], self.Wn[name + '.fc1'], self.Wn[name + '.fc2'])
+            else:
+                self.Pk[name] = ops.mlp_pack_weights(self.Wn[name + '.fc1'], self.Wn[name + '.fc2'])
 
     # ------------------------------------------------------------------ forward
     def forward(self, x: torch.Tensor, return_rep, need_grad: bool, tta_perm=None, ragged=None):
@@ -442,13 +531,12 @@ class Engine:
             B = 2 * B
         M, C = B * T * J, cfg.C
         self.B, self.Tlen, self.M = B, T, M
-        self.rawln = not need_grad and self.fold and self.drop_seed is None and self.rawln_allowed and self._can('can_fuse_mlp')
+        self.rawln = not need_grad and self.fold and self.rawln_allowed and self._can('can_fuse_mlp')
         self.prepare_weights(need_grad)
+        plan = self.plan
         h = self._f(M, C)
-        pos_drop = self.drop_seed is not None and cfg.drop > 0
-        ln0 = None      # (xhat, mean, rstd) of h when the embedding kernel normalises its own rows (folded path, plain batch, no pos_drop)
-        if (hasattr(ops, 'embed_ln_fwd') and self.fold and not self.rawln and not pos_drop and ragged is None and tta_perm is None
-                and self._can('can_embed_ln')):
+        ln0 = None      # (xhat, mean, rstd) of h when the embedding kernel normalises its own rows (a plain batch)
+        if plan.embed_norm and ragged is None and tta_perm is None and hasattr(ops, 'embed_ln_fwd') and self._can('can_embed_ln'):
             ln0 = (self._t(M, C), self._f(M), self._f(M))
             ops.embed_ln_fwd(x, P['joints_embed.weight'], P['joints_embed.bias'], P['pos_embed'], P['temp_embed'], cfg.eps, h, *ln0, B, T, J)
         elif ragged is not None and tta_perm is not None:
@@ -459,16 +547,13 @@ class Engine:
             ops.embed_fwd_tta(x, tta_perm, P['joints_embed.weight'], P['joints_embed.bias'], P['pos_embed'], P['temp_embed'], h, B // 2, T, J)
         else:
             ops.embed_fwd(x, P['joints_embed.weight'], P['joints_embed.bias'], P['pos_embed'], P['temp_embed'], h, B, T, J)
-        if pos_drop:      # (DSTformer.py:337)
+        if self.drop_seed is not None and cfg.drop > 0:      # pos_drop (DSTformer.py:337)
             from .dropmask import site_seed
             ops.dropout(h, h, cfg.drop, site_seed(self.drop_seed, -1, 0, 0, 1))
         saved: Dict[str, Any] = dict(x=x, levels=[], return_rep=return_rep)
         main, side = self._streams()
-        fuse_ln = cfg.att_fuse and hasattr(ops, 'fuse_ln_fwd')
         ln_st = ln_ts = ln_tail = None      # (xn, mean, rstd) of h already produced by the fusion kernel of the previous level
-        if self.fold and not self.rawln:
-            # folded: both Blocks of a level read the SAME plain normalisation of h (their gamma / beta live in their own weights) -- one
-            # launch for level 0 too, as the fusion kernel provides one xhat for the later levels
+        if plan.embed_norm:
             ln_st = ln_ts = ln0 if ln0 is not None else self._layernorm(h, None)
         for i in range(cfg.depth):
             if side is not None:
@@ -482,19 +567,16 @@ class Engine:
                 x_ts, sv_ts = self._block_fwd(h, f'blocks_ts.{i}', 'ts', need_grad, ln_ts)
             ln_st = ln_ts = None      # consumed; the fusion kernel below may provide the next level's
             hn = self._f(M, C)
-            if fuse_ln and not (self.rawln and i + 1 < cfg.depth):      # (no-grad: the next level's consumers read the fp32 rows themselves)
-                # the fusion kernel also normalises its output for its consumers: the first LayerNorm of both blocks of the next
-                # level (one mean / rstd for the two), or the final `norm` after the last level
+            what = plan.fuse_norm[i]
+            if what is not None:      # the fusion kernel also normalises its output for its consumers (one mean / rstd for the two)
                 alpha, mean, rstd = self._f(M, 2), self._f(M), self._f(M)
-                last = i + 1 == cfg.depth
-                # (folded, not last: ONE plain normalisation -- no gamma / beta -- serves both blocks of the next level)
-                n1, n2 = (('norm', None) if last else (None, None) if self.fold else
+                n1, n2 = (('norm', None) if what == 'norm' else (None, None) if what == 'xhat' else
                           (f"blocks_st.{i + 1}.{ORDER['st'][0][1]}", f"blocks_ts.{i + 1}.{ORDER['ts'][0][1]}"))
                 xn1, xn2 = self._t(M, C), (self._t(M, C) if n2 else None)
                 gb = [P[f'{n}.{k}'] if n else None for n in (n1, n2) for k in ('weight', 'bias')]
                 ops.fuse_ln_fwd(x_st, x_ts, P[f'ts_attn.{i}.weight'], P[f'ts_attn.{i}.bias'], hn, alpha,
                                 gb[0], gb[1], xn1, gb[2], gb[3], xn2, cfg.eps, mean, rstd)
-                if last:
+                if what == 'norm':
                     ln_tail = (xn1, mean, rstd)
                 else:
                     ln_st, ln_ts = (xn1, mean, rstd), (xn2 if n2 else xn1, mean, rstd)
@@ -539,47 +621,42 @@ class Engine:
         """`ln` = (xn, mean, rstd) of x when its producer already normalised it (the fusion kernel of the previous level, for the
         first sub-layer of a Block); never anything else."""
         svs = []
-        order = ORDER[kind]
-        pend = None      # no-grad: an attention whose proj + residual has been left to the MLP kernel that follows: dict(o=, proj=)
-        for sub, (typ, norm, mod, mode) in enumerate(order):
-            nxt = order[sub + 1][1] if sub + 1 < len(order) else None      # the norm that reads this sub-layer's output
+        o = None      # no-grad: output of an attention whose proj + residual is left to the MLP kernel that follows
+        for sub, (typ, norm, mod, mode) in enumerate(ORDER[kind]):
+            sp = self.plan.sub[pre, sub]
             if typ == 'attn':
-                defer = self.rawln and self.proj_mlp and sub + 1 < len(order) and order[sub + 1][0] == 'mlp'
-                x, sv, ln, pend = self._attn_fwd(x, pre, norm, mod, mode, need_grad, sub, ln, nxt, defer_proj=defer)
+                x, sv, ln, o = self._attn_fwd(x, pre, norm, mod, mode, need_grad, sub, ln, sp)
             else:
-                x, sv, ln = self._mlp_fwd(x, pre, norm, mod, need_grad, sub, ln, nxt, pending_proj=pend)
-                pend = None
+                x, sv, ln = self._mlp_fwd(x, pre, norm, mod, need_grad, sub, ln, sp, o)
+                o = None
             svs.append(sv)
-        assert pend is None, 'an attention deferred its proj to an MLP that never came'
         return x, svs
 
-    def _resid_gemm(self, a, lin, x, dm, pre, nxt):
+    def _resid_gemm(self, a, lin, x, dm, sp):
         """y = x + a . W^T + b (fp32 residual stream): returns (y, ln) -- ln = (xhat, mean, rstd) of y for the next sub-layer when the
         row-owner kernel ran (it owns whole rows, so LayerNorm's statistics cost it nothing), else None."""
         cfg, ops, P = self.cfg, self.ops, self.P
         y = self._f(self.M, cfg.C)
-        drop = dm is not None and dm.branch      # proj_drop / MLP drop + DropPath on the branch (DSTformer.py:84,148-149,241-242)
-        # (the kernel addresses its rows with 32-bit offsets: beyond `resid_rows` the tile kernel + LayerNorm take over)
-        if self.fold and nxt is not None and lin in self.Pf and self.resid_rows and not drop:
+        if sp.lin_out == 'rows':
             xn, mean, rstd = self._op(self.M, cfg.C), self._f(self.M), self._f(self.M)
             ops.rows_resid_ln(a, self.Pf[lin], P[lin + '.bias'], x, y, xn, mean, rstd, cfg.eps)
             return y, (xn, mean, rstd)
         ops.gemm_nt(a, self.Wn[lin], P[lin + '.bias'], EPI_RESID, resid=x, out_f=y)
-        if drop and not self.rawln:
+        if dm is not None and dm.branch:      # proj_drop / MLP drop + DropPath on the branch (DSTformer.py:84,148-149,241-242)
             ops.residual_drop(y, x, cfg.J, dm.p, dm.seed_branch, dm.p_path, dm.seed_path)
         return y, None
 
-    def _attn_fwd(self, x, pre, norm, attn, mode, need_grad, sub=0, ln=None, nxt=None, defer_proj=False):
+    def _attn_fwd(self, x, pre, norm, attn, mode, need_grad, sub, ln, sp):
         cfg, ops, P = self.cfg, self.ops, self.P
         M, C = self.M, cfg.C
         qkv = self._t(M, 3 * C)
         lin = f'{pre}.{attn}.qkv'
-        if self.rawln:      # no-grad: LayerNorm + qkv straight from the fp32 rows (operand, statistics and row constants made in the kernel)
+        if sp.lin_in == 'raw':      # no-grad: LayerNorm + qkv straight from the fp32 rows (operand, statistics and row constants made in the kernel)
             xn = mean = rstd = None
             ops.rows_gemm_nk_ln(x, self.Pk[lin], self.Bf[lin], self.Rs[lin], cfg.eps, qkv)
         else:
             xn, mean, rstd = self._norm_in(x, pre, norm, ln)
-            ops.gemm_nt(xn, self.Wn[lin], self.Bf[lin] if self.fold else P.get(lin + '.bias'), EPI_STORE, out_t=qkv)
+            ops.gemm_nt(xn, self.Wn[lin], self.Bf[lin] if self.plan.fold else P.get(lin + '.bias'), EPI_STORE, out_t=qkv)
         dm = self._drops(pre, sub)
         o, lse = self._t(M, C), self._f(M, cfg.H)
         if self.ragged is not None and mode == MODE_TEMPORAL:      # every clip its own length; the B Tlen frames are one packed batch
@@ -587,31 +664,28 @@ class Engine:
             ops.attn_fwd_ragged(qkv, o, lse, clip_tab, n_clips, self.B * self.Tlen, max_len, cfg.J, cfg.H, cfg.scale)
         else:
             ops.attn_fwd(qkv, o, lse, self.B, self.Tlen, cfg.J, cfg.H, cfg.scale, mode, drop=dm.attn if dm else None)
-        if defer_proj:      # no-grad: proj + residual run inside the MLP kernel that follows
-            return x, None, None, dict(o=o, proj=f'{pre}.{attn}.proj')
+        if sp.lin_out == 'deferred':
+            return x, None, None, o
         o_op = self._mm(o)      # (bf16x3: the operand planes are kept for the weight gradient too -- o itself stays fp32 for the attention backward)
-        y, ln_y = self._resid_gemm(o_op, f'{pre}.{attn}.proj', x, dm, pre, nxt)
+        y, ln_y = self._resid_gemm(o_op, f'{pre}.{attn}.proj', x, dm, sp)
         sv = self._saved(x, xn, mean, rstd, dm, qkv=qkv, o=o, lse=lse) if need_grad else None
         if sv is not None and self.x3 and self.x3_planes and not self.recompute:
             sv['o_op'] = o_op
         return y, sv, ln_y, None
 
     def _saved(self, x, xn, mean, rstd, dm, **core):
-        if self.fold:      # backward needs xhat and rstd only: the fp32 sub-layer input is not kept
+        if self.plan.fold:      # backward needs xhat and rstd only: the fp32 sub-layer input is not kept
             return dict(x=None, mean=None, rstd=rstd, xn=xn, dm=dm, **core)
         return dict(x=x, mean=mean, rstd=rstd, xn=None if self.recompute else xn, dm=dm, **core)
 
-    def _mlp_fwd(self, x, pre, norm, mlp, need_grad, sub=1, ln=None, nxt=None, pending_proj=None):
+    def _mlp_fwd(self, x, pre, norm, mlp, need_grad, sub, ln, sp, o=None):
         cfg, ops, P = self.cfg, self.ops, self.P
         M, C = self.M, cfg.C
         lin = f'{pre}.{mlp}.fc1'
-        if self.rawln:                # no-grad: the whole sub-layer is one kernel; the hidden never reaches HBM, the operand is bf16(x) made in the kernel
+        if sp.lin_out == 'fused':     # no-grad: the whole sub-layer is one kernel; the hidden never reaches HBM, the operand is bf16(x) made in the kernel
             y = self._f(M, C)
-            if pending_proj is not None:      # x + proj(o) first, in the same kernel
-                if self.Pk_proj.get(f'{pre}.{mlp}') != pending_proj['proj']:
-                    raise RuntimeError(f"{pre}.{mlp}: packed with {self.Pk_proj.get(f'{pre}.{mlp}')} in front, asked to run {pending_proj['proj']}")
-                ops.proj_mlp_fused_fwd(pending_proj['o'], self.Pk[f'{pre}.{mlp}'], P[pending_proj['proj'] + '.bias'], self.Bf[lin],
-                                       P[f'{pre}.{mlp}.fc2.bias'], self.Rs[lin], x, y, cfg.eps)
+            if sp.front is not None:      # x + proj(o) first, in the same kernel
+                ops.proj_mlp_fused_fwd(o, self.Pk[f'{pre}.{mlp}'], P[sp.front + '.bias'], self.Bf[lin], P[f'{pre}.{mlp}.fc2.bias'], self.Rs[lin], x, y, cfg.eps)
             else:
                 ops.mlp_fused_fwd(None, True, self.Pk[f'{pre}.{mlp}'], self.Bf[lin], P[f'{pre}.{mlp}.fc2.bias'], self.Rs[lin], x, y, None,
                                   cfg.eps, None, None)
@@ -621,18 +695,15 @@ class Engine:
         mlp_drop = dm is not None and dm.p > 0
         # u only feeds GELU' in backward; g is only fc2's operand (and the weight gradient's) unless the MLP dropout touches it first
         u, g = (self._t(M, cfg.hidden) if need_grad else None), (self._t(M, cfg.hidden) if mlp_drop else self._op(M, cfg.hidden))
-        # the derivative instead of the pre-activation where backward will run the row-owner tail (every MLP of a Block does: never the
-        # first sub-layer, so bf16 gradient in and out and no second summand)
-        save_d = bool(need_grad and self.fold and self.gelu_d and self.gstream_allowed and not self.recompute and not mlp_drop
-                      and lin in self.Pn and self.lnbwd_rows)
+        save_d = need_grad and sp.save == 'd'      # (a forward-only pass over a plan made for training saves nothing)
         if save_d:
             ops.gemm_nt_gelu_d(xn, self.Wn[lin], self.Bf[lin], u, g)
         else:
-            ops.gemm_nt(xn, self.Wn[lin], self.Bf[lin] if self.fold else P[lin + '.bias'], EPI_GELU, out_t=u, out2_t=g)
+            ops.gemm_nt(xn, self.Wn[lin], self.Bf[lin] if self.plan.fold else P[lin + '.bias'], EPI_GELU, out_t=u, out2_t=g)
         if mlp_drop:                                          # MLP drop after the activation (DSTformer.py:82)
             ops.dropout(g, g, dm.p, dm.seed_act)
         g = self._mm(g)
-        y, ln_y = self._resid_gemm(g, f'{pre}.{mlp}.fc2', x, dm, pre, nxt)
+        y, ln_y = self._resid_gemm(g, f'{pre}.{mlp}.fc2', x, dm, sp)
         sv = self._saved(x, xn, mean, rstd, dm, u=None if save_d else u, d=u if save_d else None, g=None if self.recompute else g) if need_grad else None
         return y, sv, ln_y
 
@@ -647,7 +718,7 @@ class Engine:
         M, C, R = self.M, cfg.C, cfg.R
         B, T, J = self.B, self.Tlen, cfg.J
         G = self.grads = grads
-        self.gstream = self.fold and self.gstream_allowed
+        plan = self.plan
         dpre = self._t(M, R)
         if saved.get('pool') is not None:
             _, persons, p_drop, seed = saved['pool']
@@ -671,11 +742,11 @@ class Engine:
         del dxn, dpre
         if on_ready is not None:
             on_ready(0)
-        pair = None      # the two Blocks' input gradients of the level above, T-typed (block_grad_t), instead of their fp32 sum dh
+        pair = None      # the two Blocks' input gradients of the level above, T-typed (plan.out_t), instead of their fp32 sum dh
         for i in reversed(range(cfg.depth)):
             lv = saved['levels'][i]
             # (gradient stream in the operand type: the Blocks read the T-typed copies only, the fp32 ones are not even written)
-            d_st, d_ts = (None, None) if (self.gstream and cfg.att_fuse) else (self._f(M, C), self._f(M, C))
+            d_st, d_ts = (None, None) if (plan.gstream and cfg.att_fuse) else (self._f(M, C), self._f(M, C))
             d_st_t, d_ts_t = self._t(M, C), self._t(M, C)
             if cfg.att_fuse:
                 if pair is not None:
@@ -687,11 +758,8 @@ class Engine:
             else:
                 ops.average_bwd(dh, d_st, d_ts, d_st_t, d_ts_t)
             pair = dh = None
-            # this level's Blocks hand their input gradients down T-typed when the row-owner tail can take their first sub-layer
-            out_t = bool(self.block_grad_t and self.gstream and cfg.att_fuse and (i > 0 or self.drop_seed is None) and self.lnbwd_rows
-                         and all(f'{st}.{i}.{ORDER[kind][0][2]}.qkv' in self.Pn for st, kind in STREAMS))
             main, side = self._streams()
-            if out_t:
+            if plan.out_t[i]:      # the row-owner tail takes both Blocks' first sub-layers: their input gradients go down T-typed
                 if side is not None:
                     side.wait_stream(main)
                 _, a_t = self._block_bwd(d_st, d_st_t, lv['st'], f'blocks_st.{i}', 'st', None, last_needs_t=True)
@@ -748,21 +816,20 @@ class Engine:
             typ, norm, mod, mode = ORDER[kind][idx]
             extra = extra_last if idx == 0 else None
             need_t = True if idx > 0 else last_needs_t
-            dy, dy_t = self._sub_bwd(typ, dy, dy_t, svs[idx], pre, norm, mod, mode, extra, need_t)
+            dy, dy_t = self._sub_bwd(self.plan.sub[pre, idx], typ, dy, dy_t, svs[idx], pre, norm, mod, mode, extra, need_t)
             svs[idx] = None
         return dy, dy_t
 
-    def _sub_bwd(self, typ, dy, dy_t, sv, pre, norm, mod, mode, extra, need_t):
+    def _sub_bwd(self, sp, typ, dy, dy_t, sv, pre, norm, mod, mode, extra, need_t):
         """One sub-layer: branch gradient, the core back to the Linear-in's output gradient dY, and a tail: returns (dx, dx_t)."""
         ops, G = self.ops, self.grads
         lin = f'{pre}.{mod}.{LINEARS[typ][0]}'
         dy_t = self._branch_grad(dy, dy_t, sv.get('dm'))
-        if dy_t is None and sv.get('d') is not None:
-            dy_t = dy.to(self.T)
-        # the row-owner tail takes its row means itself: the core then runs without its row dots (part = None)
-        rows = self.fold and self._rows_tail_ok(lin, dy_t, extra, need_t)
-        dY, part = self._attn_bwd(dy_t, sv, pre, mod, mode, rows) if typ == 'attn' else self._mlp_bwd(dy_t, sv, pre, mod, rows)
-        if self.fold:
+        # the row-owner tail serves a gradient that arrives and leaves in the operand type only (always so inside a Block; at its first
+        # sub-layer when the caller asks for that and adds nothing); it takes its row means itself, so the core runs without row dots
+        tail = sp.tail if sp.tail != 'rows' or (need_t and extra is None) else 'fold'
+        dY, part = self._attn_bwd(dy_t, sv, pre, mod, mode, tail) if typ == 'attn' else self._mlp_bwd(dy_t, sv, pre, mod, sp, tail)
+        if tail != 'plain':
             return self._fold_tail(dY, part, sv, lin, f'{pre}.{norm}', dy, dy_t, extra, need_t)
         dxn = self._t(self.M, self.cfg.C)
         dY = self._mm(dY)
@@ -781,16 +848,16 @@ class Engine:
             return self._mm(dy)          # bf16x3: the GEMM operand is the split of the fp32 gradient itself (unless its producer wrote the planes)
         return dy_t
 
-    def _attn_bwd(self, dy_t, sv, pre, attn, mode, rows):      # -> (dqkv, its row dots for the folded tile tail or None)
+    def _attn_bwd(self, dy_t, sv, pre, attn, mode, tail):      # -> (dqkv, its row dots for the folded tile tail or None)
         cfg, ops, G = self.cfg, self.ops, self.grads
         M, C = self.M, cfg.C
         lin, proj = f'{pre}.{attn}.qkv', f'{pre}.{attn}.proj'
         do = self._t(M, C)
         ops.gemm_tn(dy_t, sv['o_op'] if 'o_op' in sv else self._mm(sv['o']), G[proj + '.weight'], G[proj + '.bias'])
         ops.gemm_nt(dy_t, self.Wt[proj], None, EPI_STORE, out_t=do)
-        dqkv = self._t(M, 3 * C) if self.fold else self._op(M, 3 * C)     # (bf16x3: the attention backward writes the operand planes itself)
+        dqkv = self._t(M, 3 * C) if tail != 'plain' else self._op(M, 3 * C)     # (bf16x3: the attention backward writes the operand planes itself)
         dims = (self.B, self.Tlen, cfg.J, cfg.H, cfg.scale, mode)
-        if self.fold and not rows:
+        if tail == 'fold':
             part = self._f(2 * cfg.H, M, 2)       # block-major; per head: the q columns, the k + v columns
             ops.attn_bwd_stats(sv['qkv'], sv['o'], do, sv['lse'], dqkv, self.Bf[lin], self.Rs[lin], part, *dims)
             return dqkv, part
@@ -808,25 +875,21 @@ class Engine:
                                dx, dx_t, G[f'{pre}.{norm}.weight'], G[f'{pre}.{norm}.bias'])
         return dx, dx_t
 
-    def _rows_tail_ok(self, lin, dy_t, extra, need_t) -> bool:
-        """The row-owner LayerNorm-backward GEMM serves a folded pair whose gradient arrives and leaves in the operand type only."""
-        return bool(self.lnbwd_rows and self.gstream and need_t and dy_t is not None and extra is None and lin in self.Pn)
-
     def _fold_tail(self, dY, part, sv, lin, norm, dy, dy_t, extra, need_t):
         """Folded (LayerNorm -> Linear) pair, backward from the Linear's output gradient dY and its row dots `part`: weight
         gradient, then dx = dy [+ extra] + LayerNorm'(dY . W') as the epilogue of the dX GEMM, then the parameter gradients of
-        W, gamma and beta from the folded weight gradient.  With the gradient stream in the operand type (`gstream`) the incoming
+        W, gamma and beta from the folded weight gradient.  With the gradient stream in the operand type (plan.gstream) the incoming
         dy is read as dy_t and, inside a Block (need_t), only the T-typed dx is written: returns (None, dx_t)."""
         cfg, ops, P, G = self.cfg, self.ops, self.P, self.grads
         M, C = self.M, cfg.C
-        rows = part is None                # (round 5) row means taken by the dX kernel itself: no row dots, no row constants
+        rows = part is None                # the row-owner tail: row means taken by the dX kernel itself, no row dots, no row constants
         if not rows:
             rowc = self._f(M, 4)
             ops.lnbwd_rowc(part, sv['rstd'], rowc, C)
         db = G.get(lin + '.bias')
         if db is None:                     # qkv_bias=False: the column sums of dY are still needed for d(beta)
             db = self._f(dY.shape[1])
-        stream = self.gstream and dy_t is not None
+        stream = self.plan.gstream      # (a folded sub-layer always gets dy_t: from the tail above it, or from the fusion backward)
         dres = dy_t if stream else dy
         ops.gemm_tn(dY, sv['xn'], G[lin + '.weight'], db)
         ops.unfold_norm_grads(G[lin + '.weight'], db, P[lin + '.weight'], P[norm + '.weight'], P[norm + '.bias'],
@@ -840,7 +903,7 @@ class Engine:
         ops.gemm_nt_lnbwd(dY, self.Wt[lin], sv['xn'], rowc, dres, self._await(extra), dx, dx_t)
         return dx, dx_t
 
-    def _mlp_bwd(self, dy_t, sv, pre, mlp, rows):      # -> (du, its row dots for the folded tile tail or None)
+    def _mlp_bwd(self, dy_t, sv, pre, mlp, sp, tail):      # -> (du, its row dots for the folded tile tail or None)
         cfg, ops, G = self.cfg, self.ops, self.grads
         M = self.M
         lin, fc2 = f'{pre}.{mlp}.fc1', f'{pre}.{mlp}.fc2'
@@ -856,12 +919,10 @@ class Engine:
             g = self._mm(g)
         ops.gemm_tn(dy_t, g, G[fc2 + '.weight'], G[fc2 + '.bias'])
         del g
-        if sv.get('d') is not None:                           # forward saved gelu'(u): one multiply, then the row-owner tail
-            if not rows:
-                raise RuntimeError(f'{lin}: the derivative was saved for the row-owner LayerNorm backward, which cannot run here')
+        if sp.save == 'd':                                    # forward saved gelu'(u): one multiply, then the row-owner tail
             ops.gemm_nt_mul(dy_t, self.Wt[fc2], sv['d'], du)
             return du, None
-        if self.fold and not rows:
+        if tail == 'fold':
             part = self._f(cfg.hidden // 64, M, 2)
             ops.gemm_nt_dgelu_stats(dy_t, self.Wt[fc2], du, sv['u'], self.Bf[lin], self.Rs[lin], part)
             return du, part

@@ -242,6 +242,60 @@ def test_no_grad_raw_operand_sequencing(name, monkeypatch):
     assert not any(c.startswith('mlp_fused') or c.startswith('rows_gemm') or c.startswith('rows_pack') or c.startswith('proj_mlp') for c in ops_g.calls)
 
 
+@pytest.mark.parametrize('rawln', [True, False])
+def test_a_block_can_be_driven_without_forward(rawln, monkeypatch):
+    """bench.py's Block benchmark sets dev / B / Tlen / M itself, calls prepare_weights() and then _block_fwd / _block_bwd directly:
+    everything a pass needs beyond that is either given a default by the constructor or decided by the plan prepare_weights() makes.
+    Both paths of its fwd(): the forward-only pass is the no-grad sequencing, re-prepared at every change (`rawln`), or -- MBX_RAWLN=0 --
+    the training sequencing without saves on the plan that was made for training, with no second prepare_weights()."""
+    from motionbert_amd.engine import Engine
+    set_switch(monkeypatch, 'MBX_RAWLN', '1' if rawln else '0')
+    z, cfg = load_golden('tiny_trained')
+    model = build_model(cfg)
+    _load(model, z)
+    mcfg = M.make_cfg(model)
+    P = {n: p.detach() for n, p in model.named_parameters()}
+    ops = MockOps()
+    eng = Engine(ops, mcfg, P, torch.bfloat16)
+    eng.dual = False
+    B, T, J, C = 2, 9, mcfg.J, mcfg.C
+    eng.dev, eng.B, eng.Tlen, eng.M = torch.device('cpu'), B, T, B * T * J
+    prepared = []
+    monkeypatch.setattr(Engine, '_prepare_weights', lambda self, need_grad, orig=Engine._prepare_weights: (prepared.append(need_grad), orig(self, need_grad))[1])
+    eng.prepare_weights(True)
+    g = torch.Generator().manual_seed(3)
+    h = torch.randn(eng.M, C, generator=g)
+    dy = torch.randn(eng.M, C, generator=g) * 0.01
+    dy_t = dy.to(torch.bfloat16)
+    pre = 'blocks_st.0'
+    eng.grads = {n: torch.empty_like(p) for n, p in P.items() if n.startswith(pre + '.')}
+
+    def fwd(need_grad):
+        raw = (not need_grad) and eng.fold and eng.rawln_allowed and ops.can_fuse_mlp(eng.T, mcfg)
+        if raw != eng.rawln:
+            eng.rawln = raw
+            eng.prepare_weights(need_grad)
+        return eng._block_fwd(h, pre, 'st', need_grad)
+
+    assert eng.fold and eng.rawln_allowed == rawln
+    for _ in range(2):
+        y, svs = fwd(False)
+        assert eng.rawln == rawln and svs == [None] * 4 and y.dtype == torch.float32 and bool(torch.isfinite(y).all())
+        y0 = y
+        y, svs = fwd(True)
+        if not rawln:      # the same kernels with and without saves, but for fc1's epilogue (gelu'(u) saved: another erf approximation)
+            assert rel_l2(y0.numpy(), y.numpy()) < 1e-2
+        assert not eng.rawln and bool(torch.isfinite(y).all())
+        eng.gstream = eng.fold and eng.gstream_allowed
+        dx, dx_t = eng._block_bwd(dy, dy_t, svs, pre, 'st', None, last_needs_t=False)
+        assert dx_t is None and dx.dtype == torch.float32 and dx.shape == (eng.M, C) and bool(torch.isfinite(dx).all())
+        assert all(bool(torch.isfinite(v).all()) for v in eng.grads.values())
+    assert prepared == ([True, False, True, False, True] if rawln else [True])
+    # the derivative is saved by the two passes with a backward only; the forward-only ones run the fused MLP or the plain fc1 epilogue
+    assert ops.calls.count('gemm_nt.gelu_d') == 4 and ops.calls.count('proj_mlp_fused_fwd') == (4 if rawln else 0)
+    assert ops.calls.count('gemm_nt.1') == (0 if rawln else 4)
+
+
 def test_average_fusion_variant():
     z, cfg = load_golden('tiny_default')
     from oracle import dstformer_oracle as O

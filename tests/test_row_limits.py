@@ -136,10 +136,17 @@ def test_fallback_equals_the_recorded_switch_off_sequence(monkeypatch):
 def test_a_step_of_339_clips_takes_the_tile_tail():
     """What the decision is about: 339 clips x 243 frames in bf16 at dim_feat 512 used to run the forward for the row-owner tail (the saved
     GELU derivative) and meet the refusal of mbx_rows_lnbwd_t in backward"""
-    from types import SimpleNamespace
-    cfg = SimpleNamespace(C=512, hidden=1024)
-    e = SimpleNamespace(rows_lnbwd=True, rows_resid_ln=True, cfg=cfg)
+    cfg = engine.ModelCfg(dim_in=3, dim_out=3, C=512, R=512, depth=5, H=8, hidden=1024, J=17, maxlen=243, eps=1e-6, scale=0.125,
+                          att_fuse=True, qkv_bias=True)
+    caps = engine.Caps(fold=True, gelu_d=True, grad_stream=True, rows_lnbwd=True, rows_resid_ln=True, block_grad_t=True, proj_mlp=True,
+                       fuse_ln=True)
     for clips, want in ((256, (True, True)), (338, (True, True)), (339, (False, True)), (507, (False, True)), (508, (False, False))):
-        e.M = clips * 243 * 17
-        engine.Engine._choose_row_kernels(e)
-        assert (e.lnbwd_rows, e.resid_rows) == want, clips
+        plan = engine.plan_pass(cfg, caps, clips * 243 * 17, need_grad=True, rawln=False)
+        lnbwd_rows = any(sp.tail == 'rows' for sp in plan.sub.values())
+        resid_rows = any(sp.lin_out == 'rows' for sp in plan.sub.values())
+        assert (lnbwd_rows, resid_rows) == (bool(plan.pack_n), bool(plan.pack_f)) == want, clips
+        saves = {sp.save for sp in plan.sub.values()}
+        assert saves == ({'d', None} if want[0] else {'u', None}), clips
+    # at 339 clips no MLP saves the derivative
+    plan = engine.plan_pass(cfg, caps, 339 * 243 * 17, need_grad=True, rawln=False)
+    assert not any(sp.save == 'd' for sp in plan.sub.values()) and all(sp.tail == 'fold' for sp in plan.sub.values())

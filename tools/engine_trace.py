@@ -8,7 +8,13 @@ A call is recorded as its method name and its arguments bound to the provider's 
 scalar as its value.  A buffer is storage address + offset + shape, numbered by first appearance; every tensor seen is held until the
 case ends so that no address comes back.  Aliasing (`dropout(g, g)`, views of the returned tensor) and swapped arguments therefore show.
 
+The device provider (`hip_ops.get()`, an MI355X) has a case list of its own, `gpu_cases()`, for what the mock cannot reach: the second
+stream, ragged batches and flip TTA.  There every call records one more field, `stream`: 0 when it was issued on the stream that was
+current when the case began (the pass's launch stream), 1 on any other.  tests/golden/engine_trace_gpu.json was recorded at the commit
+BEFORE the engine's decisions moved into one plan per pass; tests/test_gpu_engine_trace.py compares against it.
+
     python tools/engine_trace.py --record [out.json [what it was recorded from, e.g. a commit hash]]
+    python tools/engine_trace.py --record-gpu [out.json [what it was recorded from]]
     python tools/engine_trace.py --bits       one SHA-256 per case over output, input gradient and parameter gradients (host-dependent)"""
 import functools
 import hashlib
@@ -42,8 +48,8 @@ def _signature(cls, name):
 class Recorder:
     """Forwards everything to `ops`; every method call leaves one record in `calls`."""
 
-    def __init__(self, ops):
-        self.__dict__.update(_ops=ops, calls=[], _held=[], _bufs={})
+    def __init__(self, ops, launch_stream=None):
+        self.__dict__.update(_ops=ops, calls=[], _held=[], _bufs={}, _launch=launch_stream)
 
     def __getattr__(self, name):
         attr = getattr(self._ops, name)      # AttributeError where the provider has no such kernel: hasattr() probes see the provider
@@ -54,6 +60,8 @@ class Recorder:
             bound = _signature(type(self._ops), name).bind(*args, **kwargs)
             bound.apply_defaults()
             self.calls.append([name] + [[k, self._describe(v)] for k, v in bound.arguments.items()])
+            if self._launch is not None:      # device cases: issued on the pass's launch stream (0) or on another one (1)
+                self.calls[-1].append(['stream', int(torch.cuda.current_stream() != self._launch)])
             return attr(*args, **kwargs)
         return call
 
@@ -173,6 +181,61 @@ def run_case(spec, bits=False):
     return ops.calls, digest
 
 
+GPU_CFG = dict(dim_in=3, dim_out=3, dim_feat=256, dim_rep=256, depth=2, num_heads=8, mlp_ratio=2, num_joints=17, maxlen=16)
+GPU_B, GPU_T, GPU_CLIPS = 2, 9, (9, 5)
+
+
+def gpu_cases():
+    """[(name, spec)] for the device provider, at the smallest shape at which every capability of HipOps holds (dim_feat 256, head
+    dim 32, hidden 512; 2 clips of 9 frames).  spec: precision, grad, off (one MBX_* switch at 0), ragged (two clips of 9 and 5 frames
+    in one forward, with flip TTA)."""
+    base = dict(precision='bf16', grad=True, off=None, ragged=False)
+    return [('bf16-grad', base), ('bf16-grad-MBX_BLOCK_GRAD_T=0', dict(base, off='MBX_BLOCK_GRAD_T')),
+            ('bf16-grad-MBX_DUAL_STREAM=0', dict(base, off='MBX_DUAL_STREAM')), ('bf16-nograd', dict(base, grad=False)),
+            ('bf16-nograd-ragged-tta', dict(base, grad=False, ragged=True)), ('bf16x3-grad', dict(base, precision='bf16x3'))]
+
+
+@functools.lru_cache(maxsize=None)
+def _gpu_model():
+    import torch.nn as nn
+    from motionbert_amd import DSTformer
+    torch.manual_seed(0)
+    return DSTformer(norm_layer=partial(nn.LayerNorm, eps=1e-6), **GPU_CFG).to('cuda:0')
+
+
+def run_gpu_case(spec):
+    """The recorded calls of one device case (seeded random weights; the prepared-weight cache is emptied first)."""
+    from motionbert_amd import engine, hip_ops, model as M
+    from motionbert_amd.augment import FLIP_PERM
+    dev = torch.device('cuda:0')
+    model = _gpu_model()
+    model.precision = spec['precision']
+    model.train(spec['grad'])
+    for p in model.parameters():
+        p.grad = None
+    g = torch.Generator().manual_seed(1)
+    engine.reload_switches({spec['off']: '0'} if spec['off'] else {})
+    try:
+        with torch.cuda.device(dev):
+            hip_ops.get().weight_cache.clear()
+            ops = Recorder(hip_ops.get(), launch_stream=torch.cuda.current_stream())
+            with torch.set_grad_enabled(spec['grad']):
+                if spec['ragged']:
+                    clip_tab, frame_t, max_len = M.ragged_tables(GPU_CLIPS, GPU_CFG['maxlen'])
+                    x = (torch.rand(1, sum(GPU_CLIPS), 17, 3, generator=g) * 2 - 1).to(dev)
+                    ragged = (torch.from_numpy(clip_tab).to(dev), torch.from_numpy(frame_t).to(dev), len(GPU_CLIPS), max_len)
+                    M.run(ops, model, x, ('tta', torch.tensor(FLIP_PERM, dtype=torch.int32, device=dev)), ragged=ragged)
+                else:
+                    x = (torch.rand(GPU_B, GPU_T, 17, 3, generator=g) * 2 - 1).to(dev).requires_grad_(spec['grad'])
+                    out = M.run(ops, model, x, False)
+                    if spec['grad']:
+                        out.sum().backward()
+            torch.cuda.synchronize()
+    finally:
+        engine.reload_switches()
+    return ops.calls
+
+
 def layouts():
     """linear_names / folded_pairs at depth 1 and 5: the flat gradient layout and the descriptor tables follow their order."""
     from motionbert_amd.engine import ModelCfg, folded_pairs, linear_names
@@ -184,11 +247,11 @@ def layouts():
     return out
 
 
-def trace_table():
+def trace_table(gpu=False):
     """{case: {'sha256': of all its calls, 'calls': 4 hex digits per call (to find the first one that differs)}}"""
     table = {}
-    for name, spec in cases():
-        calls, _ = run_case(spec)
+    for name, spec in (gpu_cases() if gpu else cases()):
+        calls = run_gpu_case(spec) if gpu else run_case(spec)[0]
         digests = [call_digest(c) for c in calls]
         table[name] = dict(sha256=hashlib.sha256(''.join(digests).encode()).hexdigest(), calls=''.join(d[:4] for d in digests))
     return table
@@ -204,6 +267,13 @@ def main():
         t = trace_table()
         with open(out, 'w') as f:
             json.dump({'recorded_from': args[2] if len(args) > 2 else 'working tree', 'cases': t, 'layouts': layouts()}, f, separators=(',', ':'))
+            f.write('\n')
+        print(f'{out}: {len(t)} cases, {sum(len(c["calls"]) // 4 for c in t.values())} calls')
+    elif args[:1] == ['--record-gpu']:
+        out = args[1] if len(args) > 1 else os.path.join(GOLDEN, 'engine_trace_gpu.json')
+        t = trace_table(gpu=True)
+        with open(out, 'w') as f:
+            json.dump({'recorded_from': args[2] if len(args) > 2 else 'working tree', 'cases': t}, f, separators=(',', ':'))
             f.write('\n')
         print(f'{out}: {len(t)} cases, {sum(len(c["calls"]) // 4 for c in t.values())} calls')
     else:
